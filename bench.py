@@ -32,12 +32,6 @@ import os
 import sys
 import time
 
-# One hardware queue per pipeline stream (+ the default stream): with the runtime's
-# default of 4, the fourth pipeline shares a queue with another one and the two
-# serialise against each other (measured: depth 4 = 208 images/s with 4 queues, 232
-# with >= 5). Must be set before the HIP runtime initialises.
-os.environ.setdefault('GPU_MAX_HW_QUEUES', '8')
-
 import numpy as np     # noqa: E402
 import torch           # noqa: E402
 
@@ -99,11 +93,14 @@ def parse_args():
   ap.add_argument('--gpus', type=int, default=1)
   ap.add_argument('--steps', type=int, default=20)
   ap.add_argument('--warmup', type=int, default=3)
-  ap.add_argument('--timed-repeats', type=int, default=5,
-                  help='the timed region of --steps steps is run this many times back to back, '
-                       'each bracketed by barrier + synchronize on both sides; value = all '
-                       'images / all region time (a 20-step region is ~50 ms: one region '
-                       'cannot resolve a 1 %% change), the regions\' spread is reported')
+  ap.add_argument('--timed-repeats', type=int, default=1,
+                  help='the timed region of --steps steps is run this many times back to back '
+                       '(default 1: --steps is the number of timed steps), each bracketed by '
+                       'barrier + synchronize on both sides; value = all images / all region '
+                       'time, the regions\' spread is reported')
+  ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                  help='after the timed region, write what its LAST step computed to DIR as '
+                       '.npy files (see dump_outputs); rank 0 only')
   ap.add_argument('--batch-per-gpu', type=int, default=None,
                   help='images per GPU per step; default 1 at --gpus 1 (config C2), 4 '
                        'at --gpus > 1 (the per-GPU shard of config C3: 32 images / 8)')
@@ -176,6 +173,37 @@ def parse_args():
                   help='skip the serial (depth 1) steps with per-stage HIP events that '
                        'follow the timed region')
   return ap.parse_args()
+
+
+def dump_outputs(out_dir, poses, net, sparse_heads, sample=1 << 20):
+  """--dump-outputs: what one step of the timed path computed, for comparing two builds
+  output for output (same arguments -> same frames, weights and seeds; the logits layers are
+  calibrated on the build's own forward pass of frame 0, as in every run).
+    pose_ids.npy   [n, 3] float64: scene_id, im_id, obj_id of each pose record
+    pose_R.npy     [n, 3, 3] float64, pose_t.npy [n, 3] float64, pose_score.npy [n] float64
+                   -- the records collect() returned for the step, in its order;
+    head_<name>.npy  float32: the plan's head tensor of that step (what the correspondence
+                   stage read), flattened; above `sample` values a fixed sample of `sample`
+                   sorted indices drawn with seed 0 (not with --sparse-heads, whose dense
+                   buffers hold the target objects only): at most 12 MB in all at the default."""
+  os.makedirs(out_dir, exist_ok=True)
+  n = len(poses)
+  arrays = {
+      'pose_ids': np.array([[p['scene_id'], p['im_id'], p['obj_id']] for p in poses],
+                           np.float64).reshape(n, 3),
+      'pose_R': np.array([p['R'] for p in poses], np.float64).reshape(n, 3, 3),
+      'pose_t': np.array([p['t'] for p in poses], np.float64).reshape(n, 3),
+      'pose_score': np.array([p['score'] for p in poses], np.float64).reshape(n)}
+  if not sparse_heads:
+    rng = np.random.default_rng(0)
+    for name in sorted(net.logits):
+      flat = net.logits[name].reshape(-1)
+      if flat.numel() > sample:
+        idx = torch.from_numpy(np.sort(rng.integers(0, flat.numel(), sample))).to(flat.device)
+        flat = flat[idx]
+      arrays['head_' + name] = flat.float().cpu().numpy()
+  for name, a in arrays.items():
+    np.save(os.path.join(out_dir, name + '.npy'), a)
 
 
 def cpu_baseline(ckpt, store, args, frames):
@@ -556,6 +584,11 @@ def main():
   clk = torch.zeros((64, 2), dtype=torch.int64, device=dev)
   clk_stream = None      # created after the timed region (an extra stream changes
                          # the stream -> hardware-queue mapping of the pipelines)
+  last_poses = []        # the records of the step collected last (--dump-outputs)
+
+  def collect(p):
+    last_poses[:] = p.collect()[0]
+    return last_poses
 
   def run(first, count, probe=False, use=None, one_at_a_time=False):
     """`count` steps; step i is launched on pipes[i % depth] after the step that
@@ -569,7 +602,7 @@ def main():
     for i in range(first, first + count):
       p = ps[i % d]
       if len(inflight) == d * (1 if one_at_a_time else p.queue):   # the oldest in flight is this pipeline's
-        local += inflight.pop(0).collect()[0]
+        local += collect(inflight.pop(0))
       imgs, tg, idx = pool[i % n_pool]
       p.launch(imgs, Ks, tg, image_ids=idx, seed=i, after_net=planter(i % n_pool))
       inflight.append(p)
@@ -578,7 +611,7 @@ def main():
             ctypes.c_void_p(clk[i % clk.shape[0]].data_ptr()), 200,
             ctypes.c_void_p(clk_stream.cuda_stream)), 'clock_probe')
     while inflight:
-      local += inflight.pop(0).collect()[0]
+      local += collect(inflight.pop(0))
     # rank-independent record capacity: every target object of every image of the
     # `count` steps, two instances each
     return edist.gather_poses(local, max(1, count * B * args.objs_per_image * 2 *
@@ -612,9 +645,12 @@ def main():
   n_poses /= max(world, 1)
   repeats = len(region_s)
   elapsed = sum(region_s) / repeats           # seconds per region of --steps steps
+  last_pipe = pipes[(args.warmup + repeats * args.steps - 1) % depth]
+  if args.dump_outputs and rank == 0:
+    dump_outputs(args.dump_outputs, last_poses, last_pipe.net, args.sparse_heads)
 
   # correspondence statistics of the last step (work actually done by corr/RANSAC)
-  totals = pipes[(args.warmup + repeats * args.steps - 1) % depth].last_totals
+  totals = last_pipe.last_totals
   images = args.steps * B * world
   value = images / elapsed
   result = {

@@ -39,7 +39,7 @@ def _pipeline_stream(dev, instance):
   """The HIP stream of pipeline number `instance` on a device: created once per process and
   handed out again when a pipeline with that number is built anew. Streams land on the
   runtime's hardware queues in creation order: the first four a process creates get queues of
-  their own (GPU_MAX_HW_QUEUES=8), a second set of four ran 0.29 ms per step slower (2.06 ->
+  their own (eight hardware queues per process in that measurement), a second set of four ran 0.29 ms per step slower (2.06 ->
   2.36 ms; some of them share a queue), a third set as fast as the first
   (profiles/r06/stream_sets_and_hw_queues.txt). A process that rebuilds its pipelines therefore
   keeps the streams it had."""

@@ -115,7 +115,7 @@ def test_pipeline_never_clamps_instance_counts_silently():
   assert all(p['R'].shape == (3, 3) and p['t'].shape == (3, 1) for p in poses)
 
 
-def test_a_timed_out_hand_off_is_reported_not_hidden(tmp_path):
+def test_a_timed_out_hand_off_is_reported_not_hidden(tmp_path, gpu_children):
   """The refits of a slot are summed by four workgroups that meet in global memory; a
   workgroup that waits too long for its siblings gives up (bounded spin). With the bound
   set to ZERO polls (EPOS_FIT_SPIN_MAX=0, read once per process: a subprocess) every

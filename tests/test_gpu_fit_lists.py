@@ -40,7 +40,7 @@ np.savez(sys.argv[1], **out)
 '''
 
 
-def test_neighbour_lists_equal_window_scans(tmp_path):
+def test_neighbour_lists_equal_window_scans(tmp_path, gpu_children):
   """Five builds of the same labelling: window scans with the candidates in scalar registers
   followed by delta sweeps over the flipped candidates (the default), full scans every sweep
   (EPOS_FIT_DELTA=0), the LDS-staged scans they replaced (EPOS_FIT_SCAN=0), with and without

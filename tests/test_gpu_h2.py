@@ -766,7 +766,7 @@ def test_block_sums_need_the_fp16_pair_kernel(lib):
     _check(lib.epos_pointwise_conv_f32(ctypes.byref(a), None))
 
 
-def test_first_fp16_pair_launch_inside_a_capture_is_refused_not_broken(tmp_path):
+def test_first_fp16_pair_launch_inside_a_capture_is_refused_not_broken(tmp_path, gpu_children):
   """The fp16-pair GEMM allocates its 64-byte zero chunk (and, without a caller-provided
   absmax slot, its slot ring) on the first launch of a device. Inside a stream capture
   that allocation / legacy-stream memset would invalidate the capture: the launch is REFUSED

@@ -518,7 +518,7 @@ def test_clock_probe_reports_a_plausible_core_clock(lib):
 @pytest.mark.parametrize('env', [{'EPOS_GEMM_SPLIT': '0'}, {'EPOS_GEMM_SPLIT_ACC': '1'},
                                  {'EPOS_GEMM_SPLIT_ROWS': '64'},
                                  {'EPOS_GEMM_SPLIT_ROWS': '128'}])
-def test_pointwise_gemm_split_switches(env):
+def test_pointwise_gemm_split_switches(env, gpu_children):
   """The process-wide switches of the split-operand GEMM (read once per process, hence a
   subprocess each): fp32-MFMA kernel instead, one accumulator, forced tile height -- all
   must give the same result within the fp32 tolerance."""

@@ -122,7 +122,7 @@ def test_maxpool_subsample_add_relu():
   assert np.array_equal(Yt.cpu().numpy(), np.maximum(a + b, 0))
 
 
-def test_split_gemm_network_is_not_less_accurate_than_fp32_mfma(tmp_path):
+def test_split_gemm_network_is_not_less_accurate_than_fp32_mfma(tmp_path, gpu_children):
   """The whole network through the split-operand GEMM (default) and through the
   fp32-MFMA GEMM (EPOS_GEMM_SPLIT=0, read once per process: two subprocesses), both
   against the oracle carried out in fp64 on the same fp32 weights: the split path's

@@ -172,7 +172,7 @@ def test_concurrent_pipelines_are_deterministic():
           assert np.array_equal(a['R'], b['R']) and np.array_equal(a['t'], b['t'])
 
 
-def test_bench_multi_rank_flow_on_one_gpu():
+def test_bench_multi_rank_flow_on_one_gpu(gpu_children):
   """bench.py under torchrun with two ranks mapped onto the one GPU of the test box
   (EPOS_FORCE_DEVICE=0) and gloo for the pose-record all_gather / barriers
   (EPOS_DIST_BACKEND=gloo: RCCL refuses two ranks on one device): the N > 1 code path

@@ -136,7 +136,7 @@ dist.destroy_process_group()
 '''
 
 
-def test_two_rank_gloo_gather(tmp_path):
+def test_two_rank_gloo_gather(tmp_path, gpu_children):
   script = tmp_path / 'worker.py'
   script.write_text(WORKER % {'root': ROOT})
   env = dict(os.environ, MASTER_ADDR='127.0.0.1')

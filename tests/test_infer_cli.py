@@ -103,7 +103,7 @@ def test_fragments_pkl_roundtrip(tmp_path):
 
 
 @pytest.mark.gpu
-def test_infer_synthetic_end_to_end(tmp_path):
+def test_infer_synthetic_end_to_end(tmp_path, gpu_children):
   env = dict(os.environ, TF_MODELS_PATH=str(tmp_path))
   (tmp_path / 'toy').mkdir()
   (tmp_path / 'toy' / 'params.yml').write_text('infer_crop_size: "128,96"\n')
@@ -121,7 +121,7 @@ def test_infer_synthetic_end_to_end(tmp_path):
 
 
 @pytest.mark.gpu
-def test_infer_operator_path_with_max_correspondences(tmp_path):
+def test_infer_operator_path_with_max_correspondences(tmp_path, gpu_children):
   env = dict(os.environ, TF_MODELS_PATH=str(tmp_path))
   (tmp_path / 'toy').mkdir()
   (tmp_path / 'toy' / 'params.yml').write_text('infer_crop_size: "128,96"\n')
@@ -135,7 +135,7 @@ def test_infer_operator_path_with_max_correspondences(tmp_path):
 
 
 @pytest.mark.gpu
-def test_infer_opencv_ransac_method_gives_one_unscored_pose_per_object(tmp_path):
+def test_infer_opencv_ransac_method_gives_one_unscored_pose_per_object(tmp_path, gpu_children):
   """--fitting_method=opencv_ransac (infer.py:505-528): at most one pose per
   (image, object), score 0.0. PARITY UNPINNED: cv2 is not installable; the model
   comes from this build's P3P-RANSAC."""
@@ -157,7 +157,7 @@ def test_infer_opencv_ransac_method_gives_one_unscored_pose_per_object(tmp_path)
 
 
 @pytest.mark.gpu
-def test_infer_pipeline_depth_gives_the_same_poses(tmp_path):
+def test_infer_pipeline_depth_gives_the_same_poses(tmp_path, gpu_children):
   """--pipeline_depth 3 (three batches in flight on their own streams) writes the same
   rows as the serial run, up to the time column."""
   rows = {}
@@ -177,7 +177,7 @@ def test_infer_pipeline_depth_gives_the_same_poses(tmp_path):
 
 
 @pytest.mark.gpu
-def test_infer_from_tfrecord(tmp_path):
+def test_infer_from_tfrecord(tmp_path, gpu_children):
   """--infer_tfrecord_names path: records written with the build's own encoder
   (the reference writes them with TensorFlow, scripts/create_tfrecord.py)."""
   import io
@@ -213,7 +213,7 @@ def test_infer_from_tfrecord(tmp_path):
 
 
 @pytest.mark.gpu
-def test_infer_streaming_default_matches_the_serial_dense_run(tmp_path):
+def test_infer_streaming_default_matches_the_serial_dense_run(tmp_path, gpu_children):
   """The drop-in's default configuration since round 6 -- frames decoded by the prefetcher's
   threads into pinned uint8 buffers, uploaded as bytes and cast on the device, four steps in
   flight, fragment heads evaluated for the target objects only -- writes the same CSV rows as
@@ -262,7 +262,7 @@ def test_infer_streaming_default_matches_the_serial_dense_run(tmp_path):
 
 
 @pytest.mark.gpu
-def test_infer_restores_tf_checkpoint(tmp_path):
+def test_infer_restores_tf_checkpoint(tmp_path, gpu_children):
   """<model>/train/model.ckpt-N.{index,data-*} is restored by variable name
   (infer.py:670-683) through the TensorFlow-free TensorBundle reader."""
   from epos_amd import tf_checkpoint, weights
@@ -325,7 +325,7 @@ def test_fragments_from_bop_ply_models(tmp_path, monkeypatch):
 
 
 @pytest.mark.gpu
-def test_infer_two_ranks_with_an_odd_frame_count(tmp_path):
+def test_infer_two_ranks_with_an_odd_frame_count(tmp_path, gpu_children):
   """Three frames over two ranks (shards of 2 and 1): the pose gather must not depend on
   the rank-local shard size (two torchrun ranks on the one GPU, gloo for the gather)."""
   import socket
@@ -359,12 +359,13 @@ def test_infer_two_ranks_with_an_odd_frame_count(tmp_path):
 
 
 @pytest.mark.gpu
-def test_infer_eight_ranks_cover_32_frames_exactly_once(tmp_path):
-  """The C3 arrangement as a dry run on the one-GPU box: 32 frames over EIGHT torchrun
-  ranks (4 per rank, gloo for the gather, every rank on device 0). Every frame must be
-  processed by exactly one rank and the merged BOP CSV must equal the single-rank CSV row
-  for row (poses bit for bit) -- what tools/run_scale.sh will exercise over RCCL the day an
-  8-GPU node runs it."""
+def test_infer_three_ranks_cover_32_frames_exactly_once(tmp_path, gpu_children):
+  """The multi-rank arrangement of C3 as a dry run on one GPU: 32 frames over THREE torchrun
+  ranks (shards of 11 / 11 / 10 frames, batches of 4: every rank ends on a partial batch;
+  gloo for the gather, every rank on device 0). Three ranks beside the test workers keep the
+  processes that hold the GPU at six or fewer. Every frame must be processed by exactly one
+  rank and the merged BOP CSV must equal the single-rank CSV row for row (poses bit for
+  bit) -- what tools/run_scale.sh will exercise over RCCL the day an 8-GPU node runs it."""
   import socket
   with socket.socket() as sck:
     sck.bind(('127.0.0.1', 0))
@@ -377,15 +378,15 @@ def test_infer_eight_ranks_cover_32_frames_exactly_once(tmp_path):
             '--num_objs', '3', '--batch', '4']
   out = subprocess.run(
       [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1',
-       '--nproc-per-node', '8', '--master-addr', '127.0.0.1', '--master-port',
-       str(port)] + common + ['--infer_name', 'eight'],
+       '--nproc-per-node', '3', '--master-addr', '127.0.0.1', '--master-port',
+       str(port)] + common + ['--infer_name', 'three'],
       env=env, capture_output=True, text=True, timeout=1500)
   assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
   one = subprocess.run([sys.executable] + common + ['--infer_name', 'one'],
                        env=env, capture_output=True, text=True, timeout=900)
   assert one.returncode == 0, one.stdout[-2000:] + one.stderr[-2000:]
   from epos_amd import bop_io
-  a = bop_io.load_bop_results(str(tmp_path / 'toy' / 'infer' / 'estimated-poses_eight.csv'))
+  a = bop_io.load_bop_results(str(tmp_path / 'toy' / 'infer' / 'estimated-poses_three.csv'))
   b = bop_io.load_bop_results(str(tmp_path / 'toy' / 'infer' / 'estimated-poses_one.csv'))
   key = lambda r: (r['im_id'], r['obj_id'], r['score'])      # noqa: E731
   assert len(a) == len(b) and len(a) > 0
@@ -399,25 +400,19 @@ def test_infer_eight_ranks_cover_32_frames_exactly_once(tmp_path):
   assert max(seen.values()) == 1                            # no frame fitted twice
 
 
-def test_entry_points_ask_for_one_hardware_queue_per_pipeline():
-  """infer.py and bench.py put GPU_MAX_HW_QUEUES into the environment BEFORE torch (and with
-  it the HIP runtime) is imported: with the runtime's default of four queues two of the four
-  pipelines share one and serialise against each other (profiles/r06/infer_diag_hw_queues.txt:
-  infer.py ran at 0.81 of bench.py until it did this too)."""
+def test_entry_points_leave_the_hardware_queue_count_to_the_environment():
+  """infer.py, bench.py and the package never set GPU_MAX_HW_QUEUES: a card's hardware queue
+  slots are shared by every process on it, so how many a process may open is the
+  environment's choice. Checked in the sources (no assignment of any kind) and in a fresh
+  interpreter (importing epos_amd does not put the variable into the environment)."""
   import ast
-  for name in ('infer.py', 'bench.py'):
+  for name in ('infer.py', 'bench.py', os.path.join('epos_amd', '__init__.py')):
     tree = ast.parse(open(os.path.join(ROOT, name)).read())
-    set_at = torch_at = None
-    for node in tree.body:
-      src = ast.dump(node)
-      if set_at is None and 'GPU_MAX_HW_QUEUES' in src and 'setdefault' in src:
-        set_at = node.lineno
-      if torch_at is None and isinstance(node, (ast.Import, ast.ImportFrom)) and any(
-          a.name.split('.')[0] == 'torch' for a in node.names):
-        torch_at = node.lineno
-    assert set_at is not None and torch_at is not None and set_at < torch_at, (name, set_at, torch_at)
+    for node in ast.walk(tree):
+      if isinstance(node, ast.Constant) and node.value == 'GPU_MAX_HW_QUEUES':
+        raise AssertionError('%s:%d names GPU_MAX_HW_QUEUES' % (name, node.lineno))
   out = subprocess.run(
-      [sys.executable, '-c', 'import os, epos_amd; print(os.environ["GPU_MAX_HW_QUEUES"])'],
+      [sys.executable, '-c', 'import os, epos_amd; print(os.environ.get("GPU_MAX_HW_QUEUES"))'],
       capture_output=True, text=True, cwd=ROOT, env={k: v for k, v in os.environ.items()
                                                    if k != 'GPU_MAX_HW_QUEUES'})
-  assert out.stdout.strip() == '8', out.stdout + out.stderr
+  assert out.returncode == 0 and out.stdout.strip() == 'None', out.stdout + out.stderr

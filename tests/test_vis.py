@@ -86,7 +86,7 @@ def test_tfrecord_gt_poses_from_quaternions():
 
 
 @pytest.mark.gpu
-def test_infer_vis_end_to_end(tmp_path):
+def test_infer_vis_end_to_end(tmp_path, gpu_children):
   env = dict(os.environ, TF_MODELS_PATH=str(tmp_path))
   (tmp_path / 'toy').mkdir()
   (tmp_path / 'toy' / 'params.yml').write_text('infer_crop_size: "128,96"\n')

@@ -1,5 +1,5 @@
 import os, sys
-sys.path.insert(0, '/root/repo' if os.path.isdir('/root/repo/epos_amd') else os.getcwd())
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
 from epos_amd import model, synthetic, weights
 O, F = 21, 64

@@ -1,6 +1,5 @@
 import os, sys, time
-os.environ.setdefault('GPU_MAX_HW_QUEUES', '8')
-sys.path.insert(0, '/root/repo')
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
 from epos_amd import pipeline, synthetic, weights, model
 O, F = 21, 64

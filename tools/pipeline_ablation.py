@@ -6,7 +6,6 @@ capture (results are garbage by construction; only the times mean something).
     python tools/pipeline_ablation.py            # full, -dw, -gemm, -fit ...
 """
 import os, sys, time
-os.environ.setdefault('GPU_MAX_HW_QUEUES', '8')
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
 from epos_amd import model, pipeline, synthetic, weights

@@ -6,13 +6,12 @@
 #
 # One rank per device (torchrun, rendezvous on 127.0.0.1), each rank pinned to the CPU cores
 # of its share of the socket(s) (the host side of a step is ~0.3 ms of Python + one pinned
-# D2H copy per step: ranks that migrate between NUMA nodes lose 5-10 %), eight HIP hardware
-# queues per process (one per pipeline stream, bench.py sets it too), dmabuf IPC for RCCL.
+# D2H copy per step: ranks that migrate between NUMA nodes lose 5-10 %), dmabuf IPC for RCCL.
 # Checks per N: the line's n_gpus, config.dist_backend == nccl, config.rccl_ranks_seen == N;
 # prints the aggregate images/s, the per-rank figure and the efficiency vs N = 1.
 set -euo pipefail
 cd "$(dirname "$0")/.."
-export HSA_ENABLE_IPC_MODE_LEGACY=0 GPU_MAX_HW_QUEUES=8
+export HSA_ENABLE_IPC_MODE_LEGACY=0
 ndev=$(python -c 'import torch; print(torch.cuda.device_count())')
 [ "$ndev" -ge 1 ] || { echo "no HIP device"; exit 1; }
 ns=("$@"); [ ${#ns[@]} -gt 0 ] || ns=(1 2 4 8)
