@@ -70,7 +70,8 @@ class CorrExtractor(object):
     self.slots = torch.zeros(S, 2, dtype=torch.int32, device=d)
     self.px_off = torch.empty(S, P, dtype=torch.int32, device=d)
     self.corr_off = torch.empty(S, P, dtype=torch.int32, device=d)
-    self.frag_mask = torch.empty(S, P, dtype=torch.int64, device=d)
+    # kept-fragment bitmask: ceil(F / 64) words per pixel (include/epos_hip.h)
+    self.frag_mask = torch.empty(S, P, (num_frags + 63) // 64, dtype=torch.int64, device=d)
     self.totals = torch.zeros(S, 2, dtype=torch.int32, device=d)
     self.slot_base = torch.zeros(S + 1, dtype=torch.int64, device=d)
     self.overflow = torch.zeros(1, dtype=torch.int32, device=d)

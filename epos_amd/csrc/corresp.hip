@@ -6,9 +6,11 @@
 // (pixel, kept fragment) in raster order, then ascending fragment id
 // (np.nonzero order, corresp.py:52,67). Here that is a stable stream compaction
 // in three launches, all integer-exact:
-//   1. corr_mask:  one wave per 64 pixels; lane = pixel for the object-confidence
+//   1. corr_mask:  one wave per 16 pixels; lane = pixel for the object-confidence
 //                  test (ballot), then lane = fragment (F <= 64) for each masked
 //                  pixel: wave max, threshold, ballot -> 64-bit kept-fragment mask.
+//                  F up to 256: lane l takes fragments l + 64k, one ballot -> one
+//                  mask word per 64 fragments (corr_mask_wide_kernel<NW>).
 //   2. corr_scan:  per slot exclusive scans (masked-pixel index, first row).
 //   3. corr_fill:  lane = fragment; row = slot base + pixel base + rank of the
 //                  fragment inside the mask (popcount of lower bits).
@@ -206,6 +208,136 @@ __global__ __launch_bounds__(256) void corr_fill_kernel(
 }
 
 // --------------------------------------------------------------------------
+// 64 < F <= 256: NW = ceil(F / 64) words per pixel, frag_mask u64 [S, P, NW]. Word k
+// holds fragments 64k..64k+63 (bit = fragment - 64k). The same three launches; the
+// per-fragment part gives lane l the fragments l + 64k, k < NW (coalesced 256-byte rows).
+// --------------------------------------------------------------------------
+template <int NW>
+__global__ __launch_bounds__(256) void corr_mask_wide_kernel(
+    const float* __restrict__ obj_confs, const float* __restrict__ frag_confs,
+    const EposCorrSlot* __restrict__ slots, int P, int O, int F, float tau_a,
+    float tau_b, int32_t* px_flag, int32_t* corr_cnt, uint64_t* frag_mask) {
+  const int s = blockIdx.y;
+  const int lane = threadIdx.x & 63;
+  const int p0 = (blockIdx.x * 4 + (threadIdx.x >> 6)) * CORR_PPW;
+  if (p0 >= P) return;                       // wave-uniform
+  const int img = slots[s].image, obj = slots[s].obj_id;
+  const int p = p0 + lane;
+  const bool mine = lane < CORR_PPW && p < P;   // this lane owns a pixel
+  const int64_t pix0 = static_cast<int64_t>(img) * P;
+  bool masked = false;
+  if (mine) masked = obj_confs[(pix0 + p) * (O + 1) + obj] > tau_a;  // corresp.py:46-47
+  uint64_t todo = __ballot(masked);
+  uint64_t mybits[NW];
+#pragma unroll
+  for (int k = 0; k < NW; ++k) mybits[k] = 0;
+  while (todo) {                             // wave-uniform loop over masked pixels
+    const int j = __ffsll(static_cast<long long>(todo)) - 1;
+    todo &= todo - 1;
+    const float* fc = frag_confs + ((pix0 + p0 + j) * O + (obj - 1)) * F;
+    float v[NW];
+#pragma unroll
+    for (int k = 0; k < NW; ++k) v[k] = lane + 64 * k < F ? fc[lane + 64 * k] : -INFINITY;
+    float m = v[0];
+#pragma unroll
+    for (int k = 1; k < NW; ++k) m = fmaxf(m, v[k]);
+    m = wave_max64(m);                       // corresp.py:63 (max is order-independent)
+    const float thr = m * tau_b;             // f32 * f32 (numpy weak-scalar rule)
+#pragma unroll
+    for (int k = 0; k < NW; ++k) {
+      const uint64_t bits = __ballot(lane + 64 * k < F && v[k] > thr);   // strict >
+      if (lane == j) mybits[k] = bits;
+    }
+  }
+  if (mine) {
+    const int64_t o = static_cast<int64_t>(s) * P + p;
+    int cnt = 0;
+#pragma unroll
+    for (int k = 0; k < NW; ++k) {
+      cnt += __popcll(mybits[k]);
+      frag_mask[o * NW + k] = mybits[k];
+    }
+    px_flag[o] = masked ? 1 : 0;
+    corr_cnt[o] = cnt;
+  }
+}
+
+template <int NW>
+__global__ __launch_bounds__(256) void corr_fill_wide_kernel(
+    const float* __restrict__ obj_confs, const float* __restrict__ frag_confs,
+    const float* __restrict__ frag_coords, const double* __restrict__ centers,
+    const double* __restrict__ sizes, const EposCorrSlot* __restrict__ slots,
+    int P, int W, int O, int F, double inv_scale, const int32_t* px_off,
+    const int32_t* corr_off, const uint64_t* frag_mask, const int64_t* slot_base,
+    int64_t capacity, EposCorrOut out, int32_t* overflow) {
+  const int s = blockIdx.y;
+  const int lane = threadIdx.x & 63;
+  const int p0 = (blockIdx.x * 4 + (threadIdx.x >> 6)) * CORR_PPW;
+  if (p0 >= P) return;
+  const int img = slots[s].image, obj = slots[s].obj_id;
+  const int p = p0 + lane;
+  const int64_t pix0 = static_cast<int64_t>(img) * P;
+  uint64_t mbits[NW];
+  uint64_t any = 0;
+  int32_t pxo = 0, co = 0;
+#pragma unroll
+  for (int k = 0; k < NW; ++k) mbits[k] = 0;
+  if (lane < CORR_PPW && p < P) {
+    const int64_t o = static_cast<int64_t>(s) * P + p;
+#pragma unroll
+    for (int k = 0; k < NW; ++k) { mbits[k] = frag_mask[o * NW + k]; any |= mbits[k]; }
+    pxo = px_off[o]; co = corr_off[o];
+  }
+  uint64_t todo = __ballot(any != 0);
+  const int64_t base_s = slot_base[s];
+  const double* cen = centers + static_cast<int64_t>(obj - 1) * F * 3;
+  const double* siz = sizes + static_cast<int64_t>(obj - 1) * F;
+  while (todo) {
+    const int j = __ffsll(static_cast<long long>(todo)) - 1;
+    todo &= todo - 1;
+    const int32_t px_id = __shfl(pxo, j, 64);
+    const int pj = p0 + j;
+    const int y = pj / W, x = pj - y * W;
+    const float conf_obj = obj_confs[(pix0 + pj) * (O + 1) + obj];
+    // rank of fragment lane + 64k = kept fragments of the lower words + those below
+    // it in its own word (ascending fragment id, np.nonzero order, corresp.py:63-67)
+    int64_t row0 = base_s + __shfl(co, j, 64);
+#pragma unroll
+    for (int k = 0; k < NW; ++k) {
+      const uint64_t bits = __shfl(mbits[k], j, 64);
+      if ((bits >> lane) & 1ull) {
+        const int64_t row = row0 + __popcll(bits & ((1ull << lane) - 1ull));
+        const int f = lane + 64 * k;
+        if (row >= capacity) {
+          *overflow = 1;
+        } else {
+        const int64_t fidx = ((pix0 + pj) * O + (obj - 1)) * F + f;
+        const float conf_frag = frag_confs[fidx];
+        out.px_id[row] = px_id;
+        out.frag_id[row] = f;
+        // misc.py:26: scale * (idx + 0.5), x first (corresp.py:55-57).
+        out.coord_2d[2 * row + 0] = inv_scale * (static_cast<double>(x) + 0.5);
+        out.coord_2d[2 * row + 1] = inv_scale * (static_cast<double>(y) + 0.5);
+        const double sz = siz[f];
+#pragma unroll
+        for (int d = 0; d < 3; ++d) {
+          // corresp.py:76-78: the in-place f32 `*=` rounds the f64 product to f32
+          // before the f64 add.
+          const float local = static_cast<float>(
+              static_cast<double>(frag_coords[fidx * 3 + d]) * sz);
+          out.coord_3d[3 * row + d] = cen[f * 3 + d] + static_cast<double>(local);
+        }
+        out.conf_obj[row] = conf_obj;
+        out.conf_frag[row] = conf_frag;
+        out.conf[row] = conf_obj * conf_frag;                  // corresp.py:82-84
+        }
+      }
+      row0 += __popcll(bits);
+    }
+  }
+}
+
+// --------------------------------------------------------------------------
 // project_to_surface (corresp.py:87-88 -> datagen.py:128-154): closest point of the
 // object's triangle mesh for every predicted 3D point. The reference asks libigl's AABB
 // tree; here one wavefront per query point sweeps ALL faces (lane = face modulo 64:
@@ -320,15 +452,30 @@ extern "C" int epos_corr_count(const float* obj_confs, const float* frag_confs,
                                int32_t* totals, void* stream) {
   EPOS_REQUIRE(obj_confs && frag_confs && slots && px_off && corr_off &&
                frag_mask && totals, "null pointer");
-  EPOS_REQUIRE(F >= 1 && F <= 64, "num_frags must be in [1, 64]");
+  EPOS_REQUIRE(F >= 1 && F <= 256, "num_frags must be in [1, 256]");
   EPOS_REQUIRE(B > 0 && P > 0 && O > 0, "empty problem");
   if (S == 0) return EPOS_OK;
   hipStream_t st = static_cast<hipStream_t>(stream);
   dim3 grid(static_cast<unsigned>(ceil_div(P, 4 * CORR_PPW)), S);
-  hipLaunchKernelGGL(corr_mask_kernel, grid, dim3(256), 0, st, obj_confs,
-                     frag_confs, slots, P, O, F, min_obj_conf, min_frag_rel_conf,
-                     px_off, corr_off, frag_mask);
-  int rc = launch_status("corr_mask_kernel");
+  int rc;
+  if (F <= 64) {
+    hipLaunchKernelGGL(corr_mask_kernel, grid, dim3(256), 0, st, obj_confs,
+                       frag_confs, slots, P, O, F, min_obj_conf, min_frag_rel_conf,
+                       px_off, corr_off, frag_mask);
+    rc = launch_status("corr_mask_kernel");
+  } else {
+#define EPOS_CORR_MASK_WIDE(NW)                                                        \
+    hipLaunchKernelGGL(corr_mask_wide_kernel<NW>, grid, dim3(256), 0, st, obj_confs,   \
+                       frag_confs, slots, P, O, F, min_obj_conf, min_frag_rel_conf,    \
+                       px_off, corr_off, frag_mask)
+    switch ((F + 63) / 64) {
+      case 2: EPOS_CORR_MASK_WIDE(2); break;
+      case 3: EPOS_CORR_MASK_WIDE(3); break;
+      default: EPOS_CORR_MASK_WIDE(4); break;
+    }
+#undef EPOS_CORR_MASK_WIDE
+    rc = launch_status("corr_mask_wide_kernel");
+  }
   if (rc) return rc;
   if (P % 4 == 0 && (reinterpret_cast<uintptr_t>(px_off) & 15) == 0 &&
       (reinterpret_cast<uintptr_t>(corr_off) & 15) == 0)
@@ -360,14 +507,28 @@ extern "C" int epos_corr_fill(const float* obj_confs, const float* frag_confs,
   EPOS_REQUIRE(obj_confs && frag_confs && frag_coords && frag_centers &&
                frag_sizes && slots && px_off && corr_off && frag_mask &&
                slot_base && out && overflow, "null pointer");
-  EPOS_REQUIRE(F >= 1 && F <= 64, "num_frags must be in [1, 64]");
+  EPOS_REQUIRE(F >= 1 && F <= 256, "num_frags must be in [1, 256]");
   EPOS_REQUIRE(W > 0 && P % W == 0, "P must be a multiple of W");
   if (S == 0) return EPOS_OK;
   dim3 grid(static_cast<unsigned>(ceil_div(P, 4 * CORR_PPW)), S);
-  hipLaunchKernelGGL(corr_fill_kernel, grid, dim3(256), 0,
-                     static_cast<hipStream_t>(stream), obj_confs, frag_confs,
-                     frag_coords, frag_centers, frag_sizes, slots, P, W, O, F,
-                     inv_scale, px_off, corr_off, frag_mask, slot_base, capacity,
-                     *out, overflow);
-  return launch_status("corr_fill_kernel");
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (F <= 64) {
+    hipLaunchKernelGGL(corr_fill_kernel, grid, dim3(256), 0, st, obj_confs, frag_confs,
+                       frag_coords, frag_centers, frag_sizes, slots, P, W, O, F,
+                       inv_scale, px_off, corr_off, frag_mask, slot_base, capacity,
+                       *out, overflow);
+    return launch_status("corr_fill_kernel");
+  }
+#define EPOS_CORR_FILL_WIDE(NW)                                                        \
+  hipLaunchKernelGGL(corr_fill_wide_kernel<NW>, grid, dim3(256), 0, st, obj_confs,     \
+                     frag_confs, frag_coords, frag_centers, frag_sizes, slots, P, W, O, \
+                     F, inv_scale, px_off, corr_off, frag_mask, slot_base, capacity,   \
+                     *out, overflow)
+  switch ((F + 63) / 64) {
+    case 2: EPOS_CORR_FILL_WIDE(2); break;
+    case 3: EPOS_CORR_FILL_WIDE(3); break;
+    default: EPOS_CORR_FILL_WIDE(4); break;
+  }
+#undef EPOS_CORR_FILL_WIDE
+  return launch_status("corr_fill_wide_kernel");
 }

@@ -82,5 +82,20 @@ __device__ __forceinline__ float4 softmax64_lane16(float4 v) {
   return make_float4(v.x / s, v.y / s, v.z / s, v.w / s);
 }
 
+// Softmax over a group of 256 values held by the 64 lanes of a wave x float4 (lane l holds
+// values 4l..4l+3): max / sum by in-lane pairs first, then the 32-16-8-4-2-1 xor butterfly
+// over the wave. ONE definition for softmax_groups256_kernel and softmax_slots256_kernel
+// (layers.hip), so dense and sparse-head runs give the same bits at F = 256.
+__device__ __forceinline__ float4 softmax256_lane64(float4 v) {
+  float m = fmaxf(fmaxf(v.x, v.y), fmaxf(v.z, v.w));
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+  v.x = expf(v.x - m); v.y = expf(v.y - m); v.z = expf(v.z - m); v.w = expf(v.w - m);
+  float s = (v.x + v.y) + (v.z + v.w);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+  return make_float4(v.x / s, v.y / s, v.z / s, v.w / s);
+}
+
 }  // namespace
 }  // namespace epos

@@ -67,6 +67,8 @@ class EposNet(object):
     self.model_variant = model_variant
     if encoder_output_stride != 8 or decoder_output_stride != 4:
       raise ValueError('Only encoder OS 8 / decoder OS 4 (common.py:127-135).')
+    if not 1 <= num_frags <= 256:        # the fragment softmax / correspondence kernels
+      raise ValueError('num_frags must be in [1, 256] (got %d).' % num_frags)
     # dry_run: build the plan's STRUCTURE only (tests/test_graph_trace.py) -- buffers are
     # shape-only 'meta' tensors, no weight is packed, nothing can be launched.
     self.dry_run = bool(dry_run)
@@ -888,8 +890,6 @@ class EposNet(object):
     frag = self.logits[W.PRED_FRAG_CONF]
     self.obj_label = self._empty(B, dh, dw_, dtype=torch.int64)
     O, F = self.num_objs, self.num_frags
-    if F > 64:
-      raise ValueError('num_frags > 64 is not supported by the HIP softmax.')
 
     def run_softmax_obj(stream):
       _lib.check(lib.epos_softmax_groups_f32(_ptr(obj), m_dec, O + 1, stream),

@@ -60,7 +60,11 @@ class EposPipeline(object):
     """on_excess: what launch() does with a frame that asks for more instances of an object
     than `max_instances` (localization): 'raise' (default: EposError BEFORE anything of that
     batch is enqueued -- batches already in flight on other pipelines are unaffected and can
-    still be collected) or 'clamp' (fit `max_instances` of them and warn once)."""
+    still be collected) or 'clamp' (fit `max_instances` of them and warn once).
+    capacity: correspondence rows per batch, over all slots, at up to 64 fragments per object.
+    A masked pixel yields up to F rows, so the correspondence and fitting buffers are sized for
+    `capacity * ceil(num_frags / 64)` rows (self.capacity); for num_frags <= 64 that is
+    `capacity` itself."""
     if on_excess not in ('raise', 'clamp'):
       raise ValueError("on_excess must be 'raise' or 'clamp'")
     # queue: how many batches launch() accepts before a collect() (round 6). With 2 the
@@ -109,6 +113,8 @@ class EposPipeline(object):
     self.last_clamped, self.clamped_count = [], 0
     centers, sizes = _corresp.pack_model_store(model_store, num_objs, num_frags)
     self.obj_ids = list(model_store.dp_model['obj_ids'])
+    capacity = capacity * max(1, (num_frags + 63) // 64)
+    self.capacity = capacity
     self.corr = _corresp.CorrExtractor(
         batch, self.net.out_h, self.net.out_w, num_objs, num_frags, centers,
         sizes, self.max_slots, capacity, device)

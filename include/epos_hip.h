@@ -330,7 +330,8 @@ int epos_scatter_blocks_f32(float* dst, const int64_t* offsets, const float* src
 int epos_u8_to_f32(const uint8_t* X, float* Y, int64_t n, void* stream);
 
 /* In-place softmax over groups of `G` consecutive floats (model.py:677-678):
- * X holds n_groups * G floats, group g at X + g*G (G <= 64). */
+ * X holds n_groups * G floats, group g at X + g*G, 1 <= G <= 256 (the object head's
+ * O + 1 classes, or the F fragments of one object); G > 256: EPOS_E_INVALID. */
 int epos_softmax_groups_f32(float* X, int64_t n_groups, int G, void* stream);
 
 /* Per-pixel argmax over C channels -> int64 label (model.py:683); first maximum
@@ -350,17 +351,20 @@ typedef struct EposCorrSlot {
 } EposCorrSlot;
 
 /* Fragment-confidence softmax (model.py:678) for the given slots only: X is the
- * dense frag_conf buffer f32 [B, P, O, F]; slots [device]. Used by the sparse-head
- * mode, where the fragment heads exist only for the target objects. */
+ * dense frag_conf buffer f32 [B, P, O, F], 1 <= F <= 256 (F > 256: EPOS_E_INVALID);
+ * slots [device]. Used by the sparse-head mode, where the fragment heads exist only for
+ * the target objects. Same bits as epos_softmax_groups_f32 on those groups. */
 int epos_softmax_slots_f32(float* X, const EposCorrSlot* slots, int S, int P,
                            int O, int F, void* stream);
 
 /* Pass 1+2: per slot, count masked pixels and correspondences and compute the
  * raster-order exclusive offsets. All buffers [device].
  *   obj_confs  f32 [B, P, O+1]      (P = h*w pixels of the head map)
- *   frag_confs f32 [B, P, O, F]     (F == 64)
+ *   frag_confs f32 [B, P, O, F]     (1 <= F <= 256; F > 256: EPOS_E_INVALID)
  *   px_off, corr_off  i32 [S, P]    scratch/outputs (exclusive scans)
- *   frag_mask  u64 [S, P]           kept-fragment bitmask per pixel (0 = not masked)
+ *   frag_mask  u64 [S, P, NW]       kept-fragment bitmask per pixel (all 0 = not masked),
+ *                                   NW = ceil(F / 64) words; word k holds fragments
+ *                                   64k..64k+63, bit f - 64k. For F <= 64: [S, P].
  *   totals     i32 [S, 2]           {masked pixels, correspondences} per slot
  */
 int epos_corr_count(const float* obj_confs, const float* frag_confs,
@@ -369,7 +373,8 @@ int epos_corr_count(const float* obj_confs, const float* frag_confs,
                     int32_t* px_off, int32_t* corr_off, uint64_t* frag_mask,
                     int32_t* totals, void* stream);
 
-/* Pass 3: fills the correspondence arrays. slot_base i64[S] [device] gives each
+/* Pass 3: fills the correspondence arrays (same F range and frag_mask layout as
+ * epos_corr_count; rows of a pixel in ascending fragment id). slot_base i64[S] [device] gives each
  * slot's first row in the pooled output arrays (exclusive scan of totals[:,1],
  * computed by epos_corr_slot_bases or by the host); `capacity` rows are
  * available; rows beyond it are not written and *overflow is set to 1.
