@@ -89,6 +89,22 @@ class Im2colArgs(ctypes.Structure):
   ]
 
 
+PREPROCESS_NONE, PREPROCESS_UNIT_RANGE, PREPROCESS_SUB_MEAN = 0, 1, 2   # EPOS_PREPROCESS_*
+
+
+class Im2colKArgs(ctypes.Structure):
+  _fields_ = [
+      ('X', vp), ('ldx', ctypes.c_int64),
+      ('col', vp), ('ldcol', ctypes.c_int64),
+      ('B', ctypes.c_int32), ('Hi', ctypes.c_int32), ('Wi', ctypes.c_int32),
+      ('Ho', ctypes.c_int32), ('Wo', ctypes.c_int32), ('C', ctypes.c_int32),
+      ('k', ctypes.c_int32), ('stride', ctypes.c_int32), ('rate', ctypes.c_int32),
+      ('pad', ctypes.c_int32), ('preprocess', ctypes.c_int32),
+      ('mean_rgb', ctypes.c_float * 3),
+      ('amax_clear', vp), ('amax_words', ctypes.c_int64),
+  ]
+
+
 class CorrSlot(ctypes.Structure):
   _fields_ = [('image', ctypes.c_int32), ('obj_id', ctypes.c_int32)]
 
@@ -155,6 +171,7 @@ SYMBOLS = {
     'epos_separable_conv_f32': (ctypes.c_int, [ctypes.POINTER(SepConvArgs), vp]),
     'epos_set_h2_narrow_tile_limit': (ctypes.c_int, [ctypes.c_int]),
     'epos_im2col3x3_f32': (ctypes.c_int, [ctypes.POINTER(Im2colArgs), vp]),
+    'epos_im2col_f32': (ctypes.c_int, [ctypes.POINTER(Im2colKArgs), vp]),
     'epos_global_avg_pool_partial_f32': (ctypes.c_int, [
         vp, ctypes.c_int64, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp]),
     'epos_global_avg_pool_f32': (ctypes.c_int, [

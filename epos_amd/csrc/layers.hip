@@ -409,6 +409,62 @@ __global__ __launch_bounds__(256) void im2col3x3_kernel(EposIm2colArgs p,
 }
 
 // --------------------------------------------------------------------------
+// im2col for dense k x k convs with fused preprocessing (EposIm2colKArgs). One thread = four
+// consecutive columns of one row of col: consecutive lanes write consecutive 16-byte pieces
+// of an output image row's ldcol rows (coalesced); the taps are scalar loads of the (cached)
+// input. blockIdx.y walks the output image rows (b, yo), so the per-thread index arithmetic is
+// 32-bit; the column -> (ky, kx, c) split is done once per thread and then stepped.
+// --------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void im2col_k_kernel(EposIm2colKArgs p, int q) {
+  const int r = blockIdx.x * blockDim.x + threadIdx.x;        // (xo, 4-column group) of a row
+  if (p.amax_clear) {                                          // the plan's slot table
+    const int64_t lin = (static_cast<int64_t>(blockIdx.y) * gridDim.x + blockIdx.x) *
+                        blockDim.x + threadIdx.x;
+    if (lin < p.amax_words) p.amax_clear[lin] = 0u;
+  }
+  if (r >= p.Wo * q) return;
+  const int xo = r / q;
+  const int col0 = (r - xo * q) * 4;
+  const int kkc = p.k * p.k * p.C;
+  const int tap0 = col0 / p.C;
+  const int c0 = col0 - tap0 * p.C;
+  const int ky0 = tap0 / p.k;
+  const int kx0 = tap0 - ky0 * p.k;
+  const int x0 = xo * p.stride - p.pad;
+  // the mean as selects, not an indexed array (a dynamic index into the argument struct
+  // would put it in scratch)
+  const float m0 = p.mean_rgb[0], m1 = p.mean_rgb[1], m2 = p.mean_rgb[2];
+  const int rows = p.B * p.Ho;
+  for (int row = blockIdx.y; row < rows; row += gridDim.y) {
+    const int b = row / p.Ho, yo = row - b * p.Ho;              // uniform
+    const int y0 = yo * p.stride - p.pad;
+    const float* xb = p.X + static_cast<int64_t>(b) * p.Hi * p.Wi * p.ldx;
+    int c = c0, ky = ky0, kx = kx0;
+    float v[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      float e = 0.f;
+      const int yi = y0 + ky * p.rate, xi = x0 + kx * p.rate;
+      if (col0 + j < kkc && yi >= 0 && yi < p.Hi && xi >= 0 && xi < p.Wi) {
+        e = xb[(static_cast<int64_t>(yi) * p.Wi + xi) * p.ldx + c];
+        if (p.preprocess == EPOS_PREPROCESS_UNIT_RANGE) {
+          e = (2.0f / 255.0f) * e - 1.0f;                          // feature.py:171-174
+        } else if (p.preprocess == EPOS_PREPROCESS_SUB_MEAN) {     // feature.py:157-165
+          e = e - (c == 0 ? m0 : c == 1 ? m1 : c == 2 ? m2 : 0.f);
+        }
+      }
+      v[j] = e;
+      if (++c == p.C) {
+        c = 0;
+        if (++kx == p.k) { kx = 0; ++ky; }
+      }
+    }
+    const int64_t m = static_cast<int64_t>(row) * p.Wo + xo;
+    st4(p.col + m * p.ldcol + col0, make_float4(v[0], v[1], v[2], v[3]));
+  }
+}
+
+// --------------------------------------------------------------------------
 // Global average pool: block = (image, 64-channel group); 16 float4 lanes x 64
 // row phases; fixed-order LDS reduction (deterministic).
 // --------------------------------------------------------------------------
@@ -883,6 +939,37 @@ extern "C" int epos_im2col3x3_f32(const EposIm2colArgs* a, void* stream) {
   hipLaunchKernelGGL(im2col3x3_kernel, dim3(blocks_for(total, 256)), dim3(256), 0,
                      static_cast<hipStream_t>(stream), *a, total);
   return launch_status("im2col3x3_kernel");
+}
+
+extern "C" int epos_im2col_f32(const EposIm2colKArgs* a, void* stream) {
+  EPOS_REQUIRE(a && a->X && a->col, "null pointer");
+  EPOS_REQUIRE(a->k >= 1 && a->stride >= 1 && a->rate >= 1 && a->pad >= 0 && a->C >= 1,
+               "bad k / stride / rate / pad / C");
+  EPOS_REQUIRE(a->preprocess >= EPOS_PREPROCESS_NONE &&
+               a->preprocess <= EPOS_PREPROCESS_SUB_MEAN, "bad preprocess mode");
+  EPOS_REQUIRE(a->ldx >= a->C, "ldx < C");
+  EPOS_REQUIRE(a->ldcol >= static_cast<int64_t>(a->k) * a->k * a->C, "ldcol too small");
+  EPOS_REQUIRE(a->ldcol % 4 == 0 && reinterpret_cast<uintptr_t>(a->col) % 16 == 0,
+               "col needs ldcol % 4 == 0 and 16-byte alignment");
+  EPOS_REQUIRE(a->B >= 0 && a->Ho >= 0 && a->Wo >= 0 && a->Hi >= 1 && a->Wi >= 1,
+               "bad shape");
+  EPOS_REQUIRE(static_cast<int64_t>(a->Wo) * (a->ldcol / 4) < (1ll << 31) &&
+               static_cast<int64_t>(a->B) * a->Ho < (1ll << 31), "shape too large");
+  const int q = static_cast<int>(a->ldcol / 4);
+  const int rows = a->B * a->Ho;
+  const int64_t per_row = static_cast<int64_t>(a->Wo) * q;
+  if (rows == 0 || per_row == 0) {
+    EPOS_REQUIRE(!a->amax_clear || a->amax_words == 0,
+                 "amax_words exceeds the launch's thread count");
+    return EPOS_OK;
+  }
+  const dim3 grid(static_cast<unsigned>(blocks_for(per_row, 256)),
+                  static_cast<unsigned>(rows < 65535 ? rows : 65535));
+  EPOS_REQUIRE(!a->amax_clear || (a->amax_words >= 0 && a->amax_words <= per_row * grid.y),
+               "amax_words exceeds the launch's thread count");
+  hipLaunchKernelGGL(im2col_k_kernel, grid, dim3(256), 0, static_cast<hipStream_t>(stream), *a,
+                     q);
+  return launch_status("im2col_k_kernel");
 }
 
 extern "C" int epos_global_avg_pool_f32(const float* X, int64_t ldx, float* Y,

@@ -1,4 +1,5 @@
-"""EPOS network (DeepLabv3+/Xception-65) executor for MI355X.
+"""EPOS network (DeepLabv3+ on Xception-41/65/71 or ResNet-v1-50/101[-beta]) executor
+for MI355X.
 
 Builds, once per (batch, height, width, num_objs, num_frags), a static plan of
 fused HIP launches for the forward pass that the reference builds as a TF graph
@@ -62,8 +63,7 @@ class EposNet(object):
                model_variant='xception_65', encoder_output_stride=8,
                decoder_output_stride=4, atrous_rates=(12, 24, 36),
                multi_grid=None, device='cuda:0', dry_run=False):
-    if model_variant not in ('xception_65', 'resnet_v1_101_beta'):
-      raise ValueError('Unsupported model variant: %s' % model_variant)
+    self.variant = W.variant(model_variant)     # ValueError for the variants this build lacks
     self.model_variant = model_variant
     if encoder_output_stride != 8 or decoder_output_stride != 4:
       raise ValueError('Only encoder OS 8 / decoder OS 4 (common.py:127-135).')
@@ -501,7 +501,7 @@ class EposNet(object):
         preprocess=int(preprocess))
     lib = self.lib
     if getattr(self, '_first_im2col', None) is None:
-      self._first_im2col = (name + '/im2col', args)
+      self._first_im2col = (name + '/im2col', args, m * ldcol)
 
     def run(stream, args=args):
       _lib.check(lib.epos_im2col3x3_f32(ctypes.byref(args), stream), name)
@@ -509,6 +509,48 @@ class EposNet(object):
     w_kn, scale, bias = self._conv_params(scope, eps)
     cout = w_kn.shape[1]
     y = self._empty(self.B, ho, wo, cout)
+    self._pointwise(name, col, 0, ldcol, m, k, w_kn, scale, bias, y, 0, cout,
+                    relu=True, trace=False)
+    self._set_expr(y, 'relu(L:%s)' % name)
+    return y, ho, wo, cout
+
+  def _root_conv(self, name, x, hi, wi, cin, scope, stride, preprocess, eps):
+    """resnet_utils.conv2d_same k x k (+BN+ReLU) on the network input with the input's
+    preprocessing fused = epos_im2col_f32 + GEMM: the 7x7 stride-2 conv1 of resnet_v1_50 /
+    resnet_v1_101 (net_resnet_v1_beta.py:168-173). stride 1 -> 'SAME'; stride > 1 ->
+    fixed_padding + VALID; both pad (k - 1) // 2 in front. The image is preprocessed first and
+    padded with zeros after (feature.py:157-185 ahead of the network function)."""
+    kk = self.ckpt[scope + '/weights'].shape[0]
+    ho, wo = (hi - 1) // stride + 1, (wi - 1) // stride + 1
+    pad = (kk - 1) // 2
+    k = kk * kk * cin
+    ein = self._expr_of(x, 0, cin)
+    assert ein == 'input'
+    ein = {'unit_range': 'preprocess(input)', 'sub_mean': 'submean(input)'}[preprocess]
+    if stride > 1:                # conv2d_same: explicit padding + VALID
+      ein = 'pad(%s,%d,%d)' % (ein, pad, kk - 1 - pad)
+    cout_t = self.ckpt[scope + '/weights'].shape[3]
+    self._trace_layer(name, 'conv2d', kk, stride, 1, 'SAME' if stride == 1 else 'VALID',
+                      cin, cout_t, eps, False, ein, (ho, wo))
+    ldcol = (k + 3) // 4 * 4
+    m = self.B * ho * wo
+    col = self._empty(m, ldcol)
+    mode = {'unit_range': _lib.PREPROCESS_UNIT_RANGE, 'sub_mean': _lib.PREPROCESS_SUB_MEAN}
+    args = _lib.Im2colKArgs(
+        X=_ptr(x), ldx=cin, col=_ptr(col), ldcol=ldcol, B=self.B, Hi=hi, Wi=wi,
+        Ho=ho, Wo=wo, C=cin, k=kk, stride=stride, rate=1, pad=pad,
+        preprocess=mode[preprocess], mean_rgb=(ctypes.c_float * 3)(*W.MEAN_RGB))
+    lib = self.lib
+    if getattr(self, '_first_im2col', None) is None:
+      self._first_im2col = (name + '/im2col', args, wo * ldcol // 4 * min(self.B * ho, 65535))
+
+    def run(stream, args=args):
+      _lib.check(lib.epos_im2col_f32(ctypes.byref(args), stream), name)
+    self._add(name + '/im2col', run, 0, 'im2col')
+    w_kn, scale, bias = self._conv_params(scope, eps)
+    cout = w_kn.shape[1]
+    y = self._empty(self.B, ho, wo, cout)
+    # no bound on the col matrix (float inputs outside [0, 255] are legal): fp32 GEMM
     self._pointwise(name, col, 0, ldcol, m, k, w_kn, scale, bias, y, 0, cout,
                     relu=True, trace=False)
     self._set_expr(y, 'relu(L:%s)' % name)
@@ -583,14 +625,18 @@ class EposNet(object):
     return out, ho, wo, depth, conv3
 
   def _backbone_resnet(self):
-    """resnet_v1_101_beta (net_resnet_v1_beta.py:445-516) at output_stride 8."""
+    """resnet_v1_{50,101}[_beta] (net_resnet_v1_beta.py:233-516) at output_stride 8."""
     B, H, Wd, lib = self.B, self.H, self.W, self.lib
-    net = 'resnet_v1_101'
+    net = self.variant['scope']
     x, h, w, c = self.images, H, Wd, 3
-    for i, stride in enumerate([2, 1, 1], 1):                # :108-110
-      x, h, w, c = self._stem_conv('%s/conv1_%d' % (net, i), x, h, w, c,
-                                   '%s/conv1_%d' % (net, i), stride, i == 1,
-                                   eps=RESNET_BN_EPS)
+    if self.variant['root'] == 'beta':
+      for i, stride in enumerate([2, 1, 1], 1):              # :108-110
+        x, h, w, c = self._stem_conv('%s/conv1_%d' % (net, i), x, h, w, c,
+                                     '%s/conv1_%d' % (net, i), stride, i == 1,
+                                     eps=RESNET_BN_EPS)
+    else:                                                    # :168-173
+      x, h, w, c = self._root_conv(net + '/conv1', x, h, w, c, net + '/conv1', 2,
+                                   self.variant['preprocess'], RESNET_BN_EPS)
     ph, pw = (h + 1) // 2, (w + 1) // 2
     pooled = self._empty(B, ph, pw, c)
 
@@ -606,12 +652,12 @@ class EposNet(object):
     target, current_stride, rate = 2, 1, 1                   # 8 / 4 (:185-188)
     low_level = None
     mg = self.multi_grid
-    for bscope, base, units in W.RESNET101_BLOCKS:
+    for bscope, base, units in self.variant['blocks']:
       for u in range(units):
         scope = '%s/%s/unit_%d/bottleneck_v1' % (net, bscope, u + 1)
         stride = 2 if (u == units - 1 and bscope != 'block4') else 1
         unit_rate = mg[u] if bscope == 'block4' else 1
-        keep = bscope == 'block1' and u == 1
+        keep = bscope == self.variant['tap'] and u == 1
         if current_stride == target:
           x, h, w, c, conv3 = self._bottleneck(scope, x, h, w, c, base * 4, base,
                                                1, rate * unit_rate, keep)
@@ -625,8 +671,10 @@ class EposNet(object):
     return x, h, w, c, low_level
 
   def _backbone_xception(self):
+    """xception_{41,65,71} (net_xception.py:396-483, block tables in weights.XCEPTION_TABLES)."""
     B, H, Wd = self.B, self.H, self.W
-    net = 'xception_65'
+    net = self.variant['scope']
+    tap = self.variant['tap']
     x, h, w, c = self._stem_conv(net + '/entry_flow/conv1_1', self.images, H, Wd,
                                  3, net + '/entry_flow/conv1_1', 2, True)
     x, h, w, c = self._stem_conv(net + '/entry_flow/conv1_2', x, h, w, c,
@@ -634,20 +682,14 @@ class EposNet(object):
     # stack_blocks_dense (net_xception.py:326-393) with output_stride 8/2 = 4.
     target, current_stride, rate = 4, 1, 1
     low_level = None
-    blocks = [
-        ('entry_flow/block1', [128, 128, 128], 'conv', False, 1, 2, [1, 1, 1]),
-        ('entry_flow/block2', [256, 256, 256], 'conv', False, 1, 2, [1, 1, 1]),
-        ('entry_flow/block3', [728, 728, 728], 'conv', False, 1, 2, [1, 1, 1]),
-        ('middle_flow/block1', [728, 728, 728], 'sum', False, 16, 1, [1, 1, 1]),
-        ('exit_flow/block1', [728, 1024, 1024], 'conv', False, 1, 2, [1, 1, 1]),
-        ('exit_flow/block2', [1536, 1536, 2048], 'none', True, 1, 1,
-         self.multi_grid),
-    ]
+    blocks = [b + ((self.multi_grid if b[0] == 'exit_flow/block2' else [1, 1, 1]),)
+              for b in self.variant['blocks']]
     for bscope, depths, skip, act, units, stride, url in blocks:
       for u in range(units):
         scope = '%s/%s/unit_%d/xception_module' % (net, bscope, u + 1)
-        # the decoder taps sep-conv 2 of entry_flow/block2 BEFORE any activation
-        linear = (1,) if bscope == 'entry_flow/block2' else ()
+        # the decoder taps sep-conv 2 of the tap block (entry_flow/block2; xception_71:
+        # block3) BEFORE any activation
+        linear = (1,) if bscope == tap else ()
         if current_stride == target:
           x, h, w, c, taps = self._xception_module(
               scope, x, h, w, c, depths, skip, act, 1, rate, url, linear)
@@ -656,7 +698,7 @@ class EposNet(object):
           x, h, w, c, taps = self._xception_module(
               scope, x, h, w, c, depths, skip, act, stride, 1, url, linear)
           current_stride *= stride
-        if bscope == 'entry_flow/block2':
+        if bscope == tap:
           low_level = (taps[1], taps[1].shape[1], taps[1].shape[2], depths[1])
     return x, h, w, c, low_level
 
@@ -723,7 +765,7 @@ class EposNet(object):
       _lib.check(lib0.epos_amax_clear(_ptr(self._amax_table), self._n_slots, stream),
                  'amax_clear')
     self._add('amax_clear', run_clear)
-    if self.model_variant == 'xception_65':
+    if self.variant['family'] == 'xception':
       x, h, w, c, low_level = self._backbone_xception()
     else:
       x, h, w, c, low_level = self._backbone_resnet()
@@ -922,7 +964,7 @@ class EposNet(object):
     fi = getattr(self, '_first_im2col', None)
     if (not self.dry_run and fi is not None and len(self.ops) > 1 and
         self.ops[0][0] == 'amax_clear' and self.ops[1][0] == fi[0] and
-        os.environ.get('EPOS_AMAX_CLEAR_FOLD', '1') == '1'):
+        self._n_slots * _lib.AMAX_WORDS <= fi[2] and os.environ.get('EPOS_AMAX_CLEAR_FOLD', '1') == '1'):
       fi[1].amax_clear = _ptr(self._amax_table)
       fi[1].amax_words = self._n_slots * _lib.AMAX_WORDS
       del self.ops[0]
@@ -945,7 +987,8 @@ class EposNet(object):
         continue
       if a_id in self._dw_reads:            # A = a depthwise output: the group reads its input
         total += self._dw_reads[a_id] + rest
-      elif name.endswith('conv1_1') and self.op_kind.get(name + '/im2col') == 'im2col':
+      elif (name.endswith(('conv1_1', '/conv1')) and
+            self.op_kind.get(name + '/im2col') == 'im2col'):
         total += 4 * self.B * self.H * self.W * 3 + rest     # the image, not the im2col matrix
       else:
         total += a_bytes + rest

@@ -13,18 +13,81 @@ them with the reference's initialisers (used for synthetic benchmarks and tests
 """
 import numpy as np
 
-XCEPTION_BLOCKS = [  # net_xception.py:604-648: (scope, depths, skip, units)
-    ('entry_flow/block1', [128, 128, 128], 'conv', 1),
-    ('entry_flow/block2', [256, 256, 256], 'conv', 1),
-    ('entry_flow/block3', [728, 728, 728], 'conv', 1),
-    ('middle_flow/block1', [728, 728, 728], 'sum', 16),
-    ('exit_flow/block1', [728, 1024, 1024], 'conv', 1),
-    ('exit_flow/block2', [1536, 1536, 2048], 'none', 1),
-]
-
 RESNET101_BLOCKS = [  # net_resnet_v1_beta.py:494-505: (scope, base depth, units)
     ('block1', 64, 3), ('block2', 128, 4), ('block3', 256, 23), ('block4', 512, 3),
 ]
+
+# The other backbones of feature.py:118-129 (networks_map) that share ASPP, decoder and heads.
+# Xception tables: (scope, depths, skip, act_in_sep, units, stride) -- net_xception.py:526-590
+# (xception_41), :604-648 (xception_65), :660-738 (xception_71); exit_flow/block2 takes the
+# multi_grid unit rates.
+_XCEPTION_EXIT = [
+    ('exit_flow/block1', [728, 1024, 1024], 'conv', False, 1, 2),
+    ('exit_flow/block2', [1536, 1536, 2048], 'none', True, 1, 1),
+]
+XCEPTION_TABLES = {
+    'xception_41': [
+        ('entry_flow/block1', [128, 128, 128], 'conv', False, 1, 2),
+        ('entry_flow/block2', [256, 256, 256], 'conv', False, 1, 2),
+        ('entry_flow/block3', [728, 728, 728], 'conv', False, 1, 2),
+        ('middle_flow/block1', [728, 728, 728], 'sum', False, 8, 1)] + _XCEPTION_EXIT,
+    'xception_65': [
+        ('entry_flow/block1', [128, 128, 128], 'conv', False, 1, 2),
+        ('entry_flow/block2', [256, 256, 256], 'conv', False, 1, 2),
+        ('entry_flow/block3', [728, 728, 728], 'conv', False, 1, 2),
+        ('middle_flow/block1', [728, 728, 728], 'sum', False, 16, 1)] + _XCEPTION_EXIT,
+    'xception_71': [
+        ('entry_flow/block1', [128, 128, 128], 'conv', False, 1, 2),
+        ('entry_flow/block2', [256, 256, 256], 'conv', False, 1, 1),
+        ('entry_flow/block3', [256, 256, 256], 'conv', False, 1, 2),
+        ('entry_flow/block4', [728, 728, 728], 'conv', False, 1, 1),
+        ('entry_flow/block5', [728, 728, 728], 'conv', False, 1, 2),
+        ('middle_flow/block1', [728, 728, 728], 'sum', False, 16, 1)] + _XCEPTION_EXIT,
+}
+
+RESNET50_BLOCKS = [  # net_resnet_v1_beta.py:278-289, :351-362
+    ('block1', 64, 3), ('block2', 128, 4), ('block3', 256, 6), ('block4', 512, 3),
+]
+
+MEAN_RGB = (123.15, 115.90, 103.06)   # feature.py:154 (_MEAN_RGB)
+
+# model_variant -> how the backbone is built:
+#   family      'xception' | 'resnet'
+#   scope       the network's variable scope (feature.py:140-149, name_scope)
+#   blocks      XCEPTION_TABLES entry | RESNET*_BLOCKS
+#   root        xception: 3x3 conv1_1 / conv1_2; resnet 'beta': three 3x3 conv1_1..3
+#               (net_resnet_v1_beta.py:96-112), 'conv7': one 7x7 stride-2 conv1 (:168-173)
+#   preprocess  'unit_range' (2/255) x - 1 | 'sub_mean' x - MEAN_RGB (feature.py:176-185)
+#   tap         the block whose unit_1 separable_conv2_pointwise (xception) / unit_2 conv3
+#               (resnet) feeds the decoder (feature.py:29-73)
+VARIANTS = {
+    'xception_41': dict(family='xception', scope='xception_41', root='xception',
+                        preprocess='unit_range', tap='entry_flow/block2'),
+    'xception_65': dict(family='xception', scope='xception_65', root='xception',
+                        preprocess='unit_range', tap='entry_flow/block2'),
+    'xception_71': dict(family='xception', scope='xception_71', root='xception',
+                        preprocess='unit_range', tap='entry_flow/block3'),
+    'resnet_v1_50': dict(family='resnet', scope='resnet_v1_50', root='conv7',
+                         preprocess='sub_mean', tap='block1'),
+    'resnet_v1_50_beta': dict(family='resnet', scope='resnet_v1_50', root='beta',
+                              preprocess='unit_range', tap='block1'),
+    'resnet_v1_101': dict(family='resnet', scope='resnet_v1_101', root='conv7',
+                          preprocess='sub_mean', tap='block1'),
+    'resnet_v1_101_beta': dict(family='resnet', scope='resnet_v1_101', root='beta',
+                               preprocess='unit_range', tap='block1'),
+}
+for _name, _v in VARIANTS.items():
+  _v['blocks'] = (XCEPTION_TABLES[_name] if _v['family'] == 'xception' else
+                  RESNET50_BLOCKS if '_50' in _name else RESNET101_BLOCKS)
+
+
+def variant(model_variant):
+  """The VARIANTS entry of a model variant; ValueError for the ones this build lacks."""
+  if model_variant not in VARIANTS:
+    raise ValueError('Unsupported model variant: %s (supported: %s)' % (
+        model_variant, ', '.join(sorted(VARIANTS))))
+  return VARIANTS[model_variant]
+
 
 PRED_OBJ_CONF = 'pred_obj_conf'    # common.py:24-27
 PRED_OBJ_LABEL = 'pred_obj_label'
@@ -53,12 +116,13 @@ def variable_specs(model_variant='xception_65', num_objs=21, num_frags=64,
         'logits' (trunc-normal 0.01, model.py:437).
   """
   specs = []
-  if model_variant == 'xception_65':
-    net = 'xception_65'
+  v = variant(model_variant)
+  net = v['scope']
+  if v['family'] == 'xception':
     specs.append(('conv', net + '/entry_flow/conv1_1', (3, 3, 3, 32), 'backbone'))
     specs.append(('conv', net + '/entry_flow/conv1_2', (3, 3, 32, 64), 'backbone'))
     cin = 64
-    for bscope, depths, skip, units in XCEPTION_BLOCKS:
+    for bscope, depths, skip, _, units, _ in v['blocks']:
       for u in range(units):
         scope = '%s/%s/unit_%d/xception_module' % (net, bscope, u + 1)
         c = cin
@@ -71,15 +135,19 @@ def variable_specs(model_variant='xception_65', num_objs=21, num_frags=64,
           specs.append(('conv', scope + '/shortcut', (1, 1, cin, depths[-1]),
                         'backbone'))
         cin = depths[-1]
-  elif model_variant == 'resnet_v1_101_beta':
-    # net_resnet_v1_beta.py:96-112 (root), :38-93 (bottleneck), :494-505 (blocks);
-    # variable scope 'resnet_v1_101' (net_resnet_v1_beta.py:452).
-    net = 'resnet_v1_101'
-    cin = 3
-    for i, cout in enumerate([64, 64, 128], 1):
-      specs.append(('conv', '%s/conv1_%d' % (net, i), (3, 3, cin, cout), 'he'))
-      cin = cout
-    for bscope, base, units in RESNET101_BLOCKS:
+  else:
+    # net_resnet_v1_beta.py:96-112 (beta root) or :168-173 (7x7 root), :38-93 (bottleneck),
+    # block tables; variable scope from feature.py:140-149 ('resnet_v1_50_beta' ->
+    # 'resnet_v1_50').
+    if v['root'] == 'beta':
+      cin = 3
+      for i, cout in enumerate([64, 64, 128], 1):
+        specs.append(('conv', '%s/conv1_%d' % (net, i), (3, 3, cin, cout), 'he'))
+        cin = cout
+    else:
+      specs.append(('conv', net + '/conv1', (7, 7, 3, 64), 'he'))
+      cin = 64
+    for bscope, base, units in v['blocks']:
       for u in range(units):
         scope = '%s/%s/unit_%d/bottleneck_v1' % (net, bscope, u + 1)
         if cin != base * 4:
@@ -88,8 +156,6 @@ def variable_specs(model_variant='xception_65', num_objs=21, num_frags=64,
         specs.append(('conv', scope + '/conv2', (3, 3, base, base), 'he'))
         specs.append(('conv', scope + '/conv3', (1, 1, base, base * 4), 'he'))
         cin = base * 4
-  else:
-    raise ValueError('Unsupported model variant: %s' % model_variant)
   specs.append(('conv', 'image_pooling', (1, 1, cin, 256), 'xavier'))
   specs.append(('conv', 'aspp0', (1, 1, cin, 256), 'xavier'))
   for i, _ in enumerate(atrous_rates, 1):

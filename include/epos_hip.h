@@ -286,6 +286,32 @@ typedef struct EposIm2colArgs {
 } EposIm2colArgs;
 int epos_im2col3x3_f32(const EposIm2colArgs* args, void* stream);
 
+/* im2col for a dense k x k conv with a choice of fused input preprocessing (the root convs
+ * of every backbone, feature.py:157-185; the 7x7 stride-2 conv1 of resnet_v1_50 / _101,
+ * net_resnet_v1_beta.py:168-173):
+ * col[m, (ky*k+kx)*C + c] = pre(X[b, y*stride - pad + ky*rate, x*stride - pad + kx*rate, c])
+ * for in-bounds taps and 0 for padded ones (the reference preprocesses the image, then
+ * conv2d_same pads it with zeros); columns k*k*C .. ldcol are zero-filled. Same output
+ * contract as epos_im2col3x3_f32, which this equals bit for bit at k = 3.
+ * pre: EPOS_PREPROCESS_NONE x; _UNIT_RANGE (2/255) x - 1 (_preprocess_zero_mean_unit_range);
+ * _SUB_MEAN x - mean_rgb[c] for c < 3 and x for c >= 3 (_preprocess_subtract_imagenet_mean).
+ * Needs ldcol % 4 == 0 and a 16-byte aligned col (one float4 store per thread).
+ * amax_clear / amax_words: as in EposIm2colArgs; amax_words <= Wo*ldcol/4 * min(B*Ho, 65535). */
+#define EPOS_PREPROCESS_NONE 0
+#define EPOS_PREPROCESS_UNIT_RANGE 1
+#define EPOS_PREPROCESS_SUB_MEAN 2
+typedef struct EposIm2colKArgs {
+  const float* X; int64_t ldx;
+  float* col; int64_t ldcol;
+  int32_t B, Hi, Wi, Ho, Wo, C;
+  int32_t k, stride, rate, pad;
+  int32_t preprocess;
+  float mean_rgb[3];
+  uint32_t* amax_clear;
+  int64_t amax_words;
+} EposIm2colKArgs;
+int epos_im2col_f32(const EposIm2colKArgs* args, void* stream);
+
 /* Per-image channel means from the 32-row block sums an fp16-pair GEMM wrote
  * (EposPointwiseArgs.col_sums): Y[b, c] = (sum over the `blocks` blocks of image b) / hw. */
 int epos_global_avg_pool_partial_f32(const float* P, int64_t ldp, float* Y, int32_t B,

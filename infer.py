@@ -115,7 +115,9 @@ def build_parser():
   a('--corr_project_to_model', type=str2bool, default=False,
     help='accepted and ignored, as in the reference: common.py:78-80 defines the flag and '
          'nothing reads it (the projection switch that acts is --project_to_surface)')
-  a('--model_variant', default='xception_65')
+  a('--model_variant', default='xception_65',
+    help='backbone (feature.py:118-129): xception_41, xception_65, xception_71, '
+         'resnet_v1_50, resnet_v1_50_beta, resnet_v1_101, resnet_v1_101_beta')
   a('--atrous_rates', default='12,24,36')
   a('--encoder_output_stride', type=int, default=8)
   a('--decoder_output_stride', default='4')
@@ -226,8 +228,9 @@ def check_supported_flags(args):
         args.image_pyramid,))
   if _as_list(args.image_pooling_stride, int) not in ([1, 1],):
     bad.append('image_pooling_stride=%r (supported: 1,1)' % (args.image_pooling_stride,))
-  if args.model_variant not in ('xception_65', 'resnet_v1_101_beta'):
-    bad.append('model_variant=%r (xception_65, resnet_v1_101_beta)' % args.model_variant)
+  if args.model_variant not in weights.VARIANTS:
+    bad.append('model_variant=%r (%s)' % (args.model_variant,
+                                         ', '.join(sorted(weights.VARIANTS))))
   if int(args.encoder_output_stride) != 8:
     bad.append('encoder_output_stride=%r (supported: 8)' % args.encoder_output_stride)
   if _as_list(args.decoder_output_stride, int) != [4]:
@@ -493,8 +496,8 @@ def main(argv=None):
     num_objs = ckpt['logits/pred_obj_conf/biases'].shape[0] - 1
   elif args.synthetic:
     num_objs = args.num_objs or 21
-    ckpt = weights.random_init(num_objs=num_objs, num_frags=args.num_frags,
-                               seed=0, randomize_bn=True)
+    ckpt = weights.random_init(args.model_variant, num_objs=num_objs,
+                               num_frags=args.num_frags, seed=0, randomize_bn=True)
   else:
     raise ValueError('No checkpoint (.npz) found in {}'.format(checkpoint_dir))
   store = load_fragments(model_dir, args.num_frags)
