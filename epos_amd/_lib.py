@@ -105,6 +105,45 @@ class Im2colKArgs(ctypes.Structure):
   ]
 
 
+class PointwiseBf16Args(ctypes.Structure):
+  _fields_ = [
+      ('A', vp), ('lda', ctypes.c_int64),
+      ('Wp', vp), ('bias', vp),
+      ('R', vp), ('ldr', ctypes.c_int64),
+      ('C', vp), ('ldc', ctypes.c_int64),
+      ('M', ctypes.c_int32), ('N', ctypes.c_int32), ('K', ctypes.c_int32),
+      ('relu', ctypes.c_int32), ('sub', ctypes.c_int32),
+      ('Ho', ctypes.c_int32), ('Wo', ctypes.c_int32),
+      ('Hi', ctypes.c_int32), ('Wi', ctypes.c_int32),
+      ('c_f32', ctypes.c_int32), ('c_stream', ctypes.c_int32),
+  ]
+
+
+class DepthwiseBf16Args(ctypes.Structure):
+  _fields_ = [
+      ('X', vp), ('ldx', ctypes.c_int64),
+      ('w9c', vp), ('bias', vp),
+      ('Y', vp), ('ldy', ctypes.c_int64),
+      ('B', ctypes.c_int32), ('Hi', ctypes.c_int32), ('Wi', ctypes.c_int32),
+      ('Ho', ctypes.c_int32), ('Wo', ctypes.c_int32), ('C', ctypes.c_int32),
+      ('stride', ctypes.c_int32), ('rate', ctypes.c_int32),
+      ('relu_in', ctypes.c_int32), ('relu_out', ctypes.c_int32),
+  ]
+
+
+class Im2colBf16Args(ctypes.Structure):
+  _fields_ = [
+      ('X', vp), ('ldx', ctypes.c_int64),
+      ('x_bf16', ctypes.c_int32), ('reserved0', ctypes.c_int32),
+      ('col', vp), ('ldcol', ctypes.c_int64),
+      ('B', ctypes.c_int32), ('Hi', ctypes.c_int32), ('Wi', ctypes.c_int32),
+      ('Ho', ctypes.c_int32), ('Wo', ctypes.c_int32), ('C', ctypes.c_int32),
+      ('k', ctypes.c_int32), ('stride', ctypes.c_int32), ('rate', ctypes.c_int32),
+      ('pad', ctypes.c_int32), ('preprocess', ctypes.c_int32),
+      ('mean_rgb', ctypes.c_float * 3),
+  ]
+
+
 class CorrSlot(ctypes.Structure):
   _fields_ = [('image', ctypes.c_int32), ('obj_id', ctypes.c_int32)]
 
@@ -226,6 +265,25 @@ SYMBOLS = {
     'epos_solve_pnp_ransac_device': (ctypes.c_int, [
         vp, vp, vp, ctypes.c_int, ctypes.c_int64, vp, ctypes.POINTER(PnpRansacParams),
         vp, vp, vp, vp, vp, vp]),
+    # bf16 inference mode
+    'epos_pack_pointwise_weights_bf16': (ctypes.c_int64,
+                                         [vp, ctypes.c_int, ctypes.c_int, vp]),
+    'epos_pointwise_conv_bf16': (ctypes.c_int, [
+        ctypes.POINTER(PointwiseBf16Args), ctypes.c_int, vp]),
+    'epos_depthwise3x3_bf16': (ctypes.c_int, [ctypes.POINTER(DepthwiseBf16Args), vp]),
+    'epos_im2col_bf16': (ctypes.c_int, [ctypes.POINTER(Im2colBf16Args), vp]),
+    'epos_resize_bilinear_bf16': (ctypes.c_int, [
+        vp, ctypes.c_int64, ctypes.c_int, vp, ctypes.c_int64, ctypes.c_int, ctypes.c_int,
+        ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp]),
+    'epos_global_avg_pool_bf16': (ctypes.c_int, [
+        vp, ctypes.c_int64, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp]),
+    'epos_maxpool3x3_s2_bf16': (ctypes.c_int, [
+        vp, ctypes.c_int64, vp, ctypes.c_int64, ctypes.c_int, ctypes.c_int,
+        ctypes.c_int, ctypes.c_int, vp]),
+    'epos_subsample_bf16': (ctypes.c_int, [
+        vp, ctypes.c_int64, vp, ctypes.c_int64, ctypes.c_int, ctypes.c_int,
+        ctypes.c_int, ctypes.c_int, ctypes.c_int, vp]),
+    'epos_add_relu_bf16': (ctypes.c_int, [vp, vp, vp, ctypes.c_int64, vp]),
 }
 
 _lib = None

@@ -45,16 +45,17 @@ _NETS = {}
 
 
 def get_net(checkpoint, batch, height, width, num_objs, num_frags,
-            model_options=None, device='cuda:0', instance=0):
+            model_options=None, device='cuda:0', instance=0, precision='fp32'):
   """Returns (and caches) the HIP plan for this checkpoint and input shape.
   ``instance`` distinguishes independent plans (own activation buffers) of the
-  same network, e.g. the two halves of a double-buffered pipeline."""
+  same network, e.g. the two halves of a double-buffered pipeline. ``precision``: 'fp32'
+  (default) or 'bf16' (EposNet); plans of the two precisions are cached separately."""
   mo = model_options or ModelOptions(
       get_outputs_to_num_channels(num_objs, num_frags))
   key = (id(checkpoint), batch, height, width, num_objs, num_frags,
          mo.model_variant, mo.atrous_rates, mo.encoder_output_stride,
          mo.decoder_output_stride, tuple(mo.multi_grid or ()), str(device),
-         instance)
+         instance, precision)
   if key not in _NETS:
     if len(mo.decoder_output_stride) != 1:
       raise ValueError('one decoder stage only (common.py:127-132).')
@@ -63,14 +64,15 @@ def get_net(checkpoint, batch, height, width, num_objs, num_frags,
         model_variant=mo.model_variant,
         encoder_output_stride=mo.encoder_output_stride,
         decoder_output_stride=mo.decoder_output_stride[0],
-        atrous_rates=mo.atrous_rates, multi_grid=mo.multi_grid, device=device)
+        atrous_rates=mo.atrous_rates, multi_grid=mo.multi_grid, device=device,
+        precision=precision)
   return _NETS[key]
 
 
 def predict(images, model_options, checkpoint, upsample_logits=False,
             image_pyramid=None, num_objs=None, num_frags=None,
             frag_cls_agnostic=False, frag_loc_agnostic=False, device='cuda:0',
-            use_graph=False):
+            use_graph=False, precision='fp32'):
   """model.py:629-687. images: float32 [B,H,W,3] in [0,255] (numpy or tensor).
 
   Returns {pred_obj_conf f32[B,h,w,O+1], pred_obj_label i64[B,h,w],
@@ -85,5 +87,6 @@ def predict(images, model_options, checkpoint, upsample_logits=False,
   if frag_cls_agnostic or frag_loc_agnostic:
     raise NotImplementedError('class-agnostic fragment heads are out of scope.')
   b, h, w = images.shape[0], images.shape[1], images.shape[2]
-  net = get_net(checkpoint, b, h, w, num_objs, num_frags, model_options, device)
+  net = get_net(checkpoint, b, h, w, num_objs, num_frags, model_options, device,
+                precision=precision)
   return net.forward(images, use_graph=use_graph)

@@ -18,6 +18,12 @@ Fusion groups:
   * dense 3x3 stem convs: stride 1 with Cin % 32 == 0 (conv1_2) is an implicit GEMM
     inside the LDS-DMA kernel; the 3-channel stride-2 conv1_1 is im2col + the same GEMM.
 torch is used for device memory and streams only.
+
+precision='bf16' (opt-in; the default 'fp32' plan is unchanged): the same graph with bf16
+activation buffers and bf16 weights (BN folded in fp32, then rounded to nearest even), bf16 x
+bf16 products with fp32 accumulation and fp32 epilogues (csrc/bf16.hip), one rounding per
+stored activation. The image and its preprocessing, the image-pooling 1x1 and the three
+logits / prediction tensors stay fp32; decoder_out is a bf16 tensor. DESIGN.md, "bf16 mode".
 """
 import ctypes
 import os
@@ -31,6 +37,7 @@ from epos_amd import weights as W
 XCEPTION_BN_EPS = 1e-3   # feature.py:300-307
 HEAD_BN_EPS = 1e-5       # model.py:194-199, 307-312
 RESNET_BN_EPS = 1e-5     # feature.py:282-287
+PRECISIONS = ('fp32', 'bf16')
 
 
 def _ptr(t, offset_elems=0):
@@ -62,7 +69,12 @@ class EposNet(object):
   def __init__(self, checkpoint, batch, height, width, num_objs, num_frags=64,
                model_variant='xception_65', encoder_output_stride=8,
                decoder_output_stride=4, atrous_rates=(12, 24, 36),
-               multi_grid=None, device='cuda:0', dry_run=False):
+               multi_grid=None, device='cuda:0', dry_run=False, precision='fp32'):
+    if precision not in PRECISIONS:
+      raise ValueError('precision must be one of %s (got %r).' % (PRECISIONS, precision))
+    self.precision = precision
+    self.bf16 = precision == 'bf16'
+    self.act_dtype = torch.bfloat16 if self.bf16 else torch.float32
     self.variant = W.variant(model_variant)     # ValueError for the variants this build lacks
     self.model_variant = model_variant
     if encoder_output_stride != 8 or decoder_output_stride != 4:
@@ -113,7 +125,8 @@ class EposNet(object):
     # most of it back inside the pipelined step (+0.055 ms of depthwise slot time vs -0.02 ms
     # of GEMM and -0.05 ms of the rest): 417.5 / 419.8 vs 415.4 / 417.2 images/s, same box --
     # a small but repeatable gain (round 3 measured it neutral and kept it off).
-    self.use_h2 = (os.environ.get('EPOS_GEMM_H2', '1') != '0' and
+    # (bf16 mode: bf16 has fp32's exponent range, no slot / fp16-pair machinery)
+    self.use_h2 = (not self.bf16 and os.environ.get('EPOS_GEMM_H2', '1') != '0' and
                    os.environ.get('EPOS_GEMM_SPLIT', '1') != '0')
     self.use_presplit = self.use_h2 and os.environ.get('EPOS_H2_PRESPLIT', '1') == '1'
     self._dw_h2 = {}           # id(depthwise output) -> its (mutable) launch arguments
@@ -128,6 +141,10 @@ class EposNet(object):
     self._last_bn = (None, None)
     self.pad_rows = os.environ.get('EPOS_PAD_ROWS', '1') != '0'
     self._lds = {}
+    # bf16 mode: every im2col of the plan writes one shared scratch matrix, allocated once the
+    # plan is built (the launch arguments that point into it are patched then)
+    self._col_users, self._col_elems = [], 0
+    self._col_ids = set()        # the im2col matrices (fp32 plan: one per layer)
     self._build_plan()
 
   # ------------------------------------------------------------ buffers ---
@@ -144,10 +161,15 @@ class EposNet(object):
     row has 7 slice boundaries inside lines and ~30 % of the input is fetched by two XCDs),
     and the GEMMs' A rows and C rows are line-aligned. The padding columns are never read or
     written. EPOS_PAD_ROWS=0: dense rows (the A/B switch)."""
-    ld = (c + 31) // 32 * 32 if (self.pad_rows and c >= 256) else c
-    t = self._empty(b, h, w, ld)
+    line = 64 if self.bf16 else 32           # elements per 128-byte line
+    ld = (c + line - 1) // line * line if (self.pad_rows and c >= 256) else c
+    t = self._empty(b, h, w, ld, dtype=self.act_dtype)
     self._lds[id(t)] = ld
     return t
+
+  def _abuf(self, *shape):
+    """Dense activation buffer in the plan's activation dtype."""
+    return self._empty(*shape, dtype=self.act_dtype)
 
   def _ld(self, buf):
     """Row pitch (floats) of an activation buffer."""
@@ -241,6 +263,24 @@ class EposNet(object):
     b[:n] = bias
     return self._dev(dst), self._dev(b), kpad
 
+  def _pack_bf16(self, w_kn, scale, bias):
+    """bf16 mode: folded weights (fp32 fold, then RNE) in epos_pack_pointwise_weights_bf16's
+    layout, K zero-padded to a multiple of 8, and the fp32 bias."""
+    k, n = w_kn.shape
+    kpad = (k + 7) // 8 * 8
+    if self.dry_run:
+      return self._empty(1), self._empty(1), kpad
+    w = np.ascontiguousarray(w_kn.astype(np.float32) * scale[None, :].astype(np.float32))
+    if kpad != k:
+      w = np.concatenate([w, np.zeros((kpad - k, n), np.float32)], 0)
+    total = self.lib.epos_pack_pointwise_weights_bf16(None, kpad, n, None)
+    dst = np.empty(total, np.uint16)
+    self.lib.epos_pack_pointwise_weights_bf16(w.ctypes.data_as(ctypes.c_void_p), kpad, n,
+                                              dst.ctypes.data_as(ctypes.c_void_p))
+    b = np.zeros((n + 3) // 4 * 4, np.float32)
+    b[:n] = bias
+    return self._dev(dst), self._dev(b), kpad
+
   def _pack_split(self, w_kn, scale):
     """The same folded weights in the split-operand GEMM's layout (three exact bf16
     pieces per weight, MFMA fragment order): epos_pack_pointwise_weights_split."""
@@ -314,10 +354,12 @@ class EposNet(object):
                  trace=True):
     """One 1x1 conv. With ``group`` (a list) the problem is only appended to it;
     ``_flush_group`` later launches the whole list as ONE grouped GEMM."""
-    wp, bp, kpad = self._pack_pointwise(w_kn, scale, bias)
-    ws = None if relu_in else self._pack_split(w_kn, scale)
+    use_bf16 = self.bf16 and a.dtype == torch.bfloat16   # bf16 mode: bf16 A -> bf16 GEMM
+    if not use_bf16:
+      wp, bp, kpad = self._pack_pointwise(w_kn, scale, bias)
+      ws = None if relu_in else self._pack_split(w_kn, scale)
+      assert kpad == k or (kpad > k and lda >= kpad), (name, k, kpad, lda)
     n = w_kn.shape[1]
-    assert kpad == k or (kpad > k and lda >= kpad), (name, k, kpad, lda)
     # ---- structure trace: what this launch computes, from its own arguments. A stem conv
     # that runs as im2col + GEMM is recorded by _stem_conv (it passes trace=False).
     if trace:
@@ -332,6 +374,11 @@ class EposNet(object):
       if res is not None:
         eout = 'add(%s)' % ','.join(sorted([eout, self._expr_of(res, res_off, n)]))
       self._set_expr(c, self._relu_expr(eout) if relu else eout, c_off, n)
+    if use_bf16:
+      assert not relu_in, name
+      self._pointwise_bf16(name, a, a_off, lda, m, k, w_kn, scale, bias, c, c_off, ldc, relu,
+                           res, res_off, ldr, sub, ho, wo, hi, wi, group)
+      return
     # fp16-pair weights when the A operand has a bound; the output's slot
     ab = self._bound_of(a) if self.use_h2 else None
     wh = None
@@ -379,10 +426,49 @@ class EposNet(object):
     # block sums to the launch that writes the encoder output
     self._last_pw = (c, args, wh is not None and res is None and c_off == 0 and n % 4 == 0)
 
+  def _pointwise_bf16(self, name, a, a_off, lda, m, k, w_kn, scale, bias, c, c_off, ldc,
+                      relu, res=None, res_off=0, ldr=0, sub=1, ho=0, wo=0, hi=0, wi=0,
+                      group=None):
+    """bf16 mode: one 1x1 conv on the bf16 GEMM (epos_pointwise_conv_bf16). A is bf16 (a=None:
+    the shared im2col scratch, patched in by _build_plan); C is bf16, or fp32 for the logits.
+    Returns the launch arguments."""
+    wp, bp, kpad = self._pack_bf16(w_kn, scale, bias)
+    n = w_kn.shape[1]
+    # a K padded to 8 reads columns k .. kpad of A: only im2col matrices (zero-filled there)
+    assert kpad == k or (a is None and lda >= kpad), (name, k, kpad, lda)
+    args = _lib.PointwiseBf16Args(
+        A=_ptr(a, a_off) if a is not None else None, lda=lda, Wp=_ptr(wp), bias=_ptr(bp),
+        R=_ptr(res, res_off) if res is not None else None, ldr=ldr,
+        C=_ptr(c, c_off), ldc=ldc, M=m, N=n, K=kpad, relu=int(relu), sub=sub,
+        Ho=ho, Wo=wo, Hi=hi, Wi=wi, c_f32=int(c.dtype == torch.float32), c_stream=0)
+    lib = self.lib
+    # bf16 activations and weights (2 B), the output in its own dtype, residual once
+    nbytes = (2 * (m * k + k * n) + c.element_size() * m * n +
+              (2 * m * n if res is not None else 0))
+    self.op_io[name] = (2 * m * k, nbytes - 2 * m * k, id(a))
+    if group is not None:
+      group.append((name, args, 2 * m * n * k, nbytes))
+      return args
+
+    def run(stream, args=args):
+      _lib.check(lib.epos_pointwise_conv_bf16(ctypes.byref(args), 1, stream), name)
+    self._add(name, run, 2 * m * n * k, 'gemm', nbytes)
+    return args
+
   def _flush_group(self, group):
     """Launches the collected problems as one grouped GEMM (they must agree on
     relu_in / residual; callers group accordingly)."""
     if not group:
+      return
+    if isinstance(group[0][1], _lib.PointwiseBf16Args):      # bf16 mode
+      name = '+'.join(g[0] for g in group)
+      arr = (_lib.PointwiseBf16Args * len(group))(*[g[1] for g in group])
+      lib, n = self.lib, len(group)
+
+      def run_bf16(stream, arr=arr):
+        _lib.check(lib.epos_pointwise_conv_bf16(arr, n, stream), name)
+      self._add(name, run_bf16, sum(g[2] for g in group), 'gemm', sum(g[3] for g in group))
+      del group[:]
       return
     # problems whose A is already fp16 pairs run on another kernel instantiation than the
     # ones that split their fp32 A themselves: one launch per kind
@@ -420,6 +506,19 @@ class EposNet(object):
     self._trace_layer(name, 'depthwise_conv2d', 3, stride, rate,
                       'SAME' if stride == 1 else 'VALID', c, c, eps, False, ein, (ho, wo))
     self._set_expr(y, self._relu_expr('L:' + name) if relu_out else 'L:' + name, 0, c)
+    if self.bf16:
+      args = _lib.DepthwiseBf16Args(
+          X=_ptr(x), ldx=ldx, w9c=_ptr(w9c), bias=_ptr(bias), Y=_ptr(y), ldy=ldy,
+          B=self.B, Hi=hi, Wi=wi, Ho=ho, Wo=wo, C=c, stride=stride, rate=rate,
+          relu_in=int(relu_in), relu_out=int(relu_out))
+      lib = self.lib
+      self._dw_reads[id(y)] = 2 * self.B * hi * wi * c + 40 * c
+
+      def run_bf16(stream, args=args):
+        _lib.check(lib.epos_depthwise3x3_bf16(ctypes.byref(args), stream), name)
+      self._add(name, run_bf16, 2 * 9 * self.B * ho * wo * c, 'dw',
+                2 * (self.B * hi * wi * c + self.B * ho * wo * c) + 40 * c)
+      return y, ho, wo
     xb = self._bound_of(x)
     if xb is not None:
       g, b0 = self._dw_gain, self._dw_bias0
@@ -463,6 +562,10 @@ class EposNet(object):
     cout_t = self.ckpt[scope + '/weights'].shape[3]
     self._trace_layer(name, 'conv2d', 3, stride, rate, 'SAME' if stride == 1 else 'VALID',
                       cin, cout_t, eps, False, ein, (ho, wo))
+    if self.bf16:
+      mode = _lib.PREPROCESS_UNIT_RANGE if preprocess else _lib.PREPROCESS_NONE
+      return self._conv_im2col_bf16(name, x, hi, wi, cin, scope, eps, 3, stride, rate, rate,
+                                    mode, ho, wo)
     if cin % 32 == 0 and not preprocess:
       # implicit GEMM: the LDS-DMA kernel gathers the shifted input pixels itself
       w_kn, scale, bias = self._conv_params(scope, eps)
@@ -495,6 +598,7 @@ class EposNet(object):
     ldcol = (k + 3) // 4 * 4
     m = self.B * ho * wo
     col = self._empty(m, ldcol)
+    self._col_ids.add(id(col))
     args = _lib.Im2colArgs(
         X=_ptr(x), ldx=cin, col=_ptr(col), ldcol=ldcol, B=self.B, Hi=hi, Wi=wi,
         Ho=ho, Wo=wo, C=cin, stride=stride, rate=rate, pad=rate,
@@ -532,10 +636,14 @@ class EposNet(object):
     cout_t = self.ckpt[scope + '/weights'].shape[3]
     self._trace_layer(name, 'conv2d', kk, stride, 1, 'SAME' if stride == 1 else 'VALID',
                       cin, cout_t, eps, False, ein, (ho, wo))
+    mode = {'unit_range': _lib.PREPROCESS_UNIT_RANGE, 'sub_mean': _lib.PREPROCESS_SUB_MEAN}
+    if self.bf16:
+      return self._conv_im2col_bf16(name, x, hi, wi, cin, scope, eps, kk, stride, 1, pad,
+                                    mode[preprocess], ho, wo)
     ldcol = (k + 3) // 4 * 4
     m = self.B * ho * wo
     col = self._empty(m, ldcol)
-    mode = {'unit_range': _lib.PREPROCESS_UNIT_RANGE, 'sub_mean': _lib.PREPROCESS_SUB_MEAN}
+    self._col_ids.add(id(col))
     args = _lib.Im2colKArgs(
         X=_ptr(x), ldx=cin, col=_ptr(col), ldcol=ldcol, B=self.B, Hi=hi, Wi=wi,
         Ho=ho, Wo=wo, C=cin, k=kk, stride=stride, rate=1, pad=pad,
@@ -553,6 +661,37 @@ class EposNet(object):
     # no bound on the col matrix (float inputs outside [0, 255] are legal): fp32 GEMM
     self._pointwise(name, col, 0, ldcol, m, k, w_kn, scale, bias, y, 0, cout,
                     relu=True, trace=False)
+    self._set_expr(y, 'relu(L:%s)' % name)
+    return y, ho, wo, cout
+
+  def _conv_im2col_bf16(self, name, x, hi, wi, cin, scope, eps, kk, stride, rate, pad, mode,
+                        ho, wo):
+    """bf16 mode: a dense kk x kk conv (+BN+ReLU) = epos_im2col_bf16 into the plan's shared
+    column scratch + the bf16 GEMM (the trace record is the caller's). x is the fp32 image
+    (mode = its preprocessing) or a bf16 activation."""
+    k = kk * kk * cin
+    ldcol = (k + 7) // 8 * 8
+    m = self.B * ho * wo
+    self._col_elems = max(self._col_elems, m * ldcol)
+    args = _lib.Im2colBf16Args(
+        X=_ptr(x), ldx=cin, x_bf16=int(x.dtype == torch.bfloat16), col=None, ldcol=ldcol,
+        B=self.B, Hi=hi, Wi=wi, Ho=ho, Wo=wo, C=cin, k=kk, stride=stride, rate=rate, pad=pad,
+        preprocess=mode, mean_rgb=(ctypes.c_float * 3)(*W.MEAN_RGB))
+    self._col_users.append((args, 'col'))
+    lib = self.lib
+
+    def run(stream, args=args):
+      _lib.check(lib.epos_im2col_bf16(ctypes.byref(args), stream), name)
+    self._add(name + '/im2col', run, 0, 'im2col')
+    w_kn, scale, bias = self._conv_params(scope, eps)
+    cout = w_kn.shape[1]
+    y = self._abuf(self.B, ho, wo, cout)
+    gargs = self._pointwise_bf16(name, None, 0, ldcol, m, k, w_kn, scale, bias, y, 0, cout,
+                                 relu=True)
+    self._col_users.append((gargs, 'A'))
+    # fusion-group bytes: the input is read once, the column matrix does not exist
+    a_bytes, rest, _ = self.op_io[name]
+    self.op_io[name] = (x.element_size() * self.B * hi * wi * cin, rest, id(x))
     self._set_expr(y, 'relu(L:%s)' % name)
     return y, ho, wo, cout
 
@@ -574,44 +713,49 @@ class EposNet(object):
       if stride == 1:
         shortcut = x
       else:                                    # resnet_utils.subsample (:71-72)
-        shortcut = self._empty(B, ho, wo, depth)
+        shortcut = self._abuf(B, ho, wo, depth)
+        sub_fn = 'epos_subsample_bf16' if self.bf16 else 'epos_subsample_f32'
 
         def run_sub(stream, x=x, y=shortcut):
-          _lib.check(lib.epos_subsample_f32(_ptr(x), cin, _ptr(y), depth, B, hi,
-                                            wi, cin, stride, stream), 'subsample')
+          _lib.check(getattr(lib, sub_fn)(_ptr(x), cin, _ptr(y), depth, B, hi,
+                            wi, cin, stride, stream), 'subsample')
         self._add(scope + '/shortcut_subsample', run_sub)
-        self._glue_bytes = getattr(self, '_glue_bytes', 0) + 8 * B * ho * wo * depth
+        self._glue_bytes = (getattr(self, '_glue_bytes', 0) +
+                            2 * shortcut.element_size() * B * ho * wo * depth)
         self._set_expr(shortcut, 'subsample(%s,%d)' % (self._expr_of(x, 0, cin), stride))
         if self._bound_of(x) is not None:
           self._set_bound(shortcut, *self._bound_of(x))
     else:
       w_kn, sc, bi = self._conv_params(scope + '/shortcut', eps)
-      shortcut = self._empty(B, ho, wo, depth)
+      shortcut = self._abuf(B, ho, wo, depth)
       self._pointwise(scope + '/shortcut', x, 0, cin, m_out, cin, w_kn, sc, bi,
                       shortcut, 0, depth, relu=False, sub=stride, ho=ho, wo=wo,
                       hi=hi, wi=wi)
     w_kn, sc, bi = self._conv_params(scope + '/conv1', eps)
-    r1 = self._empty(B, hi, wi, db)
+    r1 = self._abuf(B, hi, wi, db)
     self._pointwise(scope + '/conv1', x, 0, cin, m_in, cin, w_kn, sc, bi, r1, 0,
                     db, relu=True)
     r2, _, _, _ = self._stem_conv(scope + '/conv2', r1, hi, wi, db,
                                   scope + '/conv2', stride, False, eps=eps,
                                   rate=rate)
     w_kn, sc, bi = self._conv_params(scope + '/conv3', eps)
-    out = self._empty(B, ho, wo, depth)
+    out = self._abuf(B, ho, wo, depth)
     conv3 = None
     if keep_conv3:
-      conv3 = self._empty(B, ho, wo, depth)
+      conv3 = self._abuf(B, ho, wo, depth)
       self._pointwise(scope + '/conv3', r2, 0, db, m_out, db, w_kn, sc, bi, conv3,
                       0, depth, relu=False)
 
+      add_fn = 'epos_add_relu_bf16' if self.bf16 else 'epos_add_relu_f32'
+
       def run_add(stream, a=conv3, b=shortcut, y=out):
-        _lib.check(lib.epos_add_relu_f32(_ptr(a), _ptr(b), _ptr(y),
-                                         m_out * depth, stream), 'add_relu')
+        _lib.check(getattr(lib, add_fn)(_ptr(a), _ptr(b), _ptr(y), m_out * depth, stream), 'add_relu')
       self._add(scope + '/add_relu', run_add)
-      self._glue_bytes = getattr(self, '_glue_bytes', 0) + 12 * m_out * depth
+      self._glue_bytes = getattr(self, '_glue_bytes', 0) + 3 * out.element_size() * m_out * depth
       self._set_expr(out, 'relu(add(%s))' % ','.join(sorted(
           [self._expr_of(conv3), self._expr_of(shortcut)])))
+      if self.bf16:                            # no absmax slots in bf16 mode
+        return out, ho, wo, depth, conv3
       oslot = self._new_slot()
       self._set_bound(out, oslot)
 
@@ -638,13 +782,14 @@ class EposNet(object):
       x, h, w, c = self._root_conv(net + '/conv1', x, h, w, c, net + '/conv1', 2,
                                    self.variant['preprocess'], RESNET_BN_EPS)
     ph, pw = (h + 1) // 2, (w + 1) // 2
-    pooled = self._empty(B, ph, pw, c)
+    pooled = self._abuf(B, ph, pw, c)
+    pool_fn = 'epos_maxpool3x3_s2_bf16' if self.bf16 else 'epos_maxpool3x3_s2_f32'
 
     def run_pool(stream, x=x, y=pooled, h=h, w=w, c=c):
-      _lib.check(lib.epos_maxpool3x3_s2_f32(_ptr(x), c, _ptr(y), c, B, h, w, c,
-                                            stream), 'maxpool')
+      _lib.check(getattr(lib, pool_fn)(_ptr(x), c, _ptr(y), c, B, h, w, c, stream), 'maxpool')
     self._add(net + '/pool1', run_pool)                      # :190
-    self._glue_bytes = getattr(self, '_glue_bytes', 0) + 4 * B * (h * w + ph * pw) * c
+    self._glue_bytes = (getattr(self, '_glue_bytes', 0) +
+                        pooled.element_size() * B * (h * w + ph * pw) * c)
     self._set_expr(pooled, 'maxpool(%s,3,2,SAME)' % self._expr_of(x, 0, c))
     if self._bound_of(x) is not None:          # a max-pool output is bounded by its input
       self._set_bound(pooled, *self._bound_of(x))
@@ -764,7 +909,8 @@ class EposNet(object):
     def run_clear(stream):
       _lib.check(lib0.epos_amax_clear(_ptr(self._amax_table), self._n_slots, stream),
                  'amax_clear')
-    self._add('amax_clear', run_clear)
+    if not self.bf16:
+      self._add('amax_clear', run_clear)
     if self.variant['family'] == 'xception':
       x, h, w, c, low_level = self._backbone_xception()
     else:
@@ -775,7 +921,7 @@ class EposNet(object):
 
     # ---- ASPP (model.py:213-265): branches write slices of one 1280-wide buffer.
     nb = 2 + len(self.atrous_rates)
-    cat = self._empty(B, eh, ew, 256 * nb)
+    cat = self._abuf(B, eh, ew, 256 * nb)
     ldcat = 256 * nb
     m_enc = B * eh * ew
     pooled = self._empty(B, ec)
@@ -787,7 +933,7 @@ class EposNet(object):
     # (EPOS_POOL_FOLD=0: the stand-alone reduction, as for ResNet, whose last launch carries
     # a residual, and for batches whose images are not a whole number of 32-row blocks).
     lp = getattr(self, '_last_pw', None)
-    fold_pool = (not self.dry_run and os.environ.get('EPOS_POOL_FOLD', '1') == '1' and
+    fold_pool = (not self.dry_run and not self.bf16 and os.environ.get('EPOS_POOL_FOLD', '1') == '1' and
                  lp is not None and lp[0] is x and lp[2] and
                  ((eh * ew) % 32 == 0 or B == 1))
     self.pool_folded = bool(fold_pool)
@@ -802,9 +948,10 @@ class EposNet(object):
                                                         blocks, ec, eh * ew, stream),
                    'avg_pool_partial')
     else:
+      avg_fn = 'epos_global_avg_pool_bf16' if self.bf16 else 'epos_global_avg_pool_f32'
+
       def run_pool(stream, x=x, pooled=pooled):
-        _lib.check(lib.epos_global_avg_pool_f32(_ptr(x), ec, _ptr(pooled), B,
-                                                eh * ew, ec, stream), 'avg_pool')
+        _lib.check(getattr(lib, avg_fn)(_ptr(x), ec, _ptr(pooled), B, eh * ew, ec, stream), 'avg_pool')
     self._add('image_pooling/mean', run_pool)
     self._set_expr(pooled, 'mean(%s)' % self._expr_of(x, 0, ec))
     w_kn, sc, bi = self._conv_params('image_pooling', HEAD_BN_EPS)
@@ -813,6 +960,11 @@ class EposNet(object):
                     pool_feat, 0, 256, relu=True)
 
     def run_bcast(stream, pool_feat=pool_feat, cat=cat):
+      if self.bf16:            # the fp32 pooled branch broadcast into the bf16 concat
+        _lib.check(lib.epos_resize_bilinear_bf16(
+            _ptr(pool_feat), 256, 1, _ptr(cat), ldcat, B, 1, 1, eh, ew, 256, stream),
+                   'image_pooling/resize')
+        return
       _lib.check(lib.epos_resize_bilinear_f32(
           _ptr(pool_feat), 256, _ptr(cat), ldcat, B, 1, 1, eh, ew, 256, stream),
                  'image_pooling/resize')
@@ -841,7 +993,7 @@ class EposNet(object):
                    'image_pooling/absmax')
       self._add('image_pooling/absmax', run_pool_amax)
     w_kn, sc, bi = self._conv_params('concat_projection', HEAD_BN_EPS)
-    proj = self._empty(B, eh, ew, 256)
+    proj = self._abuf(B, eh, ew, 256)
     self._pointwise('concat_projection', cat, 0, ldcat, m_enc, ldcat, w_kn, sc,
                     bi, proj, 0, 256, relu=True)
     self.aspp_concat, self.concat_projection = cat, proj
@@ -853,10 +1005,15 @@ class EposNet(object):
     assert (lh, lw) == (dh, dw_), ((lh, lw), (dh, dw_))
     # (padding the concat's rows 304 -> 320 and the stem's im2col rows 28 -> 32 as well:
     # measured neutral, profiles/r06/ab_pad_level.txt -- left dense)
-    dcat = self._empty(B, dh, dw_, 304)
+    dcat = self._abuf(B, dh, dw_, 304)
     ldd = self._ld(dcat)
 
     def run_up(stream, proj=proj, dcat=dcat, ldd=ldd):
+      if self.bf16:
+        _lib.check(lib.epos_resize_bilinear_bf16(
+            _ptr(proj), 256, 0, _ptr(dcat), ldd, B, eh, ew, dh, dw_, 256, stream),
+                   'decoder/resize')
+        return
       _lib.check(lib.epos_resize_bilinear_f32(
           _ptr(proj), 256, _ptr(dcat), ldd, B, eh, ew, dh, dw_, 256, stream),
                  'decoder/resize')
@@ -881,7 +1038,7 @@ class EposNet(object):
       d, _, _ = self._depthwise(scope + '_depthwise', x, self._ld(x), dh, dw_, c, 1, 1,
                                 scope + '_depthwise', HEAD_BN_EPS, False, True)
       w_kn, sc, bi = self._conv_params(scope + '_pointwise', HEAD_BN_EPS)
-      y = self._empty(B, dh, dw_, 256)
+      y = self._abuf(B, dh, dw_, 256)
       self._pointwise(scope + '_pointwise', d, 0, self._ld(d), m_dec, c, w_kn, sc, bi, y,
                       0, 256, relu=True)
       x, c = y, 256
@@ -920,6 +1077,9 @@ class EposNet(object):
     oname, oargs, oflops = obj_only[0][:3]
 
     def run_obj_head(stream, args=oargs):
+      if self.bf16:
+        _lib.check(lib.epos_pointwise_conv_bf16(ctypes.byref(args), 1, stream), oname)
+        return
       _lib.check(lib.epos_pointwise_conv_f32(ctypes.byref(args), stream), oname)
     self._obj_head_op = (oname, run_obj_head)
     self._obj_head_flops = oflops
@@ -958,6 +1118,12 @@ class EposNet(object):
                            'shape': [B, dh, dw_, O, F]},
         W.PRED_FRAG_LOC: {'expr': 'reshape(%s,%s)' % (el, [O, F, 3]),
                           'shape': [B, dh, dw_, O, F, 3]}}
+    # bf16 mode: the shared im2col scratch, sized for the largest column matrix of the plan
+    if self._col_users:
+      col = self._empty(self._col_elems, dtype=torch.bfloat16)
+      self._col_ids.add(id(col))
+      for args, field in self._col_users:
+        setattr(args, field, _ptr(col))
     # The slot table is zeroed by the plan's first launch. Round 4: that is the im2col of the
     # first stem conv itself (EposIm2colArgs.amax_clear) when it directly follows -- one
     # launch less per image (EPOS_AMAX_CLEAR_FOLD=0 keeps the separate kernel).
@@ -1040,6 +1206,11 @@ class EposNet(object):
     packs = []
     for o in range(O):
       one_c, one_l = np.ones(F, np.float32), np.ones(3 * F, np.float32)
+      if self.bf16:
+        packs.append((self._pack_bf16(wc[:, o * F:(o + 1) * F], one_c, bc[o * F:(o + 1) * F]),
+                      self._pack_bf16(wl[:, o * 3 * F:(o + 1) * 3 * F], one_l,
+                                      bl[o * 3 * F:(o + 1) * 3 * F])))
+        continue
       pc = self._pack_pointwise(wc[:, o * F:(o + 1) * F], one_c,
                                 bc[o * F:(o + 1) * F])
       pc = pc + (self._pack_split(wc[:, o * F:(o + 1) * F], one_c),
@@ -1070,6 +1241,17 @@ class EposNet(object):
     for kind in (0, 1):
       probs = []
       for im, obj_id in slots:
+        if self.bf16:
+          wp, bp, _ = self._sparse_packs[obj_id - 1][kind]
+          n = F if kind == 0 else 3 * F
+          buf = conf if kind == 0 else loc
+          ldc = O * n
+          probs.append(_lib.PointwiseBf16Args(
+              A=_ptr(x, im * P * 256), lda=256, Wp=_ptr(wp), bias=_ptr(bp), R=None, ldr=0,
+              C=_ptr(buf, im * P * ldc + (obj_id - 1) * n), ldc=ldc, M=P, N=n, K=256,
+              relu=0, sub=1, c_f32=1))
+          flops += 2 * P * n * 256
+          continue
         wp, bp, _, ws, wh = self._sparse_packs[obj_id - 1][kind]
         xb = self._bound_of(x)
         if xb is None:
@@ -1089,6 +1271,10 @@ class EposNet(object):
         flops += 2 * P * n * 256
       for i in range(0, len(probs), 8):
         chunk = probs[i:i + 8]
+        if self.bf16:
+          arr = (_lib.PointwiseBf16Args * len(chunk))(*chunk)
+          _lib.check(lib.epos_pointwise_conv_bf16(arr, len(chunk), s), 'sparse heads')
+          continue
         arr = (_lib.PointwiseArgs * len(chunk))(*chunk)
         _lib.check(lib.epos_pointwise_conv_grouped_f32(arr, len(chunk), s), 'sparse heads')
     if slots:

@@ -56,11 +56,14 @@ class EposPipeline(object):
                corr_min_frag_rel_conf=0.5, max_slots=None, capacity=1 << 20,
                max_instances=4, model_options=None, device='cuda:0',
                use_graph=True, instance=0, sparse_heads=False,
-               fitting_method='progressive_x', on_excess='raise', queue=1):
+               fitting_method='progressive_x', on_excess='raise', queue=1,
+               precision='fp32'):
     """on_excess: what launch() does with a frame that asks for more instances of an object
     than `max_instances` (localization): 'raise' (default: EposError BEFORE anything of that
     batch is enqueued -- batches already in flight on other pipelines are unaffected and can
     still be collected) or 'clamp' (fit `max_instances` of them and warn once).
+    precision: the network's numeric mode, 'fp32' (default) or 'bf16' (EposNet); the
+    correspondence and fitting stages run unchanged on its fp32 head tensors.
     capacity: correspondence rows per batch, over all slots, at up to 64 fragments per object.
     A masked pixel yields up to F rows, so the correspondence and fitting buffers are sized for
     `capacity * ceil(num_frags / 64)` rows (self.capacity); for num_frags <= 64 that is
@@ -88,7 +91,8 @@ class EposPipeline(object):
     self.B, self.H, self.W = batch, height, width
     self.O, self.F = num_objs, num_frags
     self.net = _model.get_net(checkpoint, batch, height, width, num_objs,
-                              num_frags, model_options, device, instance)
+                              num_frags, model_options, device, instance,
+                              precision=precision)
     self.use_graph = use_graph
     # sparse_heads: evaluate the fragment heads only for the (image, target
     # object) slots of the batch instead of all O objects. Identical poses (the

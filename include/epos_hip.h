@@ -574,6 +574,89 @@ int epos_solve_pnp_ransac_device(const double* xy, const double* xyz,
                                  double* poses, int32_t* success, uint8_t* inlier_mask,
                                  int32_t* info, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * bf16 inference mode (EposNet(precision='bf16')). Activations are stored as bf16 (the top
+ * 16 bits of an IEEE fp32, rounded to nearest even); products are bf16 x bf16 on the matrix
+ * cores with fp32 accumulation; every epilogue (bias, residual, ReLU) runs in fp32 and rounds
+ * once when it stores. Pointers typed uint16_t hold bf16 bit patterns.
+ * --------------------------------------------------------------------------------------- */
+
+/* Folded 1x1 weights W [K][N] (fp32, row-major) -> bf16 (RNE) in the layout of
+ * epos_pointwise_conv_bf16: dst[((k / 8) * Npad + n) * 8 + k % 8] for k < round_up(K, 32),
+ * n < Npad = round_up(N, 128), zero outside [K) x [N). Returns the element count
+ * (round_up(K, 32) * Npad); dst == NULL only queries it. K, N >= 1. */
+int64_t epos_pack_pointwise_weights_bf16(const float* W, int K, int N, uint16_t* dst);
+
+/* C[m, n] = act(sum_{k<K} A[row(m), k] * W[k, n] + bias[n] (+ R[m, n])), bf16 x bf16 products,
+ * fp32 accumulation and epilogue, ReLU last. A [device]: bf16 rows of lda elements (only
+ * columns < K are read); row(m) as in EposPointwiseArgs (sub > 1: 1x1 stride-`sub` conv of a
+ * [B, Hi, Wi] map, M = B*Ho*Wo). Wp: epos_pack_pointwise_weights_bf16; bias: N floats or
+ * NULL; R: optional bf16 residual rows of ldr elements; C: rows of ldc elements, bf16
+ * (c_f32 == 0, rounded to nearest even) or fp32 (c_f32 != 0; c_stream != 0: non-temporal
+ * stores). K % 8 == 0, lda % 8 == 0, lda >= K, A 16-byte aligned. */
+typedef struct EposPointwiseBf16Args {
+  const uint16_t* A; int64_t lda;
+  const uint16_t* Wp; const float* bias;
+  const uint16_t* R; int64_t ldr;
+  void* C; int64_t ldc;
+  int32_t M, N, K;
+  int32_t relu;
+  int32_t sub;
+  int32_t Ho, Wo, Hi, Wi;   /* only read when sub > 1 */
+  int32_t c_f32;
+  int32_t c_stream;
+} EposPointwiseBf16Args;
+/* 1..8 independent problems in one launch. */
+int epos_pointwise_conv_bf16(const EposPointwiseBf16Args* args, int count, void* stream);
+
+/* Depthwise 3x3 with the semantics of epos_depthwise3x3_f32 (stride 1 SAME with `rate`;
+ * stride 2 fixed_padding + VALID; relu_in / relu_out) on bf16 X / Y: fp32 folded weights
+ * w9c [9][C] and bias [C], fp32 math, one RNE rounding per output.
+ * C, ldx, ldy multiples of 8; X, Y, w9c, bias 16-byte aligned. */
+typedef struct EposDepthwiseBf16Args {
+  const uint16_t* X; int64_t ldx;
+  const float* w9c; const float* bias;
+  uint16_t* Y; int64_t ldy;
+  int32_t B, Hi, Wi, Ho, Wo, C;
+  int32_t stride, rate;
+  int32_t relu_in, relu_out;
+} EposDepthwiseBf16Args;
+int epos_depthwise3x3_bf16(const EposDepthwiseBf16Args* args, void* stream);
+
+/* k x k im2col into bf16 columns: col[m, (ky*k+kx)*C + c] = bf16(pre(X[...])) as in
+ * epos_im2col_f32, zero for padded taps and for the columns k*k*C .. ldcol. X is the fp32
+ * image (x_bf16 == 0, with the three preprocess modes) or a bf16 activation (x_bf16 != 0,
+ * preprocess must be EPOS_PREPROCESS_NONE). ldcol % 8 == 0, col 16-byte aligned. */
+typedef struct EposIm2colBf16Args {
+  const void* X; int64_t ldx;
+  int32_t x_bf16;
+  int32_t reserved0;
+  uint16_t* col; int64_t ldcol;
+  int32_t B, Hi, Wi, Ho, Wo, C;
+  int32_t k, stride, rate, pad;
+  int32_t preprocess;
+  float mean_rgb[3];
+} EposIm2colBf16Args;
+int epos_im2col_bf16(const EposIm2colBf16Args* args, void* stream);
+
+/* The glue layers of the bf16 plan: the fp32 kernels' semantics on bf16 tensors (fp32 math,
+ * one RNE rounding per stored value). C, ld* multiples of 8 and 16-byte aligned rows. */
+/* Bilinear resize, align_corners=True; X is bf16, or fp32 when x_f32 != 0 (the image-pooling
+ * broadcast from its fp32 1x1 output). */
+int epos_resize_bilinear_bf16(const void* X, int64_t ldx, int x_f32, uint16_t* Y,
+                              int64_t ldy, int B, int Hi, int Wi, int Ho, int Wo, int C,
+                              void* stream);
+/* Global mean over H*W into fp32: X [B, HW, C] (ldx) -> Y [B, C]. */
+int epos_global_avg_pool_bf16(const uint16_t* X, int64_t ldx, float* Y, int B, int HW, int C,
+                              void* stream);
+int epos_maxpool3x3_s2_bf16(const uint16_t* X, int64_t ldx, uint16_t* Y, int64_t ldy,
+                            int B, int Hi, int Wi, int C, void* stream);
+int epos_subsample_bf16(const uint16_t* X, int64_t ldx, uint16_t* Y, int64_t ldy, int B,
+                        int Hi, int Wi, int C, int factor, void* stream);
+/* Y = relu(A + B) over n contiguous bf16 values, n % 8 == 0. */
+int epos_add_relu_bf16(const uint16_t* A, const uint16_t* B, uint16_t* Y, int64_t n,
+                       void* stream);
+
 #ifdef __cplusplus
 }
 #endif

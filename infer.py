@@ -97,6 +97,8 @@ def build_parser():
   a('--max_correspondences', type=int, default=None)
   a('--max_instances_to_fit', type=int, default=None)
   a('--detection_instance_cap', type=int, default=DETECTION_INSTANCE_CAP)   # not in the reference
+  # not in the reference: the network's numeric mode ("bf16 mode")
+  a('--precision', type=str, default='fp32', choices=['fp32', 'bf16'])
   a('--max_fitting_iterations', type=int, default=400)
   a('--vis', type=str2bool, default=False)
   a('--vis_gt_poses', type=str2bool, default=True)           # infer.py:126-146
@@ -589,7 +591,8 @@ def main(argv=None):
       corr_min_obj_conf=args.corr_min_obj_conf,
       corr_min_frag_rel_conf=args.corr_min_frag_rel_conf,
       max_instances=max_inst, model_options=mo, device=dev, instance=j,
-      sparse_heads=sparse_heads, fitting_method=args.fitting_method, queue=lq)
+      sparse_heads=sparse_heads, fitting_method=args.fitting_method, queue=lq,
+      precision=args.precision)
            for j in range(depth)]
   pipe = pipes[0]
   if rank == 0:
