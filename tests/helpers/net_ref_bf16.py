@@ -14,7 +14,7 @@ Storage points of the plan ("bf16 mode"), as the wrappers restate the
     the ResNet unit whose conv3 is the decoder tap stores conv3 first (separate add + ReLU);
   * resize, max-pool, subsample, concat and the global mean read bf16 (the image-pooling
     broadcast reads the fp32 1x1 output);
-  * weights: BN folded in float32 (as weights.fold_bn / EposNet._pack_bf16), rounded to bf16,
+  * weights: BN folded in float32 (as weights.fold_bn / Bf16Mode._weights), rounded to bf16,
     re-expressed in the unfolded checkpoint (w' = bf16(w * scale) / scale in float64); the logits
     weights rounded as they are; depthwise and image-pooling weights stay fp32;
   * the logits are not rounded (fp32 heads).

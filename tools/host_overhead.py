@@ -20,10 +20,10 @@ infl = []
 for i in range(n):
   p = pipes[i % 4]
   if len(infl) == 4:
-    q = infl.pop(0); a = time.perf_counter(); q._done.synchronize(); b = time.perf_counter(); q.collect(); tc += time.perf_counter() - b
+    q = infl.pop(0); a = time.perf_counter(); q._dones[q._pending[0][-1]].synchronize(); b = time.perf_counter(); q.collect(); tc += time.perf_counter() - b
   a = time.perf_counter(); p.launch(img, Ks, tg, image_ids=[1], seed=i); tl += time.perf_counter() - a
   infl.append(p)
 while infl:
-  q = infl.pop(0); q._done.synchronize(); b = time.perf_counter(); q.collect(); tc += time.perf_counter() - b
+  q = infl.pop(0); q._dones[q._pending[0][-1]].synchronize(); b = time.perf_counter(); q.collect(); tc += time.perf_counter() - b
 tot = time.perf_counter() - t0
 print('per step: wall %.3f ms, host in launch() %.3f ms, host in collect() after the wait %.3f ms' % (tot / n * 1e3, tl / n * 1e3, tc / n * 1e3))
