@@ -15,7 +15,10 @@ shard stays 4 images at N = 2 and 4 too). The ranks exchange nothing per step; t
 pose records are gathered once (RCCL all_gather) before the timed region closes. Weights are random-init with the
 reference's initialisers (no network access for the released checkpoints).
 
-Prints ONE JSON line on rank 0 with the driver's contract fields plus
+Prints ONE JSON line on rank 0 with the driver's contract fields and the configuration. A
+plain run does nothing else: set-up, warm-up, the timed steps, --dump-outputs. With --full the
+line also carries what takes runs of its own after the timed region ("serial_depth1",
+"planted", the in-step decomposition, clock and power under load) and
   "roofline":     matrix-pipe roofline of the dominant kernel (pointwise_gemm_split_f32:
                   fp32 GEMM as six bf16 piece products), measured with HIP events
                   around every GEMM launch; its "traffic" (HBM-side bytes per launch) is
@@ -101,6 +104,13 @@ def parse_args():
   ap.add_argument('--dump-outputs', metavar='DIR', default=None,
                   help='after the timed region, write what its LAST step computed to DIR as '
                        '.npy files (see dump_outputs); rank 0 only')
+  ap.add_argument('--full', action='store_true',
+                  help='after the timed region, also measure and check what takes runs of its '
+                       'own: the in-step decomposition, clock and power under load, the serial '
+                       'steps with per-stage times, the GEMM / depthwise rooflines with their '
+                       'HBM traffic and the CPU baseline (the --no-* and --traffic options '
+                       'leave them out one by one), and the --planted-poses check; default: '
+                       'the result line of the timed steps only')
   ap.add_argument('--batch-per-gpu', type=int, default=None,
                   help='images per GPU per step; default 1 at --gpus 1 (config C2), 4 '
                        'at --gpus > 1 (the per-GPU shard of config C3: 32 images / 8)')
@@ -142,7 +152,7 @@ def parse_args():
                   help='batches enqueued per pipeline before the oldest is collected '
                        '(EposPipeline(queue=)): with 2 a pipeline\'s next batch is already in its '
                        'stream when the current one finishes, so the stream does not wait for the '
-                       'host between two batches (default 2: +0.3..+0.8 %, profiles/r06/ab_launch_queue_*.txt; '
+                       'host between two batches (default 2: +0.3..+0.8 %%, profiles/r06/ab_launch_queue_*.txt; '
                        'the strictly serial figure serial_depth1 always launches and collects one at a time)')
   ap.add_argument('--pipeline-depth', type=int, default=0,
                   help='batches in flight per GPU: with >= 2, the fitting tail of '
@@ -280,8 +290,7 @@ def measure_traffic_live(args, timeout=240):
            '--height', str(args.height), '--width', str(args.width),
            '--num-objs', str(args.num_objs), '--num-frags', str(args.num_frags),
            '--objs-per-image', str(args.objs_per_image), '--model-variant',
-           args.model_variant, '--no-cpu-baseline', '--no-roofline', '--no-stage-times',
-           '--traffic', 'off', '--weights', args.weights]
+           args.model_variant, '--weights', args.weights]     # a plain run: no --full
     if args.sparse_heads:
       cmd.append('--sparse-heads')
     env = dict(os.environ, TMPDIR='/tmp', EPOS_BENCH_CHILD='1')
@@ -477,6 +486,15 @@ def smi_sample(idx):
     return None, None
 
 
+def emit(result, rank, world):
+  """Every rank is done: rank 0 prints the one JSON line."""
+  edist.barrier()
+  if rank == 0:
+    print(json.dumps(result))
+  if world > 1:
+    torch.distributed.destroy_process_group()
+
+
 def main():
   args = parse_args()
   rank, world, local_rank = edist.init_from_env()
@@ -491,7 +509,8 @@ def main():
   torch.cuda.set_device(dev_index)
   dev = 'cuda:%d' % dev_index
   # the box's idle power, before this process has put any work on the device
-  smi_index = smi_device_index(dev_index) if (world == 1 and not args.no_roofline) else None
+  smi_index = (smi_device_index(dev_index)
+               if (world == 1 and args.full and not args.no_roofline) else None)
   idle_w = None
   if smi_index is not None:
     idle = [smi_sample(smi_index)[0] for _ in range(3)]
@@ -714,6 +733,18 @@ def main():
           'algorithmic_gflop_per_image': round(pipe.net.flops / B / 1e9, 1),
       },
   }
+  # Comparability (ADVICE r2): what a step is made of, at the top level of the line
+  fitp = pipe.fit
+  result['batch_per_gpu'] = B
+  result['pipeline_depth'] = depth
+  result['launch_queue'] = pipe.queue
+  result['fit'] = {'method': args.fitting_method, 'max_iters': int(fitp.max_iters),
+                   'lo_iters': int(fitp.lo_iters), 'gc_sweeps': int(fitp.gc_sweeps),
+                   'pearl_iters': int(fitp.pearl_iters), 'max_instances': args.instances,
+                   'rounds_per_step': args.instances + (2 if args.instances > 1 else 0)}
+  if not args.full:     # a plain run: the line of the timed steps, nothing more
+    emit(result, rank, world)
+    return
   # --planted-poses: the poses that come back are the planted ones (every pool frame once more
   # through pipes[0], outside the timed region): < 1 degree, < 5 mm
   if plants is not None:
@@ -758,15 +789,6 @@ def main():
                'live fragments per pixel; 3D noise of 1 px of reprojection; the given fraction '
                'of masked pixels turned into outliers); three launches per step inside the '
                'timed region; the check runs every pool frame once more after it'}
-  # Comparability (ADVICE r2): what a step is made of, at the top level of the line
-  fitp = pipe.fit
-  result['batch_per_gpu'] = B
-  result['pipeline_depth'] = depth
-  result['launch_queue'] = pipe.queue
-  result['fit'] = {'method': args.fitting_method, 'max_iters': int(fitp.max_iters),
-                   'lo_iters': int(fitp.lo_iters), 'gc_sweeps': int(fitp.gc_sweeps),
-                   'pearl_iters': int(fitp.pearl_iters), 'max_instances': args.instances,
-                   'rounds_per_step': args.instances + (2 if args.instances > 1 else 0)}
   # Decomposition of the TIMED step (same pipelined regime, same steps): the plans' graphs
   # are re-captured without their GEMM / depthwise launches and the same `steps` steps are
   # timed again; step - that = what those kernels cost inside the step, overlap with the
@@ -944,11 +966,7 @@ def main():
       and args.fitting_method == 'progressive_x'):
     result['cpu_baseline'] = cpu_baseline(ckpt, store, args,
                                           args.cpu_baseline_images)
-  edist.barrier()
-  if rank == 0:
-    print(json.dumps(result))
-  if world > 1:
-    torch.distributed.destroy_process_group()
+  emit(result, rank, world)
 
 
 if __name__ == '__main__':

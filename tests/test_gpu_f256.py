@@ -391,7 +391,7 @@ def test_infer_f256_with_fragments_from_ply_models(tmp_path, gpu_children):
 @pytest.mark.parametrize('sparse', [False, True], ids=['dense', 'sparse'])
 def test_bench_f256_prints_its_json_line(sparse, gpu_children):
   cmd = ['timeout', '-k', '10', '900', sys.executable, os.path.join(ROOT, 'bench.py'),
-         '--num-frags', '256', '--steps', '3', '--warmup', '1', '--no-cpu-baseline',
+         '--num-frags', '256', '--steps', '3', '--warmup', '1', '--full', '--no-cpu-baseline',
          '--traffic', 'off'] + (['--sparse-heads'] if sparse else [])
   out = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=930)
   assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-3000:]

@@ -191,7 +191,7 @@ def test_bench_multi_rank_flow_on_one_gpu(gpu_children):
   cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1',
          '--nproc-per-node', '2', '--master-addr', '127.0.0.1', '--master-port',
          str(port), os.path.join(root, 'bench.py'), '--gpus', '2', '--steps', '4',
-         '--warmup', '1', '--no-cpu-baseline', '--no-roofline']
+         '--warmup', '1', '--full', '--no-cpu-baseline', '--no-roofline']
   out = subprocess.run(cmd, env=env, cwd=root, capture_output=True, text=True,
                        timeout=600)
   assert out.returncode == 0, out.stderr[-2000:]

@@ -2,7 +2,7 @@
 # Same-box comparison of bench.py argument sets (interleaved, REPS rounds):
 #   bash tools/ab_args.sh "" "--pipeline-depth 2" "--sparse-heads --pipeline-depth 4"
 # extra environment / common arguments: COMMON="--steps 40 ..." (default below)
-COMMON=${COMMON:---steps 40 --warmup 8 --no-cpu-baseline --traffic off}
+COMMON=${COMMON:---steps 40 --warmup 8 --full --no-cpu-baseline --traffic off}
 for rep in $(seq ${REPS:-2}); do for A in "$@"; do
   python bench.py $COMMON $A 2>/tmp/ab_err.txt | tail -1 | python -c "
 import json,sys

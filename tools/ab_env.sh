@@ -4,7 +4,7 @@
 ENVS=()
 while [ $# -gt 0 ] && [ "$1" != "--" ]; do ENVS+=("$1"); shift; done
 [ "${1:-}" = "--" ] && shift
-COMMON=${COMMON:---steps 40 --warmup 8 --no-cpu-baseline --traffic off}
+COMMON=${COMMON:---steps 40 --warmup 8 --full --no-cpu-baseline --traffic off}
 for rep in $(seq ${REPS:-2}); do for E in "${ENVS[@]}"; do
   env $E python bench.py $COMMON "$@" 2>/tmp/ab_err.txt | tail -1 | python -c "
 import json,sys

@@ -3,7 +3,7 @@
 # (interleaved runs: A B A B; prints images/s, ms/step, serial images/s and the in-step split)
 A=$1; B=$2; shift 2
 for rep in 1 2; do for L in "$A" "$B"; do
-  EPOS_HIP_LIB=$L python bench.py --steps 60 --warmup 8 --no-cpu-baseline --traffic static "$@" 2>/dev/null | tail -1 | python -c "
+  EPOS_HIP_LIB=$L python bench.py --steps 60 --warmup 8 --full --no-cpu-baseline --traffic static "$@" 2>/dev/null | tail -1 | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); i=d['roofline'].get('in_step') or {}
 s=d.get('serial_depth1') or {}
