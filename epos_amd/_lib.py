@@ -204,6 +204,8 @@ SYMBOLS = {
                                 [ctypes.POINTER(PointwiseArgs), vp]),
     'epos_pointwise_conv_grouped_f32': (ctypes.c_int, [
         ctypes.POINTER(PointwiseArgs), ctypes.c_int, vp]),
+    'epos_heads_gemm_f32': (ctypes.c_int, [
+        ctypes.POINTER(PointwiseArgs), ctypes.c_int, vp]),
     'epos_conv3x3_f32': (ctypes.c_int, [ctypes.POINTER(Conv3x3Args), ctypes.c_void_p]),
     'epos_depthwise3x3_f32': (ctypes.c_int,
                               [ctypes.POINTER(DepthwiseArgs), vp]),

@@ -37,6 +37,13 @@ bool split_eligible(const EposPointwiseArgs* args, int count);
 int launch_grouped_h2(const EposPointwiseArgs* args, int count, hipStream_t s,
                       const int* conv_cin = nullptr, const int* conv_rate = nullptr);
 bool h2_eligible(const EposPointwiseArgs* args, int count);
+// heads_gemm_h2.hip: the A-stationary form of the fp16-pair GEMM for the dense logits heads
+// (one A shared by the group, K = 256, no residual / ReLU / absmax / column sums); same bits.
+bool heads_eligible(const EposPointwiseArgs* args, int count);
+int launch_heads_h2(const EposPointwiseArgs* args, int count, const float* zero_chunk,
+                    hipStream_t s);
+// pointwise_gemm_h2.hip: 16 zero bytes in device memory (nullptr during a first-use capture)
+const float* h2_zero_chunk(hipStream_t s);
 
 namespace {
 

@@ -159,6 +159,26 @@ extern "C" int epos_pointwise_conv_grouped_f32(const EposPointwiseArgs* args,
   return grouped_impl(args, count, stream);
 }
 
+// The dense logits heads (the plan's grouped head launch): the A-stationary fp16-pair kernel
+// (heads_gemm_h2.hip) when the group has its shape, otherwise exactly the grouped GEMM above.
+// Same bits either way.
+extern "C" int epos_heads_gemm_f32(const EposPointwiseArgs* args, int count, void* stream) {
+  using namespace epos;
+  EPOS_REQUIRE(args && count >= 1 && count <= MAX_GROUP, "1..8 problems per group");
+  if (!h2_eligible(args, count) || !heads_eligible(args, count))
+    return epos_pointwise_conv_grouped_f32(args, count, stream);
+  for (int i = 0; i < count; ++i) {
+    EPOS_REQUIRE(args[i].reserved0 == 0, "EposPointwiseArgs.reserved0 must be 0 (ABI 7)");
+    const int rc = validate(&args[i]);
+    if (rc) return rc;
+  }
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const float* z = h2_zero_chunk(s);
+  EPOS_REQUIRE(z, "cannot allocate the zero chunk (first fp16-pair launch on this device "
+                  "during a stream capture? launch once before capturing)");
+  return launch_heads_h2(args, count, z, s);
+}
+
 static int grouped_impl(const EposPointwiseArgs* args, int count, void* stream) {
   using namespace epos;
   hipStream_t s = static_cast<hipStream_t>(stream);

@@ -1023,6 +1023,8 @@ unsigned* ring_slot(hipStream_t s) {
 
 }  // namespace
 
+const float* h2_zero_chunk(hipStream_t s) { return zero_chunk_dev(s); }
+
 // A group goes to the h2 kernel when every problem carries fp16-pair weights and has no
 // pre-activation ReLU; like split_eligible the choice depends on nothing else, so a layer
 // gives the same bits alone or in a group.

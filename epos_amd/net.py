@@ -581,7 +581,9 @@ class EposNet(object):
     # identical bits -- and measured it slower than the softmax's own memory-bound launch:
     # 410.6 / 415.6 vs 419.2 / 421.3 images/s, profiles/r04/ab_head_softmax.txt; removed in
     # round 5.)
-    mode.flush(grp)              # the three heads: one grouped launch
+    # the three heads: one grouped launch; in fp32 mode on the A-stationary heads kernel
+    # (csrc/heads_gemm_h2.hip, same bits; EPOS_HEADS_KERNEL=0 keeps the generic grouped GEMM)
+    mode.flush(grp, heads=os.environ.get('EPOS_HEADS_KERNEL', '1') == '1')
     # Sparse-head mode (pipeline option): only the object head runs densely; the
     # fragment heads are evaluated per (image, target object) -- see
     # run_sparse_heads().

@@ -62,6 +62,7 @@ class Fp32Mode(object):
     fn = net._fn
     self.gemm = fn('epos_pointwise_conv_grouped_f32')
     self.gemm1 = fn('epos_pointwise_conv_f32')
+    self.heads = fn('epos_heads_gemm_f32')
     self.dw = fn('epos_depthwise3x3_f32')
     self.conv3x3 = fn('epos_conv3x3_f32')
     self.im2col3x3 = fn('epos_im2col3x3_f32')
@@ -232,14 +233,16 @@ class Fp32Mode(object):
     # to the launch that writes the encoder output
     self._last_pw = (c, args, h and res is None and c_off == 0 and n % 4 == 0)
 
-  def flush(self, group):
+  def flush(self, group, heads=False):
     """Launches the collected problems as one grouped GEMM -- one per kind: problems whose A
     is already fp16 pairs run on another kernel instantiation than the ones that split
-    their fp32 A themselves."""
+    their fp32 A themselves. heads: the dense logits heads, through epos_heads_gemm_f32 (the
+    A-stationary kernel; same bits as the grouped GEMM)."""
     for kind in sorted({g[1].a_presplit for g in group}):
       part = [g for g in group if g[1].a_presplit == kind]
       arr = (_lib.PointwiseArgs * len(part))(*[g[1] for g in part])
-      self.net._launch('+'.join(g[0] for g in part), self.gemm, (arr, len(part)), 'gemm',
+      fn = self.heads if heads and not kind else self.gemm
+      self.net._launch('+'.join(g[0] for g in part), fn, (arr, len(part)), 'gemm',
                        sum(g[2] for g in part), sum(g[3] for g in part))
     del group[:]
 
@@ -475,8 +478,9 @@ class Bf16Mode(object):
     net._launch(name, self.gemm_f32, (args, 1), 'gemm', 2 * m * n * k, nbytes)
     return args
 
-  def flush(self, group):
-    """Launches the collected problems as one grouped GEMM."""
+  def flush(self, group, heads=False):
+    """Launches the collected problems as one grouped GEMM (heads: no kernel of its own in
+    this mode)."""
     if group:
       arr = (_lib.PointwiseBf16Args * len(group))(*[g[1] for g in group])
       self.net._launch('+'.join(g[0] for g in group), self.gemm, (arr, len(group)), 'gemm',

@@ -184,6 +184,14 @@ int epos_pointwise_conv_f32(const EposPointwiseArgs* args, void* stream);
 int epos_pointwise_conv_grouped_f32(const EposPointwiseArgs* args, int count,
                                     void* stream);
 
+/* The dense logits heads: the same contract and the same bits as
+ * epos_pointwise_conv_grouped_f32. A group whose problems share one A (pointer, lda, M and
+ * absmax slots / gain / bias; a_amax given), have K = 256, sub = 1, fp16-pair weights and no
+ * residual, ReLU, pre-split A, c_amax or col_sums runs on an A-stationary kernel (each A
+ * panel loaded and split once for many N tiles); any other group is passed on to
+ * epos_pointwise_conv_grouped_f32. */
+int epos_heads_gemm_f32(const EposPointwiseArgs* args, int count, void* stream);
+
 /* (ABI <= 6 also had a persistent stream-K form of the grouped GEMM on the fp32-MFMA ring,
  * epos_pointwise_conv_grouped_sk_f32 / _ws_f32 + a workspace: correct, tested, and slower
  * than the data-parallel kernels end to end (177 vs 213 images/s in round 1); removed in
