@@ -144,6 +144,14 @@ class Im2colBf16Args(ctypes.Structure):
   ]
 
 
+class ResizeSrc(ctypes.Structure):
+  _fields_ = [('X', vp), ('ldx', ctypes.c_int64), ('Hi', ctypes.c_int32),
+              ('Wi', ctypes.c_int32)]
+
+
+MERGE_MAX, MERGE_MEAN = 0, 1       # EPOS_MERGE_*
+
+
 class CorrSlot(ctypes.Structure):
   _fields_ = [('image', ctypes.c_int32), ('obj_id', ctypes.c_int32)]
 
@@ -286,6 +294,10 @@ SYMBOLS = {
         vp, ctypes.c_int64, vp, ctypes.c_int64, ctypes.c_int, ctypes.c_int,
         ctypes.c_int, ctypes.c_int, ctypes.c_int, vp]),
     'epos_add_relu_bf16': (ctypes.c_int, [vp, vp, vp, ctypes.c_int64, vp]),
+    # multi-scale inference
+    'epos_resize_merge_f32': (ctypes.c_int, [
+        ctypes.POINTER(ResizeSrc), ctypes.c_int, vp, ctypes.c_int64, ctypes.c_int, ctypes.c_int,
+        ctypes.c_int, ctypes.c_int, ctypes.c_int, vp]),
 }
 
 _lib = None

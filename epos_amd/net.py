@@ -78,7 +78,8 @@ class EposNet(object):
   def __init__(self, checkpoint, batch, height, width, num_objs, num_frags=64,
                model_variant='xception_65', encoder_output_stride=8,
                decoder_output_stride=4, atrous_rates=(12, 24, 36),
-               multi_grid=None, device='cuda:0', dry_run=False, precision='fp32'):
+               multi_grid=None, device='cuda:0', dry_run=False, precision='fp32',
+               decoder_hw=None):
     if precision not in PRECISIONS:
       raise ValueError('precision must be one of %s (got %r).' % (PRECISIONS, precision))
     self.precision = precision
@@ -99,6 +100,11 @@ class EposNet(object):
     self.num_objs, self.num_frags = num_objs, num_frags
     self.atrous_rates = tuple(atrous_rates)
     self.multi_grid = list(multi_grid) if multi_grid else [1, 1, 1]
+    # decoder_hw: the size the decoder resizes its two inputs to, (scale_dimension(w, 1/4),
+    # scale_dimension(h, 1/4)) of crop_size (model.py:355-356). None: the stride-4 map of the
+    # input. Multi-scale inference passes the size the reference's multi_scale_logits gives
+    # a scale != 1 (epos_amd/multiscale.py); the low-level features are then resized too.
+    self.decoder_hw = tuple(decoder_hw) if decoder_hw is not None else None
     self.ckpt = checkpoint
     self._keep = []          # device tensors owned by the plan
     self.ops = []            # (name, callable(stream))
@@ -535,6 +541,8 @@ class EposNet(object):
     dh = scale_dimension(H, 1.0 / 4)
     dw_ = scale_dimension(Wd, 1.0 / 4)
     assert (lh, lw) == (dh, dw_), ((lh, lw), (dh, dw_))
+    if self.decoder_hw is not None:
+      dh, dw_ = self.decoder_hw
     # (padding the concat's rows 304 -> 320 and the stem's im2col rows 28 -> 32 as well:
     # measured neutral, profiles/r06/ab_pad_level.txt -- left dense)
     dcat = self._abuf(B, dh, dw_, 304)
@@ -543,8 +551,19 @@ class EposNet(object):
     self._set_expr(dcat, self._expr_of(proj) if (eh, ew) == (dh, dw_) else
                    'resize(%s,%dx%d)' % (self._expr_of(proj), dh, dw_), 0, 256)
     m_dec = B * dh * dw_
-    self._conv1x1('decoder/feature_projection0', HEAD_BN_EPS, ll, 0, lc, m_dec, lc, dcat,
-                  256, ldd, relu=True)
+    if (lh, lw) == (dh, dw_):
+      self._conv1x1('decoder/feature_projection0', HEAD_BN_EPS, ll, 0, lc, m_dec, lc, dcat,
+                    256, ldd, relu=True)
+    else:
+      # (decoder_hw) the projected low-level features at their own size, resized into the
+      # concat's slice (model.py:358-361 resizes both decoder inputs)
+      low = self._abuf(B, lh, lw, 48)
+      self._conv1x1('decoder/feature_projection0', HEAD_BN_EPS, ll, 0, lc, B * lh * lw, lc,
+                    low, 0, 48, relu=True)
+      mode.resize('decoder/resize_low_level', low, 48, dcat[..., 256:], ldd, lh, lw, dh, dw_,
+                  48)
+      self._set_expr(dcat, 'resize(%s,%dx%d)' % (self._expr_of(low), dh, dw_), 256, 48)
+      mode.same_bound(dcat, low)
     mode.concat_bound(dcat, proj)
     self.decoder_concat = dcat[..., :304]
     x, c = dcat, 304

@@ -22,6 +22,7 @@ from epos_amd import _lib
 from epos_amd import corresp as _corresp
 from epos_amd import fitting as _fitting
 from epos_amd import model as _model
+from epos_amd import multiscale as _ms
 from epos_amd import weights as W
 
 LOCALIZATION = 'localization'   # common.py
@@ -57,13 +58,18 @@ class EposPipeline(object):
                max_instances=4, model_options=None, device='cuda:0',
                use_graph=True, instance=0, sparse_heads=False,
                fitting_method='progressive_x', on_excess='raise', queue=1,
-               precision='fp32'):
+               precision='fp32', image_pyramid=None, merge_method=None):
     """on_excess: what launch() does with a frame that asks for more instances of an object
     than `max_instances` (localization): 'raise' (default: EposError BEFORE anything of that
     batch is enqueued -- batches already in flight on other pipelines are unaffected and can
     still be collected) or 'clamp' (fit `max_instances` of them and warn once).
     precision: the network's numeric mode, 'fp32' (default) or 'bf16' (EposNet); the
     correspondence and fitting stages run unchanged on its fp32 head tensors.
+    image_pyramid / merge_method: multi-scale inference (epos_amd/multiscale.py); None or
+    [1.0] = single scale. merge_method None = model_options.merge_method ('max' by default).
+    The correspondences are placed with output_scale = max(1, max(P)) / 4, the stride of the
+    merged heads (for pyramids with every scale <= 1 that is the reference's 1/4; DESIGN.md,
+    "multi-scale mode"). Sparse heads are not available with a pyramid (ValueError).
     capacity: correspondence rows per batch, over all slots, at up to 64 fragments per object.
     A masked pixel yields up to F rows, so the correspondence and fitting buffers are sized for
     `capacity * ceil(num_frags / 64)` rows (self.capacity); for num_frags <= 64 that is
@@ -90,16 +96,26 @@ class EposPipeline(object):
     self.dev = torch.device(device)
     self.B, self.H, self.W = batch, height, width
     self.O, self.F = num_objs, num_frags
+    scales = _ms.normalize_pyramid(image_pyramid)
+    if scales is not None:
+      if sparse_heads:
+        raise ValueError('sparse_heads=True is not available with an image pyramid.')
+      model_options = model_options or _model.ModelOptions(
+          _model.get_outputs_to_num_channels(num_objs, num_frags))
+      if merge_method is not None:
+        model_options = model_options._replace(
+            merge_method=_ms.check_merge_method(merge_method))
     self.net = _model.get_net(checkpoint, batch, height, width, num_objs,
                               num_frags, model_options, device, instance,
-                              precision=precision)
+                              precision=precision, image_pyramid=scales)
     self.use_graph = use_graph
     # sparse_heads: evaluate the fragment heads only for the (image, target
     # object) slots of the batch instead of all O objects. Identical poses (the
     # correspondence stage never reads another object's channels,
     # corresp.py:42-43); the dense prediction dict is then NOT available.
     self.sparse_heads = sparse_heads
-    self.output_scale = 1.0 / 4            # decoder output stride 4 (infer.py:586-591)
+    # decoder output stride 4 (infer.py:586-591) of the largest scale >= 1
+    self.output_scale = (max(1.0, max(scales)) if scales else 1.0) / 4
     self.tau_a, self.tau_b = corr_min_obj_conf, corr_min_frag_rel_conf
     self.max_slots = max_slots or batch * num_objs
     self.max_k = max_instances

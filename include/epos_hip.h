@@ -665,6 +665,26 @@ int epos_subsample_bf16(const uint16_t* X, int64_t ldx, uint16_t* Y, int64_t ldy
 int epos_add_relu_bf16(const uint16_t* A, const uint16_t* B, uint16_t* Y, int64_t n,
                        void* stream);
 
+/* ------------------------------------------------------------------------- *
+ * Multi-scale inference (image_pyramid + merge_method, model.py:515-626; added
+ * without an ABI version change: nothing existing moved).
+ * ------------------------------------------------------------------------- */
+#define EPOS_MERGE_MAX 0    /* merge_method 'max': reduce_max over the scales */
+#define EPOS_MERGE_MEAN 1   /* merge_method 'avg': reduce_mean (sum in source order, then / S) */
+typedef struct EposResizeSrc {
+  const float* X;   /* [device] [B, Hi, Wi, C] with row pitch ldx >= C */
+  int64_t ldx;
+  int32_t Hi, Wi;   /* >= 1 */
+} EposResizeSrc;
+/* Y[b,y,x,c] = merge over s of resize_bilinear_align_corners(X_s)[b,y,x,c] (misc.py:94-107,
+ * TF's arithmetic: scale = (in-1)/(out-1) as a float, lo = floor(o*scale),
+ * hi = min(ceil(o*scale), in-1), top = tl + (tr-tl)*lx, top + (bot-top)*ly, no FMA). srcs is a
+ * HOST array of S sources (1 <= S <= 8); Y [B, Ho, Wo, C] with ldy >= C; any C >= 1. S = 1 is
+ * a plain resize (a same-size source is an exact copy). merge: EPOS_MERGE_MAX | _MEAN. Vector
+ * accesses where every pitch and base pointer allows them. */
+int epos_resize_merge_f32(const EposResizeSrc* srcs, int S, float* Y, int64_t ldy, int B,
+                          int Ho, int Wo, int C, int merge, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -46,7 +46,7 @@ if ROOT not in sys.path:
   sys.path.insert(0, ROOT)
 
 from epos_amd import bop_io, dist as edist, fitting, model, pipeline   # noqa: E402
-from epos_amd import synthetic, weights                                # noqa: E402
+from epos_amd import multiscale, synthetic, weights                    # noqa: E402
 
 PARAMS_FILENAME = 'params.yml'   # common.py
 
@@ -97,6 +97,10 @@ def build_parser():
   a('--max_correspondences', type=int, default=None)
   a('--max_instances_to_fit', type=int, default=None)
   a('--detection_instance_cap', type=int, default=DETECTION_INSTANCE_CAP)   # not in the reference
+  # not in the reference: run the --image_pyramid ("multi-scale mode"). Off by
+  # default: the same params.yml key configures multi-scale TRAINING, and S networks per frame
+  # are a cost to ask for.
+  a('--multi_scale_inference', type=str2bool, default=False)
   # not in the reference: the network's numeric mode ("bf16 mode")
   a('--precision', type=str, default='fp32', choices=['fp32', 'bf16'])
   a('--max_fitting_iterations', type=int, default=400)
@@ -226,8 +230,12 @@ def check_supported_flags(args):
       bad.append('%s=%r (supported: %r; %s)' % (name, getattr(args, name), want, why))
   pyr = _as_list(args.image_pyramid, float)
   if pyr not in (None, [], [1.0]):
-    bad.append('image_pyramid=%r (single scale only, model.py:545-546,597)' % (
-        args.image_pyramid,))
+    if not str2bool(str(getattr(args, 'multi_scale_inference', False))):
+      bad.append('image_pyramid=%r (single scale unless --multi_scale_inference=true, '
+                 'model.py:545-546,597)' % (args.image_pyramid,))
+    else:
+      multiscale.normalize_pyramid(pyr)                       # ValueError if invalid
+      multiscale.check_merge_method(args.merge_method)
   if _as_list(args.image_pooling_stride, int) not in ([1, 1],):
     bad.append('image_pooling_stride=%r (supported: 1,1)' % (args.image_pooling_stride,))
   if args.model_variant not in weights.VARIANTS:
@@ -240,6 +248,23 @@ def check_supported_flags(args):
   if bad:
     raise NotImplementedError(
         'flags outside what this build implements (common.py:60-154): ' + '; '.join(bad))
+
+
+def resolve_sparse_heads(args, needs_dense, pyramid):
+  """--sparse_heads: auto = on for localization unless the dense heads are read (--vis,
+  --save_corresp, the operator path) or an image pyramid is on (its merge reads every
+  object's heads of every scale); true where that is not possible raises ValueError."""
+  sh = str(args.sparse_heads).lower()
+  if sh == 'auto':
+    return args.task_type == pipeline.LOCALIZATION and not needs_dense and pyramid is None
+  sparse_heads = str2bool(sh)
+  if sparse_heads and pyramid is not None:
+    raise ValueError('--sparse_heads=true is not available with --image_pyramid '
+                     '(multi-scale heads are dense).')
+  if sparse_heads and (needs_dense or args.task_type != pipeline.LOCALIZATION):
+    raise ValueError('--sparse_heads=true needs --task_type=localization without --vis / '
+                     '--save_corresp / the operator path (they read every object\'s heads)')
+  return sparse_heads
 
 
 def load_fragments(model_dir, num_frags):
@@ -573,14 +598,8 @@ def main(argv=None):
     lq = 1
   if depth == 1:
     lq = 1                         # strictly one batch at a time means launch -> collect
-  sh = str(args.sparse_heads).lower()
-  if sh == 'auto':
-    sparse_heads = args.task_type == pipeline.LOCALIZATION and not needs_dense
-  else:
-    sparse_heads = str2bool(sh)
-    if sparse_heads and (needs_dense or args.task_type != pipeline.LOCALIZATION):
-      raise ValueError('--sparse_heads=true needs --task_type=localization without --vis / '
-                       '--save_corresp / the operator path (they read every object\'s heads)')
+  pyramid = multiscale.normalize_pyramid(_as_list(args.image_pyramid, float) or None)
+  sparse_heads = resolve_sparse_heads(args, needs_dense, pyramid)
   # the decoder processes start (import numpy / PIL) while the plans are built; nothing is
   # decoded before the loop below asks for it
   from epos_amd import frames as eframes
@@ -592,9 +611,18 @@ def main(argv=None):
       corr_min_frag_rel_conf=args.corr_min_frag_rel_conf,
       max_instances=max_inst, model_options=mo, device=dev, instance=j,
       sparse_heads=sparse_heads, fitting_method=args.fitting_method, queue=lq,
-      precision=args.precision)
+      precision=args.precision, image_pyramid=pyramid,
+      merge_method=args.merge_method if pyramid is not None else None)
            for j in range(depth)]
   pipe = pipes[0]
+  if rank == 0 and pyramid is not None:
+    print('plan: image pyramid %s, merge %s, merged heads %dx%d' % (
+        pyramid, args.merge_method, pipe.net.out_h, pipe.net.out_w))
+    if max(pyramid) > 1.0:
+      print('NOTE --image_pyramid with a scale above 1: the correspondences use the merged '
+            'heads\' stride, output_scale = %g / 4; the reference passes 1/4 whatever the '
+            'pyramid (scripts/infer.py:586-591,721) and would misplace them by a factor %g '
+            '(DESIGN.md, "multi-scale mode").' % (max(pyramid), max(pyramid)))
   if rank == 0:
     print('plan: {} image(s) per step, {} step(s) in flight{}, {} heads, {} GEMM layers on the '
           'fp16-pair kernel ({} on the bf16 x 6 fallback)'.format(
@@ -639,7 +667,7 @@ def main(argv=None):
       for b, f in enumerate(chunk[:n_real]):
         c = ecorresp.establish_many_to_many(
             pred['pred_obj_conf'][b], pred['pred_frag_conf'][b],
-            pred['pred_frag_loc'][b], list(f.targets), store, 0.25,
+            pred['pred_frag_loc'][b], list(f.targets), store, pipe.output_scale,
             args.corr_min_obj_conf, args.corr_min_frag_rel_conf, False,
             args.task_type == pipeline.LOCALIZATION, device=dev)
         save_correspondences(infer_dir, args.infer_name, f, i0 + b, c,
