@@ -599,7 +599,8 @@ extern "C" int epos_resize_bilinear_bf16(const void* X, int64_t ldx, int x_f32, 
   EPOS_REQUIRE(X && Y, "null pointer");
   EPOS_REQUIRE(C % 8 == 0 && ldx % 8 == 0 && ldy % 8 == 0 && al16(Y) && (x_f32 || al16(X)),
                "C, ldx, ldy multiples of 8, 16-byte aligned");
-  EPOS_REQUIRE(Hi >= 1 && Wi >= 1 && Ho >= 1 && Wo >= 1, "empty map");
+  EPOS_REQUIRE(B >= 1 && Hi >= 1 && Wi >= 1 && Ho >= 1 && Wo >= 1 && C >= 1, "empty map");
+  EPOS_REQUIRE(ldx >= C && ldy >= C, "ldx, ldy >= C");
   const float sy = Ho > 1 ? static_cast<float>(Hi - 1) / (Ho - 1) : 0.f;
   const float sx = Wo > 1 ? static_cast<float>(Wi - 1) / (Wo - 1) : 0.f;
   const int c8n = C / 8;
@@ -615,7 +616,8 @@ extern "C" int epos_global_avg_pool_bf16(const uint16_t* X, int64_t ldx, float* 
                                          int HW, int C, void* stream) {
   EPOS_REQUIRE(X && Y, "null pointer");
   EPOS_REQUIRE(C % 8 == 0 && ldx % 8 == 0 && al16(X), "C, ldx multiples of 8");
-  EPOS_REQUIRE(B >= 1 && HW >= 1, "empty map");
+  EPOS_REQUIRE(B >= 1 && HW >= 1 && C >= 1, "empty map");
+  EPOS_REQUIRE(ldx >= C, "ldx >= C");
   hipLaunchKernelGGL(global_avg_pool_bf16_kernel, dim3(grid_for(C, 64), B), dim3(256), 0,
                      static_cast<hipStream_t>(stream), X, ldx, Y, HW, C);
   return launch_status("global_avg_pool_bf16_kernel");
@@ -626,6 +628,8 @@ extern "C" int epos_maxpool3x3_s2_bf16(const uint16_t* X, int64_t ldx, uint16_t*
   EPOS_REQUIRE(X && Y, "null pointer");
   EPOS_REQUIRE(C % 8 == 0 && ldx % 8 == 0 && ldy % 8 == 0 && al16(X) && al16(Y),
                "multiples of 8");
+  EPOS_REQUIRE(B >= 1 && Hi >= 1 && Wi >= 1 && C >= 1, "empty map");
+  EPOS_REQUIRE(ldx >= C && ldy >= C, "ldx, ldy >= C");
   const int Ho = (Hi + 1) / 2, Wo = (Wi + 1) / 2;          // TF 'SAME'
   const int ty = (Ho - 1) * 2 + 3 - Hi, tx = (Wo - 1) * 2 + 3 - Wi;
   const int pad_y = ty > 0 ? ty / 2 : 0, pad_x = tx > 0 ? tx / 2 : 0;
@@ -644,6 +648,8 @@ extern "C" int epos_subsample_bf16(const uint16_t* X, int64_t ldx, uint16_t* Y, 
   EPOS_REQUIRE(C % 8 == 0 && ldx % 8 == 0 && ldy % 8 == 0 && al16(X) && al16(Y),
                "multiples of 8");
   EPOS_REQUIRE(factor >= 1, "factor >= 1");
+  EPOS_REQUIRE(B >= 1 && Hi >= 1 && Wi >= 1 && C >= 1, "empty map");
+  EPOS_REQUIRE(ldx >= C && ldy >= C, "ldx, ldy >= C");
   const int Ho = (Hi - 1) / factor + 1, Wo = (Wi - 1) / factor + 1;
   const int c8n = C / 8;
   const int64_t total = static_cast<int64_t>(B) * Ho * Wo * c8n;
@@ -657,7 +663,8 @@ extern "C" int epos_subsample_bf16(const uint16_t* X, int64_t ldx, uint16_t* Y, 
 extern "C" int epos_add_relu_bf16(const uint16_t* A, const uint16_t* B, uint16_t* Y, int64_t n,
                                   void* stream) {
   EPOS_REQUIRE(A && B && Y, "null pointer");
-  EPOS_REQUIRE(n % 8 == 0 && al16(A) && al16(B) && al16(Y), "n % 8 == 0, 16-byte aligned");
+  EPOS_REQUIRE(n >= 0 && n % 8 == 0 && al16(A) && al16(B) && al16(Y),
+               "n % 8 == 0, 16-byte aligned");
   if (n <= 0) return EPOS_OK;
   hipLaunchKernelGGL(add_relu_bf16_kernel, dim3(grid_for(n / 8, 256)), dim3(256), 0,
                      static_cast<hipStream_t>(stream), A, B, Y, n / 8);

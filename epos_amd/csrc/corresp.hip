@@ -453,7 +453,7 @@ extern "C" int epos_corr_count(const float* obj_confs, const float* frag_confs,
   EPOS_REQUIRE(obj_confs && frag_confs && slots && px_off && corr_off &&
                frag_mask && totals, "null pointer");
   EPOS_REQUIRE(F >= 1 && F <= 256, "num_frags must be in [1, 256]");
-  EPOS_REQUIRE(B > 0 && P > 0 && O > 0, "empty problem");
+  EPOS_REQUIRE(B > 0 && P > 0 && O > 0 && S >= 0, "empty problem");
   if (S == 0) return EPOS_OK;
   hipStream_t st = static_cast<hipStream_t>(stream);
   dim3 grid(static_cast<unsigned>(ceil_div(P, 4 * CORR_PPW)), S);
@@ -490,6 +490,7 @@ extern "C" int epos_corr_count(const float* obj_confs, const float* frag_confs,
 extern "C" int epos_corr_slot_bases(const int32_t* totals, int S,
                                     int64_t* slot_base, void* stream) {
   EPOS_REQUIRE(totals && slot_base, "null pointer");
+  EPOS_REQUIRE(S >= 0, "S >= 0");
   hipLaunchKernelGGL(corr_slot_bases_kernel, dim3(1), dim3(64), 0,
                      static_cast<hipStream_t>(stream), totals, S, slot_base);
   return launch_status("corr_slot_bases_kernel");
@@ -509,6 +510,10 @@ extern "C" int epos_corr_fill(const float* obj_confs, const float* frag_confs,
                slot_base && out && overflow, "null pointer");
   EPOS_REQUIRE(F >= 1 && F <= 256, "num_frags must be in [1, 256]");
   EPOS_REQUIRE(W > 0 && P % W == 0, "P must be a multiple of W");
+  EPOS_REQUIRE(B > 0 && P > 0 && O > 0 && S >= 0, "empty problem");
+  EPOS_REQUIRE(capacity <= 0 || (out->px_id && out->frag_id && out->coord_2d && out->coord_3d &&
+                                 out->conf && out->conf_obj && out->conf_frag),
+               "null output array with capacity > 0");
   if (S == 0) return EPOS_OK;
   dim3 grid(static_cast<unsigned>(ceil_div(P, 4 * CORR_PPW)), S);
   hipStream_t st = static_cast<hipStream_t>(stream);

@@ -976,6 +976,7 @@ extern "C" int epos_global_avg_pool_f32(const float* X, int64_t ldx, float* Y,
                                         int B, int HW, int C, void* stream) {
   EPOS_REQUIRE(X && Y, "null pointer");
   EPOS_REQUIRE(C % 4 == 0 && ldx % 4 == 0 && HW > 0, "C, ldx multiples of 4");
+  EPOS_REQUIRE(B > 0 && C > 0 && ldx >= C, "B, C > 0; ldx >= C");
   hipLaunchKernelGGL(global_avg_pool_kernel,
                      dim3(static_cast<unsigned>(ceil_div(C, 64)), B), dim3(1024),
                      0, static_cast<hipStream_t>(stream), X, ldx, Y, HW, C);
@@ -1034,6 +1035,8 @@ extern "C" int epos_resize_bilinear_f32(const float* X, int64_t ldx, float* Y,
                                         int Ho, int Wo, int C, void* stream) {
   EPOS_REQUIRE(X && Y, "null pointer");
   EPOS_REQUIRE(C % 4 == 0 && ldx % 4 == 0 && ldy % 4 == 0, "multiples of 4");
+  EPOS_REQUIRE(B > 0 && Hi > 0 && Wi > 0 && Ho > 0 && Wo > 0 && C > 0, "empty map");
+  EPOS_REQUIRE(ldx >= C && ldy >= C, "ldx, ldy >= C");
   const float sy = Ho > 1 ? static_cast<float>(Hi - 1) / (Ho - 1) : 0.f;
   const float sx = Wo > 1 ? static_cast<float>(Wi - 1) / (Wo - 1) : 0.f;
   const int c4n = C / 4;
@@ -1074,6 +1077,7 @@ extern "C" int epos_softmax_groups_f32(float* X, int64_t n_groups, int G,
 extern "C" int epos_argmax_i64(const float* X, int64_t ldx, int64_t* labels,
                                int64_t P, int C, void* stream) {
   EPOS_REQUIRE(X && labels, "null pointer");
+  EPOS_REQUIRE(P >= 0 && C >= 1 && ldx >= C, "P >= 0; C >= 1; ldx >= C");
   if (P == 0) return EPOS_OK;
   hipLaunchKernelGGL(argmax_kernel, dim3(blocks_for(P, 256)), dim3(256), 0,
                      static_cast<hipStream_t>(stream), X, ldx, labels, P, C);
@@ -1106,6 +1110,8 @@ extern "C" int epos_maxpool3x3_s2_f32(const float* X, int64_t ldx, float* Y,
                                       void* stream) {
   EPOS_REQUIRE(X && Y, "null pointer");
   EPOS_REQUIRE(C % 4 == 0 && ldx % 4 == 0 && ldy % 4 == 0, "multiples of 4");
+  EPOS_REQUIRE(B > 0 && Hi > 0 && Wi > 0 && C > 0, "empty map");
+  EPOS_REQUIRE(ldx >= C && ldy >= C, "ldx, ldy >= C");
   const int Ho = (Hi + 1) / 2, Wo = (Wi + 1) / 2;          // TF 'SAME'
   const int ty = (Ho - 1) * 2 + 3 - Hi, tx = (Wo - 1) * 2 + 3 - Wi;
   const int pad_y = ty > 0 ? ty / 2 : 0, pad_x = tx > 0 ? tx / 2 : 0;
@@ -1124,6 +1130,8 @@ extern "C" int epos_subsample_f32(const float* X, int64_t ldx, float* Y,
   EPOS_REQUIRE(X && Y, "null pointer");
   EPOS_REQUIRE(C % 4 == 0 && ldx % 4 == 0 && ldy % 4 == 0 && factor >= 1,
                "multiples of 4");
+  EPOS_REQUIRE(B > 0 && Hi > 0 && Wi > 0 && C > 0, "empty map");
+  EPOS_REQUIRE(ldx >= C && ldy >= C, "ldx, ldy >= C");
   const int Ho = (Hi - 1) / factor + 1, Wo = (Wi - 1) / factor + 1;
   const int c4n = C / 4;
   const int64_t total = static_cast<int64_t>(B) * Ho * Wo * c4n;
@@ -1137,7 +1145,7 @@ extern "C" int epos_subsample_f32(const float* X, int64_t ldx, float* Y,
 extern "C" int epos_add_relu_f32(const float* A, const float* B, float* Y,
                                  int64_t n, void* stream) {
   EPOS_REQUIRE(A && B && Y, "null pointer");
-  EPOS_REQUIRE(n % 4 == 0, "n must be a multiple of 4");
+  EPOS_REQUIRE(n >= 0 && n % 4 == 0, "n must be a multiple of 4");
   if (n == 0) return EPOS_OK;
   hipLaunchKernelGGL(add_relu_kernel, dim3(blocks_for(n / 4, 256)), dim3(256), 0,
                      static_cast<hipStream_t>(stream), A, B, Y, n / 4);

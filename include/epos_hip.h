@@ -325,7 +325,13 @@ int epos_im2col_f32(const EposIm2colKArgs* args, void* stream);
 int epos_global_avg_pool_partial_f32(const float* P, int64_t ldp, float* Y, int32_t B,
                                      int32_t blocks, int32_t C, int32_t hw, void* stream);
 
-/* Global mean over H*W (model.py:220): X [B, HW, C] (ldx) -> Y [B, C]. */
+/* Global mean over H*W (model.py:220): X [B, HW, C] (ldx) -> Y [B, C].
+ *
+ * The glue launchers below (mean, resize, max pool, subsample, add+relu, argmax and their bf16
+ * forms) refuse with EPOS_E_INVALID, before anything is launched, every call under which a
+ * kernel would leave the tensors it was given: a pitch below the channel count (ldx < C,
+ * ldy < C), a batch, map size or channel count below 1, a negative element count. These calls
+ * were never valid; the refusals are additive (ABI version unchanged). */
 int epos_global_avg_pool_f32(const float* X, int64_t ldx, float* Y, int B,
                              int HW, int C, void* stream);
 
@@ -369,7 +375,7 @@ int epos_u8_to_f32(const uint8_t* X, float* Y, int64_t n, void* stream);
 int epos_softmax_groups_f32(float* X, int64_t n_groups, int G, void* stream);
 
 /* Per-pixel argmax over C channels -> int64 label (model.py:683); first maximum
- * wins (tf.argmax / np.argmax tie rule). */
+ * wins (tf.argmax / np.argmax tie rule). C >= 1, ldx >= C, P >= 0 (P == 0: nothing to do). */
 int epos_argmax_i64(const float* X, int64_t ldx, int64_t* labels, int64_t P,
                     int C, void* stream);
 
@@ -432,7 +438,9 @@ int epos_corr_fill(const float* obj_confs, const float* frag_confs,
                    int64_t capacity, const EposCorrOut* out, int32_t* overflow,
                    void* stream);
 
-/* slot_base[s] = sum_{t<s} totals[t][1]; slot_base[S] = grand total. [device] */
+/* slot_base[s] = sum_{t<s} totals[t][1]; slot_base[S] = grand total. [device]
+ * S >= 0 in all three correspondence calls; B, P, O >= 1; epos_corr_fill wants all seven
+ * output arrays when capacity > 0 (EPOS_E_INVALID otherwise). */
 int epos_corr_slot_bases(const int32_t* totals, int S, int64_t* slot_base,
                          void* stream);
 

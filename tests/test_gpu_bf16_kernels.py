@@ -10,6 +10,7 @@ import pytest
 import torch
 
 from helpers.bf16_ref import bf16_round, bf16_round_bits, bf16_to_f32
+from helpers.glue_ref import resize_f32
 
 pytestmark = pytest.mark.gpu
 
@@ -382,19 +383,8 @@ def test_resize_and_mean(src_f32):
   L.check(lib.epos_resize_bilinear_bf16(_p(x_dev), C, int(src_f32), _p(y), ldy, B, Hi, Wi, Ho,
                                         Wo, C, None), 'resize')
   torch.cuda.synchronize()
-  sy = np.float32((Hi - 1) / (Ho - 1)) if Ho > 1 else np.float32(0)
-  sx = np.float32((Wi - 1) / (Wo - 1)) if Wo > 1 else np.float32(0)
-  fy = np.arange(Ho, dtype=np.float32) * sy
-  fx = np.arange(Wo, dtype=np.float32) * sx
-  y0, x0 = np.floor(fy).astype(int), np.floor(fx).astype(int)
-  y1, x1 = np.minimum(np.ceil(fy).astype(int), Hi - 1), np.minimum(np.ceil(fx).astype(int), Wi - 1)
-  ly = (fy - y0.astype(np.float32))[None, :, None, None]
-  lx = (fx - x0.astype(np.float32))[None, None, :, None]
-  tl, tr = x32[:, y0][:, :, x0], x32[:, y0][:, :, x1]
-  bl, br = x32[:, y1][:, :, x0], x32[:, y1][:, :, x1]
-  top = tl + (tr - tl) * lx
-  bot = bl + (br - bl) * lx
-  want = (top + (bot - top) * ly).astype(np.float32)
+  # the fp32 kernel's arithmetic restated in numpy float32 (tests/helpers/glue_ref.py)
+  want, (tl, tr, bl, br) = resize_f32(x32, Ho, Wo)
   raw = y.view(torch.int16).cpu().numpy().view(np.uint16).reshape(B, Ho, Wo, ldy)
   got = bf16_to_f32(raw[..., :C]).astype(np.float64)
   # the kernel's fp32 arithmetic in numpy's float32, then one RNE: half a bf16 ulp, plus a few
