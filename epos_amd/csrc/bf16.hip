@@ -254,7 +254,7 @@ __global__ __launch_bounds__(256) void gemm_bf16_kernel(GemmGroup g) {
 // ---------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void depthwise3x3_bf16_kernel(EposDepthwiseBf16Args p,
                                                                 int c8n, int64_t total) {
-  EPOS_SET_PRIO(EPOS_DW_PRIO);
+  EPOS_SET_PRIO(DW_PRIO);
   const int64_t id = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
   if (id >= total) return;
   const int c = static_cast<int>(id % c8n) * 8;

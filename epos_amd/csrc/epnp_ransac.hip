@@ -25,15 +25,14 @@
 // are the bits of a scalar evaluation in the same canonical order.
 #include <float.h>
 
+#include <type_traits>
+
 #include "common.h"
 
 namespace epos {
 namespace {
 
-#ifndef EPOS_EP_SWEEPS
-#define EPOS_EP_SWEEPS 12      // timing experiments only: the oracle uses 12
-#endif
-constexpr int EP_SWEEPS = EPOS_EP_SWEEPS;
+constexpr int EP_SWEEPS = 12;        // as the oracle
 constexpr int EP_SET = 5;            // model_points of solvePnPRansac for EPNP
 
 struct EpCam { double fu, fv, uc, vc; };
@@ -924,32 +923,28 @@ __global__ __launch_bounds__(256) void cvr_select_fit(
   }
 }
 
-struct CvrLayout {
-  int64_t samples, counts, poses, idx, total;
-};
-CvrLayout cvr_layout(int S, int64_t cap, int iters) {
-  auto up = [](int64_t v) { return (v + 255) / 256 * 256; };
-  CvrLayout l;
+// The workspace of one call: the buffers of CvrWork, carved in this order from 256-byte
+// aligned sizes. base != null: fills w's pointers; base == null: w is not touched. Returns the
+// bytes the buffers take (epos_pnp_ransac_workspace_bytes).
+int64_t cvr_carve(char* base, int S, int64_t cap, int iters, CvrWork& w) {
   int64_t o = 0;
-  l.samples = o; o += up(static_cast<int64_t>(S) * iters * EP_SET * 4);
-  l.counts = o; o += up(static_cast<int64_t>(S) * iters * 4);
-  l.poses = o; o += up(static_cast<int64_t>(S) * iters * 96);
-  l.idx = o; o += up((cap > 0 ? cap : 1) * 4);
-  l.total = o;
-  return l;
+  auto take = [&](auto*& ptr, int64_t bytes) {
+    if (base) ptr = reinterpret_cast<std::remove_reference_t<decltype(ptr)>>(base + o);
+    o += (bytes + 255) / 256 * 256;
+  };
+  take(w.samples, static_cast<int64_t>(S) * iters * EP_SET * 4);
+  take(w.counts, static_cast<int64_t>(S) * iters * 4);
+  take(w.poses, static_cast<int64_t>(S) * iters * 96);
+  take(w.idx, (cap > 0 ? cap : 1) * 4);
+  return o;
 }
 
 int cvr_enqueue(const double* xy, const double* xyz, const int64_t* slot_base, int S,
                 int64_t cap, const double* Ks, const EposPnpRansacParams* p, void* work,
                 double* poses, int32_t* success, uint8_t* mask, int32_t* info,
                 hipStream_t st) {
-  const CvrLayout l = cvr_layout(S, cap, p->iterations_count);
-  char* wb = static_cast<char*>(work);
   CvrWork w;
-  w.samples = reinterpret_cast<int32_t*>(wb + l.samples);
-  w.counts = reinterpret_cast<int32_t*>(wb + l.counts);
-  w.poses = reinterpret_cast<double*>(wb + l.poses);
-  w.idx = reinterpret_cast<int32_t*>(wb + l.idx);
+  cvr_carve(static_cast<char*>(work), S, cap, p->iterations_count, w);
   w.iters = p->iterations_count;
   w.min_points = p->min_point_number;
   const float t2 = static_cast<float>(p->reprojection_error * p->reprojection_error);
@@ -979,7 +974,8 @@ extern "C" void epos_pnp_ransac_params_default(EposPnpRansacParams* p) {
 extern "C" int64_t epos_pnp_ransac_workspace_bytes(int S, int64_t n_capacity,
                                                    const EposPnpRansacParams* p) {
   if (!p || S < 0 || n_capacity < 0 || p->iterations_count < 1) return EPOS_E_INVALID;
-  return cvr_layout(S, n_capacity, p->iterations_count).total;
+  CvrWork unused;
+  return cvr_carve(nullptr, S, n_capacity, p->iterations_count, unused);
 }
 
 extern "C" int epos_solve_pnp_ransac_device(

@@ -47,7 +47,7 @@ __device__ __forceinline__ float4 fma4(float4 a, float4 b, float4 c) {
 __global__ __launch_bounds__(256) void depthwise3x3_kernel(EposDepthwiseArgs p,
                                                            int c4n,
                                                            int64_t total) {
-  EPOS_SET_PRIO(EPOS_DW_PRIO);
+  EPOS_SET_PRIO(DW_PRIO);
   int64_t id = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
   const bool h2 = p.y_h2 != 0;                 // uniform
   // the output scale's slot word is requested first and reduced behind the taps' loads (see
@@ -121,15 +121,9 @@ __global__ __launch_bounds__(256) void depthwise3x3_kernel(EposDepthwiseArgs p,
 // divisions by launch constants use precomputed multipliers, ReLU is one v_med3 per
 // component and a compile-time option, and a wave whose lanes all lie in the interior
 // of the image (no tap outside) takes a path without any clamp or select.
-#ifndef EPOS_DW_REP
-#define EPOS_DW_REP 1     // x-runs per thread (they share the nine weight vectors)
-#endif
-#ifndef EPOS_DW_MIN_BLOCKS
-#define EPOS_DW_MIN_BLOCKS 4     // <= 128 VGPRs: see DESIGN.md (co-residency with GEMM waves)
-#endif
-#ifndef EPOS_DW_MIN_BLOCKS2
-#define EPOS_DW_MIN_BLOCKS2 3    // the two-row kernel: <= 168 VGPRs
-#endif
+constexpr int DW_REP = 1;            // x-runs per thread (they share the nine weight vectors)
+constexpr int DW_MIN_BLOCKS = 4;     // <= 128 VGPRs: see DESIGN.md (co-residency with GEMM waves)
+constexpr int DW_MIN_BLOCKS2 = 3;    // the two-row kernel: <= 168 VGPRs
 struct FastDiv {                 // n / d for any 32-bit n (Granlund-Montgomery)
   unsigned mul, sh1, sh2, d;
 };
@@ -168,10 +162,10 @@ __device__ __forceinline__ float4 relu4_1op(float4 v) {
 // rows are taken in groups of 2 * rate; slot (g, i), i < rate, owns rows 2*rate*g + i and
 // + rate. Same fmaf chain per output as ROWS = 1: identical bits.
 template <int L, bool RELU_IN, bool RELU_OUT, int ROWS>
-__global__ __launch_bounds__(256, (ROWS == 2 ? EPOS_DW_MIN_BLOCKS2 : EPOS_DW_MIN_BLOCKS)) void depthwise3x3_s1_kernel(
+__global__ __launch_bounds__(256, (ROWS == 2 ? DW_MIN_BLOCKS2 : DW_MIN_BLOCKS)) void depthwise3x3_s1_kernel(
     EposDepthwiseArgs p, int c4n, int nres, int nchunk, int nrows, DwPartition part) {
   constexpr int NR = ROWS + 2;                 // input rows held per column
-  EPOS_SET_PRIO(EPOS_DW_PRIO);
+  EPOS_SET_PRIO(DW_PRIO);
   {
     // One round trip for the kernel arguments (~70 words): left to itself the compiler
     // fetches them where they are first used -- seven dependent scalar-load rounds in front
@@ -213,7 +207,7 @@ __global__ __launch_bounds__(256, (ROWS == 2 ? EPOS_DW_MIN_BLOCKS2 : EPOS_DW_MIN
     am_raw = s1[li];
     am_raw2 = s2[li];
   }
-  static_assert(EPOS_DW_REP == 1, "the scale reduction sits inside the (one) run of a thread");
+  static_assert(DW_REP == 1, "the scale reduction sits inside the (one) run of a thread");
   auto dw_scale_finish = [&] {
     if (h2) {
       float hinv;
@@ -266,7 +260,7 @@ __global__ __launch_bounds__(256, (ROWS == 2 ? EPOS_DW_MIN_BLOCKS2 : EPOS_DW_MIN
     const unsigned g = fdiv(static_cast<unsigned>(ys), part.drate);
     y = static_cast<int>(2 * r * g + (ys - g * r));
   }
-  live = live && res + chunk * (EPOS_DW_REP * L) * r < p.Wo && y < p.Ho;
+  live = live && res + chunk * (DW_REP * L) * r < p.Wo && y < p.Ho;
   // A wave without any live lane leaves. In a wave that keeps some, the dead lanes stay (the
   // scale reduction below is wave-wide): they walk the run at the image's origin -- valid
   // addresses, never "interior" -- and store nothing.
@@ -286,10 +280,10 @@ __global__ __launch_bounds__(256, (ROWS == 2 ? EPOS_DW_MIN_BLOCKS2 : EPOS_DW_MIN
   const int ldx = static_cast<int>(p.ldx), ldy = static_cast<int>(p.ldy);
   const int rowpitch = p.Wi * ldx;
   const unsigned yrow1 = static_cast<unsigned>(r * p.Wo * ldy);   // output row y + rate
-  // EPOS_DW_REP consecutive runs per thread share the weight vectors
+  // DW_REP consecutive runs per thread share the weight vectors
 #pragma unroll 1
-  for (int rep = 0; rep < EPOS_DW_REP; ++rep) {
-  const int x0 = res + (chunk * EPOS_DW_REP + rep) * L * r;
+  for (int rep = 0; rep < DW_REP; ++rep) {
+  const int x0 = res + (chunk * DW_REP + rep) * L * r;
   if (x0 >= p.Wo) break;
   // every tap of every output of this run inside the image?
   const bool interior = y - r >= 0 && y + (ROWS == 2 ? 2 : 1) * r < p.Hi && x0 - r >= 0 &&
@@ -573,27 +567,19 @@ __global__ __launch_bounds__(256) void softmax_groups_kernel(float* X,
 // (softmax64_lane16: h2_scale.h)
 // The dense fragment-confidence head is 103 MB at C2: read once, written once, re-read only
 // sparsely by the correspondence stage -- streaming (non-temporal) accesses keep it from
-// sweeping the Infinity Cache (EPOS_SOFTMAX_NT=0 at build time restores plain accesses).
-#ifndef EPOS_SOFTMAX_NT
-#define EPOS_SOFTMAX_NT 1
-#endif
+// sweeping the Infinity Cache.
 typedef float sm_f32x4 __attribute__((ext_vector_type(4)));
 __global__ __launch_bounds__(256) void softmax_groups64_kernel(float* X, int64_t n_groups) {
   const int lane = threadIdx.x & 63;
   const int64_t g = (static_cast<int64_t>(blockIdx.x) * 4 + (threadIdx.x >> 6)) * 4 + (lane >> 4);
   const bool on = g < n_groups;
   float* x = X + (on ? g : 0) * 64 + (lane & 15) * 4;
-#if EPOS_SOFTMAX_NT
   const sm_f32x4 in = __builtin_nontemporal_load(reinterpret_cast<const sm_f32x4*>(x));
-  const float4 r = softmax64_lane16(make_float4(in[0], in[1], in[2], in[3]));
+  const float4 r = softmax64_lane16(make_float4(in[0], in[1], in[2], in[3]));   // shuffles: all lanes take part
   if (on) {
     const sm_f32x4 o = {r.x, r.y, r.z, r.w};
     __builtin_nontemporal_store(o, reinterpret_cast<sm_f32x4*>(x));
   }
-#else
-  const float4 r = softmax64_lane16(ld4(x));             // shuffles: all lanes take part
-  if (on) st4(x, r);
-#endif
 }
 
 __global__ __launch_bounds__(256) void softmax_slots64_kernel(
@@ -630,20 +616,16 @@ __global__ __launch_bounds__(256) void softmax_slots_kernel(
 // 64 < G <= 256 (up to 256 fragments per object): one wave per group.
 // G == 256 on a 16-byte-aligned buffer: lane l holds values 4l..4l+3 as one float4
 // (softmax256_lane64: h2_scale.h). The dense F = 256 fragment head is 413 MB at C2, read
-// once and written once: streaming accesses under EPOS_SOFTMAX_NT, as for G == 64.
+// once and written once: streaming accesses, as for G == 64.
 __global__ __launch_bounds__(256) void softmax_groups256_kernel(float* X, int64_t n_groups) {
   const int lane = threadIdx.x & 63;
   const int64_t g = static_cast<int64_t>(blockIdx.x) * 4 + (threadIdx.x >> 6);
   if (g >= n_groups) return;                          // wave-uniform
   float* x = X + g * 256 + lane * 4;
-#if EPOS_SOFTMAX_NT
   const sm_f32x4 in = __builtin_nontemporal_load(reinterpret_cast<const sm_f32x4*>(x));
   const float4 r = softmax256_lane64(make_float4(in[0], in[1], in[2], in[3]));
   const sm_f32x4 o = {r.x, r.y, r.z, r.w};
   __builtin_nontemporal_store(o, reinterpret_cast<sm_f32x4*>(x));
-#else
-  st4(x, softmax256_lane64(ld4(x)));
-#endif
 }
 
 __global__ __launch_bounds__(256) void softmax_slots256_kernel(
@@ -818,17 +800,14 @@ extern "C" int epos_depthwise3x3_f32(const EposDepthwiseArgs* a, void* stream) {
   const int c4n = a->C / 4;
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (a->stride == 1 && a->Hi == a->Ho && a->Wi == a->Wo) {
-#ifndef EPOS_DW_L
-#define EPOS_DW_L 4
-#endif
-    constexpr int L = EPOS_DW_L;
+    constexpr int L = 4;                   // outputs per run
     static const int threads = [] {        // EPOS_DW_THREADS=64|128|256 (tuning)
       const char* e = getenv("EPOS_DW_THREADS");
       return e ? atoi(e) : 256;
     }();
     const int nres = a->rate < a->Wo ? a->rate : a->Wo;
     const int per_res = static_cast<int>(ceil_div(a->Wo, a->rate));
-    const int nchunk = static_cast<int>(ceil_div(per_res, L * EPOS_DW_REP));
+    const int nchunk = static_cast<int>(ceil_div(per_res, L * DW_REP));
     // two output rows per thread (EPOS_DW_ROWS=1 keeps one: the A/B switch)
     static const int rows_env = [] {
       const char* e = getenv("EPOS_DW_ROWS");

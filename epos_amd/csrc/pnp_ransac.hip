@@ -36,6 +36,7 @@
 #include <stdlib.h>
 
 #include <algorithm>
+#include <type_traits>
 
 #include "common.h"
 
@@ -1203,15 +1204,6 @@ __device__ __forceinline__ void for_each_neighbour(const double* xy, const doubl
 // 256 threads per tile: 1024 (16 waves share a tile's window) is 20 % faster for one
 // image at a time (fitting 0.55 vs 0.66 ms) but costs throughput with several images in
 // flight (310 vs 320 images/s, same box: the large workgroups displace GEMM workgroups)
-#ifndef EPOS_GS_WAVES
-#define EPOS_GS_WAVES 16
-#endif
-#ifndef EPOS_GS_POINTS
-#define EPOS_GS_POINTS 1
-#endif
-#ifndef EPOS_GC_THREADS
-#define EPOS_GC_THREADS 256
-#endif
 #ifdef EPOS_GC_STATS              // tools/gc_stats.py: tiles visited, candidates streamed
 __device__ unsigned long long g_gc_stats[4];
 #endif
@@ -1220,7 +1212,7 @@ struct GcCand {
   int32_t q;          // fixed-point residual
   int32_t ol;         // slot-local index | label << 30
 };
-constexpr int GC_T = EPOS_GC_THREADS;  // threads per tile workgroup
+constexpr int GC_T = 256;             // threads per tile workgroup
 constexpr int GC_W = GC_T / 64;       // waves: each takes every GC_W-th candidate
 // BUILD = true (ransac_nb_build, once per call, right after ransac_init): the same tiles and
 // windows, but instead of relabelling every found neighbour is appended to the point's list
@@ -1367,9 +1359,6 @@ __global__ __launch_bounds__(GC_T) void ransac_gc_sweep(
       // addresses: broadcasts) are issued together from clamped positions, the tests are
       // arithmetic. (The first version -- early-outs between dependent LDS reads -- ran at
       // ~1500 cycles per candidate; eight scalar arrays still at ~1000.)
-#ifdef EPOS_GC_ABL_NOLOOP       // ablation (tools/): everything but the pair tests
-      if (cnt < 0)
-#endif
       for (int j0 = sub; j0 < cnt; j0 += 4 * GC_W) {
         GcCand r[4];
         int okj[4];
@@ -1449,8 +1438,8 @@ __global__ __launch_bounds__(GC_T) void ransac_gc_sweep(
 // rows -- and every loaded candidate is tested GS_P times. The waves' partial counts meet in
 // LDS by integer atomics (exact, order free). Same integers as ransac_gc_sweep<false>
 // (tests/test_gpu_fit_lists.py runs both).
-constexpr int GS_W = EPOS_GS_WAVES;      // waves per workgroup: shares of the window
-constexpr int GS_P = EPOS_GS_POINTS;     // points per lane: adjacent tiles per workgroup
+constexpr int GS_W = 16;                 // waves per workgroup: shares of the window
+constexpr int GS_P = 1;                  // points per lane: adjacent tiles per workgroup
 constexpr int GS_T = GS_W * 64;
 constexpr int GS_BLOCK = 2048;           // 2048 x 2^20 < 2^32: the 32-bit sum cannot wrap
 
@@ -1548,26 +1537,6 @@ __global__ __launch_bounds__(GS_T) void ransac_gc_scan(
       // the slot and never tested)
       GsGeoV ga0 = gv[c < clast ? c : clast], ga1 = gv[c + 1 < clast ? c + 1 : clast];
       GsDynV da0 = dv[c < clast ? c : clast], da1 = dv[c + 1 < clast ? c + 1 : clast];
-#if defined(EPOS_GS_ABL_NOLOAD)   // ablation (tools/): the arithmetic alone, one candidate reused
-      const GsGeoV gb0 = gv[c + 2 < clast ? c + 2 : clast], gb1 = gv[c + 3 < clast ? c + 3 : clast];
-      const GsDynV db0 = dv[c + 2 < clast ? c + 2 : clast], db1 = dv[c + 3 < clast ? c + 3 : clast];
-      for (; c + 4 <= c1; c += 4) {
-        EPOS_GS_TEST(ga0, da0)
-        EPOS_GS_TEST(ga1, da1)
-        EPOS_GS_TEST(gb0, db0)
-        EPOS_GS_TEST(gb1, db1)
-        asm volatile("" ::: "memory");
-      }
-#elif defined(EPOS_GS_ABL_NOMATH)  // ablation: the scalar loads alone
-      for (; c + 4 <= c1; c += 4) {
-        const GsGeoV gb0 = gv[c + 2], gb1 = gv[c + 3];
-        const GsDynV db0 = dv[c + 2], db1 = dv[c + 3];
-        deg[0] += (ga0.x == 1e300 ? 1u : 0u) + (ga1.x == 1e300 ? 1u : 0u) + (da0.z == -5 ? 1u : 0u) + (da1.z == -5 ? 1u : 0u);
-        const int64_t e0 = c + 4 < clast ? c + 4 : clast, e1 = c + 5 < clast ? c + 5 : clast;
-        ga0 = gv[e0]; ga1 = gv[e1]; da0 = dv[e0]; da1 = dv[e1];
-        deg[0] += (gb0.x == 1e300 ? 1u : 0u) + (gb1.x == 1e300 ? 1u : 0u) + (db0.z == -5 ? 1u : 0u) + (db1.z == -5 ? 1u : 0u);
-      }
-#else
       for (; c + 4 <= c1; c += 4) {
         const GsGeoV gb0 = gv[c + 2], gb1 = gv[c + 3];
         const GsDynV db0 = dv[c + 2], db1 = dv[c + 3];
@@ -1578,7 +1547,6 @@ __global__ __launch_bounds__(GS_T) void ransac_gc_scan(
         EPOS_GS_TEST(gb0, db0)
         EPOS_GS_TEST(gb1, db1)
       }
-#endif
       if (c < c1) {                       // up to three left: ga0 / ga1 hold c, c + 1
         EPOS_GS_TEST(ga0, da0)
         if (c + 1 < c1) EPOS_GS_TEST(ga1, da1)
@@ -2315,63 +2283,57 @@ __global__ __launch_bounds__(256) void pearl_commit(const int64_t* slot_base,
   }
 }
 
-inline int64_t align_up(int64_t x) { return (x + 255) / 256 * 256; }
-
-struct Layout {
-  int64_t hyp_score, hyp_pose, hyp_count, active, n_active, done, inl_bits, total;
-  int64_t words_total;
-  int64_t cur_pose, cur_score, cur_count, state, tries, last_new, gq, lab_a, lab_b;
-  int64_t pearl_pose, pearl_acc, pearl_state, pearl_moved, lab_c, pearl_dt;
-  int64_t lo_cnt, lo_data, lo_timeout;
-  int64_t nb_cnt, nb_pool, nb_ok;
-  int64_t geo, dyn_a, dyn_b, win, acc, flip_a, flip_b;
-};
-
 // cooperating launches per call: select + refit of every round (max_k + 2 rounds at most)
 int lo_launches(int max_k) { return 2 * (max_k + 2); }
 
-Layout make_layout(int S, int64_t n_cap, int max_iters, int max_k) {
-  Layout L;
+// The workspace of one call: every buffer of Work, carved in this order from 256-byte
+// aligned offsets. base != null: fills w's pointers and words_total; base == null: w is not
+// touched. Returns the bytes the buffers take (epos_fit_workspace_bytes).
+int64_t carve_work(char* base, int S, int64_t n_cap, int max_iters, int max_k, Work& w) {
   int64_t off = 0;
+  auto take = [&](auto*& ptr, int64_t bytes) {
+    if (base) ptr = reinterpret_cast<std::remove_reference_t<decltype(ptr)>>(base + off);
+    off = (off + bytes + 255) / 256 * 256;
+  };
   const int64_t nh = static_cast<int64_t>(S) * max_iters * MAX_SOL;
-  L.hyp_score = off; off = align_up(off + nh * 8);
-  L.hyp_pose = off; off = align_up(off + nh * 12 * 8);
-  L.hyp_count = off; off = align_up(off + nh * 4);
-  L.active = off; off = align_up(off + (n_cap + 1) * 4);
-  L.n_active = off; off = align_up(off + (S + 1) * 4);
-  L.done = off; off = align_up(off + (S + 1) * 4);
-  L.words_total = n_cap / 64 + S + 2;
-  L.inl_bits = off; off = align_up(off + L.words_total * (max_k + 1) * 8);
-  L.cur_pose = off; off = align_up(off + (S + 1) * 12 * 8);
-  L.cur_score = off; off = align_up(off + (S + 1) * 8);
-  L.cur_count = off; off = align_up(off + (S + 1) * 4);
-  L.state = off; off = align_up(off + (S + 1) * 4);
-  L.tries = off; off = align_up(off + (S + 1) * 4);
-  L.last_new = off; off = align_up(off + (S + 1) * 4);
-  L.gq = off; off = align_up(off + (n_cap + 1) * 4);
-  L.lab_a = off; off = align_up(off + n_cap + 1);
-  L.lab_b = off; off = align_up(off + n_cap + 1);
-  L.lo_cnt = off; off = align_up(off + static_cast<int64_t>(S + 1) * lo_launches(max_k) * 4);
-  L.lo_data = off; off = align_up(off + static_cast<int64_t>(S + 1) * 2 * LO_G * 4 * LO_NV * 8);
-  L.lo_timeout = off; off = align_up(off + 8);
-  L.nb_cnt = off; off = align_up(off + (n_cap + 1) * NB_W * 2);
-  L.nb_pool = off; off = align_up(off + (n_cap + 1) * NB_W * NB_SUB * 2);
-  L.nb_ok = off; off = align_up(off + (S + 1) * 4);
-  L.geo = off; off = align_up(off + (n_cap + 1) * 32);
-  L.dyn_a = off; off = align_up(off + (n_cap + 1) * 16);
-  L.dyn_b = off; off = align_up(off + (n_cap + 1) * 16);
-  L.win = off; off = align_up(off + L.words_total * 2 * 4);
-  L.acc = off; off = align_up(off + (n_cap + 1) * 16);
-  L.flip_a = off; off = align_up(off + n_cap + 1);
-  L.flip_b = off; off = align_up(off + n_cap + 1);
-  L.pearl_pose = off; off = align_up(off + (S + 1) * PEARL_MAX_K * 12 * 8);
-  L.pearl_acc = off; off = align_up(off + (S + 1) * 4 * PEARL_BINS * 8);
-  L.pearl_state = off; off = align_up(off + (S + 1) * 4);
-  L.pearl_moved = off; off = align_up(off + (S + 1) * 4);
-  L.lab_c = off; off = align_up(off + n_cap + 1);
-  L.pearl_dt = off; off = align_up(off + (n_cap + 1) * PEARL_DT * 4);
-  L.total = off;
-  return L;
+  const int64_t words_total = n_cap / 64 + S + 2;
+  if (base) w.words_total = words_total;
+  take(w.hyp_score, nh * 8);
+  take(w.hyp_pose, nh * 12 * 8);
+  take(w.hyp_count, nh * 4);
+  take(w.active, (n_cap + 1) * 4);
+  take(w.n_active, (S + 1) * 4);
+  take(w.done, (S + 1) * 4);
+  take(w.inl_bits, words_total * (max_k + 1) * 8);
+  take(w.cur_pose, (S + 1) * 12 * 8);
+  take(w.cur_score, (S + 1) * 8);
+  take(w.cur_count, (S + 1) * 4);
+  take(w.state, (S + 1) * 4);
+  take(w.tries, (S + 1) * 4);
+  take(w.last_new, (S + 1) * 4);
+  take(w.gq, (n_cap + 1) * 4);
+  take(w.lab_a, n_cap + 1);
+  take(w.lab_b, n_cap + 1);
+  take(w.lo_cnt, static_cast<int64_t>(S + 1) * lo_launches(max_k) * 4);
+  take(w.lo_data, static_cast<int64_t>(S + 1) * 2 * LO_G * 4 * LO_NV * 8);
+  take(w.lo_timeout, 8);
+  take(w.nb_cnt, (n_cap + 1) * NB_W * 2);
+  take(w.nb_pool, (n_cap + 1) * NB_W * NB_SUB * 2);
+  take(w.nb_ok, (S + 1) * 4);
+  take(w.geo, (n_cap + 1) * 32);
+  take(w.dyn_a, (n_cap + 1) * 16);
+  take(w.dyn_b, (n_cap + 1) * 16);
+  take(w.win, words_total * 2 * 4);
+  take(w.acc, (n_cap + 1) * 16);
+  take(w.flip_a, n_cap + 1);
+  take(w.flip_b, n_cap + 1);
+  take(w.pearl_pose, (S + 1) * PEARL_MAX_K * 12 * 8);
+  take(w.pearl_acc, (S + 1) * 4 * PEARL_BINS * 8);
+  take(w.pearl_state, (S + 1) * 4);
+  take(w.pearl_moved, (S + 1) * 4);
+  take(w.lab_c, n_cap + 1);
+  take(w.pearl_dt, (n_cap + 1) * PEARL_DT * 4);
+  return off;
 }
 
 // Enqueues the whole fitting stage. yorder / ypos [device, n_capacity] or null: the
@@ -2382,52 +2344,15 @@ int find6d_enqueue(const double* xy, const double* xyz, const int64_t* slot_base
                    const uint64_t* seeds, const EposFitParams* p, int32_t max_k, void* work,
                    double* poses, double* scores, int32_t* num_models, int32_t* labels,
                    const int32_t* yorder, const int32_t* ypos, hipStream_t st) {
-  const Layout L = make_layout(S, n_capacity, p->max_iters, max_k);
-  char* wb = static_cast<char*>(work);
   Work w;
-  w.hyp_score = reinterpret_cast<double*>(wb + L.hyp_score);
-  w.hyp_pose = reinterpret_cast<double*>(wb + L.hyp_pose);
-  w.hyp_count = reinterpret_cast<int32_t*>(wb + L.hyp_count);
-  w.active = reinterpret_cast<int32_t*>(wb + L.active);
-  w.n_active = reinterpret_cast<int32_t*>(wb + L.n_active);
-  w.done = reinterpret_cast<int32_t*>(wb + L.done);
-  w.inl_bits = reinterpret_cast<uint64_t*>(wb + L.inl_bits);
-  w.words_total = L.words_total;
-  w.cur_pose = reinterpret_cast<double*>(wb + L.cur_pose);
-  w.cur_score = reinterpret_cast<double*>(wb + L.cur_score);
-  w.cur_count = reinterpret_cast<int32_t*>(wb + L.cur_count);
-  w.state = reinterpret_cast<int32_t*>(wb + L.state);
-  w.tries = reinterpret_cast<int32_t*>(wb + L.tries);
-  w.last_new = reinterpret_cast<int32_t*>(wb + L.last_new);
-  w.gq = reinterpret_cast<int32_t*>(wb + L.gq);
-  w.lab_a = reinterpret_cast<uint8_t*>(wb + L.lab_a);
-  w.lab_b = reinterpret_cast<uint8_t*>(wb + L.lab_b);
-  w.lab_c = reinterpret_cast<uint8_t*>(wb + L.lab_c);
-  w.pearl_dt = reinterpret_cast<int32_t*>(wb + L.pearl_dt);
+  carve_work(static_cast<char*>(work), S, n_capacity, p->max_iters, max_k, w);
   w.yorder = yorder;
   w.ypos = ypos;
-  w.lo_cnt = reinterpret_cast<unsigned*>(wb + L.lo_cnt);
-  w.lo_data = reinterpret_cast<double*>(wb + L.lo_data);
-  w.lo_timeout = reinterpret_cast<int32_t*>(wb + L.lo_timeout);
   static const unsigned spin_max = [] {      // EPOS_FIT_SPIN_MAX=0: every hand-off that has to
     const char* e = getenv("EPOS_FIT_SPIN_MAX");   // wait at all gives up (tests of the error path)
     return e ? static_cast<unsigned>(strtoul(e, nullptr, 10)) : LO_SPIN_MAX;
   }();
   w.lo_spin_max = spin_max;
-  w.nb_cnt = reinterpret_cast<uint16_t*>(wb + L.nb_cnt);
-  w.nb_pool = reinterpret_cast<int16_t*>(wb + L.nb_pool);
-  w.nb_ok = reinterpret_cast<int32_t*>(wb + L.nb_ok);
-  w.geo = reinterpret_cast<double*>(wb + L.geo);
-  w.dyn_a = reinterpret_cast<GcDyn*>(wb + L.dyn_a);
-  w.dyn_b = reinterpret_cast<GcDyn*>(wb + L.dyn_b);
-  w.win = reinterpret_cast<int32_t*>(wb + L.win);
-  w.acc = reinterpret_cast<GcAcc*>(wb + L.acc);
-  w.flip_a = reinterpret_cast<int8_t*>(wb + L.flip_a);
-  w.flip_b = reinterpret_cast<int8_t*>(wb + L.flip_b);
-  w.pearl_pose = reinterpret_cast<double*>(wb + L.pearl_pose);
-  w.pearl_acc = reinterpret_cast<unsigned long long*>(wb + L.pearl_acc);
-  w.pearl_state = reinterpret_cast<int32_t*>(wb + L.pearl_state);
-  w.pearl_moved = reinterpret_cast<int32_t*>(wb + L.pearl_moved);
   const int n_lo = lo_launches(max_k);
   const bool gc = p->gc_sweeps > 0 && p->spatial_coherence_weight > 0.0 &&
                   p->neighborhood_ball_radius > 0.0;
@@ -2594,7 +2519,8 @@ extern "C" void epos_fit_params_default(EposFitParams* p) {
 extern "C" int64_t epos_fit_workspace_bytes(int S, int64_t n_capacity,
                                             const EposFitParams* p, int32_t max_k) {
   if (!p || S < 0 || n_capacity < 0 || max_k < 1) return EPOS_E_INVALID;
-  return make_layout(S, n_capacity, p->max_iters, max_k).total;
+  Work unused;
+  return carve_work(nullptr, S, n_capacity, p->max_iters, max_k, unused);
 }
 
 extern "C" int epos_find6d_poses_device(

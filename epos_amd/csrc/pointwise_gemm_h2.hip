@@ -598,11 +598,7 @@ void pointwise_gemm_h2_f32(GroupedArgs ga_) {
       // meant to hide under
       asm volatile("" : "+v"(x0), "+v"(x1));
       unsigned hh, mm;
-#ifdef EPOS_H2_ABL_NOSPLIT          // ablation (tools/bench_gemm_h2_abl.py): wrong results
-      hh = __float_as_uint(x0) ^ 0x3c003c00u; mm = __float_as_uint(x1) & 0x3bff3bffu;
-#else
       split_pair(x0, x1, sa, hh, mm);
-#endif
       nh[u] = hh; nm[u] = mm;
     };
     constexpr bool ISSUE = MODE <= 1;
@@ -613,12 +609,7 @@ void pointwise_gemm_h2_f32(GroupedArgs ga_) {
       constexpr int DMA = decltype(dma_tag)::value;
       constexpr int SPL = decltype(spl_tag)::value;
       mfma_f16(a, b, c);
-#ifdef EPOS_H2_ABL_NODMA
-      constexpr bool kIssue = false;
-#else
-      constexpr bool kIssue = true;
-#endif
-      if constexpr (kIssue && ISSUE && DMA >= 0 && DMA < H2_NP) {
+      if constexpr (ISSUE && DMA >= 0 && DMA < H2_NP) {
         __builtin_amdgcn_sched_barrier(0);
         issue_piece(kt + LA, s4, std::integral_constant<int, DMA>{},
                     std::integral_constant<bool, MODE == 1>{});
@@ -648,16 +639,12 @@ void pointwise_gemm_h2_f32(GroupedArgs ga_) {
       // my reads of this stage are complete (fragments are in registers); my pieces of
       // tile kt+1 have landed once at most the later tiles' pieces are outstanding
       // (of tile kt+LA: the four pieces issued above)
-#ifndef EPOS_H2_ABL_NOBAR
       if constexpr (MODE <= 1) h2_wait_vm_lgkm0<(LA - 2) * NP + H2_NP>();
       else h2_wait_vm_lgkm0<(LA - MODE) * NP>();
       __builtin_amdgcn_s_barrier();
-#endif
-#ifndef EPOS_H2_ABL_NOREAD
       if constexpr (PS) read_a_ps(s1, nh, nm); else read_a(s1);
       read_b(s1, std::integral_constant<int, 0>{});
       read_b(s1, std::integral_constant<int, 1>{});
-#endif
       __builtin_amdgcn_sched_barrier(0);
     }
     // second half: blocks 2 (and 3); the next stage's A fragment is split behind the MFMAs
@@ -676,10 +663,8 @@ void pointwise_gemm_h2_f32(GroupedArgs ga_) {
     }
 #undef H2_D
     if constexpr (MODE != LAST) {
-#ifndef EPOS_H2_ABL_NOREAD
       read_b(s1, std::integral_constant<int, 2>{});
       if constexpr (LIVE == 4) read_b(s1, std::integral_constant<int, 3>{});
-#endif
       ah = nh; am = nm;
     }
   };
@@ -800,9 +785,6 @@ void pointwise_gemm_h2_f32(GroupedArgs ga_) {
 
   H2_STAMP(3);
   // ---- epilogue --------------------------------------------------------------
-#ifdef EPOS_H2_ABL_NOEPI            // ablation (tools/power_components_h2.py): no epilogue
-  if (p.ldr != 0x7fffffff) return;  // (always taken; the compiler cannot know)
-#endif
   if constexpr (!EARLY_EPI) {
     // (requesting these at the top of the last K step was tried: the residual variants sit
     // at 256 VGPRs and spill)
@@ -817,9 +799,6 @@ void pointwise_gemm_h2_f32(GroupedArgs ga_) {
     float* ws = smem + wave * 32 * Geo::EP_ROW;
     float amax = vec_epilogue_h2<HAS_RES, NB>(ws, acc, corr, cn, EARLY_EPI ? bias4 : nullptr,
                                               inv_a, p, m0 + wrow * 32, n0w, lane);
-#ifdef EPOS_H2_AMAX_PER_WAVE      // A/B: the former one-atomic-per-wave publish
-    if (p.c_amax) { amax_publish(p.c_amax, amax, lane, blockIdx.x * NW + wave); return; }
-#endif
     if (p.c_amax) {
       // ONE atomic per workgroup: the workgroups of a launch finish together, and their
       // atomics all land on the slot's two cache lines -- one per wave (912 for a middle-flow

@@ -189,9 +189,6 @@ __global__ __launch_bounds__(THREADS, 2) void pointwise_gemm_split_f32(GroupedAr
       static_cast<const char*>(p.Ws) + static_cast<int64_t>(tile_n) * nks * SP_W_BYTES));
 
   auto issue_piece = [&](int kt, int stage, auto piece_tag, auto tail_tag) {
-#ifdef EPOS_SPLIT_ABL_DMAHOT
-    kt = kt & 1;        // ablation: always the same two K steps (cache-hot sources)
-#endif
     constexpr int PIECE = decltype(piece_tag)::value;
     constexpr bool TAIL = decltype(tail_tag)::value;
     const unsigned so = static_cast<unsigned>(stage) * SP_STAGE;
@@ -211,12 +208,8 @@ __global__ __launch_bounds__(THREADS, 2) void pointwise_gemm_split_f32(GroupedAr
         // waves per SIMD, 1657 -> 1732 TFLOP/s bf16); the pieces that may need the zero
         // block (last partial K step, implicit-conv taps) keep the per-lane pointer.
         const float* ab = abase + (kt * SP_BK - PIECE * 256);      // uniform
-#ifdef EPOS_SPLIT_M0_EACH
-        glds16_s_m0(avoff[PIECE], ab + PIECE * 256, a_dst[PIECE] + so);
-#else
         if constexpr (PIECE == 0) glds16_s_m0(avoff[0], ab, a_dst[0] + so);
         else glds16_s_off<PIECE * 1024>(avoff[PIECE], ab);
-#endif
         return;
       } else {
         src = asrc[PIECE] + kt * SP_BK;
@@ -224,20 +217,12 @@ __global__ __launch_bounds__(THREADS, 2) void pointwise_gemm_split_f32(GroupedAr
       }
       // pieces of one kind are 1 KB apart in LDS: one M0 write for the first, the
       // instruction offset (added to both addresses) for the others
-#ifdef EPOS_SPLIT_M0_EACH
-      glds16_v_m0(src, a_dst[PIECE] + so);
-#else
       if constexpr (PIECE == 0) glds16_v_m0(src, a_dst[0] + so);
       else glds16_v_off<PIECE * 1024>(src - PIECE * 256);
-#endif
     } else {
       const float* wb = wsb + static_cast<int64_t>(kt) * (SP_W_BYTES / 4);
-#ifdef EPOS_SPLIT_M0_EACH
-      glds16_s_m0(wvoff[PIECE - RB], wb, w_dst[PIECE - RB] + so);
-#else
       if constexpr (PIECE == RB) glds16_s_m0(wvoff[0], wb, w_dst[0] + so);
       else glds16_s_off<(PIECE - RB) * 1024>(wvoff[0], wb);
-#endif
     }
   };
   auto issue = [&](int kt, int stage) {
@@ -310,20 +295,7 @@ __global__ __launch_bounds__(THREADS, 2) void pointwise_gemm_split_f32(GroupedAr
   // bf16 pieces of this wave's A fragment for the stage being computed; the next
   // stage's are split in the middle of the current one (between its MFMAs)
   u32x4 ah, am, al;
-  auto split_xa = [&](u32x4& hi, u32x4& mid, u32x4& lo) {
-#ifdef EPOS_SPLIT_ABL_NOSPLIT
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const float* x0 = reinterpret_cast<const float*>(&xa[0]);
-      const float* x1 = reinterpret_cast<const float*>(&xa[1]);
-      hi[j] = __float_as_uint(x0[j]); mid[j] = __float_as_uint(x1[j]);
-      lo[j] = hi[j] ^ mid[j];
-    }
-#else
-    split8(xa[0], xa[1], hi, mid, lo);
-#endif
-  };
-  split_xa(ah, am, al);
+  split8(xa[0], xa[1], ah, am, al);
   // MODE 0: issue tile kt+3 (full)  1: issue tile kt+3 (the last, maybe partial)
   //      2: kt+2 is the last tile   3: kt+1 is the last tile   4: last tile
   // LIVE: column blocks of this wave that hold any column < N (CB, or CB - 1 for the
@@ -341,15 +313,11 @@ __global__ __launch_bounds__(THREADS, 2) void pointwise_gemm_split_f32(GroupedAr
     auto split_val = [&](auto j_tag) {
       constexpr int j = decltype(j_tag)::value;
       const float x = reinterpret_cast<const float*>(&xa[j >> 2])[j & 3];
-#ifdef EPOS_SPLIT_ABL_NOSPLIT
-      hb[j] = __float_as_uint(x); mb[j] = hb[j] ^ 0x3f80u; lb[j] = hb[j] ^ 0x40u;
-#else
       hb[j] = __float_as_uint(x);
       const float r1 = x - __uint_as_float(hb[j] & 0xffff0000u);
       mb[j] = __float_as_uint(r1);
       const float r2 = r1 - __uint_as_float(mb[j] & 0xffff0000u);
       lb[j] = __float_as_uint(r2);
-#endif
       if constexpr (j & 1) {
         nh[j >> 1] = pack_hi16(hb[j - 1], hb[j]);
         nm[j >> 1] = pack_hi16(mb[j - 1], mb[j]);
@@ -364,33 +332,24 @@ __global__ __launch_bounds__(THREADS, 2) void pointwise_gemm_split_f32(GroupedAr
       auto one = [&](const u32x4& a, const u32x4& b, f32x16& c, auto n_tag) {
         constexpr int n = decltype(n_tag)::value;       // 0..5 within the block
         mfma_bf16(a, b, c);
-#ifdef EPOS_SPLIT_ABL_NODMA
-        constexpr bool kIssue = false;
-#else
-        constexpr bool kIssue = true;
-#endif
-        // the LDS-DMA pieces of tile kt+3 go out one at a time between MFMAs: after
-        // every second MFMA of column blocks 0 and 1 (CB 4), after each of the first
-        // four MFMAs of block 0 (CB 2)
-        constexpr int piece = DMA0 < 0 ? -1 : CB == 4 ? ((n & 1) ? DMA0 + n / 2 : -1) : DMA0 + n;
-        if constexpr (kIssue && piece >= 0 && piece < NP) {
+        // the LDS-DMA pieces of tile kt+3 go out one at a time between MFMAs: after each
+        // of the first four MFMAs of block 0 (CB 2; with CB 4 the pairs below issue them)
+        constexpr int piece = DMA0 < 0 ? -1 : DMA0 + n;
+        if constexpr (piece >= 0 && piece < NP) {
           __builtin_amdgcn_sched_barrier(0);
           issue_piece(kt + 3, s3, std::integral_constant<int, piece>{},
                       std::integral_constant<bool, MODE == 1>{});
           __builtin_amdgcn_sched_barrier(0);
         }
-        // second half: the next stage's A values are split one (CB 4) or two (CB 2) per
-        // MFMA, pinned between the MFMAs (the bf16 MFMA leaves the vector ALU free);
-        // the first slots cover the LDS latency of the fragment just requested
+        // second half: a lone block is six MFMAs, so the next stage's A values are split
+        // two per MFMA, pinned between the MFMAs (the bf16 MFMA leaves the vector ALU free);
+        // the first slot covers the LDS latency of the fragment just requested
         if constexpr (SLOT0 >= 0 && MODE != 4) {
-          constexpr int slot = SLOT0 + n;
-          constexpr bool kOnePerSlot = CB == 4 && LIVE == 4;     // 12 MFMAs, else 6
-          constexpr int first = kOnePerSlot ? slot - 2 : 2 * (slot - 1);
-          constexpr int cnt = kOnePerSlot ? 1 : 2;
+          constexpr int first = 2 * (SLOT0 + n - 1);
           if constexpr (first >= 0 && first < 8) {
             __builtin_amdgcn_sched_barrier(0);
             split_val(std::integral_constant<int, first>{});
-            if constexpr (cnt == 2) split_val(std::integral_constant<int, first + 1>{});
+            split_val(std::integral_constant<int, first + 1>{});
             __builtin_amdgcn_sched_barrier(0);
           }
         }
@@ -418,13 +377,8 @@ __global__ __launch_bounds__(THREADS, 2) void pointwise_gemm_split_f32(GroupedAr
       auto step = [&](const u32x4& a, const u32x4& b, f32x16& c, auto s_tag) {
         constexpr int s = decltype(s_tag)::value;        // 0..11 within the pair
         mfma_bf16(a, b, c);
-#ifdef EPOS_SPLIT_ABL_NODMA
-        constexpr bool kIssue = false;
-#else
-        constexpr bool kIssue = true;
-#endif
         constexpr int piece = (DMA0 < 0 || !(s & 1)) ? -1 : DMA0 + s / 2;
-        if constexpr (kIssue && piece >= 0 && piece < NP) {
+        if constexpr (piece >= 0 && piece < NP) {
           __builtin_amdgcn_sched_barrier(0);
           issue_piece(kt + 3, s3, std::integral_constant<int, piece>{},
                       std::integral_constant<bool, MODE == 1>{});
@@ -452,25 +406,16 @@ __global__ __launch_bounds__(THREADS, 2) void pointwise_gemm_split_f32(GroupedAr
       step(ah, bp[ca][0], acc[ca], std::integral_constant<int, 10>{});
       step(ah, bp[cbb][0], acc[cbb], std::integral_constant<int, 11>{});
     };
-#ifndef EPOS_SPLIT_NOILV
-    constexpr bool kPair = CB == 4;
-#else
-    constexpr bool kPair = false;
-#endif
     // first half of the column blocks (+ the DMA pieces), barrier, second half
-    if constexpr (kPair) {
+    if constexpr (CB == 4) {
       pair(std::integral_constant<int, 0>{}, std::integral_constant<int, 1>{},
            std::integral_constant<int, ISSUE ? 0 : -1>{}, NoDma{});
-    } else if constexpr (CB == 4) {
-      block(std::integral_constant<int, 0>{}, std::integral_constant<int, ISSUE ? 0 : -1>{}, NoDma{});
-      block(std::integral_constant<int, 1>{}, std::integral_constant<int, ISSUE ? 3 : -1>{}, NoDma{});
     } else {
       block(std::integral_constant<int, 0>{}, std::integral_constant<int, ISSUE ? 0 : -1>{}, NoDma{});
     }
     if constexpr (MODE != 4) {
       // my reads of this stage are complete (fragments are in registers); my pieces
       // of tile kt+1 have landed once at most the later tiles' pieces are outstanding
-#ifndef EPOS_SPLIT_ABL_NOBAR
       if (MODE <= 1) {
         if (NP == 5) asm volatile("s_waitcnt vmcnt(10) lgkmcnt(0)" ::: "memory");
         else asm volatile("s_waitcnt vmcnt(8) lgkmcnt(0)" ::: "memory");
@@ -480,25 +425,19 @@ __global__ __launch_bounds__(THREADS, 2) void pointwise_gemm_split_f32(GroupedAr
       }
       else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
       __builtin_amdgcn_s_barrier();
-#endif
-#ifndef EPOS_SPLIT_ABL_NOREAD
       read_a(s1);
       read_b(s1, std::integral_constant<int, 0>{});
       if constexpr (CB == 4) read_b(s1, std::integral_constant<int, 1>{});
-#endif
       __builtin_amdgcn_sched_barrier(0);
     }
-    if constexpr (kPair && LIVE == 4) {
+    if constexpr (CB == 4 && LIVE == 4) {
       pair(std::integral_constant<int, 2>{}, std::integral_constant<int, 3>{}, NoDma{},
            std::integral_constant<int, 0>{});
     } else if constexpr (CB == 4) {
       block(std::integral_constant<int, 2>{}, NoDma{}, std::integral_constant<int, 0>{});
-      if constexpr (LIVE == 4)
-        block(std::integral_constant<int, 3>{}, NoDma{}, std::integral_constant<int, 6>{});
     } else {
       block(std::integral_constant<int, 1>{}, NoDma{}, std::integral_constant<int, 0>{});
     }
-#ifndef EPOS_SPLIT_ABL_NOREAD
     if constexpr (MODE != 4) {
       if constexpr (CB == 4) {
         read_b(s1, std::integral_constant<int, 2>{});
@@ -507,7 +446,6 @@ __global__ __launch_bounds__(THREADS, 2) void pointwise_gemm_split_f32(GroupedAr
         read_b(s1, std::integral_constant<int, 1>{});
       }
     }
-#endif
     if constexpr (MODE != 4) { ah = nh; am = nm; al = nl; }
   };
   auto k_loop = [&](auto live_tag) {

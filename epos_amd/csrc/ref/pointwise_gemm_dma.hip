@@ -30,20 +30,6 @@ namespace {
 // ---------------------------------------------------------------------------
 __device__ __attribute__((aligned(16))) float g_zero_chunk[4] = {0.f, 0.f, 0.f, 0.f};
 
-// Build with -DEPOS_GEMM_TRACE (tools/gemm_trace.py) to record per-workgroup phase
-// timestamps (s_memrealtime, 100 MHz) of the LDS-DMA kernel.
-#ifdef EPOS_GEMM_TRACE
-__device__ unsigned long long g_trace[8192 * 8];
-__device__ unsigned long long g_trace_units[512 * 32];   // stream-K: end time of each unit
-#define EPOS_TRACE(slot)                                                     \
-  do {                                                                       \
-    if (threadIdx.x == 0 && blockIdx.x < 8192)                               \
-      g_trace[blockIdx.x * 8 + (slot)] = wall_clock64();                     \
-  } while (0)
-#else
-#define EPOS_TRACE(slot) do {} while (0)
-#endif
-
 constexpr int DMA_B_BYTES = (BK / 4) * BN * 16;          // 16384
 constexpr int DMA_A_BYTES = 64 * BK * 4;                 // 8192
 constexpr int DMA_STAGE_BYTES = DMA_A_BYTES + DMA_B_BYTES;
@@ -77,16 +63,6 @@ __global__ __launch_bounds__(THREADS) void pointwise_gemm_dma_f32(GroupedArgs ga
   const int wave_u = __builtin_amdgcn_readfirstlane(wave);
   const int wm = LAYOUT == 0 ? wave >> 1 : wave, wn = LAYOUT == 0 ? wave & 1 : 0;
   const int l31 = lane & 31, h = lane >> 5;
-  EPOS_TRACE(0);
-#ifdef EPOS_GEMM_TRACE
-  if (t == 0 && blockIdx.x < 8192) {
-    unsigned hw, xcc;
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-    g_trace[blockIdx.x * 8 + 4] = (static_cast<unsigned long long>(xcc) << 32) | hw;
-    g_trace[blockIdx.x * 8 + 5] = clock64();
-  }
-#endif
 
   (void)ga_;
   const GroupedArgs* __restrict__ gp =
@@ -223,23 +199,15 @@ __global__ __launch_bounds__(THREADS) void pointwise_gemm_dma_f32(GroupedArgs ga
     for (int r = 0; r < 16; ++r) acc[j][r] = 0.f;
 
   // ---- prologue: tiles 0 and 1 in flight, tile 0 landed + visible -----------
-#ifdef EPOS_GEMM_TRACE
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // finer prologue split (first 512 WGs)
-  if (t == 0 && blockIdx.x < 512) g_trace_units[blockIdx.x * 32] = wall_clock64();
-#endif
   if (nk == 1) {
     issue(0, 0, std::true_type{});
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   } else {
     issue(0, 0, std::false_type{});
     if (nk == 2) issue(1, 1, std::true_type{}); else issue(1, 1, std::false_type{});
-#ifdef EPOS_GEMM_TRACE
-    if (t == 0 && blockIdx.x < 512) g_trace_units[blockIdx.x * 32 + 1] = wall_clock64();
-#endif
     asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
   }
   __builtin_amdgcn_s_barrier();
-  EPOS_TRACE(1);
   read_frags(0, std::integral_constant<int, 0>{});
 
   // MODE 0: issue tile kt+2 (full)   1: issue tile kt+2 (the last, maybe partial)
@@ -256,16 +224,12 @@ __global__ __launch_bounds__(THREADS) void pointwise_gemm_dma_f32(GroupedArgs ga
       constexpr int g = decltype(g_tag)::value;
       const float4 ca = fa, cb0 = fb[0], cb1 = fb[1];
       if constexpr (g < 3) {
-#ifndef EPOS_ABL_NOREAD
         read_frags(stage, std::integral_constant<int, g + 1>{});
-#endif
       } else if constexpr (MODE != 3) {
         // my reads of this stage are complete, my pieces of tile kt+1 have landed
-#ifndef EPOS_ABL_NOBAR
         if (MODE <= 1) asm volatile("s_waitcnt vmcnt(6) lgkmcnt(0)" ::: "memory");
         else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
-#endif
         read_frags(s1, std::integral_constant<int, 0>{});
       }
       __builtin_amdgcn_sched_barrier(0);
@@ -278,12 +242,7 @@ __global__ __launch_bounds__(THREADS) void pointwise_gemm_dma_f32(GroupedArgs ga
           acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(afp[sidx], b0p[sidx], acc[0], 0, 0, 0);
           acc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(afp[sidx], b1p[sidx], acc[1], 0, 0, 0);
           constexpr int piece = g * 4 + sidx;
-#ifdef EPOS_ABL_NODMA
-          constexpr bool kIssue = false;
-#else
-          constexpr bool kIssue = true;
-#endif
-          if constexpr (kIssue && MODE <= 1 && piece < 6) {
+          if constexpr (MODE <= 1 && piece < 6) {
             __builtin_amdgcn_sched_barrier(0);
             issue_piece(kt + 2, s2, std::integral_constant<int, piece>{},
                         std::integral_constant<bool, MODE == 1>{});
@@ -331,20 +290,12 @@ __global__ __launch_bounds__(THREADS) void pointwise_gemm_dma_f32(GroupedArgs ga
     }
     tile(kt, stage, M3{});
   }
-  EPOS_TRACE(2);
 
   // ---- epilogue (as pointwise_gemm_f32<64>) ---------------------------------
   if (vec_epilogue_ok(p, HAS_RES)) {
     __syncthreads();
     float* ws = smem + wave * 32 * EP_ROW;
     vec_epilogue<1, 2, HAS_RES>(ws, acc, p, m0 + wm * 32, n0 + wn * 64, lane);
-#ifdef EPOS_GEMM_TRACE
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
-    EPOS_TRACE(3);
-#ifdef EPOS_GEMM_TRACE
-    if (t == 0 && blockIdx.x < 8192) g_trace[blockIdx.x * 8 + 6] = clock64();
-#endif
     return;
   }
   const bool relu = p.relu != 0;
@@ -436,12 +387,3 @@ namespace {
 const int registered_dma = (fp32_mfma_ref().dma = &launch_grouped_dma, 0);
 }  // namespace
 }  // namespace epos
-
-#ifdef EPOS_GEMM_TRACE
-extern "C" int epos_debug_read_trace(void* dst, size_t bytes) {
-  return static_cast<int>(hipMemcpyFromSymbol(dst, HIP_SYMBOL(epos::g_trace), bytes));
-}
-extern "C" int epos_debug_read_trace_units(void* dst, size_t bytes) {
-  return static_cast<int>(hipMemcpyFromSymbol(dst, HIP_SYMBOL(epos::g_trace_units), bytes));
-}
-#endif

@@ -12,7 +12,7 @@ tests/test_depthwise_regimes.py checks that the table reaches every regime witho
 """
 import collections
 
-L = 4            # EPOS_DW_L: outputs per run
+L = 4            # outputs per run (L of epos_depthwise3x3 in layers.hip)
 WAVE = 64
 
 Regime = collections.namedtuple(

@@ -300,3 +300,37 @@ def test_product_library_carries_no_fp32_mfma_gemm_and_the_test_build_does():
   lib = ctypes.CDLL(ref)
   for name in _lib.SYMBOLS:
     assert hasattr(lib, name), name
+
+
+# (S, n_capacity, max_iters, max_k) -> bytes of epos_fit_workspace_bytes and of
+# epos_pnp_ransac_workspace_bytes (iterations_count = max_iters; it has no max_k). The byte
+# counts are those of the library at commit b717b1d, before each workspace was described by one
+# carve-in-order routine: the buffers behind a by-value kernel argument must not move.
+WORKSPACE_BYTES = [
+    ((0, 0, 400, 1), 19456, 256),
+    ((1, 1, 400, 1), 204544, 48640),
+    ((1, 63, 1, 1), 118528, 1024),
+    ((1, 64, 400, 4), 293632, 48640),
+    ((21, 1 << 20, 400, 1), 1490107648, 5202688),
+    ((240, 1 << 20, 400, 4), 1530806528, 15714304),
+    ((3, 100000, 37, 6), 141899520, 413696),
+]
+
+
+def test_fit_workspace_sizes_are_pinned():
+  from epos_amd import _lib
+  lib = _lib.load()
+  fit = _lib.FitParams()
+  lib.epos_fit_params_default(ctypes.byref(fit))
+  pnp = _lib.PnpRansacParams()
+  lib.epos_pnp_ransac_params_default(ctypes.byref(pnp))
+  for (S, cap, iters, max_k), fit_bytes, pnp_bytes in WORKSPACE_BYTES:
+    fit.max_iters = iters
+    pnp.iterations_count = iters
+    case = (S, cap, iters, max_k)
+    assert lib.epos_fit_workspace_bytes(S, cap, ctypes.byref(fit), max_k) == fit_bytes, case
+    assert lib.epos_pnp_ransac_workspace_bytes(S, cap, ctypes.byref(pnp)) == pnp_bytes, case
+  EPOS_E_INVALID = -1
+  assert lib.epos_fit_workspace_bytes(1, 64, ctypes.byref(fit), 0) == EPOS_E_INVALID
+  assert lib.epos_fit_workspace_bytes(1, 64, None, 1) == EPOS_E_INVALID
+  assert lib.epos_pnp_ransac_workspace_bytes(1, 64, None) == EPOS_E_INVALID

@@ -1,18 +1,11 @@
 #!/usr/bin/env python
 """Micro-benchmark of epos_depthwise3x3_f32 on the network's shapes (warm clocks),
 next to a plain device copy of the same tensor (the streaming floor at that size).
-EPOS_DW_L / EPOS_DW_THREADS select kernel variants."""
+EPOS_DW_MODE / EPOS_DW_THREADS / EPOS_DW_ROWS select kernel variants."""
 import ctypes, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from epos_amd import _lib
-defs = os.environ.get('DW_DEFS', '').split()         # ablation builds of layers.hip
-if defs:
-  import subprocess
-  from epos_amd import build
-  path = os.path.join(build.LIB_DIR, 'libepos_hip_dw%s.so' % ''.join(d.replace('-D', '_') for d in defs))
-  subprocess.check_call([build.HIPCC] + build.FLAGS + defs + ['-o', path] + build.sources())
-  _lib.lib_path = lambda: path
 lib = _lib.load()
 H2 = '--h2' in sys.argv          # fp16-pair output (what the plan's depthwise layers write)
 def p(t): return ctypes.c_void_p(t.data_ptr())

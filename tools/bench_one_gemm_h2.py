@@ -29,7 +29,7 @@ if '--copy' in sys.argv:          # a plain copy of A beside the GEMM (PMC calib
   B2 = torch.empty_like(A)
   for _ in range(it): B2.copy_(A)
   torch.cuda.synchronize()
-if '--time' in sys.argv:          # warm launches back to back, HIP events (round 6: EPOS_H2_PERSIST A/B)
+if '--time' in sys.argv:          # warm launches back to back, HIP events (round 6: the A/B of the tile-walking workgroups)
   for _ in range(200): lib.epos_pointwise_conv_f32(ctypes.byref(a), None)
   e0 = torch.cuda.Event(enable_timing=True); e1 = torch.cuda.Event(enable_timing=True)
   e0.record()

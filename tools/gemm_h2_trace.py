@@ -13,8 +13,8 @@ sys.path.insert(0, ROOT)
 from epos_amd import build
 PATH = os.path.join(build.LIB_DIR, 'libepos_gemm_h2_trace.so')
 if len(sys.argv) > 1 and sys.argv[1] == 'build':
-  subprocess.check_call([build.HIPCC] + build.FLAGS + ['-Wno-inline-asm', '-DEPOS_GEMM_TRACE'] +
-                        os.environ.get('TRACE_DEFS', '').split() + ['-o', PATH] + build.sources())
+  subprocess.check_call([build.HIPCC] + build.FLAGS + ['-Wno-inline-asm', '-DEPOS_GEMM_TRACE',
+                                                       '-o', PATH] + build.sources())
   sys.exit(0)
 import numpy as np, torch
 from epos_amd import _lib
