@@ -251,6 +251,11 @@ SYMBOLS = {
         ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double, vp, vp, vp,
         vp, ctypes.c_int64, ctypes.POINTER(CorrOut), vp, vp]),
     'epos_corr_slot_bases': (ctypes.c_int, [vp, ctypes.c_int, vp, vp]),
+    'epos_corr_order_tile_rows': (ctypes.c_int, []),
+    'epos_corr_order_workspace_bytes': (ctypes.c_int64, [ctypes.c_int, ctypes.c_int64]),
+    'epos_corr_order_by_conf': (ctypes.c_int, [
+        vp, vp, vp, vp, vp, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int64,
+        ctypes.c_int, vp, vp, vp, vp, vp, vp, vp, vp]),
     'epos_project_to_mesh_f64': (ctypes.c_int, [
         ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64,
         ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
@@ -267,6 +272,9 @@ SYMBOLS = {
     'epos_find6d_poses_device': (ctypes.c_int, [
         vp, vp, vp, ctypes.c_int, ctypes.c_int64, vp, vp, vp,
         ctypes.POINTER(FitParams), ctypes.c_int32, vp, vp, vp, vp, vp, vp]),
+    'epos_find6d_poses_device_ordered': (ctypes.c_int, [
+        vp, vp, vp, ctypes.c_int, ctypes.c_int64, vp, vp, vp,
+        ctypes.POINTER(FitParams), ctypes.c_int32, vp, vp, vp, vp, vp, vp, vp, vp]),
     'epos_pnp_ransac_params_default': (None, [ctypes.POINTER(PnpRansacParams)]),
     'epos_solve_pnp_ransac': (ctypes.c_int, [
         vp, vp, ctypes.c_int64, vp, ctypes.POINTER(PnpRansacParams), vp, vp, vp]),

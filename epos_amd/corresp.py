@@ -134,6 +134,54 @@ class CorrExtractor(object):
         _stream(self.dev)), 'epos_corr_fill')
 
 
+def confidence_order(conf):
+  """The confidence order of one object's correspondences (scripts/infer.py:425-440: PROSAC
+  order / top max_correspondences): conf descending, ties by ascending row. The reference's
+  np.argsort(conf)[::-1] leaves ties to an unstable sort; this is one of the permutations
+  it may return, and the total order the device stage (CorrOrderer) applies."""
+  return np.argsort(-np.asarray(conf), kind='stable')
+
+
+class CorrOrderer(object):
+  """Device-side confidence order / truncation of a CorrExtractor's rows (csrc/
+  corresp_order.hip), with preallocated outputs: run() after fill(), on the same stream,
+  nothing synchronises. The fitting calls then read coord_2d / coord_3d / slot_base (and,
+  Progressive-X, yorder / ypos) of THIS object instead of the extractor's.
+
+  max_correspondences: None or <= 0 = keep every row; use_prosac: order every slot (PROSAC
+  samples from a prefix), otherwise only the slots that are truncated.
+  """
+
+  def __init__(self, extractor, max_correspondences=None, use_prosac=False):
+    self.ex = ex = extractor
+    self.lib = ex.lib
+    self.max_corr = int(max_correspondences) if max_correspondences is not None else 0
+    self.always_sort = 1 if use_prosac else 0
+    d, n = ex.dev, max(ex.capacity, 1)
+    self.capacity = ex.capacity
+    self.slot_base = torch.zeros(ex.max_slots + 1, dtype=torch.int64, device=d)
+    self.coord_2d = torch.empty(n, 2, dtype=torch.float64, device=d)
+    self.coord_3d = torch.empty(n, 3, dtype=torch.float64, device=d)
+    self.src_row = torch.empty(n, dtype=torch.int32, device=d)
+    self.yorder = torch.empty(n, dtype=torch.int32, device=d)
+    self.ypos = torch.empty(n, dtype=torch.int32, device=d)
+    wbytes = self.lib.epos_corr_order_workspace_bytes(ex.max_slots, ex.capacity)
+    if wbytes < 0:
+      raise _lib.EposError('epos_corr_order_workspace_bytes failed')
+    self.work = torch.empty(max(wbytes, 1), dtype=torch.uint8, device=d)
+
+  def run(self):
+    ex = self.ex
+    if not ex.S:
+      return
+    _lib.check(self.lib.epos_corr_order_by_conf(
+        _ptr(ex.conf), _ptr(ex.px_id), _ptr(ex.coord_2d), _ptr(ex.coord_3d),
+        _ptr(ex.slot_base), ex.S, ex.capacity, ex.w, self.max_corr, self.always_sort,
+        _ptr(self.work), _ptr(self.slot_base), _ptr(self.coord_2d), _ptr(self.coord_3d),
+        _ptr(self.src_row), _ptr(self.yorder), _ptr(self.ypos), _stream(ex.dev)),
+               'epos_corr_order_by_conf')
+
+
 def establish_many_to_many(
       obj_confs, frag_confs, frag_coords, gt_obj_ids, model_store, output_scale,
       min_obj_conf, min_frag_rel_conf, project_to_surface, only_annotated_objs,

@@ -2523,21 +2523,33 @@ extern "C" int64_t epos_fit_workspace_bytes(int S, int64_t n_capacity,
   return carve_work(nullptr, S, n_capacity, p->max_iters, max_k, unused);
 }
 
+extern "C" int epos_find6d_poses_device_ordered(
+    const double* xy, const double* xyz, const int64_t* slot_base, int S,
+    int64_t n_capacity, const double* Ks, const int32_t* max_models,
+    const uint64_t* seeds, const EposFitParams* p, int32_t max_k, void* work,
+    double* poses, double* scores, int32_t* num_models, int32_t* labels,
+    void* stream, const int32_t* yorder, const int32_t* ypos) {
+  EPOS_REQUIRE(xy && xyz && slot_base && Ks && max_models && seeds && p && work &&
+               poses && scores && num_models && labels, "null pointer");
+  EPOS_REQUIRE(!yorder == !ypos, "yorder and ypos: both or neither");
+  EPOS_REQUIRE(max_k >= 1 && p->max_iters >= 1, "max_k and max_iters must be >= 1");
+  EPOS_REQUIRE(p->gc_sweeps >= 0 && p->gc_sweeps <= 16, "gc_sweeps must be in [0, 16]");
+  EPOS_REQUIRE(p->pearl_iters >= 0 && p->pearl_iters <= 8, "pearl_iters must be in [0, 8]");
+  if (S == 0) return EPOS_OK;
+  return find6d_enqueue(xy, xyz, slot_base, S, n_capacity, Ks, max_models, seeds, p, max_k,
+                        work, poses, scores, num_models, labels, yorder, ypos,
+                        static_cast<hipStream_t>(stream));
+}
+
 extern "C" int epos_find6d_poses_device(
     const double* xy, const double* xyz, const int64_t* slot_base, int S,
     int64_t n_capacity, const double* Ks, const int32_t* max_models,
     const uint64_t* seeds, const EposFitParams* p, int32_t max_k, void* work,
     double* poses, double* scores, int32_t* num_models, int32_t* labels,
     void* stream) {
-  EPOS_REQUIRE(xy && xyz && slot_base && Ks && max_models && seeds && p && work &&
-               poses && scores && num_models && labels, "null pointer");
-  EPOS_REQUIRE(max_k >= 1 && p->max_iters >= 1, "max_k and max_iters must be >= 1");
-  EPOS_REQUIRE(p->gc_sweeps >= 0 && p->gc_sweeps <= 16, "gc_sweeps must be in [0, 16]");
-  EPOS_REQUIRE(p->pearl_iters >= 0 && p->pearl_iters <= 8, "pearl_iters must be in [0, 8]");
-  if (S == 0) return EPOS_OK;
-  return find6d_enqueue(xy, xyz, slot_base, S, n_capacity, Ks, max_models, seeds, p, max_k,
-                        work, poses, scores, num_models, labels, nullptr, nullptr,
-                        static_cast<hipStream_t>(stream));
+  return epos_find6d_poses_device_ordered(xy, xyz, slot_base, S, n_capacity, Ks, max_models,
+                                          seeds, p, max_k, work, poses, scores, num_models,
+                                          labels, stream, nullptr, nullptr);
 }
 
 extern "C" int epos_find6d_poses(const double* xy, const double* xyz, int64_t n,

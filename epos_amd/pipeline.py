@@ -58,7 +58,8 @@ class EposPipeline(object):
                max_instances=4, model_options=None, device='cuda:0',
                use_graph=True, instance=0, sparse_heads=False,
                fitting_method='progressive_x', on_excess='raise', queue=1,
-               precision='fp32', image_pyramid=None, merge_method=None):
+               precision='fp32', image_pyramid=None, merge_method=None,
+               max_correspondences=None):
     """on_excess: what launch() does with a frame that asks for more instances of an object
     than `max_instances` (localization): 'raise' (default: EposError BEFORE anything of that
     batch is enqueued -- batches already in flight on other pipelines are unaffected and can
@@ -70,6 +71,13 @@ class EposPipeline(object):
     The correspondences are placed with output_scale = max(1, max(P)) / 4, the stride of the
     merged heads (for pyramids with every scale <= 1 that is the reference's 1/4; DESIGN.md,
     "multi-scale mode"). Sparse heads are not available with a pyramid (ValueError).
+    max_correspondences / fit_params.use_prosac (scripts/infer.py:425-440): with either set,
+    launch() orders every slot's correspondences by confidence on the device (PROSAC) and
+    keeps the best max_correspondences of a slot that has more (corresp.CorrOrderer), between
+    the correspondence and the fitting stage; with neither, that stage does not exist. The
+    fitting stage then sees the ordered / kept rows: self.labels (the opencv method's inlier
+    mask) is indexed by kept row within self.order.slot_base, and self.order.src_row maps a
+    kept row back to the extractor's slot-local row.
     capacity: correspondence rows per batch, over all slots, at up to 64 fragments per object.
     A masked pixel yields up to F rows, so the correspondence and fitting buffers are sized for
     `capacity * ceil(num_frags / 64)` rows (self.capacity); for num_frags <= 64 that is
@@ -139,6 +147,13 @@ class EposPipeline(object):
         batch, self.net.out_h, self.net.out_w, num_objs, num_frags, centers,
         sizes, self.max_slots, capacity, device)
     self.fit = fit_params or _fitting.fit_params()
+    # the confidence-ordered copy of the correspondences the fitting stage then reads: once per
+    # pipeline and stream-ordered like the extractor's buffers (queue=2 stays valid)
+    self.max_correspondences = max_correspondences
+    self.order = None
+    if max_correspondences is not None or self.fit.use_prosac:
+      self.order = _corresp.CorrOrderer(self.corr, max_correspondences,
+                                        bool(self.fit.use_prosac))
     S = self.max_slots
     d = self.dev
     wbytes = self.lib.epos_fit_workspace_bytes(S, capacity, ctypes.byref(self.fit),
@@ -309,16 +324,29 @@ class EposPipeline(object):
                        pred[W.PRED_FRAG_LOC], self.output_scale)
         if timing:
           ev[2].record()
+        src = self.corr
+        if self.order is not None:        # counted as fitting time, as the reference's sort is
+          self.order.run()
+          src = self.order
         if self.fitting_method == 'opencv_ransac':
           # one pose per slot: poses [S, 1, 12], num_models = success flag, scores 0.0; the
           # inlier mask (u8 per correspondence) lands in the bytes of the label buffer
           self.scores.zero_()
           _lib.check(self.lib.epos_solve_pnp_ransac_device(
-              _ptr(self.corr.coord_2d), _ptr(self.corr.coord_3d),
-              _ptr(self.corr.slot_base), S, self.corr.capacity, _ptr(self.Ks),
+              _ptr(src.coord_2d), _ptr(src.coord_3d),
+              _ptr(src.slot_base), S, self.corr.capacity, _ptr(self.Ks),
               ctypes.byref(self.cv_params), _ptr(self.work), _ptr(self.poses),
               _ptr(self.num_models), _ptr(self.labels), None,
               ctypes.c_void_p(self.stream.cuda_stream)), 'epos_solve_pnp_ransac_device')
+        elif self.order is not None:
+          _lib.check(self.lib.epos_find6d_poses_device_ordered(
+              _ptr(src.coord_2d), _ptr(src.coord_3d),
+              _ptr(src.slot_base), S, self.corr.capacity, _ptr(self.Ks),
+              _ptr(self.max_models), _ptr(self.seeds), ctypes.byref(self.fit),
+              max_k, _ptr(self.work), _ptr(self.poses), _ptr(self.scores),
+              _ptr(self.num_models), _ptr(self.labels),
+              ctypes.c_void_p(self.stream.cuda_stream), _ptr(src.yorder), _ptr(src.ypos)),
+                     'epos_find6d_poses_device_ordered')
         else:
           _lib.check(self.lib.epos_find6d_poses_device(
               _ptr(self.corr.coord_2d), _ptr(self.corr.coord_3d),

@@ -444,6 +444,41 @@ int epos_corr_fill(const float* obj_confs, const float* frag_confs,
 int epos_corr_slot_bases(const int32_t* totals, int S, int64_t* slot_base,
                          void* stream);
 
+/* Confidence order, truncation and row-order permutation of the pooled correspondences
+ * (scripts/infer.py:425-440: PROSAC order / top max_correspondences by confidence), between
+ * epos_corr_fill and the fitting call, all buffers [device], nothing synchronises or
+ * allocates. With n_s = slot_base[s+1] - slot_base[s] (both bounds clamped to
+ * [0, capacity]: after an overflow of epos_corr_fill nothing at or beyond capacity is read),
+ * K = max_corr (<= 0: no limit), per slot:
+ *   - the confidence order -- conf descending, ties by ascending original row -- applies
+ *     iff always_sort != 0 or (K > 0 and n_s > K); otherwise the rows keep their order;
+ *   - the first n'_s = (K > 0 ? min(n_s, K) : n_s) rows of that order are kept.
+ * Outputs (N' = sum of n'_s <= capacity; size them for capacity rows):
+ *   slot_base_out i64[S+1]  exclusive scan of n'_s
+ *   coord_2d_out f64[N',2], coord_3d_out f64[N',3]  the kept rows, gathered
+ *   src_row_out i32[N']     slot-local original row of every kept row
+ *   yorder, ypos i32[N']    slot-local positions of the kept rows sorted by (coord_2d y
+ *                           ascending, position ascending) -- the stable sort by y of
+ *                           epos_find6d_poses -- and the inverse: the permutations
+ *                           epos_find6d_poses_device_ordered takes (identities for a slot
+ *                           that kept its order).
+ * PRECONDITION: the rows of every slot come in raster order (coord_2d y non-decreasing), as
+ * epos_corr_fill writes them: a kept row's y is ranked by a binary search over its slot's
+ * original rows. px_id and W are not read (px_id, as epos_corr_fill writes it, counts the
+ * MASKED pixels and does not give the image row); they stay in the signature.
+ * work: epos_corr_order_workspace_bytes(S, capacity) bytes. capacity < 2^31.
+ * epos_corr_order_tile_rows(): slots of at most that many rows are ordered by one workgroup
+ * in LDS; longer ones by merge passes in global memory on top (same result either way; the
+ * passes that no slot of the call is long enough for leave at once). */
+int epos_corr_order_tile_rows(void);
+int64_t epos_corr_order_workspace_bytes(int S, int64_t capacity);
+int epos_corr_order_by_conf(const float* conf, const int64_t* px_id, const double* coord_2d,
+                            const double* coord_3d, const int64_t* slot_base, int S,
+                            int64_t capacity, int W, int64_t max_corr, int always_sort,
+                            void* work, int64_t* slot_base_out, double* coord_2d_out,
+                            double* coord_3d_out, int32_t* src_row_out, int32_t* yorder,
+                            int32_t* ypos, void* stream);
+
 /* project_to_surface (corresp.py:87-88, datagen.py:128-154: igl::AABB::squared_distance):
  * out[i] = the point of the triangle mesh (verts [nv,3] f64, faces [nf,3] int32, all
  * device) closest to pts[i] ([n,3] f64); face_idx [n] int32 or NULL receives the face.
@@ -529,8 +564,10 @@ int epos_find6d_poses(const double* xy, const double* xyz, int64_t n,
  * epos_corr_fill writes. The spatial-coherence sweeps and the joint refinement find a
  * point's neighbours in a window of rows around it and stop at the first row farther than
  * neighborhood_ball_radius: with unsorted rows neighbourhoods are silently truncated and
- * the poses change. Callers with arbitrary row order use epos_find6d_poses (it sorts
- * internally and keeps the caller's order for PROSAC) or sort first; with
+ * the poses change. Callers with arbitrary row order use
+ * epos_find6d_poses_device_ordered below, which lifts this requirement (it takes the
+ * row-order permutation as an argument), or epos_find6d_poses (it sorts internally and
+ * keeps the caller's order for PROSAC), or sort first; with
  * spatial_coherence_weight == 0 (or gc_sweeps == 0) and max_k == 1 no order is needed. */
 int64_t epos_fit_workspace_bytes(int S, int64_t n_capacity, const EposFitParams* p,
                                  int32_t max_k);
@@ -541,6 +578,21 @@ int epos_find6d_poses_device(const double* xy, const double* xyz,
                              int32_t max_k, void* work, double* poses,
                              double* scores, int32_t* num_models, int32_t* labels,
                              void* stream);
+
+/* The same call for rows in the CALLER's order (use_prosac samples from a growing prefix of
+ * it -- e.g. the confidence order of epos_corr_order_by_conf). yorder i32[N] [device]:
+ * per slot, the slot-local row indices sorted by (xy[.,1] ascending, index ascending);
+ * ypos i32[N]: its inverse (ypos[slot_base[s] + yorder[slot_base[s] + i]] = i). The
+ * neighbourhood windows walk the rows through them. Both null = epos_find6d_poses_device
+ * (and its precondition); exactly one null: EPOS_E_INVALID. */
+int epos_find6d_poses_device_ordered(const double* xy, const double* xyz,
+                                     const int64_t* slot_base, int S, int64_t n_capacity,
+                                     const double* Ks, const int32_t* max_models,
+                                     const uint64_t* seeds, const EposFitParams* p,
+                                     int32_t max_k, void* work, double* poses,
+                                     double* scores, int32_t* num_models, int32_t* labels,
+                                     void* stream, const int32_t* yorder,
+                                     const int32_t* ypos);
 
 /* ------------------------------------------------------------------------- *
  * The OpenCV fitting method (replaces cv2.solvePnPRansac(objectPoints, imagePoints, K,

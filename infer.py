@@ -157,8 +157,8 @@ def build_parser():
     help='batches in flight (independent plans on their own HIP streams, each with its own '
          'per-stage timers). 0 (default) = bench.py\'s rule: 4 at one image per batch, 2 from '
          'four images per batch on, 3 in between; 1 = strictly one batch at a time (the '
-         'reference\'s loop). --vis, --save_corresp and the operator path (--use_prosac, '
-         '--max_correspondences, --project_to_surface) read the plan\'s buffers after every '
+         'reference\'s loop). --vis, --save_corresp and the operator path '
+         '(--project_to_surface, --order_on_device=false) read the plan\'s buffers after every '
          'step and always run at depth 1. The poses do not depend on the depth.')
   a('--launch_queue', type=int, default=int(os.environ.get('EPOS_LAUNCH_QUEUE', '2')),
     help='batches enqueued per plan before the oldest is collected: with 2 a plan\'s next '
@@ -171,6 +171,12 @@ def build_parser():
          'localization mode (corresp.py:39-43), so the poses are bit-identical and ~7 %% of the '
          'step is saved. auto (default) = on for --task_type=localization unless --vis, '
          '--save_corresp or the operator path need the dense prediction; true / false force it')
+  a('--order_on_device', type=str2bool, default=True,
+    help='true (default): --use_prosac / --max_correspondences order and cap the '
+         'correspondences by confidence on the device, inside the fused pipeline (sparse '
+         'heads, several steps in flight). false: the run goes operator by operator (network '
+         '-> correspondences -> host sort -> one fitting call per object, one step at a time, '
+         'dense heads) -- same poses, kept for A/B runs on one box.')
   a('--decode_threads', type=int, default=0,
     help='decoder processes working ahead of the GPU (0 = min(8, cores - 2); '
          'EPOS_DECODE_PROCS=0 makes them in-process threads)')
@@ -248,6 +254,18 @@ def check_supported_flags(args):
   if bad:
     raise NotImplementedError(
         'flags outside what this build implements (common.py:60-154): ' + '; '.join(bad))
+
+
+def fitting_path(use_prosac, max_correspondences, project_to_surface, order_on_device):
+  """(operator_path, order_in_pipeline). operator_path: the run goes operator by operator
+  (process_by_operators) instead of through the fused device pipeline -- for
+  --project_to_surface (the mesh query is not part of the pipeline) and whenever
+  --order_on_device is false. order_in_pipeline: the fused pipeline gets the device-side
+  confidence order (--use_prosac and/or --max_correspondences on the fused path)."""
+  operator_path = bool(project_to_surface) or not order_on_device
+  order_in_pipeline = not operator_path and (bool(use_prosac) or
+                                             max_correspondences is not None)
+  return operator_path, order_in_pipeline
 
 
 def resolve_sparse_heads(args, needs_dense, pyramid):
@@ -412,11 +430,11 @@ def process_by_operators(pipe, store, imgs, chunk, targets, args, fit):
       if n < 6:                                           # infer.py:420-422
         continue
       if args.use_prosac:                                 # infer.py:425-428
-        order = np.argsort(c['conf'])[::-1]
+        order = ecorresp.confidence_order(c['conf'])
         c = {k: v[order] for k, v in c.items()}
       if args.max_correspondences is not None and n > args.max_correspondences:
         keep = (np.arange(n) if args.use_prosac else
-                np.argsort(c['conf'])[::-1])[:args.max_correspondences]
+                ecorresp.confidence_order(c['conf']))[:args.max_correspondences]
         c = {k: v[keep] for k, v in c.items()}           # infer.py:431-440
       num_inst = (targets[b].get(obj_id, 1)
                   if args.task_type == pipeline.LOCALIZATION else -1)
@@ -427,14 +445,17 @@ def process_by_operators(pipe, store, imgs, chunk, targets, args, fit):
         # OpenCV is not in this stack; epos_amd.fitting.solvePnPRansac runs the same
         # algorithm (5-point EPnP sets drawn by cv::RNG, float32 inlier rule, the 0.99
         # confidence bound, EPnP over the inliers) in HIP -- csrc/epnp_ransac.hip.
-        ok, r_est, t_est, _ = fitting.solvePnPRansac(
+        # The pose is taken as the kernels computed it (return_pose), as the fused pipeline
+        # reports it: R -> rvec -> Rodrigues(rvec) on the host (infer.py:526) moves R by an
+        # ulp and would make the two routes differ in the last bit.
+        ok, _, t_est, _, pose = fitting.solvePnPRansac(
             objectPoints=c['coord_3d'], imagePoints=c['coord_2d'], cameraMatrix=f.K,
             distCoeffs=None, iterationsCount=fit.max_iters,
             reprojectionError=fit.threshold, confidence=0.99,
-            flags=fitting.SOLVEPNP_EPNP)
+            flags=fitting.SOLVEPNP_EPNP, return_pose=True)
         if ok:
           poses.append({'scene_id': f.scene_id, 'im_id': f.im_id, 'obj_id': obj_id,
-                        'R': fitting.Rodrigues(r_est), 't': t_est, 'score': 0.0})
+                        'R': pose[:, :3].copy(), 't': t_est, 'score': 0.0})
         continue
       est, _, quals = fitting.find6DPoses(
           c['coord_2d'], c['coord_3d'], f.K, threshold=fit.threshold,
@@ -559,13 +580,15 @@ def main(argv=None):
       min_triangle_area=args.min_triangle_area, min_point_number=6,
       max_model_number_for_optimization=args.max_model_number_for_pearl,
       use_prosac=args.use_prosac)
-  # max_correspondences / use_prosac (both off by default, infer.py:95-97,115-117)
-  # re-order the correspondences by confidence on the host (infer.py:425-440), and
-  # project_to_surface (off by default) needs the object meshes, so
-  # those runs go operator by operator (HIP network -> HIP correspondences -> host
-  # sort -> HIP fitting per object) instead of through the fused device pipeline.
-  operator_path = (args.max_correspondences is not None or args.use_prosac or
-                   args.project_to_surface)
+  # max_correspondences / use_prosac (both off by default, infer.py:95-97,115-117) order and
+  # cap the correspondences by confidence (infer.py:425-440): inside the fused pipeline, on
+  # the device (pipeline.EposPipeline(max_correspondences=..., fit use_prosac)). Only
+  # project_to_surface (off by default; it needs the object meshes) and --order_on_device=false
+  # go operator by operator (HIP network -> HIP correspondences -> host sort -> HIP fitting
+  # per object) instead.
+  operator_path, order_in_pipeline = fitting_path(
+      args.use_prosac, args.max_correspondences, args.project_to_surface,
+      args.order_on_device)
   if args.project_to_surface:
     # infer.py:622 prepare_for_projection: the 'eval' models of the dataset
     # (datagen.py:250-252,299-306), closest-point queries on the GPU
@@ -612,7 +635,8 @@ def main(argv=None):
       max_instances=max_inst, model_options=mo, device=dev, instance=j,
       sparse_heads=sparse_heads, fitting_method=args.fitting_method, queue=lq,
       precision=args.precision, image_pyramid=pyramid,
-      merge_method=args.merge_method if pyramid is not None else None)
+      merge_method=args.merge_method if pyramid is not None else None,
+      max_correspondences=args.max_correspondences if order_in_pipeline else None)
            for j in range(depth)]
   pipe = pipes[0]
   if rank == 0 and pyramid is not None:
