@@ -162,6 +162,14 @@ class CorrOut(ctypes.Structure):
               ('conf_frag', vp)]
 
 
+class MeshRec(ctypes.Structure):
+  _fields_ = [('tri_off', ctypes.c_int64), ('fid_off', ctypes.c_int64),
+              ('box_off', ctypes.c_int64 * 4), ('count', ctypes.c_int32 * 4),
+              ('nf', ctypes.c_int32), ('nleaf', ctypes.c_int32),
+              ('nalways', ctypes.c_int32), ('top', ctypes.c_int32),
+              ('near_lo', ctypes.c_double * 3), ('near_hi', ctypes.c_double * 3)]
+
+
 class FitParams(ctypes.Structure):
   _fields_ = [
       ('threshold', ctypes.c_double),
@@ -260,6 +268,8 @@ SYMBOLS = {
         ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64,
         ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
         ctypes.c_void_p]),
+    'epos_project_rows_to_mesh_f64': (ctypes.c_int, [
+        vp, vp, vp, ctypes.c_int, ctypes.c_int64, vp, ctypes.c_int, vp, vp, vp, vp, vp]),
     'epos_fragmentation_fps': (ctypes.c_int, [
         vp, ctypes.c_int64, ctypes.c_int, vp, vp, vp, vp, vp]),
     'epos_fit_params_default': (None, [ctypes.POINTER(FitParams)]),

@@ -182,6 +182,44 @@ class CorrOrderer(object):
                'epos_corr_order_by_conf')
 
 
+NO_MODELS_MESSAGE = (
+    'project_to_surface needs model_store.models = {obj_id: {"pts", "faces"}} '
+    '(datagen.py:68-84; epos_amd.ply.load_models)')
+
+
+class MeshProjector(object):
+  """project_to_surface for a CorrExtractor's pooled rows, in place on its coord_3d
+  (csrc/mesh_project.hip): run() after fill() and before CorrOrderer.run(), on the same stream;
+  nothing synchronises or allocates. The closest points are those of project_pts_to_model,
+  bit for bit, found through a mesh index (epos_amd/mesh_index.py) that is built and uploaded
+  here, once. models: {obj_id: {'pts', 'faces'}} (model_store.models)."""
+
+  def __init__(self, extractor, models):
+    from epos_amd import mesh_index
+    self.ex = ex = extractor
+    self.lib = ex.lib
+    self.table = mesh_index.MeshTable(models, ex.O, ex.dev)
+
+  def check_slots(self, slots):
+    """A slot whose object has no mesh is refused here, on the host, before the launch."""
+    bad = sorted(set(int(o) for _, o in slots if not self.table.has_mesh(int(o))))
+    if bad:
+      raise ValueError('project_to_surface: no mesh for object(s) %s' % bad)
+
+  def run(self, face_idx=None, visited=None):
+    """face_idx / visited: optional int32 device tensors of `capacity` rows (the face of every
+    row; the triangle blocks swept for it)."""
+    ex, t = self.ex, self.table
+    if not ex.S:
+      return
+    _lib.check(self.lib.epos_project_rows_to_mesh_f64(
+        _ptr(ex.coord_3d), _ptr(ex.slot_base), _ptr(ex.slots), ex.S, ex.capacity,
+        _ptr(t.recs_dev), t.num_objs, _ptr(t.geom_dev), _ptr(t.fid_dev),
+        _ptr(face_idx) if face_idx is not None else None,
+        _ptr(visited) if visited is not None else None, _stream(ex.dev)),
+               'epos_project_rows_to_mesh_f64')
+
+
 def establish_many_to_many(
       obj_confs, frag_confs, frag_coords, gt_obj_ids, model_store, output_scale,
       min_obj_conf, min_frag_rel_conf, project_to_surface, only_annotated_objs,
@@ -192,9 +230,7 @@ def establish_many_to_many(
   arrays (copied to HBM) or torch tensors already on the device.
   """
   if project_to_surface and not getattr(model_store, 'models', None):
-    raise ValueError(
-        'project_to_surface needs model_store.models = {obj_id: {"pts", "faces"}} '
-        '(datagen.py:68-84; epos_amd.ply.load_models)')
+    raise ValueError(NO_MODELS_MESSAGE)
   dev = torch.device(device)
 
   def to_dev(a):

@@ -17,6 +17,7 @@
 // One "slot" = one (image, object) pair; all slots of a batch go in one launch.
 // HBM-bound byte/compare work: no MFMA here.
 #include "common.h"
+#include "closest_tri.h"
 
 namespace epos {
 namespace {
@@ -347,48 +348,6 @@ __global__ __launch_bounds__(256) void corr_fill_wide_kernel(
 // Collision Detection" 5.1.5; fp64, only + - * /, same operation order as
 // the numpy restatement the tests check it against (bit-exact).
 // --------------------------------------------------------------------------
-__device__ __forceinline__ double dot3d(const double* a, const double* b) {
-  return a[0] * b[0] + a[1] * b[1] + a[2] * b[2];
-}
-
-__device__ __forceinline__ void closest_on_triangle(const double* p, const double* a,
-                                                    const double* b, const double* c,
-                                                    double* q) {
-  double ab[3], ac[3], ap[3];
-  for (int i = 0; i < 3; ++i) { ab[i] = b[i] - a[i]; ac[i] = c[i] - a[i]; ap[i] = p[i] - a[i]; }
-  const double d1 = dot3d(ab, ap), d2 = dot3d(ac, ap);
-  if (d1 <= 0.0 && d2 <= 0.0) { q[0] = a[0]; q[1] = a[1]; q[2] = a[2]; return; }
-  double bp[3];
-  for (int i = 0; i < 3; ++i) bp[i] = p[i] - b[i];
-  const double d3 = dot3d(ab, bp), d4 = dot3d(ac, bp);
-  if (d3 >= 0.0 && d4 <= d3) { q[0] = b[0]; q[1] = b[1]; q[2] = b[2]; return; }
-  const double vc = d1 * d4 - d3 * d2;
-  if (vc <= 0.0 && d1 >= 0.0 && d3 <= 0.0) {
-    const double v = d1 / (d1 - d3);
-    for (int i = 0; i < 3; ++i) q[i] = a[i] + v * ab[i];
-    return;
-  }
-  double cp[3];
-  for (int i = 0; i < 3; ++i) cp[i] = p[i] - c[i];
-  const double d5 = dot3d(ab, cp), d6 = dot3d(ac, cp);
-  if (d6 >= 0.0 && d5 <= d6) { q[0] = c[0]; q[1] = c[1]; q[2] = c[2]; return; }
-  const double vb = d5 * d2 - d1 * d6;
-  if (vb <= 0.0 && d2 >= 0.0 && d6 <= 0.0) {
-    const double w = d2 / (d2 - d6);
-    for (int i = 0; i < 3; ++i) q[i] = a[i] + w * ac[i];
-    return;
-  }
-  const double va = d3 * d6 - d5 * d4;
-  if (va <= 0.0 && (d4 - d3) >= 0.0 && (d5 - d6) >= 0.0) {
-    const double w = (d4 - d3) / ((d4 - d3) + (d5 - d6));
-    for (int i = 0; i < 3; ++i) q[i] = b[i] + w * (c[i] - b[i]);
-    return;
-  }
-  const double denom = 1.0 / (va + vb + vc);
-  const double v = vb * denom, w = vc * denom;
-  for (int i = 0; i < 3; ++i) q[i] = a[i] + ab[i] * v + ac[i] * w;
-}
-
 __global__ __launch_bounds__(256) void project_to_mesh_kernel(
     const double* __restrict__ pts, int64_t n, const double* __restrict__ verts,
     const int32_t* __restrict__ faces, int64_t nf, double* out, int32_t* face_idx) {

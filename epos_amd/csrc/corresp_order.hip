@@ -28,6 +28,7 @@
 // pipeline raises at collect()) nothing at or beyond `capacity` is read and nothing beyond
 // the kept rows is written.
 #include "common.h"
+#include "slot_search.h"
 
 namespace epos {
 namespace {
@@ -35,22 +36,6 @@ namespace {
 constexpr int ORDER_TILE = 4096;       // keys per workgroup of the LDS sort (32 KB)
 constexpr int ORDER_T = 512;           // its threads
 constexpr int ORDER_B = 256;           // threads of the per-row kernels
-
-__device__ __forceinline__ int64_t clamp_row(int64_t v, int64_t cap) {
-  return v < 0 ? 0 : v > cap ? cap : v;
-}
-
-// The segment (slot) that holds pooled row g: the last s with seg[s] <= g. Empty slots
-// share their bound with a neighbour and are never returned. seg[0] <= g < seg[S] (clamped).
-__device__ __forceinline__ int find_slot(const int64_t* __restrict__ seg, int S, int64_t cap,
-                                         int64_t g) {
-  int lo = 0, hi = S;                  // answer in [lo, hi)
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (clamp_row(seg[mid], cap) <= g) lo = mid; else hi = mid;
-  }
-  return lo;
-}
 
 // float -> uint32 whose unsigned order is the float's DESCENDING order
 __device__ __forceinline__ uint32_t desc_bits(float f) {

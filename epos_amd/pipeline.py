@@ -59,7 +59,7 @@ class EposPipeline(object):
                use_graph=True, instance=0, sparse_heads=False,
                fitting_method='progressive_x', on_excess='raise', queue=1,
                precision='fp32', image_pyramid=None, merge_method=None,
-               max_correspondences=None):
+               max_correspondences=None, project_to_surface=False):
     """on_excess: what launch() does with a frame that asks for more instances of an object
     than `max_instances` (localization): 'raise' (default: EposError BEFORE anything of that
     batch is enqueued -- batches already in flight on other pipelines are unaffected and can
@@ -78,6 +78,11 @@ class EposPipeline(object):
     fitting stage then sees the ordered / kept rows: self.labels (the opencv method's inlier
     mask) is indexed by kept row within self.order.slot_base, and self.order.src_row maps a
     kept row back to the extractor's slot-local row.
+    project_to_surface (corresp.py:87-88): replace every correspondence's 3D point by the
+    closest point of the object's mesh (model_store.models), on the device, between the
+    correspondence stage and the ordering / fitting stages (corresp.MeshProjector; counted
+    as correspondence time, as in the reference). ValueError if the store has no meshes or an
+    object of the store has none. Off: that stage does not exist.
     capacity: correspondence rows per batch, over all slots, at up to 64 fragments per object.
     A masked pixel yields up to F rows, so the correspondence and fitting buffers are sized for
     `capacity * ceil(num_frags / 64)` rows (self.capacity); for num_frags <= 64 that is
@@ -154,6 +159,15 @@ class EposPipeline(object):
     if max_correspondences is not None or self.fit.use_prosac:
       self.order = _corresp.CorrOrderer(self.corr, max_correspondences,
                                         bool(self.fit.use_prosac))
+    self.surface = None
+    if project_to_surface:
+      models = getattr(model_store, 'models', None)
+      if not models:
+        raise ValueError(_corresp.NO_MODELS_MESSAGE)
+      missing = [o for o in self.obj_ids if o not in models]
+      if missing:
+        raise ValueError(_corresp.NO_MODELS_MESSAGE + '; no mesh for object(s) %s' % missing)
+      self.surface = _corresp.MeshProjector(self.corr, models)
     S = self.max_slots
     d = self.dev
     wbytes = self.lib.epos_fit_workspace_bytes(S, capacity, ctypes.byref(self.fit),
@@ -322,6 +336,8 @@ class EposPipeline(object):
                         self.tau_a, self.tau_b)
         self.corr.fill(pred[W.PRED_OBJ_CONF], pred[W.PRED_FRAG_CONF],
                        pred[W.PRED_FRAG_LOC], self.output_scale)
+        if self.surface is not None:
+          self.surface.run()
         if timing:
           ev[2].record()
         src = self.corr

@@ -487,6 +487,40 @@ int epos_project_to_mesh_f64(const double* pts, int64_t n, const double* verts,
                              int64_t nv, const int32_t* faces, int64_t nf, double* out,
                              int32_t* face_idx, void* stream);
 
+/* project_to_surface inside the fused pipeline: the same closest points, bit for bit, for
+ * the pooled rows of epos_corr_fill IN PLACE, through a mesh index built on the host
+ * (epos_amd/mesh_index.py; DESIGN.md, "Mesh index"). All buffers [device], nothing
+ * synchronises or allocates, the launch is sized from `capacity`.
+ *
+ * Index of one mesh: its faces in Morton order of their centroids, 64 to a leaf; level 0 of
+ * the boxes bounds the leaves, node i of level l+1 covers nodes 64i .. 64i+63 of level l, the
+ * top level has at most 64 nodes. Faces the pruning argument does not cover are kept out of
+ * the tree, in `nalways` further blocks that every query sweeps.
+ *   geom      f64: triangle blocks of 9 x 64 doubles ([k][lane], k = ax ay az bx .. cz), the
+ *                  nleaf tree leaves first, then the always-swept blocks; box groups of
+ *                  6 x 64 doubles ([k][lane], k = lo xyz, hi xyz), one group per parent
+ *   face_ids  i32: 64 per triangle block, the ORIGINAL face index, -1 = empty place
+ * recs[obj_id - 1], num_objs of them; nf == 0 = no mesh (rows of such a slot stay as they
+ * are; the Python layer refuses them before the launch). */
+typedef struct EposMeshRec {
+  int64_t tri_off;          /* geom offset (doubles) of the triangle blocks           */
+  int64_t fid_off;          /* face_ids offset of the same blocks                     */
+  int64_t box_off[4];       /* geom offset (doubles) of the box groups of level l     */
+  int32_t count[4];         /* nodes of level l (count[0] = nleaf)                    */
+  int32_t nf, nleaf, nalways, top;   /* faces, tree leaves, always blocks, top level  */
+  double near_lo[3], near_hi[3];     /* queries outside this box sweep every leaf     */
+} EposMeshRec;
+/* Rows r < min(slot_base[S], capacity) of coord_3d f64[N,3]; row r belongs to the slot s with
+ * slot_base[s] <= r < slot_base[s+1] and is replaced by the closest point of the mesh of
+ * slots[s].obj_id -- what epos_project_to_mesh_f64 returns for it (ties -> lowest original
+ * face index; no finite distance -> (0,0,0), face nf). face_idx i32[N] or NULL: the face;
+ * visited i32[N] or NULL: triangle blocks swept for the row (tests observe the pruning). */
+int epos_project_rows_to_mesh_f64(double* coord_3d, const int64_t* slot_base,
+                                  const EposCorrSlot* slots, int S, int64_t capacity,
+                                  const EposMeshRec* recs, int num_objs, const double* geom,
+                                  const int32_t* face_ids, int32_t* face_idx,
+                                  int32_t* visited, void* stream);
+
 /* ------------------------------------------------------------------------- *
  * Model preprocessing (replaces epos_lib/fragment.py:8-54, fragmentation_fps,
  * called once per object by ObjectModelStore.fragment_models, datagen.py:86-126).

@@ -177,6 +177,11 @@ def build_parser():
          'heads, several steps in flight). false: the run goes operator by operator (network '
          '-> correspondences -> host sort -> one fitting call per object, one step at a time, '
          'dense heads) -- same poses, kept for A/B runs on one box.')
+  a('--surface_on_device', type=str2bool, default=False,
+    help='not in the reference. true: --project_to_surface runs inside the fused pipeline '
+         '(closest points through a mesh index, on the device; sparse heads, several steps in '
+         'flight) -- the same poses as the default, operator-by-operator route of that flag, '
+         'which stays the default.')
   a('--decode_threads', type=int, default=0,
     help='decoder processes working ahead of the GPU (0 = min(8, cores - 2); '
          'EPOS_DECODE_PROCS=0 makes them in-process threads)')
@@ -256,13 +261,14 @@ def check_supported_flags(args):
         'flags outside what this build implements (common.py:60-154): ' + '; '.join(bad))
 
 
-def fitting_path(use_prosac, max_correspondences, project_to_surface, order_on_device):
+def fitting_path(use_prosac, max_correspondences, project_to_surface, order_on_device,
+                 surface_on_device=False):
   """(operator_path, order_in_pipeline). operator_path: the run goes operator by operator
   (process_by_operators) instead of through the fused device pipeline -- for
-  --project_to_surface (the mesh query is not part of the pipeline) and whenever
-  --order_on_device is false. order_in_pipeline: the fused pipeline gets the device-side
+  --project_to_surface unless --surface_on_device puts the mesh query into the pipeline, and
+  whenever --order_on_device is false. order_in_pipeline: the fused pipeline gets the device-side
   confidence order (--use_prosac and/or --max_correspondences on the fused path)."""
-  operator_path = bool(project_to_surface) or not order_on_device
+  operator_path = (bool(project_to_surface) and not surface_on_device) or not order_on_device
   order_in_pipeline = not operator_path and (bool(use_prosac) or
                                              max_correspondences is not None)
   return operator_path, order_in_pipeline
@@ -583,12 +589,14 @@ def main(argv=None):
   # max_correspondences / use_prosac (both off by default, infer.py:95-97,115-117) order and
   # cap the correspondences by confidence (infer.py:425-440): inside the fused pipeline, on
   # the device (pipeline.EposPipeline(max_correspondences=..., fit use_prosac)). Only
-  # project_to_surface (off by default; it needs the object meshes) and --order_on_device=false
-  # go operator by operator (HIP network -> HIP correspondences -> host sort -> HIP fitting
-  # per object) instead.
+  # project_to_surface (off by default; it needs the object meshes) without
+  # --surface_on_device=true, and --order_on_device=false, go operator by operator (HIP network
+  # -> HIP correspondences -> host sort -> HIP fitting per object) instead. With
+  # --surface_on_device=true the mesh query is a stage of the fused pipeline
+  # (pipeline.EposPipeline(project_to_surface=True)) and the run resolves like a plain one.
   operator_path, order_in_pipeline = fitting_path(
       args.use_prosac, args.max_correspondences, args.project_to_surface,
-      args.order_on_device)
+      args.order_on_device, args.surface_on_device)
   if args.project_to_surface:
     # infer.py:622 prepare_for_projection: the 'eval' models of the dataset
     # (datagen.py:250-252,299-306), closest-point queries on the GPU
@@ -636,7 +644,8 @@ def main(argv=None):
       sparse_heads=sparse_heads, fitting_method=args.fitting_method, queue=lq,
       precision=args.precision, image_pyramid=pyramid,
       merge_method=args.merge_method if pyramid is not None else None,
-      max_correspondences=args.max_correspondences if order_in_pipeline else None)
+      max_correspondences=args.max_correspondences if order_in_pipeline else None,
+      project_to_surface=bool(args.project_to_surface) and not operator_path)
            for j in range(depth)]
   pipe = pipes[0]
   if rank == 0 and pyramid is not None:
