@@ -170,6 +170,14 @@ class MeshRec(ctypes.Structure):
               ('near_lo', ctypes.c_double * 3), ('near_hi', ctypes.c_double * 3)]
 
 
+class RenderInst(ctypes.Structure):
+  _fields_ = [('vert_base', ctypes.c_int32), ('face_base', ctypes.c_int32),
+              ('n_faces', ctypes.c_int32), ('reserved0', ctypes.c_int32),
+              ('R', ctypes.c_double * 9), ('t', ctypes.c_double * 3),
+              ('fx', ctypes.c_double), ('fy', ctypes.c_double),
+              ('cx', ctypes.c_double), ('cy', ctypes.c_double)]
+
+
 class FitParams(ctypes.Structure):
   _fields_ = [
       ('threshold', ctypes.c_double),
@@ -316,6 +324,17 @@ SYMBOLS = {
     'epos_resize_merge_f32': (ctypes.c_int, [
         ctypes.POINTER(ResizeSrc), ctypes.c_int, vp, ctypes.c_int64, ctypes.c_int, ctypes.c_int,
         ctypes.c_int, ctypes.c_int, ctypes.c_int, vp]),
+    # mesh renderer
+    'epos_render_lane_max_pixels': (ctypes.c_int, []),
+    'epos_render_raster': (ctypes.c_int, [
+        vp, ctypes.c_int64, vp, ctypes.c_int64, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+        ctypes.c_double, vp, vp]),
+    'epos_render_resolve': (ctypes.c_int, [
+        vp, vp, ctypes.c_int64, vp, ctypes.c_int64, vp, vp, ctypes.c_int, ctypes.c_int,
+        ctypes.c_int, ctypes.c_double, vp, vp, vp, vp, vp]),
+    'epos_gt_fields': (ctypes.c_int, [
+        vp, vp, vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp, ctypes.c_int,
+        ctypes.c_int, vp, vp, vp, vp, vp, vp]),
 }
 
 _lib = None

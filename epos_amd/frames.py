@@ -26,9 +26,12 @@ import numpy as np
 class Frame(object):
   """One input frame: scene_id, im_id, K f64[3,3], targets {obj_id: instances}, gt_poses (or
   None), and ``load(out=None)`` -> uint8 or float32 [H,W,3] pixels (decoded on demand)."""
-  __slots__ = ('scene_id', 'im_id', 'K', 'targets', 'gt_poses', '_loader', 'dtype')
+  __slots__ = ('scene_id', 'im_id', 'K', 'targets', 'gt_poses', '_loader', 'dtype',
+               'mask_source')
 
-  def __init__(self, scene_id, im_id, K, targets, loader, gt_poses=None, dtype=np.uint8):
+  def __init__(self, scene_id, im_id, K, targets, loader, gt_poses=None, dtype=np.uint8,
+               mask_source=None):
+    self.mask_source = mask_source
     self.scene_id, self.im_id = scene_id, im_id
     self.K = np.asarray(K, np.float64).reshape(3, 3)
     self.targets = targets
@@ -38,6 +41,12 @@ class Frame(object):
 
   def load(self, out=None):
     return self._loader(out)
+
+  def gt_masks(self, output_size):
+    """The ground-truth instance masks, bool [n, h, w] at output_size = (w, h), one per entry
+    of gt_poses, decoded on demand; None for input that carries none (--frames, --synthetic,
+    records without image/object/mask)."""
+    return None if self.mask_source is None else self.mask_source(output_size)
 
   def image_f32(self):
     """float32 pixels as the reference's tensors hold them (--vis, operator path)."""
@@ -71,8 +80,27 @@ def scan_tfrecords(paths, crop_size, max_height_before_crop, obj_ids, crop_seed=
       frames.append(Frame(
           meta['scene_id'], meta['im_id'], meta['K'], tg,
           _TfrecordLoader(path, off + loc[0], loc[1], geo, meta['crop_offset']),
-          meta['gt_poses'], np.float32 if resized else np.uint8))
+          meta['gt_poses'], np.float32 if resized else np.uint8,
+          _TfrecordMasks(path, off, len(data), geo, meta['crop_offset'], meta['keep'])
+          if feats.get('image/object/mask') else None))
   return frames
+
+
+class _TfrecordMasks(object):
+  """Reads a record again and decodes its instance masks (tfrecord.decode_instance_masks)."""
+  __slots__ = ('path', 'offset', 'length', 'geometry', 'crop_offset', 'keep')
+
+  def __init__(self, path, offset, length, geometry, crop_offset, keep):
+    self.path, self.offset, self.length = path, int(offset), int(length)
+    self.geometry, self.crop_offset, self.keep = tuple(geometry), tuple(crop_offset), list(keep)
+
+  def __call__(self, output_size):
+    from epos_amd import tfrecord
+    data = os.pread(_fd(self.path), self.length, self.offset)
+    if len(data) != self.length:
+      raise IOError('short read of a record in %s' % self.path)
+    return tfrecord.decode_instance_masks(tfrecord.parse_example(data), self.geometry,
+                                          self.crop_offset, output_size, self.keep)
 
 
 # ------------------------------------------------------------------ loaders ---
@@ -145,6 +173,14 @@ def _TfrecordLoader(path, offset, length, geometry, crop_offset):
                  tuple(int(x) for x in crop_offset))
 
 
+def _gt_poses_of(entry):
+  """Optional "gt_poses" of a frames.json entry: [{obj_id, R (9 numbers or 3x3), t (3)}]."""
+  if not entry.get('gt_poses'):
+    return None
+  return [{'obj_id': int(p['obj_id']), 'R': np.asarray(p['R'], np.float64).reshape(3, 3),
+           't': np.asarray(p['t'], np.float64).reshape(3, 1)} for p in entry['gt_poses']]
+
+
 def frames_from_dir(directory, meta, h, w):
   """--frames <dir>: frames.json entries + images (.npy HxWx3 or anything PIL reads)."""
   out = []
@@ -155,7 +191,7 @@ def frames_from_dir(directory, meta, h, w):
       dtype = np.uint8 if np.load(path, mmap_mode='r').dtype == np.uint8 else np.float32
     out.append(Frame(m.get('scene_id', 0), m['im_id'], m['K'],
                      {int(k): int(v) for k, v in m.get('targets', {}).items()},
-                     _Loader('file', path, h, w), dtype=dtype))
+                     _Loader('file', path, h, w), _gt_poses_of(m), dtype=dtype))
   return out
 
 

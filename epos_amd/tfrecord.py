@@ -371,6 +371,7 @@ def sample_meta(feats, crop_size, max_height_before_crop, obj_ids=None,
       'K': K, 'gt_obj_ids': [ids[i] for i in keep],
       'gt_poses': _gt_poses(feats, ids, keep),
       'geometry': (h_orig, w_orig, h_new, w_new, crop_h, crop_w),
+      'keep': keep,
   }
 
 
@@ -393,6 +394,51 @@ def decode_image(encoded, geometry, crop_offset, out=None):
     np.copyto(out, im, casting='same_kind')
     return out
   return np.ascontiguousarray(im)
+
+
+def nearest_indices(n_in, n_out):
+  """Source index of every destination index of tf.image.resize_nearest_neighbor with
+  align_corners=True: round(dst * (in - 1) / (out - 1)), the scale and the product in
+  float32, halves rounded up (TF's roundf on a non-negative value)."""
+  scale = np.float32(n_in - 1) / np.float32(n_out - 1) if n_out > 1 else np.float32(0)
+  idx = np.floor(np.arange(n_out, dtype=np.float32) * scale + np.float32(0.5)).astype(np.int64)
+  return np.minimum(idx, n_in - 1)
+
+
+def resize_nearest(im, out_h, out_w):
+  """[..., H, W] -> [..., out_h, out_w], nearest neighbour with align_corners=True."""
+  im = np.asarray(im)
+  return im[..., nearest_indices(im.shape[-2], out_h)[:, None],
+            nearest_indices(im.shape[-1], out_w)[None, :]]
+
+
+def decode_instance_masks(feats, geometry, crop_offset, output_size, keep=None):
+  """The instance masks of a sample as datagen.py:518-542 prepares them: the PNG bytes of
+  image/object/mask decoded (PIL; non-zero = inside, as _decode_png_instance_masks), resized
+  to the scaled input size (nearest neighbour, align_corners=True), cropped, and resized again
+  to output_size = (w, h). keep: indices of the instances to return (sample_meta's 'keep';
+  default all). Returns bool [n, out_h, out_w], or None when the record has no masks.
+  PARITY UNPINNED against TensorFlow-written files, like the rest of this reader."""
+  from PIL import Image
+  enc = feats.get('image/object/mask')
+  if not enc:
+    return None
+  h_orig, w_orig, h_new, w_new, crop_h, crop_w = geometry
+  off_h, off_w = crop_offset
+  out_w, out_h = output_size
+  keep = range(len(enc)) if keep is None else keep
+  out = np.zeros((len(keep), out_h, out_w), bool)
+  for j, i in enumerate(keep):
+    with Image.open(io.BytesIO(enc[i])) as pil:
+      m = np.asarray(pil)
+    if m.ndim == 3:
+      m = m[..., 0]
+    if m.shape != (h_orig, w_orig):
+      raise ValueError('instance mask %d is %s, the image %s' % (i, m.shape, (h_orig, w_orig)))
+    m = resize_nearest(m > 0, h_new, w_new)
+    m = m[off_h:off_h + crop_h, off_w:off_w + crop_w]
+    out[j] = resize_nearest(m, out_h, out_w)
+  return out
 
 
 def decode_sample(feats, crop_size, max_height_before_crop, obj_ids=None,

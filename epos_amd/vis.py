@@ -117,10 +117,34 @@ def model_points(store, obj_id):
   return np.asarray(store.frag_centers[obj_id], np.float64)
 
 
-def overlay_object_poses(rgb, K, poses, store, splat=1):
+def overlay_mesh_poses(rgb, K, poses, renderer):
+  """vis.visualize_object_poses (vis.py:141-176) over epos_amd.render.Renderer: the shaded
+  mesh of every pose (one batched launch), the colour renderings combined by a saturating add
+  in pose order, then blended 0.3 / 0.7 with the image. Poses of objects the renderer does
+  not hold are skipped."""
+  rgb = np.asarray(rgb)
+  h, w = rgb.shape[:2]
+  poses = [p for p in poses if renderer.has_object(p['obj_id'])]
+  ren = np.zeros((h, w, 3), np.float32)
+  if poses:
+    out = renderer.render_instances(
+        [p['obj_id'] for p in poses], np.stack([np.asarray(p['R'], np.float64).reshape(3, 3)
+                                                for p in poses]),
+        np.stack([np.asarray(p['t'], np.float64).reshape(3) for p in poses]), K, size=(w, h),
+        outputs=('color',))
+    for m_rgb in out['color'].cpu().numpy():
+      ren = np.minimum(ren + m_rgb.astype(np.float32), 255.0)
+  vis_im = 0.3 * rgb.astype(np.float32) + 0.7 * ren
+  return np.minimum(vis_im, 255.0).astype(np.uint8)
+
+
+def overlay_object_poses(rgb, K, poses, store, splat=1, renderer=None):
   """Estimated (or ground-truth) poses on top of the image: each object's model points,
   coloured by their object-frame position, z-buffered per pixel, blended 0.3 / 0.7 with
-  the image like vis.visualize_object_poses (vis.py:141-176), plus the object frame."""
+  the image like vis.visualize_object_poses (vis.py:141-176), plus the object frame.
+  renderer: an epos_amd.render.Renderer draws the shaded meshes instead (overlay_mesh_poses)."""
+  if renderer is not None:
+    return overlay_mesh_poses(rgb, K, poses, renderer)
   rgb = np.asarray(rgb)
   h, w = rgb.shape[:2]
   ren = np.zeros((h, w, 3), np.float32)
@@ -182,11 +206,48 @@ def visualize_pred_frag(frag_confs, frag_coords, output_size, store, vis_prefix,
   return paths
 
 
+def _unit_range(a):
+  a = a - a.min()
+  m = a.max()
+  return a / m if m > 0 else a
+
+
+def visualize_gt_frag(gt_fields, store, vis_prefix, vis_dir):
+  """The four images of vis.visualize_gt_frag (vis.py:179-248) from the maps of
+  epos_amd.render (host arrays obj_label, frag_label, frag_loc, frag_weight of one image):
+  the assigned fragment's centre, the local coordinates scaled back by the fragment size,
+  their sum (the reconstructed object coordinates) and the weights, each normalised to its
+  own range as the reference does. Returns the paths written."""
+  from PIL import Image
+  obj = np.asarray(gt_fields['obj_label'])
+  lab = np.asarray(gt_fields['frag_label'])
+  loc = np.asarray(gt_fields['frag_loc'], np.float64)
+  centers_vis = np.zeros(obj.shape + (3,))
+  coords_vis = np.zeros(obj.shape + (3,))
+  for obj_id in np.unique(obj[obj > 0]):
+    m = obj == obj_id
+    centers_vis[m] = np.asarray(store.frag_centers[int(obj_id)], np.float64)[lab[m]]
+    coords_vis[m] = loc[m] * np.asarray(store.frag_sizes[int(obj_id)], np.float64)[lab[m]][:, None]
+  images = {'labels': _unit_range(centers_vis), 'coords': _unit_range(coords_vis),
+            'reconst': _unit_range(centers_vis + coords_vis),
+            'weights': _unit_range(np.asarray(gt_fields['frag_weight'], np.float64))}
+  os.makedirs(vis_dir, exist_ok=True)
+  paths = []
+  for key in ('labels', 'coords', 'reconst', 'weights'):
+    path = os.path.join(vis_dir, '%s_gt_frag_%s.png' % (vis_prefix, key))
+    Image.fromarray((255.0 * images[key]).astype(np.uint8)).save(path)
+    paths.append(path)
+  return paths
+
+
 def visualize(rgb, K, predictions, pred_poses, im_ind, store, vis_dir, gt_poses=None,
-              gt_obj_label=None, flags=None):
+              gt_obj_label=None, flags=None, renderer=None, gt_fields=None):
   """One image's visualisations (infer.py:150-291). predictions: host arrays of ONE image
   -- pred_obj_label [h,w], pred_obj_conf [h,w,O+1], pred_frag_conf [h,w,O,F],
-  pred_frag_loc [h,w,O,F,3]. Returns the paths written."""
+  pred_frag_loc [h,w,O,F,3]. renderer: an epos_amd.render.Renderer draws the pose overlays as
+  shaded meshes (default: the point splat). gt_fields: the ground-truth maps of this image
+  (epos_amd.render, host arrays) -- they give the "gt obj labels" tile and, with
+  vis_gt_frag_fields, the images of visualize_gt_frag. Returns the paths written."""
   from PIL import Image
   fl = {'vis_gt_poses': True, 'vis_pred_poses': True, 'vis_gt_obj_labels': True,
         'vis_pred_obj_labels': True, 'vis_pred_obj_confs': False,
@@ -196,11 +257,15 @@ def visualize(rgb, K, predictions, pred_poses, im_ind, store, vis_dir, gt_poses=
   prefix = '%06d' % im_ind
   tiles = [write_text(resize(rgb, TILE_SIZE), 'input')]
   if fl['vis_gt_poses'] and gt_poses:
-    tiles.append(write_text(resize(overlay_object_poses(rgb, K, gt_poses, store),
+    tiles.append(write_text(resize(overlay_object_poses(rgb, K, gt_poses, store,
+                                                        renderer=renderer),
                                    TILE_SIZE), 'gt poses'))
   if fl['vis_pred_poses']:
-    tiles.append(write_text(resize(overlay_object_poses(rgb, K, pred_poses, store),
+    tiles.append(write_text(resize(overlay_object_poses(rgb, K, pred_poses, store,
+                                                        renderer=renderer),
                                    TILE_SIZE), 'pred poses'))
+  if gt_obj_label is None and gt_fields is not None:
+    gt_obj_label = gt_fields['obj_label']
   if fl['vis_gt_obj_labels'] and gt_obj_label is not None:
     tiles.append(write_text(resize(colorize_label_map(gt_obj_label), TILE_SIZE),
                             'gt obj labels'))
@@ -214,6 +279,8 @@ def visualize(rgb, K, predictions, pred_poses, im_ind, store, vis_dir, gt_poses=
       tiles.append(write_text(np.dstack([g, g, g]), 'cls %d' % c))
   os.makedirs(vis_dir, exist_ok=True)
   paths = []
+  if fl['vis_gt_frag_fields'] and gt_fields is not None:
+    paths += visualize_gt_frag(gt_fields, store, prefix, vis_dir)
   if fl['vis_pred_frag_fields']:
     hh, ww = np.asarray(predictions['pred_obj_label']).shape
     paths += visualize_pred_frag(predictions['pred_frag_conf'], predictions['pred_frag_loc'],

@@ -779,6 +779,90 @@ typedef struct EposResizeSrc {
 int epos_resize_merge_f32(const EposResizeSrc* srcs, int S, float* Y, int64_t ldy, int B,
                           int Ho, int Wo, int C, int merge, void* stream);
 
+/* ------------------------------------------------------------------------- *
+ * Mesh renderer (csrc/render.hip; added without an ABI version change: nothing
+ * existing moved). A batched z-buffered triangle rasteriser and the ground-truth
+ * maps built from its images. The three launchers only enqueue on `stream`: no host
+ * synchronisation, no allocation. tests/helpers/render_ref.py restates every rule
+ * below in numpy; the kernels equal it bit for bit.
+ *
+ * Geometry (a defined function of the input, not of the launch):
+ *   camera-space vertex   Xc = R X + t, fp64, each row summed left to right, no FMA
+ *   projection            u = fx Xc / Zc + cx, v = fy Yc / Zc + cy
+ *   sample point          pixel (x, y) is sampled at image coordinates (x + .5, y + .5)
+ *   near rule             a triangle with any vertex at Zc < near is dropped whole --
+ *                         there is NO clipping: a surface that crosses the near plane
+ *                         loses every triangle that touches it
+ *   snapping              rint(u * 256), rint(v * 256) as int64 (1/256 pixel); a triangle
+ *                         with any |snapped coordinate| >= 2^31 is dropped
+ *   coverage              exact integer edge functions (64-bit while every |coordinate|
+ *                         < 2^29, 128-bit above: both exact), top-left fill rule; a shared
+ *                         edge gives its two triangles negated values, so a closed mesh has
+ *                         neither cracks nor double hits; both windings are drawn;
+ *                         zero-area triangles cover nothing
+ *   depth                 b_i = E_i / (E_0 + E_1 + E_2) in fp64 (E_i the edge value opposite
+ *                         vertex i; a 128-bit value converts as high half * 2^64 + low
+ *                         half), z = 1 / (b_0/z_0 + b_1/z_1 + b_2/z_2), rounded once to fp32
+ *   key                   (fp32 bits of z) << 32 | face index within the instance, combined
+ *                         by a 64-bit unsigned atomic min: the nearest surface wins, equal
+ *                         fp32 depth goes to the lowest face index, in every launch order
+ * The sample point, the near rule and the shading are this build's definitions
+ * (bop_renderer is not available to compare with): parity unpinned.
+ * ------------------------------------------------------------------------- */
+typedef struct EposRenderInst {
+  int32_t vert_base;   /* first vertex of the instance's mesh in the pooled arrays */
+  int32_t face_base;   /* first face; its vertex indices are relative to vert_base */
+  int32_t n_faces;
+  int32_t reserved0;
+  double R[9];         /* row-major rotation, model -> camera */
+  double t[3];         /* translation, mm */
+  double fx, fy, cx, cy;
+} EposRenderInst;
+/* Bounding-box sample count above which a triangle is walked by its whole wavefront instead
+ * of by one lane (the result does not depend on it). */
+int epos_render_lane_max_pixels(void);
+/* verts f64 [n_verts,3], faces i32 [n_faces,3] (pooled), insts [n_inst] -- all [device].
+ * keys u64 [n_inst,h,w] is cleared to all ones on the stream, then rasterised into. near > 0
+ * (mm). Faces or vertices outside the pooled arrays are skipped. h, w <= 32768 and
+ * n_inst * h * w < 2^31 (here and in the resolve call); every refusal comes before the first
+ * launch. */
+int epos_render_raster(const double* verts, int64_t n_verts, const int32_t* faces,
+                       int64_t n_faces, const EposRenderInst* insts, int n_inst, int h, int w,
+                       double near, uint64_t* keys, void* stream);
+/* Keys -> images, each output optional (NULL skips it), [device]:
+ *   depth f32 [n_inst,h,w]        camera z in mm, 0 = background
+ *   face i32 [n_inst,h,w]         winning face within the instance, -1 = background
+ *   local_pos f32 [n_inst,h,w,3]  perspective-correct model-space position:
+ *                                 (sum_i q_i X_i) / (sum_i q_i), q_i = b_i / z_i, 0 = background
+ *   color u8 [n_inst,h,w,3]       the same interpolation of the vertex colours (colors u8
+ *                                 [n_verts,3], required with this output), times the headlight
+ *                                 term L = 0.3 + 0.7 nz^2 / (nx^2 + ny^2 + nz^2), n = (P1 - P0)
+ *                                 x (P2 - P0) in camera space (L = 0.3 when n = 0); stored as
+ *                                 floor(c L + 0.5) clamped to 0..255
+ * The barycentrics are recomputed from the winning face exactly as in the raster pass; same
+ * verts / faces / insts / near as the raster call. */
+int epos_render_resolve(const uint64_t* keys, const double* verts, int64_t n_verts,
+                        const int32_t* faces, int64_t n_faces, const uint8_t* colors,
+                        const EposRenderInst* insts, int n_inst, int h, int w, double near,
+                        float* depth, int32_t* face, float* local_pos, uint8_t* color,
+                        void* stream);
+/* Ground-truth maps of one image from per-instance renderings (datagen.py:570-604,
+ * datagen_utils.py:161-232, knn_frags = 1). depth f32 [n_inst,h,w], local_pos f32
+ * [n_inst,h,w,3], masks u8 [n_inst,h,w] or NULL, obj_ids i32 [n_inst] (1-based; an instance
+ * whose id is outside 1..num_objs takes no pixel), centers f64 [num_objs,num_frags,3], sizes
+ * f64 [num_objs,num_frags], 1 <= num_frags <= 256 (EPOS_E_INVALID otherwise).
+ * Visibility: with masks, the instances are scanned from the last to the first and a pixel goes
+ * to the first one with mask != 0 and depth > 0; without, the nearest depth > 0 wins, ties to
+ * the higher index. Outputs (each optional): obj_label i32 [h,w] (0 = none), instance i32
+ * [h,w] (-1 = none), frag_label i32 [h,w] (nearest centre by dx^2 + dy^2 + dz^2 summed in
+ * that order in fp64, ties to the lowest index), frag_loc f32 [h,w,3] = (xyz - centre) / size
+ * in fp64 on the fp32 xyz, rounded to fp32, frag_weight f32 [h,w] (1 where assigned). */
+int epos_gt_fields(const float* depth, const float* local_pos, const uint8_t* masks,
+                   const int32_t* obj_ids, int n_inst, int h, int w, const double* centers,
+                   const double* sizes, int num_objs, int num_frags, int32_t* obj_label,
+                   int32_t* instance, int32_t* frag_label, float* frag_loc,
+                   float* frag_weight, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -21,7 +21,8 @@ Input frames: ``--infer_tfrecord_names a,b`` reads <TF_DATA_PATH>/<name>.tfrecor
 like the reference (infer.py:581-583) but without TensorFlow (epos_amd/tfrecord.py:
 TFRecord framing + tf.Example parsing + PIL decoding; frames that would need the
 reference's resize raise). Alternatively ``--frames <dir>`` holding ``frames.json``
-(list of {scene_id, im_id, path, K[9], targets {obj_id: count}}) + images (.npy
+(list of {scene_id, im_id, path, K[9], targets {obj_id: count}, optionally gt_poses
+[{obj_id, R[9], t[3]}] for --vis}) + images (.npy
 HxWx3 or anything PIL reads), or ``--synthetic N`` seeded synthetic frames.
 
 Reference quirks kept on purpose: only the *localization* task has targets (the
@@ -112,6 +113,12 @@ def build_parser():
   a('--vis_pred_obj_confs', type=str2bool, default=False)
   a('--vis_gt_frag_fields', type=str2bool, default=False)
   a('--vis_pred_frag_fields', type=str2bool, default=False)
+  a('--vis_renderer', choices=('splat', 'mesh'), default='splat',
+    help='not in the reference. splat (default): pose overlays as a z-buffered point splat '
+         'on the host; no ground-truth label tile, no ground-truth fragment fields. mesh: the '
+         'object meshes are rendered on the device (epos_amd/render.py; needs --dataset and '
+         '$BOP_PATH for the \'eval\' models): shaded pose overlays, the "gt obj labels" tile '
+         'and --vis_gt_frag_fields for frames that carry gt_poses')
   # epos_lib/common.py:60-154 (the model flags the hot path reads)
   a('--dataset', default=None)
   a('--num_frags', type=int, default=64)
@@ -512,11 +519,14 @@ def main(argv=None):
           'equal cv2\'s bit for bit: the factorisations are this build\'s own and the '
           'R -> rvec -> R round trip through cv::Rodrigues in front of the inlier test is '
           'not made (DESIGN.md (f2)).')
-  if args.vis and args.vis_gt_frag_fields:
+  mesh_vis = bool(args.vis) and args.vis_renderer == 'mesh'
+  if mesh_vis and not (args.dataset and os.environ.get('BOP_PATH')):
+    raise ValueError('--vis_renderer mesh needs --dataset and $BOP_PATH (object models)')
+  if args.vis and args.vis_gt_frag_fields and not mesh_vis:
     raise NotImplementedError(
         '--vis_gt_frag_fields needs the ground-truth fragment fields of the training '
         'pipeline (datagen.py:478-544), which the inference reader does not build.')
-  if args.vis and args.vis_gt_obj_labels:
+  if args.vis and args.vis_gt_obj_labels and not mesh_vis:
     # the GT label map comes from the instance masks of the training reader
     # (datagen.py:478-544); the inference reader holds none, so that tile is left out --
     # said once here instead of silently (scripts/infer.py:150-291 draws it)
@@ -606,6 +616,17 @@ def main(argv=None):
       raise ValueError('--project_to_surface needs --dataset and $BOP_PATH (object models)')
     store.models = ply.load_models(bop, args.dataset, 'eval',
                                    obj_ids=store.dp_model['obj_ids'])
+  renderer = None
+  if mesh_vis:
+    # scripts/infer.py:633-638: the renderer holds the 'eval' models (those of
+    # --project_to_surface when it loaded them already)
+    from epos_amd import ply, render as erender
+    models = getattr(store, 'models', None) or ply.load_models(
+        os.environ['BOP_PATH'], args.dataset, 'eval', obj_ids=store.dp_model['obj_ids'])
+    renderer = erender.Renderer(dev)
+    for o in sorted(models):
+      renderer.add_model(o, models[o])
+    frag_pool = erender.pool_fragments(store.frag_centers, store.frag_sizes)
   B = args.batch
   # Instances per object (infer.py:456-468 of the reference): localization fits as many as
   # the frame's annotations hold -- the plan is sized for the largest count among the frames
@@ -711,9 +732,31 @@ def main(argv=None):
       flags = {k: getattr(args, k) for k in vars(args) if k.startswith('vis_')}
       for b, f in enumerate(chunk[:n_real]):
         est = [p for p in poses if (p['scene_id'], p['im_id']) == (f.scene_id, f.im_id)]
+        gt_fields = None
+        gi = [i for i, p in enumerate(f.gt_poses or []) if renderer is not None and
+              renderer.has_object(p['obj_id']) and p['obj_id'] in store.frag_centers]
+        gt = [f.gt_poses[i] for i in gi]
+        if gt:
+          # the ground-truth maps at the output resolution, with output_K of datagen.py:482-488
+          oh, ow = pred['pred_obj_label'][b].shape
+          sy, sx = h / float(oh), w / float(ow)
+          oK = np.array([[f.K[0, 0] / sx, 0.0, f.K[0, 2] / sx],
+                         [0.0, f.K[1, 1] / sy, f.K[1, 2] / sy], [0.0, 0.0, 1.0]])
+          # frames without instance masks (--frames, --synthetic) take the depth rule
+          masks = f.gt_masks((ow, oh))
+          if masks is not None:
+            if len(masks) != len(f.gt_poses):
+              raise ValueError('frame %s/%s: %d instance masks for %d ground-truth poses' % (
+                  f.scene_id, f.im_id, len(masks), len(f.gt_poses)))
+            masks = masks[gi]
+          gt_fields = {k: v.cpu().numpy() for k, v in erender.gt_fields(
+              renderer, oK, [p['obj_id'] for p in gt], np.stack([p['R'] for p in gt]),
+              np.stack([np.asarray(p['t']).reshape(3) for p in gt]), (ow, oh), frag_pool[0],
+              frag_pool[1], masks).items()}
         evis.visualize(f.image_f32(), f.K, {k: v[b] for k, v in pred.items()}, est, i0 + b,
                        store, os.path.join(model_dir, 'vis'),
-                       gt_poses=f.gt_poses, flags=flags)
+                       gt_poses=f.gt_poses, flags=flags, renderer=renderer,
+                       gt_fields=gt_fields)
     if rank == 0:                               # infer.py:730-734
       print('Image: {}, prediction: {:.3f}, establish_corr: {:.3f}, fitting: '
             '{:.3f}, total time: {:.3f}'.format(
