@@ -335,6 +335,12 @@ SYMBOLS = {
     'epos_gt_fields': (ctypes.c_int, [
         vp, vp, vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp, ctypes.c_int,
         ctypes.c_int, vp, vp, vp, vp, vp, vp]),
+    # evaluation
+    'epos_eval_lds_max_cls': (ctypes.c_int, []),
+    'epos_eval_confusion': (ctypes.c_int, [
+        vp, vp, ctypes.c_int64, ctypes.c_int, ctypes.c_int, vp, vp, vp]),
+    'epos_eval_frag_hits': (ctypes.c_int, [
+        vp, vp, vp, vp, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp]),
 }
 
 _lib = None

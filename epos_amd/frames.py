@@ -27,11 +27,12 @@ class Frame(object):
   """One input frame: scene_id, im_id, K f64[3,3], targets {obj_id: instances}, gt_poses (or
   None), and ``load(out=None)`` -> uint8 or float32 [H,W,3] pixels (decoded on demand)."""
   __slots__ = ('scene_id', 'im_id', 'K', 'targets', 'gt_poses', '_loader', 'dtype',
-               'mask_source')
+               'mask_source', 'image_path')
 
   def __init__(self, scene_id, im_id, K, targets, loader, gt_poses=None, dtype=np.uint8,
-               mask_source=None):
+               mask_source=None, image_path=''):
     self.mask_source = mask_source
+    self.image_path = image_path
     self.scene_id, self.im_id = scene_id, im_id
     self.K = np.asarray(K, np.float64).reshape(3, 3)
     self.targets = targets
@@ -82,7 +83,7 @@ def scan_tfrecords(paths, crop_size, max_height_before_crop, obj_ids, crop_seed=
           _TfrecordLoader(path, off + loc[0], loc[1], geo, meta['crop_offset']),
           meta['gt_poses'], np.float32 if resized else np.uint8,
           _TfrecordMasks(path, off, len(data), geo, meta['crop_offset'], meta['keep'])
-          if feats.get('image/object/mask') else None))
+          if feats.get('image/object/mask') else None, meta['image_path']))
   return frames
 
 
@@ -191,7 +192,8 @@ def frames_from_dir(directory, meta, h, w):
       dtype = np.uint8 if np.load(path, mmap_mode='r').dtype == np.uint8 else np.float32
     out.append(Frame(m.get('scene_id', 0), m['im_id'], m['K'],
                      {int(k): int(v) for k, v in m.get('targets', {}).items()},
-                     _Loader('file', path, h, w), _gt_poses_of(m), dtype=dtype))
+                     _Loader('file', path, h, w), _gt_poses_of(m), dtype=dtype,
+                     image_path=path))
   return out
 
 

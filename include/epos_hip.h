@@ -863,6 +863,45 @@ int epos_gt_fields(const float* depth, const float* local_pos, const uint8_t* ma
                    int32_t* instance, int32_t* frag_label, float* frag_loc,
                    float* frag_weight, void* stream);
 
+/* ------------------------------------------------------------------------- *
+ * Evaluation (csrc/eval.hip; added without an ABI version change: nothing existing
+ * moved). Integer reductions over label maps; both launchers only enqueue on
+ * `stream` and ADD into their tables, which they never clear: the caller zeroes a
+ * table once per evaluation and accumulates over every batch. All sums are integer,
+ * so the tables do not depend on the launch; tests/helpers/eval_ref.py restates
+ * them in numpy and the kernels equal it exactly. Every refusal (EPOS_E_INVALID)
+ * comes before the first launch; P == 0 does nothing and returns 0.
+ * ------------------------------------------------------------------------- */
+/* Largest num_cls whose confusion matrix a workgroup keeps privately in LDS (32-bit counters,
+ * flushed with one 64-bit atomic per non-zero cell); above it the pixels go to the global table
+ * directly. The result does not depend on it. */
+int epos_eval_lds_max_cls(void);
+/* Confusion matrix of eval_utils.py:52-87: gt_label i32 [P], pred_label i64 [P] (P = B*h*w,
+ * 0 <= P <= 2^40), cm i64 [num_cls,num_cls] with row = ground truth, column = prediction,
+ * bad i64 [1], all [device]. A pixel whose ground truth equals ignore_label is skipped (this
+ * rule comes first, also for an ignore_label inside 0..num_cls-1). Any other pixel whose ground
+ * truth or prediction lies outside 0..num_cls-1 adds 1 to *bad and nothing to cm (the reference
+ * would raise IndexError there). 1 <= num_cls <= 256. */
+int epos_eval_confusion(const int32_t* gt_label, const int64_t* pred_label, int64_t P,
+                        int num_cls, int ignore_label, int64_t* cm, int64_t* bad, void* stream);
+/* Fragment hit counts. THIS BUILD'S DEFINITION: the reference evaluates the object
+ * segmentation only (its hook lists the fragment tensors commented out) and defines no
+ * fragment metric. gt_obj_label, gt_frag_label i32 [P]; pred_obj_label i64 [P] or NULL;
+ * pred_frag_conf f32 [P,num_objs,num_frags] (the dense head); counts i64 [num_objs+1,3]; all
+ * [device]. For every pixel p whose ground-truth object o lies in 1..num_objs (0, ignore_label
+ * and ids outside that range are skipped and read no confidence):
+ *   f* = argmax_f pred_frag_conf[p,o-1,f], the first maximum wins; a NaN compares as -inf, so
+ *        it never beats a number (a row without any number gives f* = 0)
+ *   counts[o,0] += 1
+ *   counts[o,1] += (f* == gt_frag_label[p])
+ *   counts[o,2] += (f* == gt_frag_label[p] && pred_obj_label[p] == o)   (untouched when
+ *                  pred_obj_label is NULL)
+ * Row 0 stays as it was. 1 <= num_objs <= 4095, 1 <= num_frags <= 256. */
+int epos_eval_frag_hits(const int32_t* gt_obj_label, const int32_t* gt_frag_label,
+                        const int64_t* pred_obj_label, const float* pred_frag_conf, int64_t P,
+                        int num_objs, int num_frags, int ignore_label, int64_t* counts,
+                        void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -353,6 +353,35 @@ def find_checkpoint(checkpoint_dir, name):
   return cands[-1] if cands else None
 
 
+def load_checkpoint(args, checkpoint_dir):
+  """(checkpoint dict, num_objs, path): the TensorFlow checkpoint of <model>/train (the latest
+  or --checkpoint_name, infer.py:670-674), else an .npz, else -- with --synthetic -- random
+  weights (path None)."""
+  ckpt_path = find_checkpoint(checkpoint_dir, args.checkpoint_name)
+  tf_prefix = None
+  if args.checkpoint_name is not None and os.path.exists(
+      os.path.join(checkpoint_dir, args.checkpoint_name + '.index')):
+    tf_prefix = os.path.join(checkpoint_dir, args.checkpoint_name)
+  elif not (ckpt_path and os.path.exists(ckpt_path)):
+    from epos_amd import tf_checkpoint
+    tf_prefix = tf_checkpoint.latest_checkpoint(checkpoint_dir)  # infer.py:670-674
+  if tf_prefix is not None:
+    # A TensorFlow checkpoint (model.ckpt-N.index/.data-*), read without TF.
+    from epos_amd import tf_checkpoint
+    ckpt = tf_checkpoint.to_epos_checkpoint(
+        tf_checkpoint.load_checkpoint(tf_prefix))
+    return ckpt, ckpt['logits/pred_obj_conf/biases'].shape[0] - 1, tf_prefix
+  if ckpt_path and os.path.exists(ckpt_path):
+    ckpt = weights.load_npz(ckpt_path)
+    return ckpt, ckpt['logits/pred_obj_conf/biases'].shape[0] - 1, ckpt_path
+  if args.synthetic:
+    num_objs = args.num_objs or 21
+    ckpt = weights.random_init(args.model_variant, num_objs=num_objs,
+                               num_frags=args.num_frags, seed=0, randomize_bn=True)
+    return ckpt, num_objs, None
+  raise ValueError('No checkpoint (.npz) found in {}'.format(checkpoint_dir))
+
+
 def load_frames(args, num_objs, rank, world, store_obj_ids=None):
   """Returns this rank's list of epos_amd.frames.Frame (ids, K, targets known; pixels decoded
   on demand by the prefetcher's threads), plus the frame height and width."""
@@ -541,29 +570,7 @@ def main(argv=None):
   dev = 'cuda:%d' % dev_index
   torch.cuda.set_device(dev_index)
 
-  ckpt_path = find_checkpoint(checkpoint_dir, args.checkpoint_name)
-  tf_prefix = None
-  if args.checkpoint_name is not None and os.path.exists(
-      os.path.join(checkpoint_dir, args.checkpoint_name + '.index')):
-    tf_prefix = os.path.join(checkpoint_dir, args.checkpoint_name)
-  elif not (ckpt_path and os.path.exists(ckpt_path)):
-    from epos_amd import tf_checkpoint
-    tf_prefix = tf_checkpoint.latest_checkpoint(checkpoint_dir)  # infer.py:670-674
-  if tf_prefix is not None:
-    # A TensorFlow checkpoint (model.ckpt-N.index/.data-*), read without TF.
-    from epos_amd import tf_checkpoint
-    ckpt = tf_checkpoint.to_epos_checkpoint(
-        tf_checkpoint.load_checkpoint(tf_prefix))
-    num_objs = ckpt['logits/pred_obj_conf/biases'].shape[0] - 1
-  elif ckpt_path and os.path.exists(ckpt_path):
-    ckpt = weights.load_npz(ckpt_path)
-    num_objs = ckpt['logits/pred_obj_conf/biases'].shape[0] - 1
-  elif args.synthetic:
-    num_objs = args.num_objs or 21
-    ckpt = weights.random_init(args.model_variant, num_objs=num_objs,
-                               num_frags=args.num_frags, seed=0, randomize_bn=True)
-  else:
-    raise ValueError('No checkpoint (.npz) found in {}'.format(checkpoint_dir))
+  ckpt, num_objs, _ = load_checkpoint(args, checkpoint_dir)
   store = load_fragments(model_dir, args.num_frags)
   if store is None and not args.synthetic:
     store = fragment_from_bop_models(model_dir, args, dev)
