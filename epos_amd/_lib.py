@@ -178,6 +178,15 @@ class RenderInst(ctypes.Structure):
               ('cx', ctypes.c_double), ('cy', ctypes.c_double)]
 
 
+class PosePair(ctypes.Structure):
+  _fields_ = [('vert_base', ctypes.c_int32), ('n_verts', ctypes.c_int32),
+              ('sym_base', ctypes.c_int32), ('n_sym', ctypes.c_int32),
+              ('R_e', ctypes.c_double * 9), ('t_e', ctypes.c_double * 3),
+              ('R_g', ctypes.c_double * 9), ('t_g', ctypes.c_double * 3),
+              ('fx', ctypes.c_double), ('fy', ctypes.c_double),
+              ('cx', ctypes.c_double), ('cy', ctypes.c_double)]
+
+
 class FitParams(ctypes.Structure):
   _fields_ = [
       ('threshold', ctypes.c_double),
@@ -341,6 +350,11 @@ SYMBOLS = {
         vp, vp, ctypes.c_int64, ctypes.c_int, ctypes.c_int, vp, vp, vp]),
     'epos_eval_frag_hits': (ctypes.c_int, [
         vp, vp, vp, vp, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp]),
+    # pose errors
+    'epos_pose_error_group_syms': (ctypes.c_int, []),
+    'epos_pose_error_adi_tile': (ctypes.c_int, []),
+    'epos_pose_errors_f64': (ctypes.c_int, [
+        vp, ctypes.c_int64, vp, ctypes.c_int64, vp, vp, ctypes.c_int, ctypes.c_int, vp, vp]),
 }
 
 _lib = None

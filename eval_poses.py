@@ -1,0 +1,225 @@
+#!/usr/bin/env python
+"""Scores the poses ``infer.py`` estimated -- MSSD, MSPD and ADD(-S) recalls on MI355X.
+
+    python eval_poses.py --model=<model_name> --dataset <d>
+        (--infer_tfrecord_names a,b | --frames <dir>)
+        [--infer_name N | --result_path file.csv] [--adi true|false]
+
+The reference has no such script: it leaves pose scoring to ``bop_toolkit``, an empty submodule
+there. Environment as for ``eval.py``: TF_DATA_PATH / TF_MODELS_PATH / BOP_PATH, and
+<TF_MODELS_PATH>/<model>/params.yml overrides flag defaults.
+
+  * estimates: <model>/infer/estimated-poses[_<infer_name>].csv as ``infer.py`` wrote it (BOP'19
+    format), or --result_path;
+  * frames: metadata only -- ids, camera, targets and ground-truth poses from the TFRecords or
+    from <dir>/frames.json. No pixel is decoded, no image file has to exist, no checkpoint is
+    read;
+  * targets: Frame.targets, as in ``infer.py`` (every annotated instance of the dataset's
+    objects). Per (scene, image, object) the n best-scored estimates are kept, n = the
+    instance count. BOP'19's own test_targets_bop19.json and its rule that only instances
+    visible by at least 10 % count are NOT applied, so the recalls are not the leaderboard's;
+  * models: <BOP_PATH>/<dataset>/models_eval/ with models_info.json (diameters, symmetries);
+  * errors: epos_amd/pose_error.py, this build's definitions (include/epos_hip.h, "Pose
+    errors"); one launch sequence and one download for the whole run;
+  * results in <model>/eval/: pose_scores[_<infer_name>].json (thresholds, per-object and
+    overall recalls, counts of estimates, targets and non-finite pairs) and
+    pose_errors[_<infer_name>].csv, one row per (estimate, ground truth) pair.
+
+``mean_ar_mssd_mspd`` is the mean of AR_MSSD and AR_MSPD; it is not BOP's AR, which also
+averages AR_VSD (VSD needs the test depth images, which the TFRecords do not carry).
+"""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np     # noqa: E402
+
+ROOT = os.path.dirname(os.path.abspath(__file__))
+if ROOT not in sys.path:
+  sys.path.insert(0, ROOT)
+
+import infer           # noqa: E402
+
+
+def build_parser():
+  ap = argparse.ArgumentParser(description=__doc__,
+                               formatter_class=argparse.RawTextHelpFormatter)
+  a = ap.add_argument
+  a('--model', required=True)
+  a('--dataset', default=None)
+  a('--infer_tfrecord_names', default=None)
+  a('--infer_max_height_before_crop', type=int, default=480)
+  a('--infer_crop_size', default='640,480')
+  a('--infer_name', default=None)
+  a('--frames', default=None, help='directory with frames.json (the images are not read)')
+  a('--synthetic', type=int, default=0,
+    help='refused: synthetic frames carry no ground-truth poses')
+  a('--seed', type=int, default=0)
+  a('--result_path', default=None,
+    help='the BOP\'19 CSV (default: <model>/infer/estimated-poses[_<infer_name>].csv)')
+  a('--adi', type=infer.str2bool, default=True,
+    help='compute ADI (O(vertices^2) per pair); false: ADD(-S) recall uses ADD only for '
+         'objects without symmetries and is left out for the others')
+  return ap
+
+
+def prepare(argv=None):
+  """Parses the command line, applies params.yml and refuses what cannot be scored."""
+  args = build_parser().parse_args(argv)
+  model_dir = os.path.join(os.environ.get('TF_MODELS_PATH', '.'), args.model)
+  infer.update_flags(args, os.path.join(model_dir, infer.PARAMS_FILENAME))
+  if args.synthetic:
+    raise ValueError('eval_poses.py: --synthetic frames carry no ground-truth poses; give '
+                     '--infer_tfrecord_names or --frames <dir> with gt_poses')
+  if not (args.dataset and os.environ.get('BOP_PATH')):
+    raise ValueError('eval_poses.py needs --dataset and $BOP_PATH (models_eval)')
+  if not (args.infer_tfrecord_names or args.frames):
+    raise ValueError('No input files: give --infer_tfrecord_names or --frames <dir>.')
+  return args, model_dir
+
+
+def crop_size(args):
+  if isinstance(args.infer_crop_size, (list, tuple)):
+    return [int(x) for x in args.infer_crop_size[:2]]
+  return [int(x) for x in str(args.infer_crop_size).split(',')][:2]
+
+
+def frames_metadata(directory):
+  """frames.json -> Frames without pixels: no image file is opened."""
+  from epos_amd import frames as eframes
+  with open(os.path.join(directory, 'frames.json')) as f:
+    meta = json.load(f)
+  return [eframes.Frame(m.get('scene_id', 0), m['im_id'], m['K'],
+                        {int(k): int(v) for k, v in m.get('targets', {}).items()}, None,
+                        eframes._gt_poses_of(m), image_path=m.get('path', ''))
+          for m in meta]
+
+
+def load_frames(args, obj_ids):
+  if args.infer_tfrecord_names:
+    return infer.load_frames(args, len(obj_ids or ()), 0, 1, obj_ids)[0]
+  return frames_metadata(args.frames)
+
+
+def result_path(args, model_dir):
+  if args.result_path:
+    return args.result_path
+  suffix = '' if args.infer_name is None else '_' + args.infer_name
+  return os.path.join(model_dir, 'infer', 'estimated-poses{}.csv'.format(suffix))
+
+
+def build_groups(frames, results):
+  """One group per (frame, target object): the n best-scored estimates (n = the instance count;
+  ties keep file order) and the object's ground-truth poses. Returns (groups, ignored): the
+  estimates of images or objects that are no target."""
+  by_key = {}
+  for r in results:
+    by_key.setdefault((r['scene_id'], r['im_id'], r['obj_id']), []).append(r)
+  groups, used = [], 0
+  for f in frames:
+    for o in sorted(f.targets):
+      n_inst = f.targets[o]
+      ests = by_key.get((f.scene_id, f.im_id, o), [])
+      order = np.argsort(-np.array([e['score'] for e in ests], np.float64), kind='stable')
+      if n_inst >= 0:
+        order = order[:n_inst]
+      used += len(order)
+      groups.append({'frame': f, 'obj_id': int(o), 'ests': [ests[i] for i in order],
+                     'gts': [p for p in f.gt_poses if p['obj_id'] == o]})
+  return groups, len(results) - used
+
+
+def main(argv=None):
+  args, model_dir = prepare(argv)
+  from epos_amd import bop_io, ply, pose_error
+  frames = load_frames(args, ply.BOP_OBJ_IDS.get(args.dataset))
+  if not frames:
+    raise ValueError('no frames to score')
+  if any(f.gt_poses is None for f in frames):
+    raise ValueError('eval_poses.py: input without ground-truth poses cannot be scored '
+                     '(frames.json entries need gt_poses)')
+  path = result_path(args, model_dir)
+  if not os.path.exists(path):
+    raise ValueError('no pose estimates at {} (run infer.py first)'.format(path))
+  results = bop_io.load_bop_results(path)
+  groups, ignored = build_groups(frames, results)
+
+  bop = os.environ['BOP_PATH']
+  obj_ids = sorted(set(g['obj_id'] for g in groups))
+  info = pose_error.load_models_info(pose_error.models_info_path(bop, args.dataset, 'eval'))
+  models = ply.load_models(bop, args.dataset, 'eval', obj_ids=obj_ids)
+  dev = 'cuda:%d' % int(os.environ.get('EPOS_FORCE_DEVICE', 0))
+  ev = pose_error.PoseErrorEval(models, info, dev)
+
+  pairs, owner = [], []
+  for gi, g in enumerate(groups):
+    for ei, e in enumerate(g['ests']):
+      for ti, t in enumerate(g['gts']):
+        pairs.append({'obj_id': g['obj_id'], 'R_e': e['R'], 't_e': e['t'], 'R_g': t['R'],
+                      't_g': t['t'], 'K': g['frame'].K})
+        owner.append((gi, ei, ti))
+  err = ev.errors(pairs, want_adi=args.adi)
+  non_finite = int(np.isinf(err[:, 5]).sum()) if len(err) else 0
+
+  for g in groups:
+    g['errors'] = np.zeros((len(g['ests']), len(g['gts']), 6))
+    g['scores'] = [e['score'] for e in g['ests']]
+  for (gi, ei, ti), row in zip(owner, err):
+    groups[gi]['errors'][ei, ti] = row
+  n_syms = {o: ev.n_sym(o) for o in obj_ids}
+  width = crop_size(args)[0]
+  missing = [o for o in obj_ids if o not in ev.diameters]
+  if missing:
+    raise ValueError('models_info.json gives no diameter for object(s) {}'.format(missing))
+  rec = pose_error.recalls(groups, ev.diameters, n_syms, width)
+  if not args.adi:                       # no ADI: no ADD(-S) figure for symmetric objects
+    for o, r in rec['per_object'].items():
+      if n_syms[o] > 1:
+        r['add_s_recall'] = None
+    if any(n_syms[o] > 1 for o in obj_ids):
+      rec['overall']['add_s_recall'] = None
+
+  eval_dir = os.path.join(model_dir, 'eval')
+  os.makedirs(eval_dir, exist_ok=True)
+  suffix = '' if args.infer_name is None else '_' + args.infer_name
+  scores = {
+      'result_path': path, 'dataset': args.dataset, 'image_width': width, 'adi': bool(args.adi),
+      'thresholds': {
+          'mssd_x_diameter': list(pose_error.MSSD_FACTORS),
+          'mspd_px_at_width_640': list(pose_error.MSPD_FACTORS),
+          'mspd_px': [c * (width / 640.0) for c in pose_error.MSPD_FACTORS],
+          'add_s_x_diameter': pose_error.ADD_FACTOR,
+          'max_sym_disc_step': pose_error.MAX_SYM_DISC_STEP},
+      'diameters': {str(o): ev.diameters[o] for o in obj_ids},
+      'n_symmetries': {str(o): n_syms[o] for o in obj_ids},
+      'counts': {'frames': len(frames), 'estimates_in_file': len(results),
+                 'estimates_scored': len(results) - ignored, 'estimates_ignored': ignored,
+                 'targets': rec['overall']['targets'], 'pairs': len(pairs),
+                 'non_finite_pairs': non_finite},
+      'per_object': {str(o): r for o, r in rec['per_object'].items()},
+      'overall': rec['overall'],
+  }
+  scores_path = os.path.join(eval_dir, 'pose_scores{}.json'.format(suffix))
+  with open(scores_path, 'w') as f:
+    json.dump(scores, f, indent=1)
+  with open(os.path.join(eval_dir, 'pose_errors{}.csv'.format(suffix)), 'w') as f:
+    f.write('scene_id,im_id,obj_id,est_rank,gt_index,score,' +
+            ','.join(pose_error.ERROR_NAMES) + '\n')
+    for (gi, ei, ti), row in zip(owner, err):
+      g = groups[gi]
+      f.write('{},{},{},{},{},{},{}\n'.format(
+          g['frame'].scene_id, g['frame'].im_id, g['obj_id'], ei, ti, g['scores'][ei],
+          ','.join(repr(float(v)) for v in row)))
+  o = rec['overall']
+  print('eval_poses: {} targets, {} estimates scored, AR_MSSD={:.4f}, AR_MSPD={:.4f}, '
+        'mean={:.4f}, ADD(-S) recall={}'.format(
+            o['targets'], len(results) - ignored, o['ar_mssd'], o['ar_mspd'],
+            o['mean_ar_mssd_mspd'],
+            'n/a' if o['add_s_recall'] is None else '{:.4f}'.format(o['add_s_recall'])))
+  print('Saved pose scores to: {}'.format(scores_path))
+  return scores
+
+
+if __name__ == '__main__':
+  main()

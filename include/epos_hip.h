@@ -902,6 +902,74 @@ int epos_eval_frag_hits(const int32_t* gt_obj_label, const int32_t* gt_frag_labe
                         int num_objs, int num_frags, int ignore_label, int64_t* counts,
                         void* stream);
 
+/* ------------------------------------------------------------------------- *
+ * Pose errors (csrc/pose_error.hip; added without an ABI version change: nothing
+ * existing moved). MSSD, MSPD, ADD and ADI of (estimate, ground truth) pairs over
+ * pooled model vertices and pooled symmetry sets. The launcher only enqueues on
+ * `stream`: no host synchronisation, no allocation. tests/helpers/pose_error_ref.py
+ * restates every rule below in element-wise numpy; the kernels equal it bit for bit.
+ *
+ * These are THIS BUILD'S DEFINITIONS. They follow the published BOP'19 formulas
+ * (Hodan et al., "BOP Challenge 2020 on 6D Object Localization", section 2.2; Hinterstoisser
+ * et al. 2012 for ADD / ADI), but bop_toolkit is not available to compare with: parity with
+ * its numbers is unpinned.
+ *
+ * Arithmetic: fp64 throughout, built from + - * / sqrt only, no FMA. Every 3-term sum is
+ * taken left to right and a translation is added last. A result is a function of the input
+ * and never of the launch shape. Inputs are finite and of a size at which nothing overflows
+ * (the caller keeps non-finite poses away: epos_amd/pose_error.py gives them +inf).
+ *
+ * A symmetry is 12 numbers: R_s row-major, then t_s (mm). The set of an object is built on
+ * the host (epos_amd/pose_error.py: symmetry_transformations): the discrete part D =
+ * [identity] + symmetries_discrete; the continuous part C = rotations by i * 2 pi / n about
+ * `axis` through `offset`, i = 0..n-1, n = ceil(pi / max_sym_disc_step), max_sym_disc_step =
+ * 0.01, t = offset - R offset; the set is every c o d (c outer, d inner), or D alone without
+ * a continuous part. The identity is element 0. Including i = 0 is deliberate: the set then
+ * holds the discrete symmetries themselves (the step, not the count, is what bounds the
+ * discretisation error).
+ *
+ * For a pair (R_e, t_e; R_g, t_g; fx, fy, cx, cy) with vertices X_v and symmetries s:
+ *   composition  R' = R_g R_s (each element (a0 b0 + a1 b1) + a2 b2),
+ *                t' = ((R_g t_s, summed the same way) + t_g), composed FIRST; then
+ *                G_sv = R' X_v + t', E_v = R_e X_v + t_e, each row ((r0 x + r1 y) + r2 z) + t
+ *   MSSD         min_s max_v |E_v - G_sv|: max and min run over the squared norms
+ *                (dx^2 + dy^2) + dz^2 and one sqrt is taken at the end (sqrt is monotone)
+ *   MSPD         the same with u = (fx X) / Z + cx, v = (fy Y) / Z + cy and du^2 + dv^2; a
+ *                point whose estimate-side or ground-truth-side Z <= 0 contributes +inf
+ *   ADD          (sum_v |E_v - G_0v|) / n_verts, G_0 composed with element 0 of the set
+ *   ADI          (sum_v sqrt(min_w |E_w - G_0v|^2)) / n_verts
+ *   sum shape    p_j, j = 0..255, is the left-to-right sum of the terms with v = j (mod 256);
+ *                then p_j += p_{j+128} for j < 128, the same with 64, ... 1; the total is p_0
+ * ------------------------------------------------------------------------- */
+typedef struct EposPosePair {
+  int32_t vert_base;   /* first vertex of the object in the pooled vertices */
+  int32_t n_verts;
+  int32_t sym_base;    /* first symmetry of the object in the pooled symmetries */
+  int32_t n_sym;
+  double R_e[9];       /* estimate, row-major, model -> camera */
+  double t_e[3];       /* mm */
+  double R_g[9];       /* ground truth */
+  double t_g[3];
+  double fx, fy, cx, cy;
+} EposPosePair;
+/* Symmetries one workgroup of the MSSD / MSPD kernel owns (a set that is no multiple of it
+ * ends in a partial group), and estimate-side points per LDS tile of the ADI kernel. The
+ * results depend on neither. */
+int epos_pose_error_group_syms(void);
+int epos_pose_error_adi_tile(void);
+/* verts f64 [n_verts_total,3], syms f64 [n_syms_total,12], err f64 [n_pairs,4] = (mssd,
+ * mspd, add, adi), pairs_dev [n_pairs]: all [device]. pairs [n_pairs] is a HOST table: it is
+ * checked here and copied into pairs_dev on the stream, so it stays alive and unchanged until
+ * the stream has passed this call (pinned memory keeps the copy asynchronous). want_adi = 0
+ * leaves column 3 as it was (ADI is O(n_verts^2) per pair). Refused with EPOS_E_INVALID
+ * before the copy and the first launch: a pair with n_verts < 1 or n_sym < 1, a base or a
+ * range outside the pools, n_pairs < 0, a null pointer, n_pairs * ceil(max n_sym /
+ * epos_pose_error_group_syms()) >= 2^31. n_pairs == 0 does nothing and returns 0. */
+int epos_pose_errors_f64(const double* verts, int64_t n_verts_total, const double* syms,
+                         int64_t n_syms_total, const EposPosePair* pairs,
+                         EposPosePair* pairs_dev, int n_pairs, int want_adi, double* err,
+                         void* stream);
+
 #ifdef __cplusplus
 }
 #endif
