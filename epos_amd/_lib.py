@@ -187,6 +187,15 @@ class PosePair(ctypes.Structure):
               ('cx', ctypes.c_double), ('cy', ctypes.c_double)]
 
 
+class VsdPair(ctypes.Structure):
+  _fields_ = [('image', ctypes.c_int32), ('gt_inst', ctypes.c_int32),
+              ('est_inst', ctypes.c_int32), ('x0', ctypes.c_int32), ('y0', ctypes.c_int32),
+              ('x1', ctypes.c_int32), ('y1', ctypes.c_int32), ('reserved0', ctypes.c_int32),
+              ('fx', ctypes.c_double), ('fy', ctypes.c_double),
+              ('cx', ctypes.c_double), ('cy', ctypes.c_double),
+              ('diameter', ctypes.c_double)]
+
+
 class FitParams(ctypes.Structure):
   _fields_ = [
       ('threshold', ctypes.c_double),
@@ -355,6 +364,12 @@ SYMBOLS = {
     'epos_pose_error_adi_tile': (ctypes.c_int, []),
     'epos_pose_errors_f64': (ctypes.c_int, [
         vp, ctypes.c_int64, vp, ctypes.c_int64, vp, vp, ctypes.c_int, ctypes.c_int, vp, vp]),
+    # VSD
+    'epos_vsd_max_taus': (ctypes.c_int, []),
+    'epos_vsd_row_bands': (ctypes.c_int, []),
+    'epos_vsd_counts': (ctypes.c_int, [
+        vp, ctypes.c_int, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp, ctypes.c_int,
+        ctypes.c_double, vp, ctypes.c_int, vp, vp]),
 }
 
 _lib = None

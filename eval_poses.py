@@ -1,9 +1,12 @@
 #!/usr/bin/env python
-"""Scores the poses ``infer.py`` estimated -- MSSD, MSPD and ADD(-S) recalls on MI355X.
+"""Scores the poses ``infer.py`` estimated -- MSSD, MSPD, ADD(-S) and, with --vsd, VSD recalls
+and BOP's AR on MI355X.
 
     python eval_poses.py --model=<model_name> --dataset <d>
         (--infer_tfrecord_names a,b | --frames <dir>)
         [--infer_name N | --result_path file.csv] [--adi true|false]
+        [--vsd true --depth_split test [--vsd_delta 15] [--vsd_max_instances N]]
+        [--min_visib_fract 0.1]
 
 The reference has no such script: it leaves pose scoring to ``bop_toolkit``, an empty submodule
 there. Environment as for ``eval.py``: TF_DATA_PATH / TF_MODELS_PATH / BOP_PATH, and
@@ -26,7 +29,26 @@ there. Environment as for ``eval.py``: TF_DATA_PATH / TF_MODELS_PATH / BOP_PATH,
     pose_errors[_<infer_name>].csv, one row per (estimate, ground truth) pair.
 
 ``mean_ar_mssd_mspd`` is the mean of AR_MSSD and AR_MSPD; it is not BOP's AR, which also
-averages AR_VSD (VSD needs the test depth images, which the TFRecords do not carry).
+averages AR_VSD.
+
+--vsd true adds VSD (epos_amd/vsd.py, include/epos_hip.h "VSD"): the ground truth and the
+estimate of every pair are rendered on the device, compared with the test depth image, and
+``ar_vsd`` (mean recall over 10 taus x 10 thresholds) and ``ar`` = (ar_vsd + ar_mssd +
+ar_mspd) / 3 are reported next to the figures above, which stay. The test depth comes from
+  * --depth_split <split>: <BOP_PATH>/<dataset>/<split>/<scene:06d>/depth/<im:06d>.png with
+    the scene's scene_camera.json (cam_K, depth_scale), at the dataset's native resolution --
+    a pose is metric, so the crop or resize the network saw does not matter. This is the route
+    for TFRecord frames. Parity unpinned vs a real BOP folder (none was available);
+  * --frames <dir>: the ``depth_path`` (relative to <dir>; 16-bit PNG or .npy) and
+    ``depth_scale`` (default 1) of a frames.json entry, in the frame's own geometry and K.
+A frame without depth is an error, not a skip. --min_visib_fract F > 0 (needs a depth source
+too) first measures the visible fraction of every ground-truth instance and drops those below F
+from the targets -- BOP's "visible by at least 10 %" rule as an opt-in.
+Unpinned, as for the other errors: the VSD values are this build's definitions after the
+published formulas, not bop_toolkit's numbers; the ray of a pixel goes through x + .5, the
+sample point of this build's renderer, not necessarily bop_toolkit's; and
+test_targets_bop19.json is still not applied, so ``ar`` is BOP's formula over this script's
+targets.
 """
 import argparse
 import json
@@ -61,6 +83,17 @@ def build_parser():
   a('--adi', type=infer.str2bool, default=True,
     help='compute ADI (O(vertices^2) per pair); false: ADD(-S) recall uses ADD only for '
          'objects without symmetries and is left out for the others')
+  a('--vsd', type=infer.str2bool, default=False,
+    help='also score VSD and report ar_vsd and ar (needs --depth_split, or depth_path entries '
+         'in <frames>/frames.json)')
+  a('--depth_split', default=None,
+    help='read the test depth from <BOP_PATH>/<dataset>/<split>/<scene:06d>/depth/ and the '
+         'camera from that scene\'s scene_camera.json')
+  a('--vsd_delta', type=float, default=15.0, help='visibility tolerance in mm')
+  a('--min_visib_fract', type=float, default=0.0,
+    help='> 0: ground-truth instances visible by less than this fraction are no targets')
+  a('--vsd_max_instances', type=int, default=None,
+    help='instances rendered per chunk (default: from the image size and a 1 GiB workspace)')
   return ap
 
 
@@ -76,6 +109,12 @@ def prepare(argv=None):
     raise ValueError('eval_poses.py needs --dataset and $BOP_PATH (models_eval)')
   if not (args.infer_tfrecord_names or args.frames):
     raise ValueError('No input files: give --infer_tfrecord_names or --frames <dir>.')
+  if not 0.0 <= args.min_visib_fract <= 1.0:
+    raise ValueError('--min_visib_fract must be in 0..1')
+  if (args.vsd or args.min_visib_fract > 0) and not (args.depth_split or args.frames):
+    raise ValueError('eval_poses.py: {} needs the test depth images: give --depth_split <split> '
+                     '(read from $BOP_PATH) or --frames <dir> with depth_path entries'.format(
+                         '--vsd' if args.vsd else '--min_visib_fract'))
   return args, model_dir
 
 
@@ -109,25 +148,103 @@ def result_path(args, model_dir):
   return os.path.join(model_dir, 'infer', 'estimated-poses{}.csv'.format(suffix))
 
 
-def build_groups(frames, results):
+class DepthFrames(object):
+  """The (depth_mm f32 [h,w], K) of every frame, read on demand (the last `keep` stay in
+  memory: the VSD chunks walk the frames in order)."""
+
+  def __init__(self, sources, keep=256):
+    self.sources, self.keep = sources, keep
+    self._cache = {}
+
+  def __len__(self):
+    return len(self.sources)
+
+  def __getitem__(self, i):
+    if i not in self._cache:
+      from epos_amd import bop_io
+      path, scale, K = self.sources[i]
+      while len(self._cache) >= self.keep:
+        self._cache.pop(next(iter(self._cache)))
+      self._cache[i] = (bop_io.load_depth(path, scale), K)
+    return self._cache[i]
+
+
+def depth_sources(args, frames):
+  """Per frame (path, depth_scale, K) of its test depth image; a frame without one is an
+  error that names it."""
+  from epos_amd import bop_io
+  out = []
+  if args.depth_split:
+    cams = {}
+    bop = os.environ['BOP_PATH']
+    for f in frames:
+      if f.scene_id not in cams:
+        cam_path = bop_io.scene_camera_path(bop, args.dataset, args.depth_split, f.scene_id)
+        if not os.path.exists(cam_path):
+          raise ValueError('no scene_camera.json for scene {} at {}'.format(f.scene_id, cam_path))
+        cams[f.scene_id] = bop_io.load_scene_camera(cam_path)
+      path = bop_io.depth_path(bop, args.dataset, args.depth_split, f.scene_id, f.im_id)
+      if f.im_id not in cams[f.scene_id] or not os.path.exists(path):
+        raise ValueError('frame scene {} image {} has no test depth ({}, or its entry in '
+                         'scene_camera.json)'.format(f.scene_id, f.im_id, path))
+      cam = cams[f.scene_id][f.im_id]
+      out.append((path, cam['depth_scale'], cam['cam_K']))
+    return out
+  with open(os.path.join(args.frames, 'frames.json')) as fh:
+    meta = json.load(fh)
+  for f, m in zip(frames, meta):
+    path = os.path.join(args.frames, m['depth_path']) if m.get('depth_path') else None
+    if path is None or not os.path.exists(path):
+      raise ValueError('frame scene {} image {} has no test depth (frames.json entry without '
+                       'depth_path, or the file is missing: {})'.format(
+                           f.scene_id, f.im_id, path))
+    out.append((path, float(m.get('depth_scale', 1.0)), f.K))
+  return out
+
+
+def build_groups(frames, results, dropped=None):
   """One group per (frame, target object): the n best-scored estimates (n = the instance count;
   ties keep file order) and the object's ground-truth poses. Returns (groups, ignored): the
-  estimates of images or objects that are no target."""
+  estimates of images or objects that are no target. dropped: {(frame index, obj_id): indices
+  into that object's ground-truth poses} that are no targets (--min_visib_fract); the instance
+  count shrinks with them."""
   by_key = {}
   for r in results:
     by_key.setdefault((r['scene_id'], r['im_id'], r['obj_id']), []).append(r)
   groups, used = [], 0
-  for f in frames:
+  for fi, f in enumerate(frames):
     for o in sorted(f.targets):
       n_inst = f.targets[o]
+      gone = (dropped or {}).get((fi, int(o)), ())
+      if n_inst >= 0:
+        n_inst = max(0, n_inst - len(gone))
       ests = by_key.get((f.scene_id, f.im_id, o), [])
       order = np.argsort(-np.array([e['score'] for e in ests], np.float64), kind='stable')
       if n_inst >= 0:
         order = order[:n_inst]
       used += len(order)
-      groups.append({'frame': f, 'obj_id': int(o), 'ests': [ests[i] for i in order],
-                     'gts': [p for p in f.gt_poses if p['obj_id'] == o]})
+      gts = [p for p in f.gt_poses if p['obj_id'] == o]
+      groups.append({'frame': f, 'frame_index': fi, 'obj_id': int(o),
+                     'ests': [ests[i] for i in order],
+                     'gts': [p for k, p in enumerate(gts) if k not in gone]})
   return groups, len(results) - used
+
+
+def invisible_targets(groups, vsd_eval, depth, args):
+  """The ground-truth-only pass of --min_visib_fract: {(frame index, obj_id): indices of the
+  ground truths whose visible fraction is below the bound}."""
+  queries, owner = [], []
+  for g in groups:
+    for ti, t in enumerate(g['gts']):
+      queries.append({'frame': g['frame_index'], 'obj_id': g['obj_id'], 'R_g': t['R'],
+                      't_g': t['t'], 'R_e': None, 't_e': None})
+      owner.append((g['frame_index'], g['obj_id'], ti))
+  _, fract = vsd_eval.errors(depth, queries, delta=args.vsd_delta)
+  dropped = {}
+  for (fi, o, ti), v in zip(owner, fract):
+    if v < args.min_visib_fract:
+      dropped.setdefault((fi, o), set()).add(ti)
+  return dropped
 
 
 def main(argv=None):
@@ -139,6 +256,9 @@ def main(argv=None):
   if any(f.gt_poses is None for f in frames):
     raise ValueError('eval_poses.py: input without ground-truth poses cannot be scored '
                      '(frames.json entries need gt_poses)')
+  # a frame without test depth is refused before anything touches a device
+  use_depth = args.vsd or args.min_visib_fract > 0
+  depth = DepthFrames(depth_sources(args, frames)) if use_depth else None
   path = result_path(args, model_dir)
   if not os.path.exists(path):
     raise ValueError('no pose estimates at {} (run infer.py first)'.format(path))
@@ -151,6 +271,14 @@ def main(argv=None):
   models = ply.load_models(bop, args.dataset, 'eval', obj_ids=obj_ids)
   dev = 'cuda:%d' % int(os.environ.get('EPOS_FORCE_DEVICE', 0))
   ev = pose_error.PoseErrorEval(models, info, dev)
+  vsd_eval = n_dropped = None
+  if use_depth:
+    from epos_amd import vsd
+    vsd_eval = vsd.VsdEval(models, info, dev, max_instances=args.vsd_max_instances)
+  if args.min_visib_fract > 0:
+    dropped = invisible_targets(groups, vsd_eval, depth, args)
+    n_dropped = sum(len(v) for v in dropped.values())
+    groups, ignored = build_groups(frames, results, dropped)
 
   pairs, owner = [], []
   for gi, g in enumerate(groups):
@@ -161,6 +289,11 @@ def main(argv=None):
         owner.append((gi, ei, ti))
   err = ev.errors(pairs, want_adi=args.adi)
   non_finite = int(np.isinf(err[:, 5]).sum()) if len(err) else 0
+  if args.vsd:
+    vsd_err, gt_visib = vsd_eval.errors(
+        depth, [{'frame': groups[gi]['frame_index'], 'obj_id': p['obj_id'], 'R_g': p['R_g'],
+                 't_g': p['t_g'], 'R_e': p['R_e'], 't_e': p['t_e']}
+                for p, (gi, _, _) in zip(pairs, owner)], delta=args.vsd_delta)
 
   for g in groups:
     g['errors'] = np.zeros((len(g['ests']), len(g['gts']), 6))
@@ -179,6 +312,16 @@ def main(argv=None):
         r['add_s_recall'] = None
     if any(n_syms[o] > 1 for o in obj_ids):
       rec['overall']['add_s_recall'] = None
+  if args.vsd:
+    for g in groups:
+      g['vsd'] = np.ones((len(g['ests']), len(g['gts']), len(vsd.VSD_TAUS)))
+    for (gi, ei, ti), row in zip(owner, vsd_err):
+      groups[gi]['vsd'][ei, ti] = row
+    rec_vsd = vsd.recalls_vsd(groups)
+    for r, rv in [(rec['overall'], rec_vsd['overall'])] + [
+        (rec['per_object'][o], rec_vsd['per_object'][o]) for o in rec['per_object']]:
+      r['recall_vsd'], r['ar_vsd'] = rv['recall_vsd'], rv['ar_vsd']
+      r['ar'] = vsd.ar(rv['ar_vsd'], r['ar_mssd'], r['ar_mspd'])
 
   eval_dir = os.path.join(model_dir, 'eval')
   os.makedirs(eval_dir, exist_ok=True)
@@ -200,14 +343,25 @@ def main(argv=None):
       'per_object': {str(o): r for o, r in rec['per_object'].items()},
       'overall': rec['overall'],
   }
+  if args.vsd:
+    scores['thresholds']['vsd_taus'] = list(vsd.VSD_TAUS)
+    scores['thresholds']['vsd_thresholds'] = list(vsd.VSD_THRESHOLDS)
+    scores['vsd_delta'] = args.vsd_delta
+  if n_dropped is not None:
+    scores['min_visib_fract'] = args.min_visib_fract
+    scores['counts']['targets_dropped_by_visibility'] = n_dropped
   scores_path = os.path.join(eval_dir, 'pose_scores{}.json'.format(suffix))
   with open(scores_path, 'w') as f:
     json.dump(scores, f, indent=1)
   with open(os.path.join(eval_dir, 'pose_errors{}.csv'.format(suffix)), 'w') as f:
     f.write('scene_id,im_id,obj_id,est_rank,gt_index,score,' +
-            ','.join(pose_error.ERROR_NAMES) + '\n')
-    for (gi, ei, ti), row in zip(owner, err):
+            ','.join(pose_error.ERROR_NAMES) + (
+                ',' + ','.join('vsd_%.2f' % t for t in vsd.VSD_TAUS) + ',gt_visib_fract'
+                if args.vsd else '') + '\n')
+    for k, ((gi, ei, ti), row) in enumerate(zip(owner, err)):
       g = groups[gi]
+      if args.vsd:
+        row = list(row) + list(vsd_err[k]) + [gt_visib[k]]
       f.write('{},{},{},{},{},{},{}\n'.format(
           g['frame'].scene_id, g['frame'].im_id, g['obj_id'], ei, ti, g['scores'][ei],
           ','.join(repr(float(v)) for v in row)))
@@ -217,6 +371,9 @@ def main(argv=None):
             o['targets'], len(results) - ignored, o['ar_mssd'], o['ar_mspd'],
             o['mean_ar_mssd_mspd'],
             'n/a' if o['add_s_recall'] is None else '{:.4f}'.format(o['add_s_recall'])))
+  if args.vsd:
+    print('eval_poses: AR_VSD={:.4f}, AR={:.4f} (this build\'s definitions; '
+          'test_targets_bop19.json is not applied)'.format(o['ar_vsd'], o['ar']))
   print('Saved pose scores to: {}'.format(scores_path))
   return scores
 

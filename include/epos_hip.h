@@ -970,6 +970,70 @@ int epos_pose_errors_f64(const double* verts, int64_t n_verts_total, const doubl
                          EposPosePair* pairs_dev, int n_pairs, int want_adi, double* err,
                          void* stream);
 
+/* ------------------------------------------------------------------------- *
+ * VSD (csrc/vsd.hip; added without an ABI version change: nothing existing moved). The
+ * pixel counts of BOP'19's Visible Surface Discrepancy for (ground truth, estimate) pairs,
+ * from a test depth image and the depth renderings of the two poses (epos_render_*: camera z
+ * in mm, 0 = background). The launcher only enqueues on `stream`: no host synchronisation,
+ * no allocation. tests/helpers/vsd_ref.py restates every rule below in element-wise numpy;
+ * the kernel equals it exactly.
+ *
+ * These are THIS BUILD'S DEFINITIONS. They follow the published BOP'19 formulas (Hodan et
+ * al., "BOP Challenge 2020 on 6D Object Localization", section 2.2, and "On Evaluation of 6D
+ * Object Pose Estimation", 2016, for the visibility masks), but bop_toolkit is not available
+ * to compare with: parity with its numbers is unpinned. In particular the ray of a pixel goes
+ * through x + .5, y + .5, the sample point of this build's renderer, which is not necessarily
+ * bop_toolkit's.
+ *
+ * Per pixel (x, y) of the pair's window, fp64 throughout, built from + - * / sqrt only, no
+ * FMA, in this order:
+ *   zt = depth_test[image,y,x]; missing = !(zt > 0)       (0, negative, NaN: no measurement)
+ *   zg = depth_model[gt_inst,y,x]; ze = est_inst < 0 ? 0 : depth_model[est_inst,y,x]
+ *   rx = ((x + 0.5) - cx) / fx; ry = ((y + 0.5) - cy) / fy; s = sqrt((rx*rx + ry*ry) + 1.0)
+ *   dt = zt * s; dg = zg * s; de = ze * s                 (distances along the pixel's ray)
+ *   mask_g = zg > 0; mask_e = ze > 0
+ *   vis_g = mask_g && (missing || dg - dt <= delta)       ('bop19' rule: missing depth is
+ *                                                          visible)
+ *   vis_e = mask_e && (missing || de - dt <= delta || vis_g)
+ *   inter = vis_g && vis_e; uni = vis_g || vis_e
+ *   for inter pixels: d = fabs(dg - de) / diameter; ge[k] += (d >= taus[k])
+ * counts row = [#mask_g, #vis_g, #mask_e, #vis_e, #inter, #uni, ge[0..n_taus-1]].
+ * The host turns a row into VSD(tau_k) = (ge[k] + (#uni - #inter)) / #uni (1 where #uni = 0)
+ * and the visible fraction #vis_g / #mask_g (epos_amd/vsd.py). Every output is an integer
+ * count: a result is a function of the input alone, never of the launch shape, of
+ * epos_vsd_row_bands() or of the order in which partial sums arrive.
+ * ------------------------------------------------------------------------- */
+typedef struct EposVsdPair {
+  int32_t image;      /* index into depth_test */
+  int32_t gt_inst;    /* index into depth_model */
+  int32_t est_inst;   /* index into depth_model, or -1: no estimate (an all-background image) */
+  int32_t x0, y0, x1, y1;   /* pixel window, x0 <= x < x1, y0 <= y < y1 */
+  int32_t reserved0;
+  double fx, fy, cx, cy;
+  double diameter;    /* mm, > 0 */
+} EposVsdPair;          /* 72 bytes */
+/* The most taus one call takes (16), and the number of rows of a window that are walked side
+ * by side (workgroups per pair x wavefronts per workgroup; row r of a window belongs to
+ * wavefront r mod this). The results depend on neither. */
+int epos_vsd_max_taus(void);
+int epos_vsd_row_bands(void);
+/* depth_test f32 [n_images,h,w], depth_model f32 [n_inst,h,w], pairs_dev [n_pairs], counts i64
+ * [n_pairs, 6 + n_taus]: all [device]. pairs [n_pairs] and taus [n_taus] are HOST arrays: the
+ * table is checked here and copied into pairs_dev on the stream, so it stays alive and
+ * unchanged until the stream has passed this call (pinned memory keeps the copy asynchronous);
+ * taus is read before the call returns. Every counter of every pair is WRITTEN: the launcher
+ * clears them on the stream before the kernel adds into them. Pixels outside a pair's window
+ * are not looked at, so a window must contain both renderings (epos_amd/vsd.py: window).
+ * Refused with EPOS_E_INVALID before the copy and the first launch: image outside
+ * [0, n_images), gt_inst outside [0, n_inst), est_inst outside [0, n_inst) and not -1, a
+ * window not inside [0, w] x [0, h] or with x1 < x0 or y1 < y0, a diameter that is not finite
+ * and > 0, fx or fy zero or not finite, n_taus outside 1..epos_vsd_max_taus(), a non-finite
+ * delta, n_pairs < 0, n_inst * h * w >= 2^31, a null pointer. n_pairs == 0 does nothing and
+ * returns 0. */
+int epos_vsd_counts(const float* depth_test, int n_images, const float* depth_model, int n_inst,
+                    int h, int w, const EposVsdPair* pairs, EposVsdPair* pairs_dev, int n_pairs,
+                    double delta, const double* taus, int n_taus, int64_t* counts, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
