@@ -190,22 +190,21 @@ def relabels_background(dataset_name, image_path):
   return dataset_name == 'tless' and 'tless/train_primesense' in (image_path or '')
 
 
-def gt_maps_device(renderer, frame, output_size, frag_pool, dataset_name=None, input_size=None,
-                   ignore_label=255):
-  """The ground-truth maps of one frame, left on the device: (obj_label, frag_label), i32
-  [oh,ow] each, at output_size = (ow, oh) -- render_instances + gt_fields_device with the
-  output camera, from the instance masks when the frame carries them (by nearest depth
-  otherwise). Ground-truth instances of objects the renderer or the fragment pool do not hold
-  are left out. frag_pool: (centers [O,F,3], sizes [O,F]) of render.pool_fragments.
-  input_size = (w, h) of the frame's pixels (default: four times the output, the decoder
-  stride)."""
-  import torch
+def gt_fields_device(renderer, frame, output_size, frag_pool, counts, input_size=None,
+                     allow_empty=True):
+  """render.gt_fields of one frame's ground truth at output_size = (ow, oh), with the output
+  camera, from the instance masks when the frame carries them (by nearest depth otherwise).
+  Only the instances whose object the renderer holds and for which counts(obj_id) is true
+  take part. frag_pool: (centers [O,F,3], sizes [O,F]) of render.pool_fragments. input_size =
+  (w, h) of the frame's pixels (default: four times the output, the decoder stride). Without
+  such an instance the fields are those of an empty scene, or None with allow_empty=False."""
   from epos_amd import render
   centers, sizes = frag_pool
-  O = sizes.shape[0]
   gi = [i for i, p in enumerate(frame.gt_poses or [])
-        if renderer.has_object(p['obj_id']) and 1 <= p['obj_id'] <= O]
+        if renderer.has_object(p['obj_id']) and counts(p['obj_id'])]
   gt = [frame.gt_poses[i] for i in gi]
+  if not gt and not allow_empty:
+    return None
   ow, oh = output_size
   if input_size is None:
     input_size = (4 * ow, 4 * oh)
@@ -215,11 +214,22 @@ def gt_maps_device(renderer, frame, output_size, frag_pool, dataset_name=None, i
       raise ValueError('frame %s/%s: %d instance masks for %d ground-truth poses' % (
           frame.scene_id, frame.im_id, len(masks), len(frame.gt_poses)))
     masks = masks[gi]
-  f = render.gt_fields(
+  return render.gt_fields(
       renderer, output_K(frame.K, input_size, output_size), [p['obj_id'] for p in gt],
       np.stack([p['R'] for p in gt]) if gt else np.zeros((0, 3, 3)),
       np.stack([np.asarray(p['t']).reshape(3) for p in gt]) if gt else np.zeros((0, 3)),
       (ow, oh), centers, sizes, masks)
+
+
+def gt_maps_device(renderer, frame, output_size, frag_pool, dataset_name=None, input_size=None,
+                   ignore_label=255):
+  """The ground-truth maps of one frame, left on the device: (obj_label, frag_label), i32
+  [oh,ow] each, at output_size = (ow, oh) -- gt_fields_device over the instances of the
+  objects 1..O of the fragment pool, plus the background rule of relabels_background."""
+  import torch
+  O = frag_pool[1].shape[0]
+  f = gt_fields_device(renderer, frame, output_size, frag_pool, lambda o: 1 <= o <= O,
+                       input_size)
   obj_label = f['obj_label']
   if relabels_background(dataset_name, frame.image_path):
     obj_label = torch.where(obj_label == 0, torch.full_like(obj_label, int(ignore_label)),

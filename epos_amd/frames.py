@@ -182,18 +182,21 @@ def _gt_poses_of(entry):
            't': np.asarray(p['t'], np.float64).reshape(3, 1)} for p in entry['gt_poses']]
 
 
-def frames_from_dir(directory, meta, h, w):
-  """--frames <dir>: frames.json entries + images (.npy HxWx3 or anything PIL reads)."""
+def frames_from_dir(directory, meta, h, w, pixels=True):
+  """--frames <dir>: frames.json entries + images (.npy HxWx3 or anything PIL reads).
+  pixels=False: metadata only -- no image file is opened, an entry needs no ``path`` and the
+  frames have no loader."""
   out = []
   for m in meta:
-    path = os.path.join(directory, m['path'])
-    dtype = np.uint8
-    if path.endswith('.npy'):
-      dtype = np.uint8 if np.load(path, mmap_mode='r').dtype == np.uint8 else np.float32
+    path, loader, dtype = m.get('path', ''), None, np.uint8
+    if pixels:
+      path = os.path.join(directory, m['path'])
+      if path.endswith('.npy'):
+        dtype = np.uint8 if np.load(path, mmap_mode='r').dtype == np.uint8 else np.float32
+      loader = _Loader('file', path, h, w)
     out.append(Frame(m.get('scene_id', 0), m['im_id'], m['K'],
                      {int(k): int(v) for k, v in m.get('targets', {}).items()},
-                     _Loader('file', path, h, w), _gt_poses_of(m), dtype=dtype,
-                     image_path=path))
+                     loader, _gt_poses_of(m), dtype=dtype, image_path=path))
   return out
 
 

@@ -122,18 +122,17 @@ class VsdEval(object):
 
   def __init__(self, models, models_info, device=None, max_instances=None):
     import torch
-    from epos_amd import render
+    from epos_amd import cli
     if not torch.cuda.is_available():
       raise EposError('VSD needs a HIP device (there is no CPU fallback)')
     self.lib = _lib.load()
-    self.renderer = render.Renderer(device)
+    self.renderer = cli.eval_renderer(models, device)
     self.device = self.renderer.device
     if max_instances is not None and int(max_instances) < 2:
       raise ValueError('max_instances must be >= 2 (a ground truth and its estimate)')
     self.max_instances = None if max_instances is None else int(max_instances)
     self.corners, self.diameters = {}, {}
     for o in sorted(models):
-      self.renderer.add_model(o, models[o])
       self.corners[o] = bbox_corners(models[o]['pts'])
       if 'diameter' in models_info.get(o, {}):
         self.diameters[o] = float(models_info[o]['diameter'])

@@ -27,7 +27,6 @@ dense heads; each batch's forward pass, ground-truth maps and table update are e
 stream and nothing is downloaded before the tables are written.
 """
 import argparse
-import collections
 import json
 import os
 import sys
@@ -39,32 +38,23 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 if ROOT not in sys.path:
   sys.path.insert(0, ROOT)
 
-import infer           # noqa: E402
-from epos_amd import eval_utils   # noqa: E402
-
-# flags of infer.py's parser this script shares: the model flags of epos_lib/common.py and this
-# build's input / precision options
-_SHARED_FLAGS = (
-    'model', 'master', 'checkpoint_name', 'dataset', 'num_frags', 'model_variant',
-    'atrous_rates', 'encoder_output_stride', 'decoder_output_stride', 'upsample_logits',
-    'frag_cls_agnostic', 'frag_loc_agnostic', 'multi_grid', 'logits_kernel_size',
-    'image_pyramid', 'add_image_level_feature', 'image_pooling_stride', 'aspp_with_batch_norm',
-    'aspp_with_separable_conv', 'depth_multiplier', 'divisible_by',
-    'decoder_use_separable_conv', 'merge_method', 'prediction_with_upsampled_logits',
-    'use_bounded_activation', 'multi_scale_inference', 'precision', 'frames', 'synthetic',
-    'num_objs', 'seed', 'decode_threads', 'prefetch')
+from epos_amd import cli, eval_utils   # noqa: E402
 
 
 def build_parser():
   ap = argparse.ArgumentParser(description=__doc__,
                                formatter_class=argparse.RawTextHelpFormatter)
-  for act in infer.build_parser()._actions:
-    if act.dest in _SHARED_FLAGS:
-      kw = dict(default=act.default, type=act.type, help=act.help, required=act.required)
-      if act.choices is not None:
-        kw['choices'] = act.choices
-      ap.add_argument(*act.option_strings, **kw)
   a = ap.add_argument
+  # the model flags of epos_lib/common.py and this build's input / precision options, as
+  # infer.py defines them
+  cli.add_model_name_flags(ap)
+  a('--checkpoint_name', default=None)
+  cli.add_precision_flags(ap)
+  cli.add_dataset_flags(ap)
+  cli.add_network_flags(ap)
+  cli.add_input_flags(ap)
+  a('--seed', type=int, default=0)
+  cli.add_decode_flags(ap)
   # scripts/eval.py:34-48
   a('--eval_max_height_before_crop', type=int, default=480)
   a('--eval_crop_size', default='640,480')
@@ -82,23 +72,14 @@ def build_parser():
 def prepare(argv=None):
   """Parses the command line, applies params.yml and refuses what this build cannot run."""
   args = build_parser().parse_args(argv)
-  model_dir = os.path.join(os.environ.get('TF_MODELS_PATH', '.'), args.model)
-  infer.update_flags(args, os.path.join(model_dir, infer.PARAMS_FILENAME))   # eval.py:59
-  infer.check_supported_flags(args)
+  model_dir = cli.model_dir(args)
+  cli.update_flags(args, os.path.join(model_dir, cli.PARAMS_FILENAME))   # eval.py:59
+  cli.check_supported_flags(args)
   if not (args.dataset and os.environ.get('BOP_PATH')):
     raise ValueError('eval.py needs --dataset and $BOP_PATH (object models)')
   if args.batch_size < 1:
     raise ValueError('--batch_size must be >= 1')
   return args, model_dir
-
-
-def _frames_args(args):
-  """The namespace infer.load_frames reads, with the eval_* flags under its names."""
-  ns = argparse.Namespace(**vars(args))
-  ns.infer_crop_size = args.eval_crop_size
-  ns.infer_tfrecord_names = args.eval_tfrecord_names
-  ns.infer_max_height_before_crop = args.eval_max_height_before_crop
-  return ns
 
 
 def read_global_step(checkpoint_path):
@@ -113,15 +94,15 @@ def read_global_step(checkpoint_path):
 def main(argv=None):
   args, model_dir = prepare(argv)
   import torch
-  from epos_amd import model, multiscale, ply, render, synthetic
+  from epos_amd import model, multiscale, ply, render
   from epos_amd import frames as eframes
   checkpoint_dir = os.path.join(model_dir, 'train')            # eval.py:65
   eval_dir = os.path.join(model_dir, 'eval')                   # eval.py:71-72
   os.makedirs(eval_dir, exist_ok=True)
-  dev_index = int(os.environ.get('EPOS_FORCE_DEVICE', 0))
+  dev_index = cli.device_from_env()
   dev = 'cuda:%d' % dev_index
   torch.cuda.set_device(dev_index)
-  ckpt, num_objs, checkpoint_path = infer.load_checkpoint(args, checkpoint_dir)
+  ckpt, num_objs, checkpoint_path = cli.load_checkpoint(args, checkpoint_dir)
 
   last_path = os.path.join(eval_dir, eval_utils.LAST_EVALUATION)
   last = open(last_path).read() if os.path.exists(last_path) else None
@@ -131,39 +112,26 @@ def main(argv=None):
     return None
   print('Evaluating on: {}'.format(args.eval_tfrecord_names))  # eval.py:94
 
-  store = infer.load_fragments(model_dir, args.num_frags)
-  if store is None and not args.synthetic:
-    store = infer.fragment_from_bop_models(model_dir, args, dev)
-  if store is None:
-    if not args.synthetic:
-      raise ValueError('fragments.pkl / fragments.npz not found in ' + model_dir +
-                       ' and no BOP models under $BOP_PATH/<dataset>/models*')
-    store = synthetic.ModelStore(num_objs, args.num_frags, seed=0)
+  store = cli.resolve_store(model_dir, args, num_objs, dev)
   obj_ids = [o for o in store.dp_model['obj_ids'] if 1 <= o <= num_objs]
-  frames, h, w = infer.load_frames(_frames_args(args), num_objs, 0, 1, obj_ids)
+  frames, h, w = cli.load_frames(
+      args.eval_tfrecord_names, args.frames, args.synthetic, args.eval_crop_size,
+      args.eval_max_height_before_crop, args.seed, num_objs, obj_ids=obj_ids)
   frag_labels = (bool(store.frag_centers) if args.eval_frag_labels is None
-                 else infer.str2bool(args.eval_frag_labels))
+                 else cli.str2bool(args.eval_frag_labels))
 
   # the renderer holds the 'eval' models, as --vis_renderer mesh of infer.py does
-  models = ply.load_models(os.environ['BOP_PATH'], args.dataset, 'eval', obj_ids=obj_ids)
-  renderer = render.Renderer(dev)
-  for o in sorted(models):
-    renderer.add_model(o, models[o])
+  renderer = cli.eval_renderer(
+      ply.load_models(os.environ['BOP_PATH'], args.dataset, 'eval', obj_ids=obj_ids), dev)
   if frag_labels:
     frag_pool = render.pool_fragments(store.frag_centers, store.frag_sizes, num_objs)
   else:
     frag_pool = (np.zeros((num_objs, 1, 3)), np.ones((num_objs, 1)))
 
   B = args.batch_size
-  pyramid = multiscale.normalize_pyramid(infer._as_list(args.image_pyramid, float) or None)
-  mo = model.ModelOptions(
-      model.get_outputs_to_num_channels(num_objs, args.num_frags), crop_size=(w, h),
-      atrous_rates=infer._as_list(args.atrous_rates, int),
-      encoder_output_stride=args.encoder_output_stride,
-      decoder_output_stride=infer._as_list(args.decoder_output_stride, int),
-      model_variant=args.model_variant, multi_grid=infer._as_list(args.multi_grid, int),
-      merge_method=args.merge_method if pyramid is not None else 'max')
-  net = model.get_net(ckpt, B, h, w, num_objs, args.num_frags, mo, dev,
+  pyramid = multiscale.normalize_pyramid(cli.as_list(args.image_pyramid, float) or None)
+  net = model.get_net(ckpt, B, h, w, num_objs, args.num_frags,
+                      cli.model_options(args, num_objs, w, h, pyramid), dev,
                       precision=args.precision, image_pyramid=pyramid)
   out_size = (net.out_w, net.out_h)
   ev = eval_utils.SegmentationEval(num_objs, ignore_label=255, device=dev,
@@ -176,13 +144,8 @@ def main(argv=None):
     torch.cuda.synchronize()
 
   time_start = time.time()
-  held = collections.deque()                     # (event behind the batch's work, i0)
-  for i0, chunk, imgs in feed:
-    # a staging buffer goes back to the decoders once the step that reads it has run
-    while held and (len(held) >= held_max or held[0][0].query()):
-      done, j0 = held.popleft()
-      done.synchronize()
-      feed.release(j0)
+  # a staging buffer goes back to the decoders once the step that reads it has run
+  for i0, chunk, imgs in cli.steps_released_in_order(feed, held_max):
     pred = net.forward(imgs, use_graph=True)
     n_real = len(frames[i0:i0 + B])
     maps = [eval_utils.gt_maps_device(renderer, f, out_size, frag_pool, args.dataset,
@@ -193,14 +156,8 @@ def main(argv=None):
                 pred['pred_frag_conf'][:n_real])
     else:
       ev.update(gt_obj, pred['pred_obj_label'][:n_real])
-    done = torch.cuda.Event()
-    done.record()
-    held.append((done, i0))
     if (i0 // B + 1) % 100 == 0:
       print('Evaluating batch {}'.format(i0 // B + 1))         # eval.py:197-205
-  torch.cuda.synchronize()
-  for _, j0 in held:
-    feed.release(j0)
   loop_s = time.time() - time_start
 
   metrics = ev.write(eval_dir, read_global_step(checkpoint_path))

@@ -61,7 +61,7 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 if ROOT not in sys.path:
   sys.path.insert(0, ROOT)
 
-import infer           # noqa: E402
+from epos_amd import cli   # noqa: E402
 
 
 def build_parser():
@@ -80,10 +80,10 @@ def build_parser():
   a('--seed', type=int, default=0)
   a('--result_path', default=None,
     help='the BOP\'19 CSV (default: <model>/infer/estimated-poses[_<infer_name>].csv)')
-  a('--adi', type=infer.str2bool, default=True,
+  a('--adi', type=cli.str2bool, default=True,
     help='compute ADI (O(vertices^2) per pair); false: ADD(-S) recall uses ADD only for '
          'objects without symmetries and is left out for the others')
-  a('--vsd', type=infer.str2bool, default=False,
+  a('--vsd', type=cli.str2bool, default=False,
     help='also score VSD and report ar_vsd and ar (needs --depth_split, or depth_path entries '
          'in <frames>/frames.json)')
   a('--depth_split', default=None,
@@ -100,8 +100,8 @@ def build_parser():
 def prepare(argv=None):
   """Parses the command line, applies params.yml and refuses what cannot be scored."""
   args = build_parser().parse_args(argv)
-  model_dir = os.path.join(os.environ.get('TF_MODELS_PATH', '.'), args.model)
-  infer.update_flags(args, os.path.join(model_dir, infer.PARAMS_FILENAME))
+  model_dir = cli.model_dir(args)
+  cli.update_flags(args, os.path.join(model_dir, cli.PARAMS_FILENAME))
   if args.synthetic:
     raise ValueError('eval_poses.py: --synthetic frames carry no ground-truth poses; give '
                      '--infer_tfrecord_names or --frames <dir> with gt_poses')
@@ -118,34 +118,11 @@ def prepare(argv=None):
   return args, model_dir
 
 
-def crop_size(args):
-  if isinstance(args.infer_crop_size, (list, tuple)):
-    return [int(x) for x in args.infer_crop_size[:2]]
-  return [int(x) for x in str(args.infer_crop_size).split(',')][:2]
-
-
-def frames_metadata(directory):
-  """frames.json -> Frames without pixels: no image file is opened."""
-  from epos_amd import frames as eframes
-  with open(os.path.join(directory, 'frames.json')) as f:
-    meta = json.load(f)
-  return [eframes.Frame(m.get('scene_id', 0), m['im_id'], m['K'],
-                        {int(k): int(v) for k, v in m.get('targets', {}).items()}, None,
-                        eframes._gt_poses_of(m), image_path=m.get('path', ''))
-          for m in meta]
-
-
-def load_frames(args, obj_ids):
-  if args.infer_tfrecord_names:
-    return infer.load_frames(args, len(obj_ids or ()), 0, 1, obj_ids)[0]
-  return frames_metadata(args.frames)
-
-
 def result_path(args, model_dir):
   if args.result_path:
     return args.result_path
-  suffix = '' if args.infer_name is None else '_' + args.infer_name
-  return os.path.join(model_dir, 'infer', 'estimated-poses{}.csv'.format(suffix))
+  return os.path.join(model_dir, 'infer',
+                      'estimated-poses{}.csv'.format(cli.result_suffix(args.infer_name)))
 
 
 class DepthFrames(object):
@@ -169,9 +146,10 @@ class DepthFrames(object):
     return self._cache[i]
 
 
-def depth_sources(args, frames):
+def depth_sources(args, frames, meta):
   """Per frame (path, depth_scale, K) of its test depth image; a frame without one is an
-  error that names it."""
+  error that names it. meta: the frames.json entries the frames were made from (not read with
+  --depth_split)."""
   from epos_amd import bop_io
   out = []
   if args.depth_split:
@@ -190,8 +168,6 @@ def depth_sources(args, frames):
       cam = cams[f.scene_id][f.im_id]
       out.append((path, cam['depth_scale'], cam['cam_K']))
     return out
-  with open(os.path.join(args.frames, 'frames.json')) as fh:
-    meta = json.load(fh)
   for f, m in zip(frames, meta):
     path = os.path.join(args.frames, m['depth_path']) if m.get('depth_path') else None
     if path is None or not os.path.exists(path):
@@ -250,7 +226,13 @@ def invisible_targets(groups, vsd_eval, depth, args):
 def main(argv=None):
   args, model_dir = prepare(argv)
   from epos_amd import bop_io, ply, pose_error
-  frames = load_frames(args, ply.BOP_OBJ_IDS.get(args.dataset))
+  # metadata only: no pixel is decoded, and a --frames directory needs no image files
+  meta = cli.read_frames_json(args.frames) if args.frames else None
+  obj_ids = ply.BOP_OBJ_IDS.get(args.dataset)
+  frames = cli.load_frames(
+      args.infer_tfrecord_names, args.frames, 0, args.infer_crop_size,
+      args.infer_max_height_before_crop, args.seed, len(obj_ids or ()), obj_ids=obj_ids,
+      pixels=False, meta=meta)[0]
   if not frames:
     raise ValueError('no frames to score')
   if any(f.gt_poses is None for f in frames):
@@ -258,7 +240,7 @@ def main(argv=None):
                      '(frames.json entries need gt_poses)')
   # a frame without test depth is refused before anything touches a device
   use_depth = args.vsd or args.min_visib_fract > 0
-  depth = DepthFrames(depth_sources(args, frames)) if use_depth else None
+  depth = DepthFrames(depth_sources(args, frames, meta)) if use_depth else None
   path = result_path(args, model_dir)
   if not os.path.exists(path):
     raise ValueError('no pose estimates at {} (run infer.py first)'.format(path))
@@ -269,7 +251,7 @@ def main(argv=None):
   obj_ids = sorted(set(g['obj_id'] for g in groups))
   info = pose_error.load_models_info(pose_error.models_info_path(bop, args.dataset, 'eval'))
   models = ply.load_models(bop, args.dataset, 'eval', obj_ids=obj_ids)
-  dev = 'cuda:%d' % int(os.environ.get('EPOS_FORCE_DEVICE', 0))
+  dev = 'cuda:%d' % cli.device_from_env()
   ev = pose_error.PoseErrorEval(models, info, dev)
   vsd_eval = n_dropped = None
   if use_depth:
@@ -301,7 +283,7 @@ def main(argv=None):
   for (gi, ei, ti), row in zip(owner, err):
     groups[gi]['errors'][ei, ti] = row
   n_syms = {o: ev.n_sym(o) for o in obj_ids}
-  width = crop_size(args)[0]
+  width = cli.crop_size(args.infer_crop_size)[0]
   missing = [o for o in obj_ids if o not in ev.diameters]
   if missing:
     raise ValueError('models_info.json gives no diameter for object(s) {}'.format(missing))
@@ -325,7 +307,7 @@ def main(argv=None):
 
   eval_dir = os.path.join(model_dir, 'eval')
   os.makedirs(eval_dir, exist_ok=True)
-  suffix = '' if args.infer_name is None else '_' + args.infer_name
+  suffix = cli.result_suffix(args.infer_name)
   scores = {
       'result_path': path, 'dataset': args.dataset, 'image_width': width, 'adi': bool(args.adi),
       'thresholds': {

@@ -32,12 +32,11 @@ instances. ``infer_crop_size`` is (width, height) as consumed by the reference
 (datagen.py:448-449), despite its help string.
 """
 import argparse
-import glob
-import json
+import collections
 import os
-import pickle
 import sys
 import time
+import types
 
 import numpy as np     # noqa: E402
 import torch           # noqa: E402
@@ -46,10 +45,8 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 if ROOT not in sys.path:
   sys.path.insert(0, ROOT)
 
-from epos_amd import bop_io, dist as edist, fitting, model, pipeline   # noqa: E402
-from epos_amd import multiscale, synthetic, weights                    # noqa: E402
-
-PARAMS_FILENAME = 'params.yml'   # common.py
+from epos_amd import bop_io, cli, dist as edist, eval_utils, fitting, pipeline   # noqa: E402
+from epos_amd import multiscale                                                  # noqa: E402
 
 
 # "all found" (num_instances = -1, detection) needs a bound for the static buffers
@@ -61,18 +58,13 @@ PARAMS_FILENAME = 'params.yml'   # common.py
 DETECTION_INSTANCE_CAP = 16
 
 
-def str2bool(v):
-  return str(v).lower() in ('1', 'true', 'yes', 'y')
-
-
 def build_parser():
   ap = argparse.ArgumentParser(description=__doc__,
                                formatter_class=argparse.RawTextHelpFormatter)
   a = ap.add_argument
+  str2bool = cli.str2bool
   # scripts/infer.py:37-120
-  a('--master', default='',
-    help='accepted and ignored (scripts/infer.py:38-40: BNS name of a TensorFlow master)')
-  a('--model', required=True)
+  cli.add_model_name_flags(ap)
   a('--cpu_only', type=str2bool, default=False)
   a('--task_type', default=pipeline.LOCALIZATION)
   a('--infer_tfrecord_names', default=None)
@@ -98,12 +90,7 @@ def build_parser():
   a('--max_correspondences', type=int, default=None)
   a('--max_instances_to_fit', type=int, default=None)
   a('--detection_instance_cap', type=int, default=DETECTION_INSTANCE_CAP)   # not in the reference
-  # not in the reference: run the --image_pyramid ("multi-scale mode"). Off by
-  # default: the same params.yml key configures multi-scale TRAINING, and S networks per frame
-  # are a cost to ask for.
-  a('--multi_scale_inference', type=str2bool, default=False)
-  # not in the reference: the network's numeric mode ("bf16 mode")
-  a('--precision', type=str, default='fp32', choices=['fp32', 'bf16'])
+  cli.add_precision_flags(ap)
   a('--max_fitting_iterations', type=int, default=400)
   a('--vis', type=str2bool, default=False)
   a('--vis_gt_poses', type=str2bool, default=True)           # infer.py:126-146
@@ -119,45 +106,15 @@ def build_parser():
          'object meshes are rendered on the device (epos_amd/render.py; needs --dataset and '
          '$BOP_PATH for the \'eval\' models): shaded pose overlays, the "gt obj labels" tile '
          'and --vis_gt_frag_fields for frames that carry gt_poses')
-  # epos_lib/common.py:60-154 (the model flags the hot path reads)
-  a('--dataset', default=None)
-  a('--num_frags', type=int, default=64)
+  cli.add_dataset_flags(ap)
   a('--min_visib_fract', type=float, default=0.1)
   a('--corr_min_obj_conf', type=float, default=0.1)
   a('--corr_min_frag_rel_conf', type=float, default=0.5)
   a('--corr_project_to_model', type=str2bool, default=False,
     help='accepted and ignored, as in the reference: common.py:78-80 defines the flag and '
          'nothing reads it (the projection switch that acts is --project_to_surface)')
-  a('--model_variant', default='xception_65',
-    help='backbone (feature.py:118-129): xception_41, xception_65, xception_71, '
-         'resnet_v1_50, resnet_v1_50_beta, resnet_v1_101, resnet_v1_101_beta')
-  a('--atrous_rates', default='12,24,36')
-  a('--encoder_output_stride', type=int, default=8)
-  a('--decoder_output_stride', default='4')
-  a('--upsample_logits', type=str2bool, default=False)
-  a('--frag_cls_agnostic', type=str2bool, default=False)
-  a('--frag_loc_agnostic', type=str2bool, default=False)
-  a('--multi_grid', default=None,
-    help='e.g. 1,2,4 for the resnet_v1_*_beta checkpoints (common.py:111-115)')
-  # common.py:96-154: known to the reference, supported here at their defaults only
-  # (check_supported_flags raises otherwise -- a params.yml must not be half-applied)
-  a('--logits_kernel_size', type=int, default=1)
-  a('--image_pyramid', default=None)
-  a('--add_image_level_feature', type=str2bool, default=True)
-  a('--image_pooling_stride', default='1,1')
-  a('--aspp_with_batch_norm', type=str2bool, default=True)
-  a('--aspp_with_separable_conv', type=str2bool, default=True)
-  a('--depth_multiplier', type=float, default=1.0)
-  a('--divisible_by', type=int, default=None)
-  a('--decoder_use_separable_conv', type=str2bool, default=True)
-  a('--merge_method', default='max')
-  a('--prediction_with_upsampled_logits', type=str2bool, default=True)
-  a('--use_bounded_activation', type=str2bool, default=False)
-  # this build
-  a('--frames', default=None, help='directory with frames.json + images')
-  a('--synthetic', type=int, default=0, help='number of synthetic frames')
-  a('--num_objs', type=int, default=None,
-    help='object channels (default: from the checkpoint)')
+  cli.add_network_flags(ap)
+  cli.add_input_flags(ap)
   a('--batch', type=int, default=1, help='images per GPU per step')
   a('--seed', type=int, default=0)
   a('--pipeline_depth', type=int, default=0,
@@ -189,83 +146,8 @@ def build_parser():
          '(closest points through a mesh index, on the device; sparse heads, several steps in '
          'flight) -- the same poses as the default, operator-by-operator route of that flag, '
          'which stays the default.')
-  a('--decode_threads', type=int, default=0,
-    help='decoder processes working ahead of the GPU (0 = min(8, cores - 2); '
-         'EPOS_DECODE_PROCS=0 makes them in-process threads)')
-  a('--prefetch', type=int, default=6, help='batches decoded ahead of the GPU')
+  cli.add_decode_flags(ap)
   return ap
-
-
-def update_flags(args, params_path):
-  """common.py:157-177: YAML values override flag DEFAULTS."""
-  if not os.path.exists(params_path):
-    return
-  if os.path.basename(params_path).split('.')[1] not in ['yml', 'yaml']:
-    raise ValueError('Only YAML format is currently supported.')
-  import yaml
-  with open(params_path, 'r') as f:
-    params = yaml.safe_load(f) or {}
-  for name, val in params.items():
-    if hasattr(args, name):
-      setattr(args, name, val)
-
-
-def _as_list(v, cast):
-  if v is None:
-    return None
-  if isinstance(v, (list, tuple)):
-    return [cast(x) for x in v]
-  return [cast(x) for x in str(v).strip('[]()').split(',') if str(x).strip()]
-
-
-# Flags of common.py:60-154 the network plan implements at ONE value only. A model
-# trained with another value has a different graph (other layers, other head layout),
-# so running it through this plan would silently produce garbage: raise instead.
-_FIXED_FLAGS = [
-    ('upsample_logits', False, 'model.py:661-672: logits stay at the decoder stride'),
-    ('frag_cls_agnostic', False, 'common.py:198-202: per-object fragment heads only'),
-    ('frag_loc_agnostic', False, 'common.py:61-66: per-object fragment heads only'),
-    ('logits_kernel_size', 1, 'model.py:428-431'),
-    ('add_image_level_feature', True, 'model.py:217-226'),
-    ('aspp_with_batch_norm', True, 'model.py:187-199'),
-    ('aspp_with_separable_conv', True, 'model.py:243-256'),
-    ('decoder_use_separable_conv', True, 'model.py:369-392'),
-    ('use_bounded_activation', False, 'model.py:202,317: ReLU, not ReLU6'),
-    ('depth_multiplier', 1.0, 'MobileNet only'),
-    ('divisible_by', None, 'MobileNet only'),
-]
-
-
-def check_supported_flags(args):
-  """Raises NotImplementedError for a known common.py flag set (on the command line
-  or by params.yml) to a value this build's network plan does not implement."""
-  bad = []
-  for name, want, why in _FIXED_FLAGS:
-    got = getattr(args, name)
-    if isinstance(want, bool):
-      got = str2bool(got) if not isinstance(got, bool) else got
-    if got != want and not (want is None and got in (None, 'None', '')):
-      bad.append('%s=%r (supported: %r; %s)' % (name, getattr(args, name), want, why))
-  pyr = _as_list(args.image_pyramid, float)
-  if pyr not in (None, [], [1.0]):
-    if not str2bool(str(getattr(args, 'multi_scale_inference', False))):
-      bad.append('image_pyramid=%r (single scale unless --multi_scale_inference=true, '
-                 'model.py:545-546,597)' % (args.image_pyramid,))
-    else:
-      multiscale.normalize_pyramid(pyr)                       # ValueError if invalid
-      multiscale.check_merge_method(args.merge_method)
-  if _as_list(args.image_pooling_stride, int) not in ([1, 1],):
-    bad.append('image_pooling_stride=%r (supported: 1,1)' % (args.image_pooling_stride,))
-  if args.model_variant not in weights.VARIANTS:
-    bad.append('model_variant=%r (%s)' % (args.model_variant,
-                                         ', '.join(sorted(weights.VARIANTS))))
-  if int(args.encoder_output_stride) != 8:
-    bad.append('encoder_output_stride=%r (supported: 8)' % args.encoder_output_stride)
-  if _as_list(args.decoder_output_stride, int) != [4]:
-    bad.append('decoder_output_stride=%r (supported: 4)' % (args.decoder_output_stride,))
-  if bad:
-    raise NotImplementedError(
-        'flags outside what this build implements (common.py:60-154): ' + '; '.join(bad))
 
 
 def fitting_path(use_prosac, max_correspondences, project_to_surface, order_on_device,
@@ -288,7 +170,7 @@ def resolve_sparse_heads(args, needs_dense, pyramid):
   sh = str(args.sparse_heads).lower()
   if sh == 'auto':
     return args.task_type == pipeline.LOCALIZATION and not needs_dense and pyramid is None
-  sparse_heads = str2bool(sh)
+  sparse_heads = cli.str2bool(sh)
   if sparse_heads and pyramid is not None:
     raise ValueError('--sparse_heads=true is not available with --image_pyramid '
                      '(multi-scale heads are dense).')
@@ -298,135 +180,9 @@ def resolve_sparse_heads(args, needs_dense, pyramid):
   return sparse_heads
 
 
-def load_fragments(model_dir, num_frags):
-  """fragments.pkl (datagen.py:254-268) or fragments.npz."""
-  pkl = os.path.join(model_dir, 'fragments.pkl')
-  npz = os.path.join(model_dir, 'fragments.npz')
-  if os.path.exists(pkl):
-    with open(pkl, 'rb') as f:
-      fr = pickle.load(f)
-    centers, sizes = fr['frag_centers'], fr['frag_sizes']
-  elif os.path.exists(npz):
-    z = np.load(npz)
-    centers = {int(o): z['frag_centers'][i] for i, o in enumerate(z['obj_ids'])}
-    sizes = {int(o): z['frag_sizes'][i] for i, o in enumerate(z['obj_ids'])}
-  else:
-    return None
-  for o in centers:                                   # datagen.py:264-268
-    if centers[o].shape[0] != num_frags or sizes[o].shape[0] != num_frags:
-      raise ValueError('The loaded fragmentation is not valid.')
-  store = synthetic.ModelStore(0, num_frags)
-  store.dp_model = {'obj_ids': sorted(int(o) for o in centers)}
-  store.frag_centers = {int(o): np.asarray(v, np.float64) for o, v in centers.items()}
-  store.frag_sizes = {int(o): np.asarray(v, np.float64) for o, v in sizes.items()}
-  return store
-
-
-def fragment_from_bop_models(model_dir, args, dev):
-  """datagen.py:238-296: no fragments.pkl yet -> load the object models of the
-  dataset (<BOP_PATH>/<dataset>/models[_<type>]/obj_XXXXXX.ply; 'reconst' for T-LESS,
-  'dense' for ITODD, 'eval' for TUD-L, the original ones otherwise), fragment them by
-  furthest-point sampling on the GPU, save fragments.pkl next to params.yml."""
-  from epos_amd import fragment, ply
-  dataset = args.dataset
-  bop = os.environ.get('BOP_PATH')
-  if not dataset or not bop or dataset not in ply.BOP_OBJ_IDS:
-    return None
-  mtype = {'tless': 'reconst', 'itodd': 'dense', 'tudl': 'eval'}.get(dataset)
-  if not os.path.exists(ply.model_path(bop, dataset, ply.BOP_OBJ_IDS[dataset][0], mtype)):
-    return None
-  models = ply.load_models(bop, dataset, mtype)
-  centers, sizes = fragment.fragment_models(
-      {o: m['pts'] for o, m in models.items()}, args.num_frags, device=dev)
-  fragment.save_fragments(os.path.join(model_dir, 'fragments.pkl'), centers, sizes)
-  return load_fragments(model_dir, args.num_frags)
-
-
-def find_checkpoint(checkpoint_dir, name):
-  if name is not None:
-    path = os.path.join(checkpoint_dir, name)
-    if not path.endswith('.npz'):
-      path += '.npz'
-    return path
-  cands = sorted(glob.glob(os.path.join(checkpoint_dir, '*.npz')),
-                 key=os.path.getmtime)
-  return cands[-1] if cands else None
-
-
-def load_checkpoint(args, checkpoint_dir):
-  """(checkpoint dict, num_objs, path): the TensorFlow checkpoint of <model>/train (the latest
-  or --checkpoint_name, infer.py:670-674), else an .npz, else -- with --synthetic -- random
-  weights (path None)."""
-  ckpt_path = find_checkpoint(checkpoint_dir, args.checkpoint_name)
-  tf_prefix = None
-  if args.checkpoint_name is not None and os.path.exists(
-      os.path.join(checkpoint_dir, args.checkpoint_name + '.index')):
-    tf_prefix = os.path.join(checkpoint_dir, args.checkpoint_name)
-  elif not (ckpt_path and os.path.exists(ckpt_path)):
-    from epos_amd import tf_checkpoint
-    tf_prefix = tf_checkpoint.latest_checkpoint(checkpoint_dir)  # infer.py:670-674
-  if tf_prefix is not None:
-    # A TensorFlow checkpoint (model.ckpt-N.index/.data-*), read without TF.
-    from epos_amd import tf_checkpoint
-    ckpt = tf_checkpoint.to_epos_checkpoint(
-        tf_checkpoint.load_checkpoint(tf_prefix))
-    return ckpt, ckpt['logits/pred_obj_conf/biases'].shape[0] - 1, tf_prefix
-  if ckpt_path and os.path.exists(ckpt_path):
-    ckpt = weights.load_npz(ckpt_path)
-    return ckpt, ckpt['logits/pred_obj_conf/biases'].shape[0] - 1, ckpt_path
-  if args.synthetic:
-    num_objs = args.num_objs or 21
-    ckpt = weights.random_init(args.model_variant, num_objs=num_objs,
-                               num_frags=args.num_frags, seed=0, randomize_bn=True)
-    return ckpt, num_objs, None
-  raise ValueError('No checkpoint (.npz) found in {}'.format(checkpoint_dir))
-
-
-def load_frames(args, num_objs, rank, world, store_obj_ids=None):
-  """Returns this rank's list of epos_amd.frames.Frame (ids, K, targets known; pixels decoded
-  on demand by the prefetcher's threads), plus the frame height and width."""
-  from epos_amd import frames as eframes
-  w, h = [int(x) for x in str(args.infer_crop_size).split(',')][:2] \
-      if not isinstance(args.infer_crop_size, (list, tuple)) \
-      else args.infer_crop_size[:2]
-  if args.infer_tfrecord_names:
-    # <TF_DATA_PATH>/<name>.tfrecord for each name (infer.py:581-583,
-    # datagen.py:707-723), read without TensorFlow (epos_amd/tfrecord.py).
-    names = args.infer_tfrecord_names
-    if not isinstance(names, (list, tuple)):
-      names = [n for n in str(names).split(',') if n]
-    data_path = os.environ.get('TF_DATA_PATH', '.')
-    paths = []
-    for name in names:
-      path = os.path.join(data_path, name + '.tfrecord')
-      if not os.path.exists(path):
-        raise ValueError('No input files: {}'.format(path))   # datagen.py:720-721
-      paths.append(path)
-    # min_visib_fract=None: the reference builds its inference Dataset without a
-    # visibility filter (scripts/infer.py:614), every annotated instance is a target
-    all_frames = eframes.scan_tfrecords(
-        paths, (w, h), args.infer_max_height_before_crop,
-        store_obj_ids if store_obj_ids else None, crop_seed=args.seed)
-    b, e = edist.shard_range(len(all_frames), rank, world)
-    frames = all_frames[b:e]
-  elif args.frames:
-    meta = json.load(open(os.path.join(args.frames, 'frames.json')))
-    b, e = edist.shard_range(len(meta), rank, world)
-    frames = eframes.frames_from_dir(args.frames, meta[b:e], h, w)
-  elif args.synthetic:
-    b, e = edist.shard_range(args.synthetic, rank, world)
-    frames = eframes.synthetic_frames(range(b, e), h, w, num_objs, 5)
-  else:
-    raise ValueError(
-        'No input files: give --infer_tfrecord_names, --frames <dir> or '
-        '--synthetic N.')
-  return frames, h, w
-
-
 def save_correspondences(infer_dir, infer_name, frame, im_ind, corr, pred_time):
   """infer.py:294-345 text dump (sorted by confidence)."""
   scene_id, im_id, K = frame.scene_id, frame.im_id, frame.K
-  suffix = '' if infer_name is None else '_' + infer_name
   for obj_id, c in corr.items():
     txt = '# Corr format: u v x y z px_id frag_id conf conf_obj conf_frag\n'
     txt += 'synthetic\n{} {} {} {}\n'.format(scene_id, im_id, obj_id, pred_time)
@@ -440,7 +196,7 @@ def save_correspondences(infer_dir, infer_name, frame, im_ind, corr, pred_time):
           c['coord_2d'][i, 0], c['coord_2d'][i, 1], c['coord_3d'][i, 0],
           c['coord_3d'][i, 1], c['coord_3d'][i, 2], c['px_id'][i],
           c['frag_id'][i], c['conf'][i], c['conf_obj'][i], c['conf_frag'][i])
-    path = os.path.join(infer_dir, 'corr' + suffix,
+    path = os.path.join(infer_dir, 'corr' + cli.result_suffix(infer_name),
                         '{:06d}_corr_{:02d}.txt'.format(im_ind, obj_id))
     os.makedirs(os.path.dirname(path), exist_ok=True)
     with open(path, 'w') as f:
@@ -527,13 +283,14 @@ def process_by_operators(pipe, store, imgs, chunk, targets, args, fit):
   return poses, rt
 
 
-def main(argv=None):
+def prepare(argv=None):
+  """Parses the command line, applies params.yml, refuses what this build cannot run and
+  prints the notes. Returns (args, model_dir, (rank, world, local_rank))."""
   args = build_parser().parse_args(argv)
-  rank, world, local_rank = edist.init_from_env()
-  models_path = os.environ.get('TF_MODELS_PATH', '.')          # config.py:9-16
-  model_dir = os.path.join(models_path, args.model)
-  update_flags(args, os.path.join(model_dir, PARAMS_FILENAME))  # infer.py:561-564
-  check_supported_flags(args)
+  ranks = edist.init_from_env()
+  model_dir = cli.model_dir(args)
+  cli.update_flags(args, os.path.join(model_dir, cli.PARAMS_FILENAME))  # infer.py:561-564
+  cli.check_supported_flags(args)
   if args.cpu_only:
     raise SystemExit('--cpu_only: this build has no CPU path (MI355X only).')
   if args.fitting_method not in ('progressive_x', 'opencv_ransac'):
@@ -561,35 +318,25 @@ def main(argv=None):
     # said once here instead of silently (scripts/infer.py:150-291 draws it)
     print('note: --vis_gt_obj_labels has no ground-truth label map at inference; the tile '
           'is omitted (use --vis_gt_obj_labels=False to silence this)', file=sys.stderr)
+  return args, model_dir, ranks
+
+
+def build_pipelines(args, model_dir, ranks):
+  """Everything the loop of main() runs on, as one namespace: the model store, this rank's
+  frames, the fit parameters, the resolved depth / launch queue / heads, the renderer of
+  --vis_renderer mesh, the prefetcher and the warmed-up pipelines."""
+  rank, world, local_rank = ranks
   checkpoint_dir = os.path.join(model_dir, 'train')             # infer.py:570
-  infer_dir = os.path.join(model_dir, 'infer')
-  os.makedirs(infer_dir, exist_ok=True)
-  # EPOS_FORCE_DEVICE=0 maps every rank onto one GPU (multi-rank flow on a one-GPU
-  # test box, together with EPOS_DIST_BACKEND=gloo), as in bench.py
-  dev_index = int(os.environ.get('EPOS_FORCE_DEVICE', local_rank))
+  dev_index = cli.device_from_env(local_rank)
   dev = 'cuda:%d' % dev_index
   torch.cuda.set_device(dev_index)
 
-  ckpt, num_objs, _ = load_checkpoint(args, checkpoint_dir)
-  store = load_fragments(model_dir, args.num_frags)
-  if store is None and not args.synthetic:
-    store = fragment_from_bop_models(model_dir, args, dev)
-  if store is None:
-    if not args.synthetic:
-      raise ValueError('fragments.pkl / fragments.npz not found in ' + model_dir +
-                       ' and no BOP models under $BOP_PATH/<dataset>/models*')
-    store = synthetic.ModelStore(num_objs, args.num_frags, seed=0)
-
-  frames, h, w = load_frames(args, num_objs, rank, world,
-                            store.dp_model['obj_ids'])
-  atrous = _as_list(args.atrous_rates, int)
-  mo = model.ModelOptions(
-      model.get_outputs_to_num_channels(num_objs, args.num_frags),
-      crop_size=(w, h), atrous_rates=atrous,
-      encoder_output_stride=args.encoder_output_stride,
-      decoder_output_stride=_as_list(args.decoder_output_stride, int),
-      model_variant=args.model_variant,
-      multi_grid=_as_list(args.multi_grid, int))
+  ckpt, num_objs, _ = cli.load_checkpoint(args, checkpoint_dir)
+  store = cli.resolve_store(model_dir, args, num_objs, dev)
+  frames, h, w = cli.load_frames(
+      args.infer_tfrecord_names, args.frames, args.synthetic, args.infer_crop_size,
+      args.infer_max_height_before_crop, args.seed, num_objs, rank, world,
+      store.dp_model['obj_ids'])
   fit = fitting.fit_params(
       threshold=args.inlier_thresh,
       neighborhood_ball_radius=args.neighbour_max_dist,
@@ -623,16 +370,13 @@ def main(argv=None):
       raise ValueError('--project_to_surface needs --dataset and $BOP_PATH (object models)')
     store.models = ply.load_models(bop, args.dataset, 'eval',
                                    obj_ids=store.dp_model['obj_ids'])
-  renderer = None
-  if mesh_vis:
+  renderer = frag_pool = None
+  if args.vis and args.vis_renderer == 'mesh':
     # scripts/infer.py:633-638: the renderer holds the 'eval' models (those of
     # --project_to_surface when it loaded them already)
     from epos_amd import ply, render as erender
-    models = getattr(store, 'models', None) or ply.load_models(
-        os.environ['BOP_PATH'], args.dataset, 'eval', obj_ids=store.dp_model['obj_ids'])
-    renderer = erender.Renderer(dev)
-    for o in sorted(models):
-      renderer.add_model(o, models[o])
+    renderer = cli.eval_renderer(getattr(store, 'models', None) or ply.load_models(
+        os.environ['BOP_PATH'], args.dataset, 'eval', obj_ids=store.dp_model['obj_ids']), dev)
     frag_pool = erender.pool_fragments(store.frag_centers, store.frag_sizes)
   B = args.batch
   # Instances per object (infer.py:456-468 of the reference): localization fits as many as
@@ -657,11 +401,12 @@ def main(argv=None):
     lq = 1
   if depth == 1:
     lq = 1                         # strictly one batch at a time means launch -> collect
-  pyramid = multiscale.normalize_pyramid(_as_list(args.image_pyramid, float) or None)
+  pyramid = multiscale.normalize_pyramid(cli.as_list(args.image_pyramid, float) or None)
   sparse_heads = resolve_sparse_heads(args, needs_dense, pyramid)
   # the decoder processes start (import numpy / PIL) while the plans are built; nothing is
-  # decoded before the loop below asks for it
+  # decoded before the loop of main() asks for it
   from epos_amd import frames as eframes
+  mo = cli.model_options(args, num_objs, w, h, pyramid)
   feed = eframes.Prefetcher(frames, B, h, w, workers=args.decode_threads or None,
                             ahead=max(1, args.prefetch), inflight=depth * lq)
   pipes = [pipeline.EposPipeline(
@@ -701,13 +446,110 @@ def main(argv=None):
     tg0 = [dict(f0.targets)] * B
     if args.max_instances_to_fit is not None:
       tg0 = [{o: min(c, args.max_instances_to_fit) for o, c in t.items()} for t in tg0]
-    import collections
     for q in pipes:
       q.process_batch(blank, np.stack([f0.K] * B), tg0, task_type=args.task_type, seed=args.seed)
       q.cap_hits = collections.deque(maxlen=q.CAP_HITS_KEPT)
       q.last_cap_hits, q.cap_hit_count = [], 0
       q._warned_cap = False
     torch.cuda.synchronize()
+  return types.SimpleNamespace(
+      dev=dev, store=store, frames=frames, h=h, w=w, fit=fit, operator_path=operator_path,
+      renderer=renderer, frag_pool=frag_pool, max_inst=max_inst, depth=depth, lq=lq, feed=feed,
+      pipes=pipes)
+
+
+def save_step_correspondences(args, run, infer_dir, i0, chunk, pred_time):
+  """--save_corresp: the correspondences of the step's frames, from the dense heads the plan
+  still holds."""
+  from epos_amd import corresp as ecorresp
+  pipe = run.pipes[0]
+  pred = pipe.net.outputs()
+  for b, f in enumerate(chunk):
+    c = ecorresp.establish_many_to_many(
+        pred['pred_obj_conf'][b], pred['pred_frag_conf'][b],
+        pred['pred_frag_loc'][b], list(f.targets), run.store, pipe.output_scale,
+        args.corr_min_obj_conf, args.corr_min_frag_rel_conf, False,
+        args.task_type == pipeline.LOCALIZATION, device=run.dev)
+    save_correspondences(infer_dir, args.infer_name, f, i0 + b, c, pred_time)
+
+
+def visualize_step(args, run, model_dir, i0, chunk, poses):
+  """--vis (infer.py:540-552): one image per frame of the step in <model>/vis (:577)."""
+  from epos_amd import vis as evis
+  pred = {k: v.cpu().numpy() for k, v in run.pipes[0].net.outputs().items()}
+  flags = {k: getattr(args, k) for k in vars(args) if k.startswith('vis_')}
+  for b, f in enumerate(chunk):
+    est = [p for p in poses if (p['scene_id'], p['im_id']) == (f.scene_id, f.im_id)]
+    gt_fields = None
+    if run.renderer is not None:
+      # the ground-truth maps at the output resolution, with output_K of datagen.py:482-488;
+      # frames without instance masks (--frames, --synthetic) take the depth rule
+      oh, ow = pred['pred_obj_label'][b].shape
+      gt_fields = eval_utils.gt_fields_device(
+          run.renderer, f, (ow, oh), run.frag_pool, lambda o: o in run.store.frag_centers,
+          input_size=(run.w, run.h), allow_empty=False)
+      if gt_fields is not None:
+        gt_fields = {k: v.cpu().numpy() for k, v in gt_fields.items()}
+    evis.visualize(f.image_f32(), f.K, {k: v[b] for k, v in pred.items()}, est, i0 + b,
+                   run.store, os.path.join(model_dir, 'vis'),
+                   gt_poses=f.gt_poses, flags=flags, renderer=run.renderer,
+                   gt_fields=gt_fields)
+
+
+def write_results(args, run, ranks, infer_dir, poses_all, time_start, loop_s, host_s):
+  """After the loop: the cap-hit report, the first image's time, the gather over the ranks,
+  the CSV and the throughput lines."""
+  rank, world, _ = ranks
+  frames, pipes = run.frames, run.pipes
+  hits = sorted(set(h for q in pipes for h in q.cap_hits))
+  n_hits = sum(q.cap_hit_count for q in pipes)
+  if hits:
+    overflowed = any(q.cap_hit_count > q.CAP_HITS_KEPT for q in pipes)
+    print('Instance cap (--detection_instance_cap={}) reached {} time(s), for {} distinct '
+          '(scene, image, object) triples{}; more instances may exist there:'.format(
+              run.max_inst, n_hits, len(hits),
+              ' among the last {} hits kept per pipeline'.format(pipes[0].CAP_HITS_KEPT)
+              if overflowed else ''))
+    for sc_, im_, ob_, n_ in hits:
+      print('  scene {} image {} object {}: {} instances'.format(sc_, im_, ob_, n_))
+  # First-image time := mean time of the others (infer.py:741-749).
+  if len(poses_all) > 1 and frames:
+    first = (frames[0].scene_id, frames[0].im_id)
+    rest = [p['time'] for p in poses_all if (p['scene_id'], p['im_id']) != first]
+    if rest:
+      for p in poses_all:
+        if (p['scene_id'], p['im_id']) == first:
+          p['time'] = float(np.mean(rest))
+  # max_records=None: the ranks first agree on the largest local pose count (their
+  # shards differ by a frame whenever N % world != 0, and a rank may hold none)
+  merged = edist.gather_poses(poses_all, max_records=None) if world > 1 else poses_all
+  if rank == 0 and args.save_estimates:
+    path = os.path.join(infer_dir, 'estimated-poses{}.csv'.format(
+        cli.result_suffix(args.infer_name)))
+    bop_io.save_bop_results(path, merged, version='bop19')
+    total_s = time.time() - time_start
+    print('Saved {} pose estimates to: {}  ({:.2f} s)'.format(len(merged), path, total_s))
+    # from the first decode to the CSV on disk (this rank's frames; with N ranks each rank
+    # runs its own shard concurrently, so the job's rate is ~N x this)
+    print('Throughput: {} images in {:.3f} s = {:.1f} images/s (inference loop {:.3f} s = '
+          '{:.1f} images/s; first decode -> CSV written; plan construction and weight packing '
+          'before it are not included)'.format(
+              len(frames), total_s, len(frames) / max(total_s, 1e-9), loop_s,
+              len(frames) / max(loop_s, 1e-9)))
+    if not run.operator_path:
+      n_steps = max(1, (len(frames) + args.batch - 1) // args.batch)
+      print('Host time per step [ms]: ' + ', '.join(
+          '{} {:.3f}'.format(k, v / n_steps * 1e3) for k, v in host_s.items()))
+
+
+def main(argv=None):
+  args, model_dir, ranks = prepare(argv)
+  rank, world, _ = ranks
+  infer_dir = os.path.join(model_dir, 'infer')
+  os.makedirs(infer_dir, exist_ok=True)
+  run = build_pipelines(args, model_dir, ranks)
+  frames, feed, pipes, B = run.frames, run.feed, run.pipes, args.batch
+  depth, lq = run.depth, run.lq
 
   poses_all = []
   time_start = time.time()           # first decode -> CSV written
@@ -723,47 +565,9 @@ def main(argv=None):
         seen.add(key)
         poses_all.append(p)
     if args.save_corresp:
-      from epos_amd import corresp as ecorresp
-      pred = pipe.net.outputs()
-      for b, f in enumerate(chunk[:n_real]):
-        c = ecorresp.establish_many_to_many(
-            pred['pred_obj_conf'][b], pred['pred_frag_conf'][b],
-            pred['pred_frag_loc'][b], list(f.targets), store, pipe.output_scale,
-            args.corr_min_obj_conf, args.corr_min_frag_rel_conf, False,
-            args.task_type == pipeline.LOCALIZATION, device=dev)
-        save_correspondences(infer_dir, args.infer_name, f, i0 + b, c,
-                             rt.get('total', 0.0))
-    if args.vis:                                # infer.py:540-552, <model>/vis (:577)
-      from epos_amd import vis as evis
-      pred = {k: v.cpu().numpy() for k, v in pipe.net.outputs().items()}
-      flags = {k: getattr(args, k) for k in vars(args) if k.startswith('vis_')}
-      for b, f in enumerate(chunk[:n_real]):
-        est = [p for p in poses if (p['scene_id'], p['im_id']) == (f.scene_id, f.im_id)]
-        gt_fields = None
-        gi = [i for i, p in enumerate(f.gt_poses or []) if renderer is not None and
-              renderer.has_object(p['obj_id']) and p['obj_id'] in store.frag_centers]
-        gt = [f.gt_poses[i] for i in gi]
-        if gt:
-          # the ground-truth maps at the output resolution, with output_K of datagen.py:482-488
-          oh, ow = pred['pred_obj_label'][b].shape
-          sy, sx = h / float(oh), w / float(ow)
-          oK = np.array([[f.K[0, 0] / sx, 0.0, f.K[0, 2] / sx],
-                         [0.0, f.K[1, 1] / sy, f.K[1, 2] / sy], [0.0, 0.0, 1.0]])
-          # frames without instance masks (--frames, --synthetic) take the depth rule
-          masks = f.gt_masks((ow, oh))
-          if masks is not None:
-            if len(masks) != len(f.gt_poses):
-              raise ValueError('frame %s/%s: %d instance masks for %d ground-truth poses' % (
-                  f.scene_id, f.im_id, len(masks), len(f.gt_poses)))
-            masks = masks[gi]
-          gt_fields = {k: v.cpu().numpy() for k, v in erender.gt_fields(
-              renderer, oK, [p['obj_id'] for p in gt], np.stack([p['R'] for p in gt]),
-              np.stack([np.asarray(p['t']).reshape(3) for p in gt]), (ow, oh), frag_pool[0],
-              frag_pool[1], masks).items()}
-        evis.visualize(f.image_f32(), f.K, {k: v[b] for k, v in pred.items()}, est, i0 + b,
-                       store, os.path.join(model_dir, 'vis'),
-                       gt_poses=f.gt_poses, flags=flags, renderer=renderer,
-                       gt_fields=gt_fields)
+      save_step_correspondences(args, run, infer_dir, i0, chunk[:n_real], rt.get('total', 0.0))
+    if args.vis:
+      visualize_step(args, run, model_dir, i0, chunk[:n_real], poses)
     if rank == 0:                               # infer.py:730-734
       print('Image: {}, prediction: {:.3f}, establish_corr: {:.3f}, fitting: '
             '{:.3f}, total time: {:.3f}'.format(
@@ -790,8 +594,8 @@ def main(argv=None):
     if args.max_instances_to_fit is not None:  # infer.py:467-468
       tg = [{o: min(c, args.max_instances_to_fit) for o, c in t.items()}
             for t in tg]
-    if operator_path:
-      poses, rt = process_by_operators(pipe, store, imgs, chunk, tg, args, fit)
+    if run.operator_path:
+      poses, rt = process_by_operators(pipes[0], run.store, imgs, chunk, tg, args, run.fit)
       finish(i0, chunk, poses, rt)
       t_mark = clock()
       continue
@@ -814,45 +618,7 @@ def main(argv=None):
     finish(j0, ch, *res)
     t_now = clock(); host_s['finish'] += t_now - t_mark; t_mark = t_now
   loop_s = time.time() - time_start
-  hits = sorted(set(h for q in pipes for h in q.cap_hits))
-  n_hits = sum(q.cap_hit_count for q in pipes)
-  if hits:
-    overflowed = any(q.cap_hit_count > q.CAP_HITS_KEPT for q in pipes)
-    print('Instance cap (--detection_instance_cap={}) reached {} time(s), for {} distinct '
-          '(scene, image, object) triples{}; more instances may exist there:'.format(
-              max_inst, n_hits, len(hits),
-              ' among the last {} hits kept per pipeline'.format(pipe.CAP_HITS_KEPT)
-              if overflowed else ''))
-    for sc_, im_, ob_, n_ in hits:
-      print('  scene {} image {} object {}: {} instances'.format(sc_, im_, ob_, n_))
-  # First-image time := mean time of the others (infer.py:741-749).
-  if len(poses_all) > 1 and frames:
-    first = (frames[0].scene_id, frames[0].im_id)
-    rest = [p['time'] for p in poses_all if (p['scene_id'], p['im_id']) != first]
-    if rest:
-      for p in poses_all:
-        if (p['scene_id'], p['im_id']) == first:
-          p['time'] = float(np.mean(rest))
-  # max_records=None: the ranks first agree on the largest local pose count (their
-  # shards differ by a frame whenever N % world != 0, and a rank may hold none)
-  merged = edist.gather_poses(poses_all, max_records=None) if world > 1 else poses_all
-  if rank == 0 and args.save_estimates:
-    suffix = '' if args.infer_name is None else '_' + args.infer_name
-    path = os.path.join(infer_dir, 'estimated-poses{}.csv'.format(suffix))
-    bop_io.save_bop_results(path, merged, version='bop19')
-    total_s = time.time() - time_start
-    print('Saved {} pose estimates to: {}  ({:.2f} s)'.format(len(merged), path, total_s))
-    # from the first decode to the CSV on disk (this rank's frames; with N ranks each rank
-    # runs its own shard concurrently, so the job's rate is ~N x this)
-    print('Throughput: {} images in {:.3f} s = {:.1f} images/s (inference loop {:.3f} s = '
-          '{:.1f} images/s; first decode -> CSV written; plan construction and weight packing '
-          'before it are not included)'.format(
-              len(frames), total_s, len(frames) / max(total_s, 1e-9), loop_s,
-              len(frames) / max(loop_s, 1e-9)))
-    if not operator_path:
-      n_steps = max(1, (len(frames) + B - 1) // B)
-      print('Host time per step [ms]: ' + ', '.join(
-          '{} {:.3f}'.format(k, v / n_steps * 1e3) for k, v in host_s.items()))
+  write_results(args, run, ranks, infer_dir, poses_all, time_start, loop_s, host_s)
   if world > 1:
     torch.distributed.destroy_process_group()
 

@@ -183,8 +183,8 @@ def test_eval_cli_defaults(eval_module, tmp_path, monkeypatch):
   assert args.batch_size == 1 and args.eval_frag_labels is None
   assert args.precision == 'fp32' and args.num_frags == 64 and args.synthetic == 0
   assert not hasattr(args, 'fitting_method') and not hasattr(args, 'infer_crop_size')
-  ns = eval_module._frames_args(args)
-  assert ns.infer_crop_size == '640,480' and ns.infer_max_height_before_crop == 480
+  from epos_amd import cli
+  assert cli.crop_size(args.eval_crop_size) == (640, 480)
   # params.yml overrides the defaults
   (tmp_path / 'm').mkdir()
   (tmp_path / 'm' / 'params.yml').write_text('eval_crop_size: "128,96"\nnum_frags: 32\n')

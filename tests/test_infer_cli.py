@@ -13,17 +13,18 @@ sys.path.insert(0, ROOT)
 
 def test_params_yml_overrides_flag_defaults(tmp_path):
   import infer
+  from epos_amd import cli
   args = infer.build_parser().parse_args(['--model', 'm'])
   assert args.inlier_thresh == 4.0 and args.max_fitting_iterations == 400
   assert args.corr_min_obj_conf == 0.1 and args.corr_min_frag_rel_conf == 0.5
   p = tmp_path / 'params.yml'
   p.write_text('inlier_thresh: 2.5\nnum_frags: 32\ninfer_crop_size: "720,540"\n'
                'unknown_flag: 1\n')
-  infer.update_flags(args, str(p))                       # common.py:157-177
+  cli.update_flags(args, str(p))                       # common.py:157-177
   assert args.inlier_thresh == 2.5 and args.num_frags == 32
   assert args.infer_crop_size == '720,540'
   with pytest.raises(ValueError):
-    infer.update_flags(args, str(tmp_path / 'params.json.txt'.replace('.txt', ''))
+    cli.update_flags(args, str(tmp_path / 'params.json.txt'.replace('.txt', ''))
                        if (tmp_path / 'params.json').write_text('{}') or True
                        else None)
 
@@ -57,9 +58,10 @@ def test_unsupported_model_flags_raise(tmp_path):
   """A params.yml (or flag) that asks for a graph this build does not implement must
   stop the run, not be half-applied (common.py:96-154)."""
   import infer
+  from epos_amd import cli
   ok = infer.build_parser().parse_args(['--model', 'm', '--multi_grid', '1,2,4'])
-  infer.check_supported_flags(ok)                        # defaults + multi_grid: fine
-  assert infer._as_list(ok.multi_grid, int) == [1, 2, 4]
+  cli.check_supported_flags(ok)                        # defaults + multi_grid: fine
+  assert cli.as_list(ok.multi_grid, int) == [1, 2, 4]
   for text in ['aspp_with_separable_conv: false\n', 'upsample_logits: true\n',
                'frag_cls_agnostic: true\n', 'image_pyramid: [0.5, 1.0]\n',
                'logits_kernel_size: 3\n', 'decoder_use_separable_conv: false\n',
@@ -69,17 +71,17 @@ def test_unsupported_model_flags_raise(tmp_path):
     args = infer.build_parser().parse_args(['--model', 'm'])
     p = tmp_path / 'params.yml'
     p.write_text(text)
-    infer.update_flags(args, str(p))
+    cli.update_flags(args, str(p))
     with pytest.raises(NotImplementedError):
-      infer.check_supported_flags(args)
+      cli.check_supported_flags(args)
   # values equal to the defaults, in YAML spellings, pass
   args = infer.build_parser().parse_args(['--model', 'm'])
   (tmp_path / 'params.yml').write_text(
       'image_pyramid: [1.0]\ndecoder_output_stride: [4]\natrous_rates: [12, 24, 36]\n'
       'aspp_with_batch_norm: true\nmulti_grid: [1, 2, 4]\n')
-  infer.update_flags(args, str(tmp_path / 'params.yml'))
-  infer.check_supported_flags(args)
-  assert infer._as_list(args.atrous_rates, int) == [12, 24, 36]
+  cli.update_flags(args, str(tmp_path / 'params.yml'))
+  cli.check_supported_flags(args)
+  assert cli.as_list(args.atrous_rates, int) == [12, 24, 36]
 
 
 def test_unknown_fitting_method_raises(tmp_path, monkeypatch):
@@ -91,15 +93,15 @@ def test_unknown_fitting_method_raises(tmp_path, monkeypatch):
 
 def test_fragments_pkl_roundtrip(tmp_path):
   import pickle
-  import infer
+  from epos_amd import cli
   centers = {1: np.zeros((64, 3)), 2: np.ones((64, 3))}
   sizes = {1: np.full(64, 5.0), 2: np.full(64, 7.0)}
   with open(tmp_path / 'fragments.pkl', 'wb') as f:
     pickle.dump({'frag_centers': centers, 'frag_sizes': sizes}, f)
-  store = infer.load_fragments(str(tmp_path), 64)
+  store = cli.load_fragments(str(tmp_path), 64)
   assert store.dp_model['obj_ids'] == [1, 2] and store.frag_sizes[2][0] == 7.0
   with pytest.raises(ValueError):
-    infer.load_fragments(str(tmp_path), 32)              # datagen.py:264-268
+    cli.load_fragments(str(tmp_path), 32)              # datagen.py:264-268
 
 
 @pytest.mark.gpu
@@ -292,8 +294,7 @@ def test_fragments_from_bop_ply_models(tmp_path, monkeypatch):
   (datagen.py:238-296). Centres / sizes must equal the numpy oracle's FPS + size rule
   on the same vertices, and the model-type rule ('eval' models for TUD-L) is honoured."""
   import argparse
-  import infer
-  from epos_amd import ply
+  from epos_amd import cli, ply
   from oracle import fragment_ref
   bop = tmp_path / 'bop'
   rng = np.random.RandomState(4)
@@ -310,7 +311,7 @@ def test_fragments_from_bop_ply_models(tmp_path, monkeypatch):
   model_dir = tmp_path / 'm'
   model_dir.mkdir()
   args = argparse.Namespace(dataset='tudl', num_frags=64)
-  store = infer.fragment_from_bop_models(str(model_dir), args, 'cuda:0')
+  store = cli.fragment_from_bop_models(str(model_dir), args, 'cuda:0')
   assert (model_dir / 'fragments.pkl').exists()
   assert store.dp_model['obj_ids'] == [1, 2, 3]
   for o in store.dp_model['obj_ids']:
@@ -321,7 +322,7 @@ def test_fragments_from_bop_ply_models(tmp_path, monkeypatch):
     np.testing.assert_array_equal(store.frag_sizes[o], sizes)
   # a dataset without model files falls through (the caller then raises)
   args.dataset = 'ycbv'
-  assert infer.fragment_from_bop_models(str(model_dir), args, 'cuda:0') is None
+  assert cli.fragment_from_bop_models(str(model_dir), args, 'cuda:0') is None
 
 
 @pytest.mark.gpu

@@ -118,29 +118,29 @@ def _args(extra):
 
 
 def test_infer_flags_accept_a_pyramid_only_when_asked():
-  import infer
+  from epos_amd import cli
   for extra in (['--image_pyramid', '0.75,1.0,1.25'],
                 ['--image_pyramid', '0.5', '--merge_method', 'avg']):
     with pytest.raises(NotImplementedError):
-      infer.check_supported_flags(_args(extra))
-    infer.check_supported_flags(_args(extra + ['--multi_scale_inference', 'true']))
+      cli.check_supported_flags(_args(extra))
+    cli.check_supported_flags(_args(extra + ['--multi_scale_inference', 'true']))
   assert _args([]).multi_scale_inference is False
-  infer.check_supported_flags(_args(['--image_pyramid', '1.0']))
+  cli.check_supported_flags(_args(['--image_pyramid', '1.0']))
   for extra in (['--image_pyramid', '0.5,1.0', '--merge_method', 'median'],
                 ['--image_pyramid', '0,1.0'],
                 ['--image_pyramid', ','.join(['1.0'] * 9)]):
     with pytest.raises(ValueError):
-      infer.check_supported_flags(_args(extra + ['--multi_scale_inference', 'true']))
+      cli.check_supported_flags(_args(extra + ['--multi_scale_inference', 'true']))
 
 
 def test_infer_params_yml_pyramid_with_the_flag(tmp_path):
-  import infer
+  from epos_amd import cli
   args = _args(['--multi_scale_inference', 'true'])
   p = tmp_path / 'params.yml'
   p.write_text('image_pyramid: [0.5, 1.0]\nmerge_method: avg\n')
-  infer.update_flags(args, str(p))
-  infer.check_supported_flags(args)
-  assert infer._as_list(args.image_pyramid, float) == [0.5, 1.0]
+  cli.update_flags(args, str(p))
+  cli.check_supported_flags(args)
+  assert cli.as_list(args.image_pyramid, float) == [0.5, 1.0]
 
 
 def test_sparse_heads_with_a_pyramid():

@@ -281,6 +281,7 @@ def _frames_json(directory, gt=True):
 
 def test_eval_poses_parser_and_refusals(tmp_path, monkeypatch):
   import eval_poses
+  from epos_amd import cli
   monkeypatch.setenv('TF_MODELS_PATH', str(tmp_path))
   monkeypatch.setenv('BOP_PATH', str(tmp_path))
   flags = {a.dest for a in eval_poses.build_parser()._actions}
@@ -302,7 +303,7 @@ def test_eval_poses_parser_and_refusals(tmp_path, monkeypatch):
   os.makedirs(str(tmp_path / 'm'))
   (tmp_path / 'm' / 'params.yml').write_text('dataset: ycbv\ninfer_crop_size: [720, 540]\n')
   args, _ = eval_poses.prepare(['--model', 'm', '--frames', 'x'])
-  assert args.dataset == 'ycbv' and eval_poses.crop_size(args) == [720, 540]
+  assert args.dataset == 'ycbv' and cli.crop_size(args.infer_crop_size) == (720, 540)
   # frames without ground truth are refused before anything touches a device
   _frames_json(str(tmp_path), gt=False)
   with pytest.raises(ValueError, match='ground-truth poses'):
@@ -311,8 +312,9 @@ def test_eval_poses_parser_and_refusals(tmp_path, monkeypatch):
 
 def test_eval_poses_reads_frames_json_without_images(tmp_path):
   import eval_poses
+  from epos_amd import cli
   _frames_json(str(tmp_path))
-  frames = eval_poses.frames_metadata(str(tmp_path))
+  frames = cli.load_frames(None, str(tmp_path), 0, '640,480', 480, 0, 0, pixels=False)[0]
   assert [f.im_id for f in frames] == [0, 1] and frames[0].scene_id == 3
   assert frames[0].targets == {2: 2} and len(frames[1].gt_poses) == 2
   assert frames[0].K[0, 2] == 320.0 and os.listdir(str(tmp_path)) == ['frames.json']

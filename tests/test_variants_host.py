@@ -133,12 +133,13 @@ def test_unknown_variants_still_raise():
 
 def test_check_supported_flags_accepts_the_variants():
   import infer
+  from epos_amd import cli
   for v in NEW + ['xception_65', 'resnet_v1_101_beta']:
     args = infer.build_parser().parse_args(['--model', 'm', '--model_variant', v])
-    infer.check_supported_flags(args)
+    cli.check_supported_flags(args)
   args = infer.build_parser().parse_args(['--model', 'm', '--model_variant', 'mobilenet_v2'])
   with pytest.raises(NotImplementedError):
-    infer.check_supported_flags(args)
+    cli.check_supported_flags(args)
 
 
 @pytest.mark.parametrize('variant', ['resnet_v1_50', 'xception_71', 'resnet_v1_50_beta'])

@@ -331,6 +331,7 @@ def test_eval_poses_vsd_flags_and_refusals(tmp_path, monkeypatch):
 
 def test_depth_sources_and_lazy_frames(tmp_path, monkeypatch):
   import eval_poses
+  from epos_amd import cli
   monkeypatch.setenv('TF_MODELS_PATH', str(tmp_path))
   monkeypatch.setenv('BOP_PATH', str(tmp_path))
   _frames_json(str(tmp_path), depth=True)
@@ -338,10 +339,12 @@ def test_depth_sources_and_lazy_frames(tmp_path, monkeypatch):
   meta[1]['depth_path'], meta[1]['depth_scale'] = 'depth_1.png', 0.5
   json.dump(meta, open(str(tmp_path / 'frames.json'), 'w'))
   bop_io.save_depth_png(str(tmp_path / 'depth_1.png'), np.full((4, 6), 1000, np.uint16))
-  frames = eval_poses.frames_metadata(str(tmp_path))
+  meta = cli.read_frames_json(str(tmp_path))
+  frames = cli.load_frames(None, str(tmp_path), 0, '640,480', 480, 0, 0, pixels=False,
+                           meta=meta)[0]
   args, _ = eval_poses.prepare(['--model', 'm', '--dataset', 'tudl', '--frames', str(tmp_path),
                                 '--vsd', 'true'])
-  src = eval_poses.depth_sources(args, frames)
+  src = eval_poses.depth_sources(args, frames, meta)
   assert [s[1] for s in src] == [1.0, 0.5] and src[1][2] is frames[1].K
   lazy = eval_poses.DepthFrames(src, keep=1)
   assert len(lazy) == 2 and lazy[1][0].shape == (4, 6) and (lazy[1][0] == 500.0).all()
@@ -356,7 +359,7 @@ def test_depth_sources_and_lazy_frames(tmp_path, monkeypatch):
     bop_io.save_depth_png(str(scene / 'depth' / ('%06d.png' % i)),
                           np.full((4, 6), 100 * (i + 1), np.uint16))
   args.depth_split = 'val'
-  src = eval_poses.depth_sources(args, frames)
+  src = eval_poses.depth_sources(args, frames, meta)
   assert src[1][0] == str(scene / 'depth' / '000001.png') and src[1][1] == 0.1
   assert src[0][2].tolist() == np.reshape(cam_K, (3, 3)).tolist()
   depth, K = eval_poses.DepthFrames(src)[1]
@@ -365,13 +368,14 @@ def test_depth_sources_and_lazy_frames(tmp_path, monkeypatch):
 
 def test_build_groups_drops_invisible_targets(tmp_path):
   import eval_poses
+  from epos_amd import cli
   K = [[600.0, 0, 320.0], [0, 600.0, 240.0], [0, 0, 1]]
   pose = {'obj_id': 2, 'R': np.eye(3).reshape(-1).tolist(), 't': [0.0, 0.0, 500.0]}
   meta = [{'path': 'x', 'scene_id': 3, 'im_id': 0, 'K': K, 'targets': {'2': 3},
            'gt_poses': [pose, dict(pose, t=[1.0, 0, 500.0]), dict(pose, t=[2.0, 0, 500.0])]}]
   with open(str(tmp_path / 'frames.json'), 'w') as f:
     json.dump(meta, f)
-  frames = eval_poses.frames_metadata(str(tmp_path))
+  frames = cli.load_frames(None, str(tmp_path), 0, '640,480', 480, 0, 0, pixels=False)[0]
   results = [{'scene_id': 3, 'im_id': 0, 'obj_id': 2, 'score': s, 'R': np.eye(3),
               't': np.zeros((3, 1))} for s in (0.1, 0.9, 0.5)]
   groups, ignored = eval_poses.build_groups(frames, results)
