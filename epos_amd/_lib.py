@@ -370,6 +370,13 @@ SYMBOLS = {
     'epos_vsd_counts': (ctypes.c_int, [
         vp, ctypes.c_int, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp, ctypes.c_int,
         ctypes.c_double, vp, ctypes.c_int, vp, vp]),
+    # losses
+    'epos_loss_share_pixels': (ctypes.c_int64, [ctypes.c_int64, ctypes.c_int, ctypes.c_int]),
+    'epos_loss_workspace_bytes': (ctypes.c_int64, [
+        ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int]),
+    'epos_loss_terms': (ctypes.c_int, [
+        vp, ctypes.c_int64, vp, vp, vp, vp, vp, vp, ctypes.c_int, ctypes.c_int64, ctypes.c_int,
+        ctypes.c_int, ctypes.c_int, vp, vp, vp, vp, vp]),
 }
 
 _lib = None

@@ -235,3 +235,21 @@ def gt_maps_device(renderer, frame, output_size, frag_pool, dataset_name=None, i
     obj_label = torch.where(obj_label == 0, torch.full_like(obj_label, int(ignore_label)),
                             obj_label)
   return obj_label, f['frag_label']
+
+
+def gt_loss_fields_device(renderer, frame, output_size, frag_pool, dataset_name=None,
+                          input_size=None, ignore_label=255):
+  """All four ground-truth maps of one frame, left on the device, as epos_amd/loss.py takes
+  them: {obj_label i32 [oh,ow], frag_label i32 [oh,ow], frag_loc f32 [oh,ow,3], frag_weight
+  f32 [oh,ow]} -- the fields gt_maps_device is built on (one assigned fragment per pixel), with
+  the same background rule of relabels_background."""
+  import torch
+  O = frag_pool[1].shape[0]
+  f = gt_fields_device(renderer, frame, output_size, frag_pool, lambda o: 1 <= o <= O,
+                       input_size)
+  obj_label = f['obj_label']
+  if relabels_background(dataset_name, frame.image_path):
+    obj_label = torch.where(obj_label == 0, torch.full_like(obj_label, int(ignore_label)),
+                            obj_label)
+  return {'obj_label': obj_label, 'frag_label': f['frag_label'], 'frag_loc': f['frag_loc'],
+          'frag_weight': f['frag_weight']}

@@ -1,0 +1,284 @@
+"""The three training losses on the device -- the validation value of what the reference
+trains on (epos_lib/loss.py:99-303, called from scripts/train.py:198-235): object
+cross-entropy, fragment cross-entropy and the fragment-localisation Huber loss, over the
+reduction of csrc/loss.hip (include/epos_hip.h, "Losses").
+
+The losses are taken from the RAW logits (EposNet.forward_logits), never from probabilities,
+and from ground-truth fields with one assigned fragment per pixel (render.gt_fields /
+epos_gt_fields: the reference's gt_knn_frags = 1, train.py:82). The dense heads stay on the
+device; what comes down is one row of (O+1) x 5 + 1 numbers per image.
+
+``total_loss`` is the sum of the three weighted losses and has NO REGULARISATION TERM, unlike
+the total of train.py:280 (tf.losses.get_total_loss adds the weight decay): it is a
+validation value, comparable between checkpoints, not the number the trainer logs.
+
+Parity with TensorFlow's numbers is unpinned: there is no TensorFlow to compare with. The
+formulas are pinned to tests/helpers/loss_ref.py and, through it, to torch's cross_entropy and
+huber_loss in fp64 (tests/test_loss_host.py; DESIGN.md, "Losses").
+
+There is no CPU fallback: without the library or a device this raises EposError.
+"""
+import ctypes
+import json
+import os
+
+from epos_amd import _lib
+from epos_amd._lib import EposError
+from epos_amd import weights as W
+
+NAMES = ('obj_cls_loss', 'frag_cls_loss', 'frag_loc_loss', 'total_loss')
+TAGS = tuple('eval/' + n for n in NAMES)
+GT_KEYS = ('obj_label', 'frag_label', 'frag_loc', 'frag_weight')
+
+
+def _ptr(t):
+  return ctypes.c_void_p(t.data_ptr()) if t is not None else None
+
+
+def _flat(t, device, dtype, numel, what):
+  if t.device != device:
+    raise EposError('%s is on %s, the losses on %s' % (what, t.device, device))
+  if t.dtype != dtype:
+    raise TypeError('%s must be %s, got %s' % (what, dtype, t.dtype))
+  t = t.contiguous().reshape(-1)
+  if t.numel() != numel:
+    raise ValueError('%s holds %d values, expected %d' % (what, t.numel(), numel))
+  return t
+
+
+def _rows(t, width):
+  """(tensor, row stride) of obj logits [..., width]: a view whose rows lie a constant stride
+  apart is taken as it is (a slice of a wider head buffer), anything else is made dense."""
+  if t.stride(-1) == 1:
+    try:
+      v = t.view(-1, width)
+      if v.shape[0] < 2 or v.stride(0) >= width:
+        return v, (v.stride(0) if v.shape[0] > 1 else width)
+    except RuntimeError:
+      pass
+  return t.contiguous().view(-1, width), width
+
+
+def loss_terms(logits, gt, ignore_label=255, out=None):
+  """epos_loss_terms over one batch. logits: the dict of EposNet.forward_logits --
+  pred_obj_conf f32 [B,h,w,O+1], pred_frag_conf f32 [B,h,w,O,F], pred_frag_loc f32
+  [B,h,w,O,F,3]; gt: {obj_label i32 [B,h,w], frag_label i32 [B,h,w], frag_loc f32 [B,h,w,3],
+  frag_weight f32 [B,h,w]} (render.gt_fields per image, stacked). Returns (sums f64 [B,O+1,3],
+  counts i64 [B,O+1,2], bad i64 [B]) on the device; `out` = three such tensors (rows of a
+  larger table) to write into. Enqueues on the current stream; does not synchronise."""
+  import torch
+  lib = _lib.load()
+  obj, frag, loc = (logits[k] for k in (W.PRED_OBJ_CONF, W.PRED_FRAG_CONF, W.PRED_FRAG_LOC))
+  if not obj.is_cuda:
+    raise EposError('the losses need a HIP device (there is no CPU fallback)')
+  dev = obj.device
+  if frag.dim() < 3 or obj.dim() < 2:
+    raise ValueError('pred_frag_conf must be [..., O, F] and pred_obj_conf [..., O+1]')
+  O, F = int(frag.shape[-2]), int(frag.shape[-1])
+  if obj.shape[-1] != O + 1:
+    raise ValueError('pred_obj_conf has %d channels, pred_frag_conf %d objects' % (
+        obj.shape[-1], O))
+  gt_obj = gt['obj_label']
+  B = int(gt_obj.shape[0]) if gt_obj.dim() > 1 else 1
+  n = gt_obj.numel()
+  if B == 0 or n % B:
+    raise ValueError('obj_label must be [B, ...] with B >= 1')
+  P = n // B
+  if obj.dtype != torch.float32 or obj.device != dev:
+    raise TypeError('pred_obj_conf must be torch.float32, got %s' % obj.dtype)
+  obj2, ld = _rows(obj, O + 1)
+  if obj2.shape[0] != n:
+    raise ValueError('pred_obj_conf holds %d rows, expected %d' % (obj2.shape[0], n))
+  frag = _flat(frag, dev, torch.float32, n * O * F, 'pred_frag_conf')
+  loc = _flat(loc, dev, torch.float32, n * O * F * 3, 'pred_frag_loc')
+  g_obj = _flat(gt_obj, dev, torch.int32, n, 'obj_label')
+  g_frag = _flat(gt['frag_label'], dev, torch.int32, n, 'frag_label')
+  g_loc = _flat(gt['frag_loc'], dev, torch.float32, n * 3, 'frag_loc')
+  g_w = _flat(gt['frag_weight'], dev, torch.float32, n, 'frag_weight')
+  if out is None:
+    out = (torch.empty((B, O + 1, 3), dtype=torch.float64, device=dev),
+           torch.empty((B, O + 1, 2), dtype=torch.int64, device=dev),
+           torch.empty((B,), dtype=torch.int64, device=dev))
+  sums, counts, bad = out
+  for t, dtype, numel, what in ((sums, torch.float64, B * (O + 1) * 3, 'sums'),
+                                (counts, torch.int64, B * (O + 1) * 2, 'counts'),
+                                (bad, torch.int64, B, 'bad')):
+    if t.device != dev or t.dtype != dtype or t.numel() != numel or not t.is_contiguous():
+      raise ValueError('out: %s must be a contiguous %s tensor of %d values on %s' % (
+          what, dtype, numel, dev))
+  nbytes = lib.epos_loss_workspace_bytes(B, P, O, F)
+  _lib.check(nbytes, 'epos_loss_workspace_bytes')
+  ws = torch.empty((max(nbytes // 8, 1),), dtype=torch.int64, device=dev)
+  stream = torch.cuda.current_stream(dev)
+  with torch.cuda.device(dev):
+    _lib.check(lib.epos_loss_terms(
+        _ptr(obj2), ld, _ptr(frag), _ptr(loc), _ptr(g_obj), _ptr(g_frag), _ptr(g_loc),
+        _ptr(g_w), B, P, O, F, int(ignore_label), _ptr(ws), _ptr(sums), _ptr(counts),
+        _ptr(bad), ctypes.c_void_p(stream.cuda_stream)), 'epos_loss_terms')
+  for t in (obj2, frag, loc, g_obj, g_frag, g_loc, g_w, ws):
+    t.record_stream(stream)           # temporaries and dense copies made here outlive the call
+  return sums, counts, bad
+
+
+def image_losses(sums, counts, weights):
+  """One image's losses as the reference's batch of one (loss.py:149,224-229,298-303), from
+  its host rows sums [O+1,3] and counts [O+1,2]:
+    obj_cls_loss  = w_obj * sum_g sums[g,0] / P -- over ALL P pixels, ignored ones included
+                    (reduce_mean runs over the weighted vector)
+    frag_cls_loss = w_cls * sum_{g>=1} sums[g,1] / n_fg
+    frag_loc_loss = w_loc * sum_{g>=1} sums[g,2] / (3 n_fg)
+  both fragment losses 0 when n_fg = 0; objects added in index order, the mean taken first and
+  the weight applied last; total_loss = their sum, without a regularisation term."""
+  w_obj, w_cls, w_loc = weights
+  P = int(counts[:, 0].sum()) + int(counts[0, 1])
+  n_fg = int(counts[1:, 0].sum())
+  s = [0.0, 0.0, 0.0]
+  for g in range(sums.shape[0]):
+    s[0] += float(sums[g, 0])
+    if g >= 1:
+      s[1] += float(sums[g, 1])
+      s[2] += float(sums[g, 2])
+  out = {'obj_cls_loss': w_obj * (s[0] / P),
+         'frag_cls_loss': w_cls * (s[1] / n_fg) if n_fg else 0.0,
+         'frag_loc_loss': w_loc * (s[2] / (3 * n_fg)) if n_fg else 0.0}
+  out['total_loss'] = (out['obj_cls_loss'] + out['frag_cls_loss']) + out['frag_loc_loss']
+  return out
+
+
+def summarize(sums, counts, bad, weights, num_objs):
+  """LossEval.result on host tables sums f64 [N,O+1,3], counts i64 [N,O+1,2], bad i64 [N]."""
+  import numpy as np
+  n_bad = int(np.asarray(bad).sum())
+  if n_bad:
+    raise EposError(
+        '%d pixel(s) carry an object label outside 0..%d, a fragment label outside the '
+        'fragments, or a weight that is not a finite number > 0' % (n_bad, num_objs))
+  if not np.isfinite(sums).all():
+    raise EposError('Loss is inf or nan.')                       # train.py:281
+  w_obj, w_cls, w_loc = weights
+  N, O1 = sums.shape[0], sums.shape[1]
+  per_image = [image_losses(sums[i], counts[i], weights) for i in range(N)]
+  mean = {}
+  for name in NAMES:
+    acc = 0.0
+    for r in per_image:
+      acc += r[name]
+    mean[name] = acc / N if N else 0.0
+  tot = np.zeros((O1, 3), np.float64)
+  n = np.zeros((O1,), np.int64)
+  pixels = 0
+  for i in range(N):                                   # image order
+    tot += sums[i]
+    n += counts[i, :, 0]
+    pixels += int(counts[i, :, 0].sum()) + int(counts[i, 0, 1])
+  n_fg = int(n[1:].sum())
+  s = [0.0, 0.0, 0.0]
+  for g in range(O1):
+    s[0] += float(tot[g, 0])
+    if g >= 1:
+      s[1] += float(tot[g, 1])
+      s[2] += float(tot[g, 2])
+  pooled = {'obj_cls_loss': w_obj * (s[0] / pixels) if pixels else 0.0,
+            'frag_cls_loss': w_cls * (s[1] / n_fg) if n_fg else 0.0,
+            'frag_loc_loss': w_loc * (s[2] / (3 * n_fg)) if n_fg else 0.0}
+  pooled['total_loss'] = ((pooled['obj_cls_loss'] + pooled['frag_cls_loss']) +
+                          pooled['frag_loc_loss'])
+  per_object = {}
+  for g in range(1, O1):
+    c = int(n[g])
+    per_object[g] = {'frag_cls_loss': w_cls * (float(tot[g, 1]) / c) if c else 0.0,
+                     'frag_loc_loss': w_loc * (float(tot[g, 2]) / (3 * c)) if c else 0.0,
+                     'pixels': c}
+  return {'per_image': per_image, 'mean': mean, 'pooled': pooled, 'per_object': per_object}
+
+
+class LossEval(object):
+  """Device-resident loss tables, one row per image: sums f64 [N,O+1,3], counts i64
+  [N,O+1,2], bad i64 [N]. The weight defaults are those of train.py:72-80."""
+
+  def __init__(self, num_objs, num_frags, device=None, obj_cls_loss_weight=1.0,
+               frag_cls_loss_weight=1.0, frag_loc_loss_weight=100.0, ignore_label=255):
+    import torch
+    if not torch.cuda.is_available():
+      raise EposError('the losses need a HIP device (there is no CPU fallback)')
+    _lib.load()
+    self.device = torch.device(device if device is not None else 'cuda:0')
+    self.num_objs, self.num_frags = int(num_objs), int(num_frags)
+    self.weights = (float(obj_cls_loss_weight), float(frag_cls_loss_weight),
+                    float(frag_loc_loss_weight))
+    self.ignore_label = int(ignore_label)
+    self.rows = 0
+    self._alloc(16)
+
+  def _alloc(self, capacity):
+    import torch
+    O1 = self.num_objs + 1
+    new = (torch.empty((capacity, O1, 3), dtype=torch.float64, device=self.device),
+           torch.empty((capacity, O1, 2), dtype=torch.int64, device=self.device),
+           torch.empty((capacity,), dtype=torch.int64, device=self.device))
+    if self.rows:
+      for dst, src in zip(new, self.tables):
+        dst[:self.rows].copy_(src[:self.rows])        # on the stream, no synchronisation
+    self.tables = new
+
+  def update(self, logits, gt_fields):
+    """Appends one row per image of the batch: logits as EposNet.forward_logits returns them,
+    gt_fields as loss_terms takes them. Enqueues on the current stream; no download, no
+    synchronisation."""
+    O, F = logits[W.PRED_FRAG_CONF].shape[-2:]
+    if (int(O), int(F)) != (self.num_objs, self.num_frags):
+      raise ValueError('logits of %d objects x %d fragments, expected %d x %d' % (
+          O, F, self.num_objs, self.num_frags))
+    B = int(gt_fields['obj_label'].shape[0])
+    capacity = self.tables[2].shape[0]
+    if self.rows + B > capacity:
+      while self.rows + B > capacity:
+        capacity *= 2
+      self._alloc(capacity)
+    r0, r1 = self.rows, self.rows + B
+    loss_terms(logits, gt_fields, self.ignore_label, out=tuple(t[r0:r1] for t in self.tables))
+    self.rows = r1
+
+  def result(self):
+    """Downloads the tables once (synchronises) and returns
+      per_image   one {obj_cls_loss, frag_cls_loss, frag_loc_loss, total_loss} per image, in
+                  the order of the updates (image_losses)
+      mean        the mean over the images of each loss -- what the reference's summaries of a
+                  batch-of-one evaluation average to
+      pooled      dataset sums over dataset counts: an image without foreground does not pull
+                  the fragment losses toward 0
+      per_object  {obj_id: {frag_cls_loss, frag_loc_loss, pixels}}, pooled per object id
+    total_loss has no regularisation term (see the module docstring). Raises EposError naming
+    the count when a bad pixel was met, and EposError('Loss is inf or nan.') when a sum is not
+    finite, as train.py:281 does."""
+    import torch
+    n, O1 = self.rows, self.num_objs + 1
+    sums, counts, bad = self.tables
+    packed = torch.cat([sums[:n].reshape(n, -1).view(torch.int64), counts[:n].reshape(n, -1),
+                        bad[:n].reshape(n, 1)], dim=1).cpu().numpy()
+    h_sums = packed[:, :3 * O1].copy().view('float64').reshape(n, O1, 3)
+    h_counts = packed[:, 3 * O1:5 * O1].reshape(n, O1, 2)
+    return summarize(h_sums, h_counts, packed[:, 5 * O1], self.weights, self.num_objs)
+
+  def write(self, log_dir, global_step, image_keys=None):
+    """losses_<step>.json -- mean, pooled, per_object, the weights, the number of images and
+    per_image keyed by image_keys ('scene_id/im_id'; the row index without) -- and one
+    TensorBoard event file with eval/obj_cls_loss, eval/frag_cls_loss, eval/frag_loc_loss and
+    eval/total_loss (the means over the images). Returns the result dict."""
+    from epos_amd import tf_events
+    res = self.result()
+    keys = [str(i) for i in range(self.rows)] if image_keys is None else list(image_keys)
+    if len(keys) != self.rows or len(set(keys)) != len(keys):
+      raise ValueError('image_keys must name each of the %d images once' % self.rows)
+    os.makedirs(log_dir, exist_ok=True)
+    doc = {'global_step': int(global_step), 'num_images': self.rows,
+           'weights': dict(zip(('obj_cls_loss_weight', 'frag_cls_loss_weight',
+                                'frag_loc_loss_weight'), self.weights)),
+           'mean': res['mean'], 'pooled': res['pooled'],
+           'per_object': {str(o): v for o, v in res['per_object'].items()},
+           'per_image': dict(zip(keys, res['per_image']))}
+    with open(os.path.join(log_dir, 'losses_{}.json'.format(global_step)), 'w') as f:
+      json.dump(doc, f)
+    res['event_file'] = tf_events.write_scalars(
+        log_dir, [(t, res['mean'][k]) for t, k in zip(TAGS, NAMES)], int(global_step))
+    return res

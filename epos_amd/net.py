@@ -121,6 +121,7 @@ class EposNet(object):
     self._glue_bytes = 0
     self._graph = None
     self._graph_sparse = None
+    self._graph_logits = None                     # forward_logits(use_graph=True)
     self._graph_alt, self.alt_skip = None, None   # measurement aid: see capture_alt()
     # Structure trace: one record per parametrised layer and a canonical expression per
     # buffer (channel slices of concat buffers separately), in the grammar of
@@ -807,10 +808,41 @@ class EposNet(object):
       self.run_plan(sparse=sparse)
     return self.outputs()
 
+  def forward_logits(self, images=None, use_graph=False):
+    """Runs the dense plan WITHOUT the softmax / argmax post-ops of model.py:677-683 and
+    returns the raw logits (model.py:396-458, reshaped as model.py:117-147) as views of the
+    head buffers, valid until the next run: {pred_obj_conf [B,h,w,O+1], pred_frag_conf
+    [B,h,w,O,F], pred_frag_loc [B,h,w,O,F,3]}. What epos_amd/loss.py computes the training
+    losses from: a cross-entropy taken from fp32 probabilities is inf as soon as the target's
+    probability underflows. use_graph replays a captured graph of its own; forward(), its graph
+    and the pipeline are untouched. The head buffers are shared with forward(): outputs()
+    after forward_logits() shows logits (and the label map of the last forward()), and the
+    next forward() overwrites them with probabilities again."""
+    if images is not None:
+      self.set_images(images)
+    if use_graph:
+      if self._graph_logits is None:
+        torch.cuda.synchronize(self.dev)
+        side = _capture_stream(self.dev)
+        with torch.cuda.stream(side):
+          self.run_plan(with_post=False)     # warm-up outside capture
+        torch.cuda.synchronize(self.dev)
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g, stream=side):
+          self.run_plan(with_post=False)
+        self._graph_logits = g
+      self._graph_logits.replay()
+    else:
+      self.run_plan(with_post=False)
+    out = self.outputs()
+    del out[W.PRED_OBJ_LABEL]
+    return out
+
   def outputs(self):
     """The prediction dict of the LAST dense run as views of the plan's HBM buffers (no
     launch): what forward() returned, for callers that read the heads after a pipeline
-    step (infer.py --vis / --save_corresp)."""
+    step (infer.py --vis / --save_corresp). After forward_logits() the three heads hold raw
+    logits, not probabilities."""
     B, h, w = self.B, self.out_h, self.out_w
     O, F = self.num_objs, self.num_frags
     return {

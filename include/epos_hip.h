@@ -1034,6 +1034,77 @@ int epos_vsd_counts(const float* depth_test, int n_images, const float* depth_mo
                     int h, int w, const EposVsdPair* pairs, EposVsdPair* pairs_dev, int n_pairs,
                     double delta, const double* taus, int n_taus, int64_t* counts, void* stream);
 
+/* ------------------------------------------------------------------------- *
+ * Losses (csrc/loss.hip; added without an ABI version change: nothing existing moved). The
+ * three training losses of epos_lib/loss.py:99-303 -- object cross-entropy, fragment
+ * cross-entropy, fragment-localisation Huber loss -- as per-image, per-object sums taken from
+ * the RAW LOGITS of the dense heads, for ground-truth fields with one assigned fragment per
+ * pixel (epos_gt_fields, the reference's gt_knn_frags = 1). The launcher only enqueues on
+ * `stream`: no allocation, no host synchronisation. tests/helpers/loss_ref.py restates every
+ * rule below in element-wise numpy. Parity with TensorFlow's numbers is unpinned (DESIGN.md,
+ * "Losses").
+ *
+ * Inputs, all [device], for B images of P = h*w pixels each (p runs over the B*P pixels):
+ *   obj_logits f32, B*P rows of O+1 values with row stride ld_obj >= O+1;
+ *   frag_logits f32 [B*P, O, F]; frag_loc f32 [B*P, O, F, 3] (the head buffers as EposNet lays
+ *   them out); gt_obj i32 [B*P]; gt_frag i32 [B*P]; gt_loc f32 [B*P, 3]; gt_weight f32 [B*P];
+ *   ignore_label. 1 <= O <= 4095, 1 <= F <= 256, 0 <= P <= 2^31.
+ * Outputs, WRITTEN, not added, one row per image (the caller points them at rows of a larger
+ * table): sums f64 [B, O+1, 3], counts i64 [B, O+1, 2], bad i64 [B]. counts[b,g,1] is 0 for
+ * g >= 1.
+ *
+ * Per pixel p of image b, with g = gt_obj[p]:
+ *   Ignored pixel. g == ignore_label: the pixel adds nothing anywhere, except
+ *     counts[b,0,1] += 1. This rule comes first.
+ *   Bad pixel. Any of the following makes the pixel add 1 to bad[b] and nothing else:
+ *     g is outside 0..O;
+ *     g is in 1..O and gt_frag[p] is outside 0..F-1;
+ *     g is in 1..O and gt_weight[p] is not a finite number > 0 (the reference divides the
+ *     weight by itself at loss.py:208-210 and would yield NaN there).
+ *   Object term, every other pixel. x is the row of O+1 logits, m = max x, and
+ *     s = sum_c exp(x_c - m) in index order; ce = log(s) + (m - x_g). All of this is in fp64 on
+ *     the fp32 values. The two summands are taken as written: both are >= 0, so nothing
+ *     cancels. sums[b,g,0] += ce and counts[b,g,0] += 1.
+ *   Fragment terms, pixels with g in 1..O.
+ *     The same ce over the F logits frag_logits[p,g-1,:] with target f = gt_frag[p], added to
+ *     sums[b,g,1]. With one assigned fragment the normalised target distribution of
+ *     loss.py:196-210 is one-hot, so the weight does not enter here.
+ *     For the three values d_k = frag_loc[p,g-1,f,k] - gt_loc[p,k] in fp64:
+ *     hub_k = |d_k| <= 1 ? 0.5 * d_k * d_k : |d_k| - 0.5. This is tf.losses.huber_loss with
+ *     delta = 1. sums[b,g,2] += gt_weight[p] * (hub_0 + hub_1 + hub_2), summed left to right.
+ *     No FMA in either formula.
+ *   Reads. Background, ignored and bad pixels read no fragment logit. A foreground pixel reads
+ *     only its object's F logits and three localisation values.
+ * A NaN or Inf logit is not a bad pixel: it makes its sum non-finite, and the host reports that.
+ *
+ * Order of the sums (no floating-point atomics). An image's pixels are cut into shares of
+ * epos_loss_share_pixels(P, O, F) consecutive pixels, the last one shorter; the share is a
+ * function of P, O and F only, never of B, and no share straddles two images. A workgroup owns
+ * one share: per cell it adds the share's terms in pixel order, starting from 0.0, and writes
+ * its partial tables to `workspace` (epos_loss_workspace_bytes(B, P, O, F) bytes, 8-byte
+ * aligned, contents undefined before and after). A closing launch adds an image's partial
+ * tables in share order, starting from 0.0. So the same input gives the same bytes on every
+ * run, and an image's rows are the same bytes alone and at any position of any batch.
+ * The one freedom inside a pixel: the L lanes that share a row (L = 1 for F <= 4, else the
+ * power of two with 2L < F <= 4L; lane j holds x_c for c mod 4L in 4j..4j+3) each add their
+ * own exponentials in index order and the L partial sums are added as a butterfly, so s -- and
+ * only s -- may differ from the index-order sum by the rounding of F (or O+1) additions.
+ *
+ * Refused with EPOS_E_INVALID before the first launch: O, F, P or B out of range (B < 0,
+ * B > 65535, B * shares per image >= 2^31), ld_obj < O+1, a null pointer or a workspace that
+ * is not 8-byte aligned when B > 0 and P > 0. B == 0 or P == 0 does nothing and returns 0.
+ * ------------------------------------------------------------------------- */
+/* Pixels per share, 0 for P == 0; EPOS_E_INVALID for sizes epos_loss_terms refuses. */
+int64_t epos_loss_share_pixels(int64_t P, int num_objs, int num_frags);
+/* Bytes of workspace one call needs: B * ceil(P / share) * (5 (O+1) + 1) * 8; 0 when B == 0
+ * or P == 0; EPOS_E_INVALID for sizes epos_loss_terms refuses. */
+int64_t epos_loss_workspace_bytes(int B, int64_t P, int num_objs, int num_frags);
+int epos_loss_terms(const float* obj_logits, int64_t ld_obj, const float* frag_logits,
+                    const float* frag_loc, const int32_t* gt_obj, const int32_t* gt_frag,
+                    const float* gt_loc, const float* gt_weight, int B, int64_t P, int num_objs,
+                    int num_frags, int ignore_label, void* workspace, double* sums,
+                    int64_t* counts, int64_t* bad, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
