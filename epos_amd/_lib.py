@@ -248,6 +248,8 @@ SYMBOLS = {
         ctypes.POINTER(PointwiseArgs), ctypes.c_int, vp]),
     'epos_heads_gemm_f32': (ctypes.c_int, [
         ctypes.POINTER(PointwiseArgs), ctypes.c_int, vp]),
+    'epos_heads_gemm_plan': (ctypes.c_int, [
+        ctypes.POINTER(PointwiseArgs), ctypes.c_int, ctypes.c_int, c_i32p]),
     'epos_conv3x3_f32': (ctypes.c_int, [ctypes.POINTER(Conv3x3Args), ctypes.c_void_p]),
     'epos_depthwise3x3_f32': (ctypes.c_int,
                               [ctypes.POINTER(DepthwiseArgs), vp]),

@@ -44,8 +44,9 @@
 // v_mfma_f32_32x32x16_f16 per column block and K step in ascending K into the same
 // accumulators in the same order (corr += ah * bm, corr += am * bh, acc += ah * bh), and the
 // same element-wise epilogue: fma(corr, 2^-11, acc) * cn * inv_a + bias. An element's value
-// does not depend on the tile or workgroup that computes it. tests/test_gpu_heads.py holds
-// the two kernels to torch.equal.
+// does not depend on the tile or workgroup that computes it. tests/test_gpu_heads.py and, per
+// launch regime, tests/test_gpu_heads_regimes.py hold the two kernels to equal bit patterns;
+// epos_heads_gemm_plan (heads_plan below) tells them that this kernel is the one that ran.
 //
 // Resources (hipcc -O3 -Rpass-analysis=kernel-resource-usage, profiles/r10/): 252 VGPRs, no
 // AGPRs, 0 bytes of scratch, 75 776 B of LDS: two workgroups = two waves per SIMD. Measured:
@@ -415,9 +416,13 @@ bool heads_eligible(const EposPointwiseArgs* args, int count) {
   return true;
 }
 
-int launch_heads_h2(const EposPointwiseArgs* args, int count, const float* zero_chunk,
-                    hipStream_t s) {
-  HeadsArgs g = {};
+namespace {
+
+// The one routine behind the launch and the plan query (epos_heads_gemm_plan): false = the
+// group falls back to the grouped GEMM; otherwise g holds the kernel's arguments but for
+// zero_chunk, and `blocks` the grid. cus = 0: the current device's count.
+bool heads_fill(const EposPointwiseArgs* args, int count, int cus, HeadsArgs& g, int& blocks) {
+  if (!h2_eligible(args, count) || !heads_eligible(args, count)) return false;
   g.count = count;
   int nt = 0;
   for (int i = 0; i < count; ++i) {
@@ -428,20 +433,48 @@ int launch_heads_h2(const EposPointwiseArgs* args, int count, const float* zero_
   for (int i = count; i <= MAX_GROUP; ++i) g.tile0[i] = nt;
   g.nt = nt;
   g.panels = static_cast<int>(ceil_div(args[0].M, HD_BM));
-  g.range = choose_range(nt, g.panels, device_cus());
+  g.range = choose_range(nt, g.panels, cus > 0 ? cus : device_cus());
   g.nr = static_cast<int>(ceil_div(nt, g.range));
-  g.zero_chunk = zero_chunk;
   int items = 0;                                     // the largest XCD's item count
   for (int x = 0; x < 8; ++x) {
     const int px = ((x + 1) * g.panels >> 3) - (x * g.panels >> 3);
     items = px * g.nr > items ? px * g.nr : items;
   }
-  if (items <= 0) return EPOS_OK;
+  blocks = 8 * items;
+  return true;
+}
+
+}  // namespace
+
+bool heads_takes(const EposPointwiseArgs* args, int count) {
+  return h2_eligible(args, count) && heads_eligible(args, count);
+}
+
+int heads_plan(const EposPointwiseArgs* args, int count, int cus, int32_t* plan) {
+  HeadsArgs g = {};
+  int blocks = 0;
+  if (!heads_fill(args, count, cus, g, blocks)) return 0;
+  if (plan) {
+    plan[0] = g.nt; plan[1] = g.panels; plan[2] = g.range; plan[3] = g.nr; plan[4] = blocks;
+  }
+  return 1;
+}
+
+int launch_heads_h2(const EposPointwiseArgs* args, int count, const float* zero_chunk,
+                    hipStream_t s) {
+  HeadsArgs g = {};
+  int blocks = 0;
+  if (!heads_fill(args, count, 0, g, blocks)) {
+    set_error("launch_heads_h2: not a group of the dense-heads kernel");
+    return EPOS_E_INVALID;
+  }
+  g.zero_chunk = zero_chunk;
+  if (blocks <= 0) return EPOS_OK;
   static LdsAttrOnce once;
   const int rc = ensure_dynamic_lds(once, reinterpret_cast<const void*>(heads_gemm_h2_f32),
                                     HD_LDS, "hipFuncSetAttribute(heads_gemm_h2_f32)");
   if (rc) return rc;
-  hipLaunchKernelGGL(heads_gemm_h2_f32, dim3(8 * items), dim3(256), HD_LDS, s, g);
+  hipLaunchKernelGGL(heads_gemm_h2_f32, dim3(blocks), dim3(256), HD_LDS, s, g);
   return launch_status("heads_gemm_h2_f32");
 }
 

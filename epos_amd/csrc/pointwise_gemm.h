@@ -40,6 +40,11 @@ bool h2_eligible(const EposPointwiseArgs* args, int count);
 // heads_gemm_h2.hip: the A-stationary form of the fp16-pair GEMM for the dense logits heads
 // (one A shared by the group, K = 256, no residual / ReLU / absmax / column sums); same bits.
 bool heads_eligible(const EposPointwiseArgs* args, int count);
+// h2_eligible && heads_eligible: the group runs on the A-stationary kernel
+bool heads_takes(const EposPointwiseArgs* args, int count);
+// epos_heads_gemm_plan: 1 and {nt, panels, range, nr, grid blocks} as the launch computes them
+// (through the same routine), 0 when the group falls back. Host code only when cus > 0.
+int heads_plan(const EposPointwiseArgs* args, int count, int cus, int32_t* plan);
 int launch_heads_h2(const EposPointwiseArgs* args, int count, const float* zero_chunk,
                     hipStream_t s);
 // pointwise_gemm_h2.hip: 16 zero bytes in device memory (nullptr during a first-use capture)

@@ -165,7 +165,7 @@ extern "C" int epos_pointwise_conv_grouped_f32(const EposPointwiseArgs* args,
 extern "C" int epos_heads_gemm_f32(const EposPointwiseArgs* args, int count, void* stream) {
   using namespace epos;
   EPOS_REQUIRE(args && count >= 1 && count <= MAX_GROUP, "1..8 problems per group");
-  if (!h2_eligible(args, count) || !heads_eligible(args, count))
+  if (!heads_takes(args, count))
     return epos_pointwise_conv_grouped_f32(args, count, stream);
   for (int i = 0; i < count; ++i) {
     EPOS_REQUIRE(args[i].reserved0 == 0, "EposPointwiseArgs.reserved0 must be 0 (ABI 7)");
@@ -177,6 +177,14 @@ extern "C" int epos_heads_gemm_f32(const EposPointwiseArgs* args, int count, voi
   EPOS_REQUIRE(z, "cannot allocate the zero chunk (first fp16-pair launch on this device "
                   "during a stream capture? launch once before capturing)");
   return launch_heads_h2(args, count, z, s);
+}
+
+extern "C" int epos_heads_gemm_plan(const EposPointwiseArgs* args, int count, int cus,
+                                    int32_t* plan) {
+  using namespace epos;
+  EPOS_REQUIRE(args && count >= 1 && count <= MAX_GROUP, "1..8 problems per group");
+  EPOS_REQUIRE(cus >= 0, "cus: 0 (the current device) or a positive count");
+  return heads_plan(args, count, cus, plan);
 }
 
 static int grouped_impl(const EposPointwiseArgs* args, int count, void* stream) {

@@ -603,6 +603,7 @@ class EposNet(object):
     # round 5.)
     # the three heads: one grouped launch; in fp32 mode on the A-stationary heads kernel
     # (csrc/heads_gemm_h2.hip, same bits; EPOS_HEADS_KERNEL=0 keeps the generic grouped GEMM)
+    self.heads_group = None      # (argument array, count) of a launch through the heads entry
     mode.flush(grp, heads=os.environ.get('EPOS_HEADS_KERNEL', '1') == '1')
     # Sparse-head mode (pipeline option): only the object head runs densely; the
     # fragment heads are evaluated per (image, target object) -- see

@@ -242,6 +242,8 @@ class Fp32Mode(object):
       part = [g for g in group if g[1].a_presplit == kind]
       arr = (_lib.PointwiseArgs * len(part))(*[g[1] for g in part])
       fn = self.heads if heads and not kind else self.gemm
+      if fn is self.heads:
+        self.net.heads_group = (arr, len(part))    # what epos_heads_gemm_plan is asked about
       self.net._launch('+'.join(g[0] for g in part), fn, (arr, len(part)), 'gemm',
                        sum(g[2] for g in part), sum(g[3] for g in part))
     del group[:]

@@ -191,6 +191,14 @@ int epos_pointwise_conv_grouped_f32(const EposPointwiseArgs* args, int count,
  * panel loaded and split once for many N tiles); any other group is passed on to
  * epos_pointwise_conv_grouped_f32. */
 int epos_heads_gemm_f32(const EposPointwiseArgs* args, int count, void* stream);
+/* Which way epos_heads_gemm_f32 would go (added without an ABI version change: nothing
+ * existing moved). Returns 1 if it would launch the A-stationary kernel for this group, 0 if it
+ * would pass the group on, < 0 for a bad count. With 1 and plan != NULL, plan[5] (host)
+ * receives what the launch computes, through the same routine: {nt = 64-column tiles per
+ * panel, panels = ceil(M / 128), range = tiles per work item, nr = ranges per panel, grid
+ * blocks}. cus: compute units to balance for; 0 = the current device's. Host code: no pointer
+ * in args is dereferenced, and with cus > 0 no device is needed. */
+int epos_heads_gemm_plan(const EposPointwiseArgs* args, int count, int cus, int32_t* plan);
 
 /* (ABI <= 6 also had a persistent stream-K form of the grouped GEMM on the fp32-MFMA ring,
  * epos_pointwise_conv_grouped_sk_f32 / _ws_f32 + a workspace: correct, tested, and slower
