@@ -18,15 +18,10 @@
 // HBM-bound byte/compare work: no MFMA here.
 #include "common.h"
 #include "closest_tri.h"
+#include "wave.h"
 
 namespace epos {
 namespace {
-
-__device__ __forceinline__ float wave_max64(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-  return v;
-}
 
 // Pixels per wave in the mask / fill kernels: the per-pixel part uses the first
 // CORR_PPW lanes, the per-fragment part all 64. A wave walks its masked pixels one after
@@ -55,7 +50,7 @@ __global__ __launch_bounds__(256) void corr_mask_kernel(
     todo &= todo - 1;
     const float* fc = frag_confs + ((pix0 + p0 + j) * O + (obj - 1)) * F;
     const float v = lane < F ? fc[lane] : -INFINITY;
-    const float m = wave_max64(v);           // corresp.py:63
+    const float m = wave_max(v);           // corresp.py:63
     const float thr = m * tau_b;             // f32 * f32 (numpy weak-scalar rule)
     const uint64_t bits = __ballot(lane < F && v > thr);   // corresp.py:64, strict >
     if (lane == j) mybits = bits;
@@ -242,7 +237,7 @@ __global__ __launch_bounds__(256) void corr_mask_wide_kernel(
     float m = v[0];
 #pragma unroll
     for (int k = 1; k < NW; ++k) m = fmaxf(m, v[k]);
-    m = wave_max64(m);                       // corresp.py:63 (max is order-independent)
+    m = wave_max(m);                       // corresp.py:63 (max is order-independent)
     const float thr = m * tau_b;             // f32 * f32 (numpy weak-scalar rule)
 #pragma unroll
     for (int k = 0; k < NW; ++k) {

@@ -28,6 +28,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "wave.h"
 
 namespace epos {
 namespace {
@@ -772,19 +773,12 @@ __global__ __launch_bounds__(256) void cvr_hypotheses(
   if (n == EP_SET) cnt = lane == 0 ? EP_SET : 0;       // the single kernel call: all inliers
   else
     for (int64_t p = lane; p < n; p += 64) cnt += ep_is_inlier(P, cam, xy, xyz, p, t2) ? 1 : 0;
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) cnt += __shfl_xor(cnt, off, 64);
+  cnt = wave_sum(cnt);
   if (lane == 0) {
     *count_out = cnt;
 #pragma unroll
     for (int i = 0; i < 12; ++i) pose_out[i] = P[i];
   }
-}
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v = v + __shfl_xor(v, off, 64);
-  return v;
 }
 
 // sums of NV values over the inlier list: 256 strided partials, butterfly, (w0+w1)+(w2+w3)

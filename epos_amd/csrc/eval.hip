@@ -14,6 +14,7 @@
 // pixels go to the global table directly, one 64-bit atomic per distinct cell and wavefront
 // step.
 #include "common.h"
+#include "wave.h"
 
 namespace epos {
 namespace {
@@ -79,7 +80,7 @@ __global__ __launch_bounds__(EVAL_THREADS) void confusion_kernel(
     }
   }
   // the whole 64 KB of LDS may be the table: `bad` is summed over each wavefront in registers
-  for (int d = 1; d < 64; d <<= 1) n_bad += __shfl_xor(n_bad, d);
+  n_bad = wave_sum(n_bad);
   if (lane == 0 && n_bad) add_u64(bad, n_bad);
   __syncthreads();
   if (LDS_TABLE)

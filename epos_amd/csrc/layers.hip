@@ -1,7 +1,7 @@
 // HBM-bound layer kernels of the EPOS network for gfx950 (NHWC fp32):
 // depthwise 3x3 (+folded BN, ReLU before/after), im2col for the two dense 3x3
-// stem convs, global average pool, bilinear resize (align_corners), grouped
-// softmax and argmax. All accesses are float4 along the channel axis (the
+// stem convs, global average pool, bilinear resize (align_corners) and argmax
+// (the grouped softmax: softmax.hip). All accesses are float4 along the channel axis (the
 // contiguous axis of NHWC), 16 B per lane, so a wave moves 1 KiB per instruction.
 #include <stdlib.h>
 
@@ -531,148 +531,6 @@ __global__ __launch_bounds__(256) void resize_bilinear_kernel(
   st4(Y + ((static_cast<int64_t>(b) * Ho + yo) * Wo + xo) * ldy + c, o);
 }
 
-// --------------------------------------------------------------------------
-// Softmax over groups of G <= 64 consecutive floats; one wave per group (G > 64: below).
-// --------------------------------------------------------------------------
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-  return v;
-}
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-__global__ __launch_bounds__(256) void softmax_groups_kernel(float* X,
-                                                             int64_t n_groups,
-                                                             int G) {
-  const int lane = threadIdx.x & 63;
-  const int64_t g = static_cast<int64_t>(blockIdx.x) * 4 + (threadIdx.x >> 6);
-  if (g >= n_groups) return;
-  float* x = X + g * G;
-  const bool on = lane < G;
-  const float v = on ? x[lane] : -INFINITY;
-  const float m = wave_max(v);
-  const float e = on ? expf(v - m) : 0.f;
-  const float s = wave_sum(e);
-  if (on) x[lane] = e / s;
-}
-
-// G == 64 (the fragment axis): a wave handles FOUR groups, 16 lanes x float4 each --
-// a quarter of the waves and fewer shuffle levels than the one-float-per-lane form. The same arithmetic (max / sum: in-lane pairs first, then the 8-4-2-1 xor
-// butterfly over the 16 lanes) is used by softmax_slots64_kernel, so dense and
-// sparse-head runs stay bit-identical.
-// (softmax64_lane16: h2_scale.h)
-// The dense fragment-confidence head is 103 MB at C2: read once, written once, re-read only
-// sparsely by the correspondence stage -- streaming (non-temporal) accesses keep it from
-// sweeping the Infinity Cache.
-typedef float sm_f32x4 __attribute__((ext_vector_type(4)));
-__global__ __launch_bounds__(256) void softmax_groups64_kernel(float* X, int64_t n_groups) {
-  const int lane = threadIdx.x & 63;
-  const int64_t g = (static_cast<int64_t>(blockIdx.x) * 4 + (threadIdx.x >> 6)) * 4 + (lane >> 4);
-  const bool on = g < n_groups;
-  float* x = X + (on ? g : 0) * 64 + (lane & 15) * 4;
-  const sm_f32x4 in = __builtin_nontemporal_load(reinterpret_cast<const sm_f32x4*>(x));
-  const float4 r = softmax64_lane16(make_float4(in[0], in[1], in[2], in[3]));   // shuffles: all lanes take part
-  if (on) {
-    const sm_f32x4 o = {r.x, r.y, r.z, r.w};
-    __builtin_nontemporal_store(o, reinterpret_cast<sm_f32x4*>(x));
-  }
-}
-
-__global__ __launch_bounds__(256) void softmax_slots64_kernel(
-    float* X, const EposCorrSlot* __restrict__ slots, int P, int O) {
-  const int lane = threadIdx.x & 63;
-  const int p = (blockIdx.x * 4 + (threadIdx.x >> 6)) * 4 + (lane >> 4);
-  const int s = blockIdx.y;
-  const int img = slots[s].image, obj = slots[s].obj_id;
-  const bool on = p < P;
-  float* x = X + ((static_cast<int64_t>(img) * P + (on ? p : 0)) * O + (obj - 1)) * 64 +
-             (lane & 15) * 4;
-  const float4 r = softmax64_lane16(ld4(x));
-  if (on) st4(x, r);
-}
-
-// Softmax over the F fragment confidences of the given (image, object) slots only
-// (sparse-head mode): group of slot s, pixel p at X + ((img*P + p)*O + obj-1)*F.
-__global__ __launch_bounds__(256) void softmax_slots_kernel(
-    float* X, const EposCorrSlot* __restrict__ slots, int P, int O, int F) {
-  const int lane = threadIdx.x & 63;
-  const int p = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (p >= P) return;
-  const int s = blockIdx.y;
-  const int img = slots[s].image, obj = slots[s].obj_id;
-  float* x = X + ((static_cast<int64_t>(img) * P + p) * O + (obj - 1)) * F;
-  const bool on = lane < F;
-  const float v = on ? x[lane] : -INFINITY;
-  const float m = wave_max(v);
-  const float e = on ? expf(v - m) : 0.f;
-  const float sum = wave_sum(e);
-  if (on) x[lane] = e / sum;
-}
-
-// 64 < G <= 256 (up to 256 fragments per object): one wave per group.
-// G == 256 on a 16-byte-aligned buffer: lane l holds values 4l..4l+3 as one float4
-// (softmax256_lane64: h2_scale.h). The dense F = 256 fragment head is 413 MB at C2, read
-// once and written once: streaming accesses, as for G == 64.
-__global__ __launch_bounds__(256) void softmax_groups256_kernel(float* X, int64_t n_groups) {
-  const int lane = threadIdx.x & 63;
-  const int64_t g = static_cast<int64_t>(blockIdx.x) * 4 + (threadIdx.x >> 6);
-  if (g >= n_groups) return;                          // wave-uniform
-  float* x = X + g * 256 + lane * 4;
-  const sm_f32x4 in = __builtin_nontemporal_load(reinterpret_cast<const sm_f32x4*>(x));
-  const float4 r = softmax256_lane64(make_float4(in[0], in[1], in[2], in[3]));
-  const sm_f32x4 o = {r.x, r.y, r.z, r.w};
-  __builtin_nontemporal_store(o, reinterpret_cast<sm_f32x4*>(x));
-}
-
-__global__ __launch_bounds__(256) void softmax_slots256_kernel(
-    float* X, const EposCorrSlot* __restrict__ slots, int P, int O) {
-  const int lane = threadIdx.x & 63;
-  const int p = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (p >= P) return;                                 // wave-uniform
-  const int s = blockIdx.y;
-  const int img = slots[s].image, obj = slots[s].obj_id;
-  float* x = X + ((static_cast<int64_t>(img) * P + p) * O + (obj - 1)) * 256 + lane * 4;
-  st4(x, softmax256_lane64(ld4(x)));
-}
-
-// Any other G in (64, 256], or an unaligned buffer: lane l owns values l, l+64, l+128,
-// l+192 (those < G); max / sum in-lane first, then the xor butterfly over the wave. ONE
-// definition for the dense and the slots kernel below. All 64 lanes must take part.
-__device__ __forceinline__ void softmax_wide(float* x, int G, int lane) {
-  float v[4];
-#pragma unroll
-  for (int k = 0; k < 4; ++k) v[k] = lane + 64 * k < G ? x[lane + 64 * k] : -INFINITY;
-  const float m = wave_max(fmaxf(fmaxf(v[0], v[1]), fmaxf(v[2], v[3])));
-#pragma unroll
-  for (int k = 0; k < 4; ++k) v[k] = lane + 64 * k < G ? expf(v[k] - m) : 0.f;
-  const float s = wave_sum((v[0] + v[1]) + (v[2] + v[3]));
-#pragma unroll
-  for (int k = 0; k < 4; ++k)
-    if (lane + 64 * k < G) x[lane + 64 * k] = v[k] / s;
-}
-
-__global__ __launch_bounds__(256) void softmax_groups_wide_kernel(float* X, int64_t n_groups,
-                                                                  int G) {
-  const int lane = threadIdx.x & 63;
-  const int64_t g = static_cast<int64_t>(blockIdx.x) * 4 + (threadIdx.x >> 6);
-  if (g >= n_groups) return;                          // wave-uniform
-  softmax_wide(X + g * G, G, lane);
-}
-
-__global__ __launch_bounds__(256) void softmax_slots_wide_kernel(
-    float* X, const EposCorrSlot* __restrict__ slots, int P, int O, int F) {
-  const int lane = threadIdx.x & 63;
-  const int p = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (p >= P) return;                                 // wave-uniform
-  const int s = blockIdx.y;
-  const int img = slots[s].image, obj = slots[s].obj_id;
-  softmax_wide(X + ((static_cast<int64_t>(img) * P + p) * O + (obj - 1)) * F, F, lane);
-}
-
 __global__ __launch_bounds__(256) void argmax_kernel(const float* X, int64_t ldx,
                                                      int64_t* labels, int64_t P,
                                                      int C) {
@@ -1027,32 +885,6 @@ extern "C" int epos_resize_bilinear_f32(const float* X, int64_t ldx, float* Y,
   return launch_status("resize_bilinear_kernel");
 }
 
-extern "C" int epos_softmax_groups_f32(float* X, int64_t n_groups, int G,
-                                       void* stream) {
-  EPOS_REQUIRE(X, "null pointer");
-  EPOS_REQUIRE(G >= 1 && G <= 256, "G must be in [1, 256]");
-  if (n_groups == 0) return EPOS_OK;
-  if (G > 64) {
-    if (G == 256 && (reinterpret_cast<uintptr_t>(X) & 15) == 0) {
-      hipLaunchKernelGGL(softmax_groups256_kernel, dim3(blocks_for(n_groups, 4)), dim3(256),
-                         0, static_cast<hipStream_t>(stream), X, n_groups);
-      return launch_status("softmax_groups256_kernel");
-    }
-    hipLaunchKernelGGL(softmax_groups_wide_kernel, dim3(blocks_for(n_groups, 4)), dim3(256),
-                       0, static_cast<hipStream_t>(stream), X, n_groups, G);
-    return launch_status("softmax_groups_wide_kernel");
-  }
-  if (G == 64 && (reinterpret_cast<uintptr_t>(X) & 15) == 0) {
-    hipLaunchKernelGGL(softmax_groups64_kernel, dim3(blocks_for(n_groups, 16)), dim3(256),
-                       0, static_cast<hipStream_t>(stream), X, n_groups);
-    return launch_status("softmax_groups64_kernel");
-  }
-  hipLaunchKernelGGL(softmax_groups_kernel, dim3(blocks_for(n_groups, 4)),
-                     dim3(256), 0, static_cast<hipStream_t>(stream), X, n_groups,
-                     G);
-  return launch_status("softmax_groups_kernel");
-}
-
 extern "C" int epos_argmax_i64(const float* X, int64_t ldx, int64_t* labels,
                                int64_t P, int C, void* stream) {
   EPOS_REQUIRE(X && labels, "null pointer");
@@ -1129,29 +961,4 @@ extern "C" int epos_add_relu_f32(const float* A, const float* B, float* Y,
   hipLaunchKernelGGL(add_relu_kernel, dim3(blocks_for(n / 4, 256)), dim3(256), 0,
                      static_cast<hipStream_t>(stream), A, B, Y, n / 4);
   return launch_status("add_relu_kernel");
-}
-
-extern "C" int epos_softmax_slots_f32(float* X, const EposCorrSlot* slots, int S,
-                                      int P, int O, int F, void* stream) {
-  EPOS_REQUIRE(X && slots, "null pointer");
-  EPOS_REQUIRE(F >= 1 && F <= 256, "F must be in [1, 256]");
-  if (S == 0 || P == 0) return EPOS_OK;
-  if (F > 64) {
-    if (F == 256 && (reinterpret_cast<uintptr_t>(X) & 15) == 0) {
-      hipLaunchKernelGGL(softmax_slots256_kernel, dim3(blocks_for(P, 4), S), dim3(256), 0,
-                         static_cast<hipStream_t>(stream), X, slots, P, O);
-      return launch_status("softmax_slots256_kernel");
-    }
-    hipLaunchKernelGGL(softmax_slots_wide_kernel, dim3(blocks_for(P, 4), S), dim3(256), 0,
-                       static_cast<hipStream_t>(stream), X, slots, P, O, F);
-    return launch_status("softmax_slots_wide_kernel");
-  }
-  if (F == 64 && (reinterpret_cast<uintptr_t>(X) & 15) == 0) {
-    hipLaunchKernelGGL(softmax_slots64_kernel, dim3(blocks_for(P, 16), S), dim3(256), 0,
-                       static_cast<hipStream_t>(stream), X, slots, P, O);
-    return launch_status("softmax_slots64_kernel");
-  }
-  hipLaunchKernelGGL(softmax_slots_kernel, dim3(blocks_for(P, 4), S), dim3(256), 0,
-                     static_cast<hipStream_t>(stream), X, slots, P, O, F);
-  return launch_status("softmax_slots_kernel");
 }

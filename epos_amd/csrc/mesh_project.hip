@@ -17,21 +17,13 @@
 #include "common.h"
 #include "closest_tri.h"
 #include "slot_search.h"
+#include "wave.h"
 
 namespace epos {
 namespace {
 
 constexpr int MP_LEVELS = 4;           // box levels of EposMeshRec
 constexpr int MP_BLOCKS = 4096;        // workgroups of 4 waves; the waves stride over the rows
-
-__device__ __forceinline__ double wave_min_f64(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const double t = __shfl_xor(v, o, 64);
-    v = t < v ? t : v;
-  }
-  return v;
-}
 
 // Squared distance from p to box `lane` of a group (6 x 64 doubles: lo xyz, hi xyz), with the
 // operations of the d2 of a face -- differences, squares, (x + y) + z -- so that rounding is
@@ -102,7 +94,7 @@ __global__ __launch_bounds__(256) void project_rows_kernel(
           mine = d2; bf = f; bq[0] = q[0]; bq[1] = q[1]; bq[2] = q[2];
         }
       }
-      best = wave_min_f64(mine);
+      best = wave_min(mine);
       ++nvis;
     };
 
@@ -130,7 +122,7 @@ __global__ __launch_bounds__(256) void project_rows_kernel(
         if (pd) {
           const double b = MP_SEL(lvl, bnd);
           const bool todo = (pd >> lane) & 1;
-          const double mb = wave_min_f64(todo ? b : INFINITY);
+          const double mb = wave_min(todo ? b : INFINITY);
           // ascending bounds: once the smallest exceeds the best, so do the others
           if (!(mb > best)) j = __ffsll(static_cast<long long>(__ballot(todo && b == mb))) - 1;
         }

@@ -39,6 +39,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "wave.h"
 
 namespace epos {
 namespace {
@@ -285,17 +286,6 @@ __device__ int p3p(const double* f, const double* X, double* pose) {
 }
 
 // -------------------------------------------------------------- scoring --
-__device__ __forceinline__ double butterfly_sum(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v = v + __shfl_xor(v, off, 64);
-  return v;
-}
-__device__ __forceinline__ int butterfly_sum_i(int v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-
 // returns true if behind the camera; else e2 / Xc / r are set
 __device__ __forceinline__ bool reproj(const double* pose, const double* K,
                                        const double* xy, const double* xyz,
@@ -373,8 +363,8 @@ __device__ void score_poses(const double* poses, int ns, const double* K,
 #pragma unroll
   for (int q = 0; q < MAX_SOL; ++q) {
     if (q < ns) {
-      count[q] = butterfly_sum_i(cnt[q]);
-      score[q] = butterfly_sum(acc[q]);
+      count[q] = wave_sum(cnt[q]);
+      score[q] = wave_sum(acc[q]);
     }
   }
 }
@@ -734,7 +724,7 @@ struct LoSync {
   unsigned epoch;       // exchanges done so far in this launch
 };
 
-// The wave sums of up to 32 quantities at once. A butterfly per quantity (butterfly_sum:
+// The wave sums of up to 32 quantities at once. A butterfly per quantity (wave_sum:
 // xor 32, 16, ... 1, every lane ends with the total) moves 6 x 2 words per quantity; here the
 // first five levels HALVE the set instead -- at the level of xor-distance d a lane keeps the
 // quantities whose next index bit equals its own bit d and receives its partner's copies of
@@ -1130,12 +1120,6 @@ struct NbLists {
   const uint16_t* cnt;
   const int16_t* pool;
 };
-
-__device__ __forceinline__ int64_t butterfly_sum_i64(int64_t v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
 
 // Visits every ACTIVE neighbour of point p (slot-local index): f(q, valid), q = the
 // neighbour's POSITION in the row-sorted order (its index if the slot is not sorted) -- f is
@@ -1843,8 +1827,8 @@ __global__ __launch_bounds__(256) void ransac_refit_accept(
         inter += __popcll(a & b);
         uni += __popcll(a | b);
       }
-      inter = butterfly_sum_i(inter);
-      uni = butterfly_sum_i(uni);
+      inter = wave_sum(inter);
+      uni = wave_sum(uni);
       if (static_cast<double>(inter) >= prm.max_tanimoto_similarity * static_cast<double>(uni)) ok = false;
     }
     if (ok && static_cast<double>(n_new) < prm.min_coverage * static_cast<double>(n_inl)) ok = false;
@@ -2060,8 +2044,8 @@ __global__ __launch_bounds__(256) void pearl_energy(
                          deg += valid;
                          diff += valid && lo != lp;
                        });
-    diff = butterfly_sum_i(diff);
-    deg = butterfly_sum_i(deg);
+    diff = wave_sum(diff);
+    deg = wave_sum(deg);
     if (lane == 0) {
       // the FRACTION of disagreeing neighbours (degree-normalised Potts)
       if (deg > 0)
@@ -2140,7 +2124,7 @@ __global__ __launch_bounds__(256) void pearl_sweep(
                                });
 #pragma unroll
       for (int i = 0; i < 3; ++i) {
-        pk[i] = static_cast<unsigned>(butterfly_sum_i(static_cast<int>(pk[i])));
+        pk[i] = wave_sum(pk[i]);
 #pragma unroll
         for (int j = 0; j < 3; ++j) {
           const int c = static_cast<int>((pk[i] >> (10 * j)) & 1023u);
@@ -2161,7 +2145,7 @@ __global__ __launch_bounds__(256) void pearl_sweep(
                                 });
 #pragma unroll
       for (int m = 0; m <= PEARL_MAX_K; ++m) {
-        cnt[m] = butterfly_sum_i(cnt[m]);
+        cnt[m] = wave_sum(cnt[m]);
         deg += cnt[m];
         mine = lane == m ? cnt[m] : mine;
       }
@@ -2234,7 +2218,7 @@ __global__ __launch_bounds__(256) void pearl_refit(
     for (int i = 0; i < 12; ++i) pose[i] = poses[(static_cast<int64_t>(s) * max_k + m) * 12 + i];
     int c = 0;
     for (int64_t i = t; i < n; i += 256) c += lab[i] == m;
-    c = butterfly_sum_i(c);
+    c = wave_sum(c);
     if ((t & 63) == 0) s_cnt[t >> 6] = c;
     __syncthreads();
     c = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];

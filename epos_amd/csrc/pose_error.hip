@@ -17,6 +17,7 @@
 //                         non-negative double
 //   pose_finish_kernel    the one sqrt of MSSD and MSPD
 #include "common.h"
+#include "wave.h"
 
 namespace epos {
 namespace {
@@ -128,14 +129,6 @@ __global__ __launch_bounds__(PE_THREADS) void pose_adi_kernel(
   const double total = tree_sum(part, p);
   if (threadIdx.x == 0)
     err[4 * static_cast<int64_t>(blockIdx.x) + 3] = total / static_cast<double>(n);
-}
-
-__device__ __forceinline__ double wave_max(double v) {
-  for (int d = 1; d < 64; d <<= 1) {
-    const double o = __shfl_xor(v, d);
-    v = o > v ? o : v;
-  }
-  return v;
 }
 
 __global__ __launch_bounds__(PE_THREADS) void pose_ms_kernel(

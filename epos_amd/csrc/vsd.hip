@@ -18,6 +18,7 @@
 #include <math.h>
 
 #include "common.h"
+#include "wave.h"
 
 namespace epos {
 namespace {
@@ -36,11 +37,6 @@ constexpr int VSD_MAX_COUNTERS = VSD_FIXED + VSD_MAX_TAUS;
 struct VsdTaus {
   double v[VSD_MAX_TAUS];
 };
-
-__device__ __forceinline__ unsigned wave_sum(unsigned v) {
-  for (int d = 1; d < 64; d <<= 1) v += __shfl_xor(v, d);
-  return v;
-}
 
 __global__ __launch_bounds__(VSD_THREADS) void vsd_counts_kernel(
     const float* __restrict__ depth_test, const float* __restrict__ depth_model, int h, int w,

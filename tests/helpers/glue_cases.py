@@ -1,8 +1,8 @@
 """Shape tables of the glue-layer and correspondence kernels (tests/test_gpu_glue_layers.py,
 tests/test_gpu_corresp_regimes.py) and, per kernel, a host-side mirror of what its launcher and
-the kernel itself branch on (epos_amd/csrc/layers.hip, bf16.hip, corresp.hip), in the style of
-tests/helpers/dw_regimes.py. Pure Python: tests/test_glue_cases_host.py checks without a GPU that
-every table reaches every regime its mirror distinguishes.
+the kernel itself branch on (epos_amd/csrc/layers.hip, softmax.hip, bf16.hip, corresp.hip), in the
+style of tests/helpers/dw_regimes.py. Pure Python: tests/test_glue_cases_host.py checks without a
+GPU that every table reaches every regime its mirror distinguishes.
 
 Offsets are in ELEMENTS of the tensor's type, from the start of an allocation the caching
 allocator hands out 512-byte aligned. Every tensor stays below 64 MB (but the [B, P, O, F, 3]
@@ -263,31 +263,57 @@ ARGMAX = [
 ]
 
 # ------------------------------------------------------------------------------- softmax ---
-# G <= 64. G == 64 on a 16-byte aligned base: softmax_groups64_kernel, 16 groups per workgroup;
-# otherwise softmax_groups_kernel, one wave per group, 4 per workgroup. The slot form
-# (epos_softmax_slots_f32) picks its kernel by the same rule.
+# softmax_launch (csrc/softmax.hip) picks one of four row forms from (G, alignment of the base),
+# the same for epos_softmax_groups_f32 and epos_softmax_slots_f32:
+#   'vec4x16'   G == 64, 16-byte aligned: 16 lanes x float4 per row, 16 rows per workgroup; a
+#               lane past the last row takes row 0 and stores nothing
+#   'strided1'  any other G <= 64: one value per lane, one wave per row, 4 rows per workgroup
+#   'vec4x64'   G == 256, 16-byte aligned: 64 lanes x float4, 4 rows per workgroup
+#   'strided4'  any other G in (64, 256]: lane l owns values l + 64k, 4 rows per workgroup
+# The rows of a launch are the n groups (dense) or the P pixels of each slot (softmax_slots).
 Softmax = _nt('Softmax', 'name g n off seed', off=0, seed=0)
 SoftmaxRegime = collections.namedtuple('SoftmaxRegime', 'kernel per_block blocks partial_block')
 
 
 def softmax_regime(g, n, off):
-  assert 1 <= g <= 64
-  k = 'groups64' if g == 64 and (4 * off) % 16 == 0 else 'generic'
-  per = 16 if k == 'groups64' else 4
+  assert 1 <= g <= 256
+  aligned = (4 * off) % 16 == 0
+  if g > 64:
+    k = 'vec4x64' if g == 256 and aligned else 'strided4'
+  else:
+    k = 'vec4x16' if g == 64 and aligned else 'strided1'
+  per = 16 if k == 'vec4x16' else 4
   return SoftmaxRegime(k, per, _cdiv(n, per), n % per != 0)
+
+
+def softmax_slots(n):
+  """(B, O, P, slots) of the slot form of a case with n groups: its first B * P * O groups laid
+  out as [B, P, O, G], softmax on the listed (image, object) slots only."""
+  if n >= 6:
+    return 2, 3, n // 6, [(0, 2), (1, 1), (1, 3)]
+  return 1, 1, n, [(0, 1)]
 
 
 SOFTMAX = [Softmax('g%d_n1000' % g, g, 1000) for g in (2, 22, 31, 64)] + [   # the old test
     Softmax('g1_n1000', 1, 1000),
     Softmax('g33_n1000_off1', 33, 1000, off=1),
     Softmax('g63_n1000', 63, 1000),
-    Softmax('g64_n1000_off1', 64, 1000, off=1),               # unaligned: the generic kernel
+    Softmax('g64_n1000_off1', 64, 1000, off=1),               # unaligned: one value per lane
     Softmax('g64_n1000_off4', 64, 1000, off=4),               # aligned again
     Softmax('g64_n1', 64, 1), Softmax('g64_n3', 64, 3), Softmax('g64_n17', 64, 17),
     Softmax('g22_n1', 22, 1), Softmax('g22_n3', 22, 3), Softmax('g22_n17', 22, 17),
     Softmax('g64_n1024', 64, 1024),                           # full workgroups only
     Softmax('c2_g64_n76800', 64, 19200 * 4),                  # 120x160, four objects' fragments
     Softmax('c2_g22_n19200', 22, 19200),                      # the object head of C2
+    # 64 < G <= 256
+    Softmax('g65_n1', 65, 1), Softmax('g65_n3', 65, 3), Softmax('g65_n17', 65, 17),
+    Softmax('g128_n1000', 128, 1000),
+    Softmax('g255_n17_off1', 255, 17, off=1),
+    Softmax('g256_n1', 256, 1), Softmax('g256_n3', 256, 3), Softmax('g256_n17', 256, 17),
+    Softmax('g256_n1000', 256, 1000),
+    Softmax('g256_n1000_off1', 256, 1000, off=1),             # unaligned: the strided form
+    Softmax('g256_n1000_off4', 256, 1000, off=4),             # aligned again
+    Softmax('g128_n24', 128, 24), Softmax('g256_n24', 256, 24),   # slots: P = 4, one full workgroup
 ]
 
 # ------------------------------------------------------------------------------- scatter ---

@@ -75,11 +75,19 @@ def test_mirrors_give_the_values_worked_out_by_hand():
   assert gc.add_relu_regime(2056, vec=8) == (257, 2, True)
   assert gc.argmax_regime(1000, 22, 22) == (4, True, False, False)
   assert gc.argmax_regime(256, 1, 3) == (1, False, True, True)
-  # softmax: G = 64 takes the 16-groups-per-workgroup kernel only on a 16-byte aligned base
-  assert gc.softmax_regime(64, 17, 0) == ('groups64', 16, 2, True)
-  assert gc.softmax_regime(64, 17, 1) == ('generic', 4, 5, True)
-  assert gc.softmax_regime(64, 17, 4).kernel == 'groups64'
-  assert gc.softmax_regime(63, 1000, 0) == ('generic', 4, 250, False)
+  # softmax: G = 64 takes the 16-rows-per-workgroup form only on a 16-byte aligned base, G = 256
+  # the float4 form likewise
+  assert gc.softmax_regime(64, 17, 0) == ('vec4x16', 16, 2, True)
+  assert gc.softmax_regime(64, 17, 1) == ('strided1', 4, 5, True)
+  assert gc.softmax_regime(64, 17, 4).kernel == 'vec4x16'
+  assert gc.softmax_regime(63, 1000, 0) == ('strided1', 4, 250, False)
+  assert gc.softmax_regime(65, 17, 0) == ('strided4', 4, 5, True)
+  assert gc.softmax_regime(256, 17, 0) == ('vec4x64', 4, 5, True)
+  assert gc.softmax_regime(256, 1000, 1) == ('strided4', 4, 250, False)
+  assert gc.softmax_regime(256, 1000, 4).kernel == 'vec4x64'
+  assert gc.softmax_regime(255, 17, 0).kernel == 'strided4'
+  assert gc.softmax_slots(1000) == (2, 3, 166, [(0, 2), (1, 1), (1, 3)])
+  assert gc.softmax_slots(3) == (1, 1, 3, [(0, 1)])
   assert gc.scatter_regime(4, 64) == (256, 1, False)
   # scan: 19200 elements in chunks of 4096 when aligned, of 1024 otherwise
   r = gc.corr_regime(64, 19200)
@@ -214,14 +222,23 @@ def test_add_relu_argmax_softmax_scatter_tables_cover_every_regime():
   assert any(c.p >= 19200 for c in gc.ARGMAX)
   regs = {c.name: gc.softmax_regime(c.g, c.n, c.off) for c in gc.SOFTMAX}
   case = gc.by_name(gc.SOFTMAX)
-  assert {1, 2, 22, 31, 33, 63, 64} <= {c.g for c in gc.SOFTMAX}
-  assert any(case[n].g == 64 and r.kernel == 'generic' for n, r in regs.items()), \
-      'G = 64 at an unaligned base'
-  assert any(case[n].g == 64 and case[n].off and r.kernel == 'groups64' for n, r in regs.items())
-  for k in ('groups64', 'generic'):
+  assert {1, 2, 22, 31, 33, 63, 64, 65, 128, 255, 256} <= {c.g for c in gc.SOFTMAX}
+  for g, vec, other in ((64, 'vec4x16', 'strided1'), (256, 'vec4x64', 'strided4')):
+    assert any(case[n].g == g and r.kernel == other for n, r in regs.items()), \
+        'G = %d at an unaligned base' % g
+    assert any(case[n].g == g and case[n].off and r.kernel == vec for n, r in regs.items())
+  # every form x {dense rows, slot rows} x {one row, a partial last workgroup, full workgroups}
+  slot_regs = {c.name: gc.softmax_regime(c.g, gc.softmax_slots(c.n)[2], c.off)
+               for c in gc.SOFTMAX}
+  for k in ('vec4x16', 'strided1', 'vec4x64', 'strided4'):
     ns = {case[n].n for n, r in regs.items() if r.kernel == k}
     assert {1, 3, 17} <= ns, (k, 'n_groups of 1, 3, 17')
-    assert any(r.kernel == k and not r.partial_block for r in regs.values())
+    for rows, rg in (('dense', regs), ('slots', slot_regs)):
+      of_k = [r for r in rg.values() if r.kernel == k]
+      assert any(r.blocks == 1 and r.partial_block for r in of_k), (k, rows)
+      assert any(r.blocks > 1 and r.partial_block for r in of_k), (k, rows)
+      assert any(not r.partial_block for r in of_k), (k, rows)
+    assert any(gc.softmax_slots(case[n].n)[2] == 1 for n, r in regs.items() if r.kernel == k)
   assert all(c.n == 1000 for c in gc.SOFTMAX[:4]) and [c.g for c in gc.SOFTMAX[:4]] == \
       [2, 22, 31, 64], 'the old test'
   regs = [gc.scatter_regime(c.n_blocks, c.width) for c in gc.SCATTER]
