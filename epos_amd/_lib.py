@@ -379,6 +379,14 @@ SYMBOLS = {
     'epos_loss_terms': (ctypes.c_int, [
         vp, ctypes.c_int64, vp, vp, vp, vp, vp, vp, ctypes.c_int, ctypes.c_int64, ctypes.c_int,
         ctypes.c_int, ctypes.c_int, vp, vp, vp, vp, vp]),
+    'epos_loss_reduce': (ctypes.c_int, [
+        vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double,
+        ctypes.c_int, vp, vp, vp]),
+    'epos_loss_grad_share_pixels': (ctypes.c_int64, [
+        ctypes.c_int64, ctypes.c_int, ctypes.c_int]),
+    'epos_loss_grads': (ctypes.c_int, [
+        vp, ctypes.c_int64, vp, vp, vp, vp, vp, vp, ctypes.c_int, ctypes.c_int64, ctypes.c_int,
+        ctypes.c_int, ctypes.c_int, vp, vp, vp, ctypes.c_int64, vp, vp, vp]),
 }
 
 _lib = None

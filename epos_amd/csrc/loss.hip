@@ -15,26 +15,17 @@
 //
 // fp64 on the fp32 values, -ffp-contract=off (no FMA). Background, ignored and bad pixels read
 // no fragment value; a foreground pixel reads its object's F logits and 3 localisation values.
-#include <math.h>
-
-#include "common.h"
+#include "loss_rows.h"
 
 namespace epos {
 namespace {
 
-constexpr int LOSS_THREADS = 256;
 constexpr int64_t LOSS_SHARE_MIN = 64, LOSS_SHARE_MAX = 1024;
 // per image: a workgroup of a 120 x 160 head makes four passes over its 64 pixels at F = 64,
 // each a chain of dependent loads, so short shares and many workgroups hide more of them
 // (shares of 128: 0.098 instead of 0.055 ms at B = 1, profiles/r19/)
 constexpr int64_t LOSS_TARGET_BLOCKS = 1024;
 constexpr int CLOSE_DEPTH = 16;                    // partial tables whose loads are in flight
-constexpr int LOSS_MAX_OBJS = 4095, LOSS_MAX_FRAGS = 256;
-constexpr int64_t LOSS_MAX_PIXELS = int64_t(1) << 31;
-constexpr int64_t LOSS_MAX_BLOCKS = (int64_t(1) << 31) - 1;
-
-// classes of a pixel slot in LDS besides 0..O
-constexpr int CODE_IGNORED = -1, CODE_BAD = -2, CODE_NONE = -3;
 
 // pixels per workgroup: a function of P only (never of B)
 inline int64_t loss_share(int64_t P) {
@@ -45,21 +36,6 @@ inline int64_t loss_share(int64_t P) {
 // 8-byte words of one workgroup's workspace row: sums f64 [O+1,3], counts i64 [O+1,2], bad
 inline int64_t loss_row_words(int num_objs) { return int64_t(num_objs + 1) * 5 + 1; }
 
-// The lane's part of a row of n values: four consecutive values per step, steps 4 * L apart
-// (one 16-byte load per whole quad when VEC). fn(value) is called in index order.
-template <bool VEC, typename Fn>
-__device__ __forceinline__ void for_lane_values(const float* __restrict__ row, int n, int sub,
-                                                int L, Fn fn) {
-  for (int c = 4 * sub; c < n; c += 4 * L) {
-    if (VEC && c + 4 <= n) {
-      const float4 v = *reinterpret_cast<const float4*>(row + c);
-      fn(v.x); fn(v.y); fn(v.z); fn(v.w);
-    } else {
-      for (int k = 0; k < 4 && c + k < n; ++k) fn(row[c + k]);
-    }
-  }
-}
-
 // ce = log(sum_c exp(x_c - m)) + (m - x_t) of the row the L lanes of a pixel share; every lane
 // of the L takes part (inactive pixels with active = false: they read nothing), lane sub == 0
 // of an active pixel holds the result. The lanes' partial sums are added in a butterfly, each
@@ -67,15 +43,8 @@ __device__ __forceinline__ void for_lane_values(const float* __restrict__ row, i
 template <bool VEC>
 __device__ __forceinline__ double row_cross_entropy(const float* __restrict__ row, int n,
                                                     int target, bool active, int sub, int L) {
-  float m = -INFINITY;
-  if (active) for_lane_values<VEC>(row, n, sub, L, [&](float v) { m = fmaxf(m, v); });
-  for (int d = 1; d < L; d <<= 1) m = fmaxf(m, __shfl_xor(m, d));
-  const double md = static_cast<double>(m);
-  double s = 0.0;
-  if (active)
-    for_lane_values<VEC>(row, n, sub, L,
-                         [&](float v) { s += exp(static_cast<double>(v) - md); });
-  for (int d = 1; d < L; d <<= 1) s += __shfl_xor(s, d);
+  double md, s;
+  row_max_sum<VEC>(row, n, active, sub, L, md, s);
   if (!active || sub != 0) return 0.0;
   return log(s) + (md - static_cast<double>(row[target]));
 }
@@ -105,19 +74,8 @@ __global__ __launch_bounds__(LOSS_THREADS) void loss_terms_kernel(
     const int64_t p = image * P + p0 + i;         // pixel of the whole batch
     int g = CODE_NONE, f = 0;
     float wgt = 0.f;
-    if (i < n_here) {
-      g = gt_obj[p];
-      if (g == ignore_label) {
-        g = CODE_IGNORED;
-      } else if (g < 0 || g > num_objs) {
-        g = CODE_BAD;
-      } else if (g > 0) {
-        f = gt_frag[p];
-        wgt = gt_weight[p];
-        // !(w > 0) is true for a NaN; an infinite weight is refused as well
-        if (f < 0 || f >= num_frags || !(wgt > 0.f) || wgt == INFINITY) g = CODE_BAD;
-      }
-    }
+    if (i < n_here)
+      g = pixel_class(gt_obj, gt_frag, gt_weight, p, num_objs, num_frags, ignore_label, f, wgt);
     const double ce_obj = row_cross_entropy<VEC_OBJ>(obj_logits + p * ld_obj, num_objs + 1, g,
                                                      g >= 0, sub, L);
     const int64_t frag_row = g > 0 ? (p * num_objs + (g - 1)) * num_frags : 0;
@@ -198,17 +156,7 @@ __global__ __launch_bounds__(LOSS_THREADS) void loss_close_kernel(
 }
 
 int check_dims(const char* fn, int B, int64_t P, int num_objs, int num_frags) {
-  const char* msg = nullptr;
-  if (B < 0) msg = "B must be >= 0";
-  else if (P < 0 || P > LOSS_MAX_PIXELS) msg = "P must be in 0..2^31";
-  else if (num_objs < 1 || num_objs > LOSS_MAX_OBJS) msg = "num_objs must be in 1..4095";
-  else if (num_frags < 1 || num_frags > LOSS_MAX_FRAGS) msg = "num_frags must be in 1..256";
-  else if (B > 0 && P > 0 && ceil_div(P, loss_share(P)) > LOSS_MAX_BLOCKS / B)
-    msg = "B * workgroups per image must be below 2^31";
-  else if (B > 65535) msg = "B must be <= 65535";
-  if (!msg) return EPOS_OK;
-  set_error("%s: %s", fn, msg);
-  return EPOS_E_INVALID;
+  return check_loss_dims(fn, B, P, num_objs, num_frags, loss_share(P));
 }
 
 }  // namespace
@@ -242,8 +190,7 @@ extern "C" int epos_loss_terms(const float* obj_logits, int64_t ld_obj, const fl
   EPOS_REQUIRE(reinterpret_cast<uintptr_t>(workspace) % 8 == 0, "workspace must be 8-byte aligned");
   const int64_t share = loss_share(P);
   const int64_t per_image = ceil_div(P, share);
-  int L = 1;
-  while (4 * L < num_frags) L <<= 1;              // 1..64 lanes per pixel
+  const int L = loss_lanes(num_frags);            // 1..64 lanes per pixel
   // 16-byte loads where every row starts on a 16-byte boundary
   const bool vec_obj = ld_obj % 4 == 0 && reinterpret_cast<uintptr_t>(obj_logits) % 16 == 0;
   const bool vec_frag = num_frags % 4 == 0 && reinterpret_cast<uintptr_t>(frag_logits) % 16 == 0;

@@ -16,6 +16,13 @@ Parity with TensorFlow's numbers is unpinned: there is no TensorFlow to compare 
 formulas are pinned to tests/helpers/loss_ref.py and, through it, to torch's cross_entropy and
 huber_loss in fp64 (tests/test_loss_host.py; DESIGN.md, "Losses").
 
+Gradients (csrc/loss_grad.hip; DESIGN.md, "Losses", "Gradients"): loss_values reduces the
+tables to the batch's four values and the per-image gradient factors, loss_grads writes the
+derivative with respect to the three logit tensors, and differentiable_losses puts both behind
+a torch.autograd.Function, so that an optimiser and torch's own conv backward can fine-tune the
+logits layers on EposNet.decoder_out. Pinned to tests/helpers/loss_grad_ref.py and, through it,
+to torch's fp64 autograd; parity with TensorFlow's gradients is unpinned.
+
 There is no CPU fallback: without the library or a device this raises EposError.
 """
 import ctypes
@@ -282,3 +289,178 @@ class LossEval(object):
     res['event_file'] = tf_events.write_scalars(
         log_dir, [(t, res['mean'][k]) for t, k in zip(TAGS, NAMES)], int(global_step))
     return res
+
+
+# ------------------------------------------------------------------ gradients ---
+REDUCTIONS = {'mean': 0, 'pooled': 1}        # EPOS_LOSS_MEAN, EPOS_LOSS_POOLED
+
+
+def loss_values(sums, counts, weights, reduction='mean', out=None):
+  """epos_loss_reduce over the tables loss_terms wrote (device tensors sums f64 [B,O+1,3],
+  counts i64 [B,O+1,2]): returns (values f64 [4], scales f64 [B,3]) on the device -- the
+  batch's weighted obj_cls_loss, frag_cls_loss, frag_loc_loss and total_loss, bit-equal to
+  summarize(...)['mean'] or ['pooled'], and the per-image factors loss_grads multiplies the
+  per-pixel derivatives with. weights = (w_obj, w_cls, w_loc); `out` = two such tensors to
+  write into. Enqueues on the current stream; does not synchronise."""
+  import torch
+  lib = _lib.load()
+  if reduction not in REDUCTIONS:
+    raise ValueError("reduction must be 'mean' or 'pooled', got %r" % (reduction,))
+  if not sums.is_cuda:
+    raise EposError('the losses need a HIP device (there is no CPU fallback)')
+  dev = sums.device
+  if sums.dim() != 3 or sums.shape[0] < 1 or sums.shape[2] != 3:
+    raise ValueError('sums must be [B, O+1, 3] with B >= 1')
+  B, O1 = int(sums.shape[0]), int(sums.shape[1])
+  if out is None:
+    out = (torch.empty((4,), dtype=torch.float64, device=dev),
+           torch.empty((B, 3), dtype=torch.float64, device=dev))
+  values, scales = out
+  for t, dtype, numel, what in ((sums, torch.float64, B * O1 * 3, 'sums'),
+                                (counts, torch.int64, B * O1 * 2, 'counts'),
+                                (values, torch.float64, 4, 'values'),
+                                (scales, torch.float64, B * 3, 'scales')):
+    if t.device != dev or t.dtype != dtype or t.numel() != numel or not t.is_contiguous():
+      raise ValueError('%s must be a contiguous %s tensor of %d values on %s' % (
+          what, dtype, numel, dev))
+  w_obj, w_cls, w_loc = (float(w) for w in weights)
+  stream = torch.cuda.current_stream(dev)
+  with torch.cuda.device(dev):
+    _lib.check(lib.epos_loss_reduce(
+        _ptr(sums), _ptr(counts), B, O1 - 1, w_obj, w_cls, w_loc, REDUCTIONS[reduction],
+        _ptr(values), _ptr(scales), ctypes.c_void_p(stream.cuda_stream)), 'epos_loss_reduce')
+  return values, scales
+
+
+def loss_grads(logits, gt, scales, upstream=None, ignore_label=255, need=(True, True, True),
+               out=None):
+  """epos_loss_grads over one batch: the derivative of the losses with respect to the three
+  logit tensors. logits and gt as loss_terms takes them; scales f64 [B,3] from loss_values;
+  upstream f64 [4] on the device (the gradient arriving at loss_values' values; None = the
+  total loss alone). Returns (d_obj, d_frag, d_loc), f32 tensors shaped like pred_obj_conf,
+  pred_frag_conf and pred_frag_loc with EVERY element written, None where need[k] is false
+  (that head is then neither read nor written). `out` = three tensors (or None) to write into;
+  a d_obj whose rows lie a constant stride apart keeps its padding columns. Ignored and bad
+  pixels get zero gradient. Enqueues on the current stream; does not synchronise."""
+  import torch
+  lib = _lib.load()
+  obj, frag, loc = (logits[k] for k in (W.PRED_OBJ_CONF, W.PRED_FRAG_CONF, W.PRED_FRAG_LOC))
+  if not obj.is_cuda:
+    raise EposError('the losses need a HIP device (there is no CPU fallback)')
+  dev = obj.device
+  if frag.dim() < 3 or obj.dim() < 2:
+    raise ValueError('pred_frag_conf must be [..., O, F] and pred_obj_conf [..., O+1]')
+  O, F = int(frag.shape[-2]), int(frag.shape[-1])
+  if obj.shape[-1] != O + 1:
+    raise ValueError('pred_obj_conf has %d channels, pred_frag_conf %d objects' % (
+        obj.shape[-1], O))
+  gt_obj = gt['obj_label']
+  B = int(gt_obj.shape[0]) if gt_obj.dim() > 1 else 1
+  n = gt_obj.numel()
+  if B == 0 or n % B:
+    raise ValueError('obj_label must be [B, ...] with B >= 1')
+  P = n // B
+  if obj.dtype != torch.float32:
+    raise TypeError('pred_obj_conf must be torch.float32, got %s' % obj.dtype)
+  obj2, ld = _rows(obj, O + 1)
+  if obj2.shape[0] != n:
+    raise ValueError('pred_obj_conf holds %d rows, expected %d' % (obj2.shape[0], n))
+  ins = [obj2,
+         _flat(frag, dev, torch.float32, n * O * F, 'pred_frag_conf'),
+         _flat(loc, dev, torch.float32, n * O * F * 3, 'pred_frag_loc'),
+         _flat(gt_obj, dev, torch.int32, n, 'obj_label'),
+         _flat(gt['frag_label'], dev, torch.int32, n, 'frag_label'),
+         _flat(gt['frag_loc'], dev, torch.float32, n * 3, 'frag_loc'),
+         _flat(gt['frag_weight'], dev, torch.float32, n, 'frag_weight'),
+         _flat(scales, dev, torch.float64, B * 3, 'scales')]
+  if upstream is not None:
+    ins.append(_flat(upstream, dev, torch.float64, 4, 'upstream'))
+  outs = list(out) if out is not None else [None, None, None]
+  shapes = (obj.shape, frag.shape, loc.shape)
+  for k in range(3):
+    if not need[k]:
+      outs[k] = None
+    elif outs[k] is None:
+      outs[k] = torch.empty(shapes[k], dtype=torch.float32, device=dev)
+    elif (outs[k].device != dev or outs[k].dtype != torch.float32 or
+          outs[k].shape != shapes[k] or (k > 0 and not outs[k].is_contiguous())):
+      raise ValueError('out[%d] must be a float32 tensor of shape %s on %s%s' % (
+          k, tuple(shapes[k]), dev, ', contiguous' if k else ''))
+  d_obj2, ld_d = None, O + 1
+  if outs[0] is not None:
+    d_obj2, ld_d = _rows(outs[0], O + 1)
+    if d_obj2.data_ptr() != outs[0].data_ptr():
+      raise ValueError('out[0]: the rows of d_obj must lie a constant stride apart')
+  stream = torch.cuda.current_stream(dev)
+  with torch.cuda.device(dev):
+    _lib.check(lib.epos_loss_grads(
+        _ptr(ins[0]), ld, _ptr(ins[1]), _ptr(ins[2]), _ptr(ins[3]), _ptr(ins[4]), _ptr(ins[5]),
+        _ptr(ins[6]), B, P, O, F, int(ignore_label), _ptr(ins[7]),
+        _ptr(ins[8]) if upstream is not None else None, _ptr(d_obj2), ld_d, _ptr(outs[1]),
+        _ptr(outs[2]), ctypes.c_void_p(stream.cuda_stream)), 'epos_loss_grads')
+  for t in ins:
+    t.record_stream(stream)           # temporaries and dense copies made here outlive the call
+  return tuple(outs)
+
+
+_function = None
+
+
+def _losses_function():
+  """The torch.autograd.Function behind differentiable_losses, defined at first use: this
+  module imports without torch."""
+  global _function
+  if _function is not None:
+    return _function
+  import torch
+  from torch.autograd.function import once_differentiable
+
+  class EposLosses(torch.autograd.Function):
+
+    @staticmethod
+    def forward(ctx, obj, frag, loc, gt_obj, gt_frag, gt_loc, gt_weight, weights, reduction,
+                ignore_label):
+      logits = {W.PRED_OBJ_CONF: obj, W.PRED_FRAG_CONF: frag, W.PRED_FRAG_LOC: loc}
+      gt = dict(zip(GT_KEYS, (gt_obj, gt_frag, gt_loc, gt_weight)))
+      sums, counts, bad = loss_terms(logits, gt, ignore_label)
+      values, scales = loss_values(sums, counts, weights, reduction)
+      ctx.save_for_backward(obj, frag, loc, gt_obj, gt_frag, gt_loc, gt_weight, scales)
+      ctx.ignore_label = ignore_label
+      ctx.mark_non_differentiable(bad)
+      return values, bad
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_values, grad_bad):
+      obj, frag, loc, gt_obj, gt_frag, gt_loc, gt_weight, scales = ctx.saved_tensors
+      logits = {W.PRED_OBJ_CONF: obj, W.PRED_FRAG_CONF: frag, W.PRED_FRAG_LOC: loc}
+      gt = dict(zip(GT_KEYS, (gt_obj, gt_frag, gt_loc, gt_weight)))
+      grads = loss_grads(logits, gt, scales, upstream=grad_values.to(torch.float64),
+                         ignore_label=ctx.ignore_label, need=tuple(ctx.needs_input_grad[:3]))
+      return grads + (None,) * 7
+
+  _function = EposLosses
+  return _function
+
+
+def differentiable_losses(logits, gt, weights=(1.0, 1.0, 100.0), reduction='mean',
+                          ignore_label=255):
+  """The three losses of one batch as a differentiable device tensor. logits and gt as
+  loss_terms takes them (the logits, e.g., from torch's own convolutions on
+  EposNet.decoder_out). Returns (values, bad): values f64 [4] on the device -- obj_cls_loss,
+  frag_cls_loss, frag_loc_loss, total_loss, bit-equal to LossEval's 'mean' (or 'pooled') for
+  the same batch -- carrying a grad_fn whose backward is epos_loss_grads, once differentiable,
+  run only for the logit tensors that need a gradient; bad i64 [B], the bad-pixel counts.
+  Nothing synchronises: the caller decides when to look at `bad`. Bad and ignored pixels get
+  ZERO gradient and add nothing to the values -- a batch with bad pixels is not refused here as
+  LossEval.result refuses it. total_loss has no regularisation term (module docstring)."""
+  import torch
+  _lib.load()
+  obj = logits[W.PRED_OBJ_CONF]
+  if not torch.cuda.is_available() or not obj.is_cuda:
+    raise EposError('the losses need a HIP device (there is no CPU fallback)')
+  if reduction not in REDUCTIONS:
+    raise ValueError("reduction must be 'mean' or 'pooled', got %r" % (reduction,))
+  return _losses_function().apply(
+      obj, logits[W.PRED_FRAG_CONF], logits[W.PRED_FRAG_LOC], *(gt[k] for k in GT_KEYS),
+      tuple(float(w) for w in weights), reduction, int(ignore_label))

@@ -818,7 +818,10 @@ class EposNet(object):
     probability underflows. use_graph replays a captured graph of its own; forward(), its graph
     and the pipeline are untouched. The head buffers are shared with forward(): outputs()
     after forward_logits() shows logits (and the label map of the last forward()), and the
-    next forward() overwrites them with probabilities again."""
+    next forward() overwrites them with probabilities again. The three logits layers read
+    self.decoder_out ([B,h,w,256], fp32; a bf16 tensor in bf16 mode), valid as long: the tensor to
+    put torch's own convolutions on when fine-tuning those layers against
+    loss.differentiable_losses."""
     if images is not None:
       self.set_images(images)
     if use_graph:

@@ -1113,6 +1113,74 @@ int epos_loss_terms(const float* obj_logits, int64_t ld_obj, const float* frag_l
                     int num_frags, int ignore_label, void* workspace, double* sums,
                     int64_t* counts, int64_t* bad, void* stream);
 
+/* Loss values and gradients (csrc/loss_grad.hip; added without an ABI version change).
+ * tests/helpers/loss_grad_ref.py restates every rule below in element-wise numpy; through it
+ * the formulas are pinned to torch's fp64 autograd. Parity with TensorFlow's gradients is
+ * unpinned, as for the forward.
+ *
+ * epos_loss_reduce reads the tables epos_loss_terms wrote, sums f64 [B,O+1,3] and counts i64
+ * [B,O+1,2] [device], and WRITES values f64 [4] -- obj_cls_loss, frag_cls_loss, frag_loc_loss,
+ * total_loss of the batch, weighted -- and scales f64 [B,3], the per-image factors of the
+ * gradient [device]. Per image P_b = sum_g counts[b,g,0] + counts[b,0,1] and
+ * n_b = sum_{g>=1} counts[b,g,0]; objects are added in index order, the mean is taken first
+ * and the weight applied last, as epos_amd/loss.py image_losses does.
+ *   EPOS_LOSS_MEAN: the mean over the images of the per-image losses (a fragment loss of an
+ *     image with n_b == 0 is 0): values[k] = (sum_b l_bk) / B, the images added in order from
+ *     0.0, `/ B` last, for k = 0..2 and for the per-image totals (l_b0 + l_b1) + l_b2 (k = 3):
+ *     bit-equal to loss.summarize(...)['mean'] on the same tables. So values[3] is the mean of
+ *     the totals; it equals (values[0] + values[1]) + values[2] up to the rounding of B sums.
+ *     scales[b] = { w_obj / (P_b * B), w_cls / (n_b * B), w_loc / (3 * n_b * B) }, each one
+ *     fp64 division by the exactly representable integer product; the two fragment factors
+ *     are 0 when n_b == 0.
+ *   EPOS_LOSS_POOLED: the batch as one example set (what the reference's trainer does with a
+ *     batch): per table cell the images added in order, then the objects in order;
+ *     values[3] = (values[0] + values[1]) + values[2]; bit-equal to summarize(...)['pooled'].
+ *     scales[b] = { w_obj / sum P, w_cls / N_fg, w_loc / (3 N_fg) } for every b, the fragment
+ *     factors 0 when N_fg == 0.
+ * One launch of one workgroup, no floating-point atomics, no allocation, no synchronisation.
+ * Refused with EPOS_E_INVALID: B < 0, num_objs outside 1..4095, an unknown reduction, a null
+ * pointer when B > 0. B == 0 returns 0 and writes nothing.
+ *
+ * epos_loss_grads WRITES the derivative of sum_k u_k * values[k]'s three losses with respect to
+ * the three logit tensors: u_k = upstream[k] + upstream[3] (upstream f64 [4] [device], read on
+ * the device; NULL means {0,0,0,1}) and s_k = scales[b,k] * u_k, one fp64 product. Inputs as
+ * for epos_loss_terms; d_obj f32 with row stride ld_dobj >= O+1, d_frag f32 [B*P,O,F], d_loc
+ * f32 [B*P,O,F,3]. The pixel rules are the forward's: ignored first, then bad, then
+ * background, then foreground g in 1..O with fragment f and weight w. For every pixel p:
+ *   d_obj[p,c], c in 0..O: +0.0 for an ignored or bad pixel, otherwise
+ *     fl32( s_0 * (exp(x_c - m) / S - [c == g]) ) with m = max x and S = sum_c exp(x_c - m) in
+ *     fp64 on the fp32 values, S added as in the forward (each lane its own values in index
+ *     order, then a butterfly over the L lanes of the row): the only freedom in the result.
+ *   d_frag[p,o,c]: the row o == g-1 of a foreground pixel is
+ *     fl32( s_1 * (exp(x_c - m) / S - [c == f]) ) over that row's F logits; +0.0 elsewhere.
+ *   d_loc[p,o,c,k]: the three values at (g-1, f) of a foreground pixel are
+ *     fl32( s_2 * ( (double)w * clamp((double)q_k - (double)t_k, -1, 1) ) ), q = frag_loc,
+ *     t = gt_loc, in that order of operations without FMA: the derivative of the Huber term,
+ *     knee included (|d| <= 1 gives d); +0.0 elsewhere.
+ * EVERY element is written -- the caller zeroes nothing -- except the ld_dobj - (O+1) padding
+ * columns of d_obj, which are not touched. Any of d_obj, d_frag, d_loc may be NULL: that head
+ * is skipped, neither loaded for nor stored to; all three NULL returns 0 and launches nothing.
+ * A non-finite logit makes the elements of its own row non-finite and no others; that is not
+ * an error. A workgroup owns epos_loss_grad_share_pixels(P, O, F) consecutive pixels of one
+ * image -- a function of P alone, 0 for P == 0 -- and every element is computed from its own
+ * pixel and s_k only: one launch, no allocation, no synchronisation, no atomics, capturable
+ * in a graph, the same bytes in every run.
+ * Refused with EPOS_E_INVALID before the launch: the sizes epos_loss_terms refuses, ld_obj or
+ * ld_dobj < O+1, a null input (scales included) when B > 0 and P > 0, an output buffer that
+ * starts at an input pointer. B == 0 or P == 0 does nothing and returns 0. */
+#define EPOS_LOSS_MEAN 0
+#define EPOS_LOSS_POOLED 1
+int epos_loss_reduce(const double* sums, const int64_t* counts, int B, int num_objs,
+                     double w_obj, double w_cls, double w_loc, int reduction,
+                     double* values /* [4] */, double* scales /* [B,3] */, void* stream);
+int64_t epos_loss_grad_share_pixels(int64_t P, int num_objs, int num_frags);
+int epos_loss_grads(const float* obj_logits, int64_t ld_obj, const float* frag_logits,
+                    const float* frag_loc, const int32_t* gt_obj, const int32_t* gt_frag,
+                    const float* gt_loc, const float* gt_weight, int B, int64_t P,
+                    int num_objs, int num_frags, int ignore_label, const double* scales,
+                    const double* upstream /* device [4], or NULL = {0,0,0,1} */,
+                    float* d_obj, int64_t ld_dobj, float* d_frag, float* d_loc, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
