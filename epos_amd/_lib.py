@@ -387,6 +387,18 @@ SYMBOLS = {
     'epos_loss_grads': (ctypes.c_int, [
         vp, ctypes.c_int64, vp, vp, vp, vp, vp, vp, ctypes.c_int, ctypes.c_int64, ctypes.c_int,
         ctypes.c_int, ctypes.c_int, vp, vp, vp, ctypes.c_int64, vp, vp, vp]),
+    # weight gradients of the logits layers, momentum step
+    'epos_heads_wgrad_workspace_bytes': (ctypes.c_int64, [
+        ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    'epos_heads_wgrad_range_pixels': (ctypes.c_int64, [
+        ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    'epos_heads_wgrad_f32': (ctypes.c_int, [
+        vp, ctypes.c_int64, ctypes.c_int, vp, ctypes.c_int64, vp, vp, vp, vp, vp, vp,
+        ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp, vp,
+        vp, vp, vp, vp, vp, vp, vp]),
+    'epos_momentum_step_f32': (ctypes.c_int, [
+        vp, vp, vp, ctypes.c_int64, ctypes.c_float, ctypes.c_float, ctypes.c_float,
+        ctypes.c_float, vp]),
 }
 
 _lib = None

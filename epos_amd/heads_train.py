@@ -1,0 +1,229 @@
+"""The logits layers' weight gradients and the reference's optimiser step on the device
+(csrc/heads_wgrad.hip; include/epos_hip.h, "Weight gradients"; DESIGN.md, "Losses", "Weight
+gradients"): the next piece of a trainer after loss.differentiable_losses.
+
+  heads_weight_grads  epos_heads_wgrad_f32: dW and db of logits/pred_obj_conf, pred_frag_conf
+                      and pred_frag_loc from EposNet.decoder_out and the raw logits, without the
+                      dense logit gradients.
+  momentum_step       epos_momentum_step_f32: tf.train.MomentumOptimizer on the regularised,
+                      multiplied gradient (train.py:340-384), in place.
+  net_head_grads      from a net that has run forward_logits to checkpoint-shaped gradients.
+  HeadsOptimizer      fp32 master copies and accumulators of the six variables.
+
+Out of scope here: putting updated weights back into a built EposNet (the weight packers are
+host functions: a new net, or infer.py, picks the weights up from a checkpoint written from
+HeadsOptimizer.state()), the training loop, the learning-rate schedules, backpropagation below
+the logits, bf16 mode and multi-scale nets.
+
+Pinned to tests/helpers/heads_wgrad_ref.py and, through loss_grad_ref.py, to torch's fp64
+autograd; parity with TensorFlow's numbers is unpinned, as for the losses. There is no CPU
+fallback: without the library or a device this raises EposError.
+"""
+import ctypes
+
+from epos_amd import _lib
+from epos_amd._lib import EposError
+from epos_amd import loss as L
+from epos_amd import weights as W
+
+HEADS = (W.PRED_OBJ_CONF, W.PRED_FRAG_CONF, W.PRED_FRAG_LOC)
+
+
+def variable_names(head):
+  """(weights, biases): the checkpoint variable names of a logits layer."""
+  return 'logits/%s/weights' % head, 'logits/%s/biases' % head
+
+
+def heads_weight_grads(features, logits, gt, scales, upstream=None, ignore_label=255,
+                       need=(True, True, True), out=None, workspace=None):
+  """epos_heads_wgrad_f32 over one batch. features: the tensor the logits layers read
+  (EposNet.decoder_out), f32 [B,h,w,K] or [B*P,K], rows a constant stride apart; logits, gt,
+  scales, upstream as loss.loss_grads takes them. Returns {head name: (dW f32 [K,N], db f32
+  [N])} for pred_obj_conf (N = O+1), pred_frag_conf (O*F) and pred_frag_loc (O*F*3), None for a
+  head with need[k] false (it is then neither read nor written). `out` = {head name: (dW, db)}
+  of tensors to write into (either may be None: not computed); `workspace` = an int64 tensor of
+  at least epos_heads_wgrad_workspace_bytes / 8 values. Every element of every output is
+  written. Enqueues on the current stream; does not synchronise."""
+  import torch
+  lib = _lib.load()
+  obj, frag, loc = (logits[k] for k in HEADS)
+  if not obj.is_cuda:
+    raise EposError('the weight gradients need a HIP device (there is no CPU fallback)')
+  dev = obj.device
+  if frag.dim() < 3 or obj.dim() < 2:
+    raise ValueError('pred_frag_conf must be [..., O, F] and pred_obj_conf [..., O+1]')
+  O, F = int(frag.shape[-2]), int(frag.shape[-1])
+  if obj.shape[-1] != O + 1:
+    raise ValueError('pred_obj_conf has %d channels, pred_frag_conf %d objects' % (
+        obj.shape[-1], O))
+  gt_obj = gt['obj_label']
+  B = int(gt_obj.shape[0]) if gt_obj.dim() > 1 else 1
+  n = gt_obj.numel()
+  if B == 0 or n % B:
+    raise ValueError('obj_label must be [B, ...] with B >= 1')
+  P = n // B
+  if features.device != dev:
+    raise EposError('features are on %s, the logits on %s' % (features.device, dev))
+  if features.dtype != torch.float32:
+    raise TypeError('features must be torch.float32, got %s (a bf16 decoder_out is not '
+                    'supported: run the net with precision=\'fp32\')' % features.dtype)
+  if obj.dtype != torch.float32:
+    raise TypeError('pred_obj_conf must be torch.float32, got %s' % obj.dtype)
+  K = int(features.shape[-1])
+  feat2, lda = L._rows(features, K)
+  if feat2.shape[0] != n:
+    raise ValueError('features hold %d rows, expected %d' % (feat2.shape[0], n))
+  obj2, ld = L._rows(obj, O + 1)
+  if obj2.shape[0] != n:
+    raise ValueError('pred_obj_conf holds %d rows, expected %d' % (obj2.shape[0], n))
+  ins = [feat2, obj2,
+         L._flat(frag, dev, torch.float32, n * O * F, 'pred_frag_conf'),
+         L._flat(loc, dev, torch.float32, n * O * F * 3, 'pred_frag_loc'),
+         L._flat(gt_obj, dev, torch.int32, n, 'obj_label'),
+         L._flat(gt['frag_label'], dev, torch.int32, n, 'frag_label'),
+         L._flat(gt['frag_loc'], dev, torch.float32, n * 3, 'frag_loc'),
+         L._flat(gt['frag_weight'], dev, torch.float32, n, 'frag_weight'),
+         L._flat(scales, dev, torch.float64, B * 3, 'scales')]
+  up = None
+  if upstream is not None:
+    up = L._flat(upstream, dev, torch.float64, 4, 'upstream')
+    ins.append(up)
+  widths = (O + 1, O * F, O * F * 3)
+  result, ptrs = {}, []
+  for k, head in enumerate(HEADS):
+    pair = [None, None]
+    if need[k]:
+      given = (out or {}).get(head)
+      for j, shape in enumerate(((K, widths[k]), (widths[k],))):
+        if given is None:
+          pair[j] = torch.empty(shape, dtype=torch.float32, device=dev)
+        elif given[j] is not None:
+          t = given[j]
+          if (t.device != dev or t.dtype != torch.float32 or tuple(t.shape) != shape or
+              not t.is_contiguous()):
+            raise ValueError('out[%r][%d] must be a contiguous float32 tensor of shape %s on '
+                             '%s' % (head, j, shape, dev))
+          pair[j] = t
+    ptrs += pair
+    result[head] = tuple(pair) if need[k] else None
+  nbytes = lib.epos_heads_wgrad_workspace_bytes(B, P, O, F, K)
+  _lib.check(nbytes, 'epos_heads_wgrad_workspace_bytes')
+  if workspace is None:
+    ws = torch.empty(((nbytes + 7) // 8 or 1,), dtype=torch.int64, device=dev)
+  else:
+    ws = workspace
+    if (ws.device != dev or not ws.is_contiguous() or
+        ws.numel() * ws.element_size() < nbytes):
+      raise ValueError('workspace must be a contiguous tensor of at least %d bytes on %s' % (
+          nbytes, dev))
+  stream = torch.cuda.current_stream(dev)
+  with torch.cuda.device(dev):
+    _lib.check(lib.epos_heads_wgrad_f32(
+        L._ptr(ins[0]), lda, K, L._ptr(ins[1]), ld, L._ptr(ins[2]), L._ptr(ins[3]),
+        L._ptr(ins[4]), L._ptr(ins[5]), L._ptr(ins[6]), L._ptr(ins[7]), B, P, O, F,
+        int(ignore_label), L._ptr(ins[8]), L._ptr(up), L._ptr(ws), *[L._ptr(t) for t in ptrs],
+        ctypes.c_void_p(stream.cuda_stream)), 'epos_heads_wgrad_f32')
+  for t in ins + [ws]:
+    t.record_stream(stream)           # temporaries and dense copies made here outlive the call
+  return result
+
+
+def momentum_step(param, accum, grad, lr, momentum=0.9, weight_decay=0.0, grad_mult=1.0):
+  """epos_momentum_step_f32, in place on param and accum (f32, contiguous, on the device):
+  g = grad_mult * (grad + weight_decay * param); accum = momentum * accum + g;
+  param = param - lr * accum, each operation rounded once in fp32. Enqueues on the current
+  stream; does not synchronise."""
+  import torch
+  lib = _lib.load()
+  if not param.is_cuda:
+    raise EposError('the momentum step needs a HIP device (there is no CPU fallback)')
+  n = param.numel()
+  for t, what in ((param, 'param'), (accum, 'accum'), (grad, 'grad')):
+    if (t.device != param.device or t.dtype != torch.float32 or t.numel() != n or
+        not t.is_contiguous()):
+      raise ValueError('%s must be a contiguous float32 tensor of %d values on %s' % (
+          what, n, param.device))
+  stream = torch.cuda.current_stream(param.device)
+  with torch.cuda.device(param.device):
+    _lib.check(lib.epos_momentum_step_f32(
+        L._ptr(param), L._ptr(accum), L._ptr(grad), n, float(lr), float(momentum),
+        float(weight_decay), float(grad_mult), ctypes.c_void_p(stream.cuda_stream)),
+               'epos_momentum_step_f32')
+  return param
+
+
+def net_head_grads(net, gt, weights=(1.0, 1.0, 100.0), reduction='pooled', ignore_label=255):
+  """From a running network to checkpoint-shaped gradients: call after net.forward_logits().
+  Runs loss_terms -> loss_values -> heads_weight_grads on net.decoder_out and the net's logits.
+  Returns (values f64 [4], bad i64 [B], grads): values and bad as loss.differentiable_losses
+  returns them, grads = {'logits/<name>/weights': f32 [1,1,K,N], 'logits/<name>/biases': f32
+  [N]} on the device. fp32 single-scale nets only. Does not synchronise."""
+  import torch
+  feats = net.decoder_out
+  if feats.dtype != torch.float32:
+    raise TypeError('net_head_grads needs an fp32 net: decoder_out is %s' % feats.dtype)
+  B, h, w = int(feats.shape[0]), int(feats.shape[1]), int(feats.shape[2])
+  O, F = int(net.num_objs), int(net.num_frags)
+  logits = {W.PRED_OBJ_CONF: net.logits[W.PRED_OBJ_CONF],
+            W.PRED_FRAG_CONF: net.logits[W.PRED_FRAG_CONF].view(B, h, w, O, F),
+            W.PRED_FRAG_LOC: net.logits[W.PRED_FRAG_LOC].view(B, h, w, O, F, 3)}
+  sums, counts, bad = L.loss_terms(logits, gt, ignore_label)
+  values, scales = L.loss_values(sums, counts, weights, reduction)
+  raw = heads_weight_grads(feats, logits, gt, scales, ignore_label=ignore_label)
+  grads = {}
+  for head in HEADS:
+    dW, db = raw[head]
+    wname, bname = variable_names(head)
+    grads[wname] = dW.view(1, 1, dW.shape[0], dW.shape[1])
+    grads[bname] = db
+  return values, bad, grads
+
+
+class HeadsOptimizer(object):
+  """fp32 master copies and momentum accumulators of the six logits variables on the device.
+  variables: {'logits/<name>/weights': [1,1,K,N], 'logits/<name>/biases': [N]} (numpy arrays or
+  tensors; other keys are ignored). step(grads) applies momentum_step per variable as the
+  reference's trainer does: weights get the multiplier m = last_layer_gradient_multiplier and
+  the l2 decay, biases 2 * m and no decay (train_utils.py:84-114)."""
+
+  def __init__(self, variables, lr, momentum=0.9, weight_decay=4e-5,
+               last_layer_gradient_multiplier=1.0, device=None):
+    import torch
+    if not torch.cuda.is_available():
+      raise EposError('the optimiser needs a HIP device (there is no CPU fallback)')
+    _lib.load()
+    self.device = torch.device(device if device is not None else 'cuda:0')
+    self.lr, self.momentum = float(lr), float(momentum)
+    self.weight_decay = float(weight_decay)
+    self.multiplier = float(last_layer_gradient_multiplier)
+    self.params, self.accums = {}, {}
+    for head in HEADS:
+      for name in variable_names(head):
+        if name not in variables:
+          raise KeyError('variables lack %r' % name)
+        v = torch.as_tensor(variables[name]).to(device=self.device, dtype=torch.float32)
+        self.params[name] = v.contiguous().clone()
+        self.accums[name] = torch.zeros_like(self.params[name])
+
+  def step(self, grads, lr=None):
+    """One update of every variable from grads (as net_head_grads returns them). lr overrides
+    the constructor's for this step (the schedules are the caller's)."""
+    lr = self.lr if lr is None else float(lr)
+    for name, param in self.params.items():
+      g = grads[name]
+      if g.numel() != param.numel():
+        raise ValueError('%s: gradient of %d values, variable of %d' % (
+            name, g.numel(), param.numel()))
+      bias = name.endswith('/biases')
+      momentum_step(param, self.accums[name], g.contiguous().view(param.shape), lr,
+                    self.momentum, 0.0 if bias else self.weight_decay,
+                    2.0 * self.multiplier if bias else self.multiplier)
+
+  def state(self, with_slots=True):
+    """{variable name: numpy array} for tf_checkpoint.write_checkpoint: the six variables and,
+    with_slots, their '<name>/Momentum' accumulators. Synchronises."""
+    out = {name: p.cpu().numpy() for name, p in self.params.items()}
+    if with_slots:
+      for name, a in self.accums.items():
+        out[name + '/Momentum'] = a.cpu().numpy()
+    return out

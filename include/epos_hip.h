@@ -1181,6 +1181,86 @@ int epos_loss_grads(const float* obj_logits, int64_t ld_obj, const float* frag_l
                     const double* upstream /* device [4], or NULL = {0,0,0,1} */,
                     float* d_obj, int64_t ld_dobj, float* d_frag, float* d_loc, void* stream);
 
+/* Weight gradients (csrc/heads_wgrad.hip; added without an ABI version change). The gradient
+ * of the losses with respect to the weights and biases of the three logits layers
+ * (logits/pred_obj_conf, logits/pred_frag_conf, logits/pred_frag_loc: 1x1 convolutions on
+ * EposNet.decoder_out), taken WITHOUT forming the dense logit gradients, and the optimiser
+ * step of the reference's trainer. tests/helpers/heads_wgrad_ref.py restates both in numpy.
+ *
+ * epos_heads_wgrad_f32. A f32 [device]: the tensor the logits layers read, B*P rows of K
+ * values with row stride lda >= K, 1 <= K <= 1024. The next sixteen arguments are exactly the
+ * inputs of epos_loss_grads. Outputs f32 [device], row-major in the layout of the checkpoint
+ * variables logits/<name>/weights [1,1,K,N] and biases [N]: dW_obj [K, O+1], db_obj [O+1],
+ * dW_frag [K, O*F], db_frag [O*F], dW_loc [K, O*F*3], db_loc [O*F*3]. All outputs are WRITTEN,
+ * not added, every element of them, +0.0 for an object or a fragment without a pixel. A head
+ * whose dW and db are both NULL is skipped and nothing of it is loaded; dW NULL with db
+ * non-NULL, and the reverse, are allowed.
+ *   Definition. Let d_obj, d_frag, d_loc be the f32 values epos_loss_grads is specified to
+ *   write for the same inputs (the fl32-rounded values, with its m, its S and its butterfly
+ *   over the L lanes of a row). Then for each head h
+ *     dW_h[k,n] = fl32( sum_p (double)A[p,k] * (double)d_h[p,n] )
+ *     db_h[n]   = fl32( sum_p (double)d_h[p,n] )
+ *   over the B*P pixels, accumulated in fp64 (the product of two fp32 values is exact in fp64)
+ *   and rounded to f32 once, at the end. The sum runs over the pixels for which column n is
+ *   ACTIVE only: the O+1 object values of a pixel that is neither ignored nor bad, the F values
+ *   of the row g-1 and the three values at (g-1, f) of a foreground pixel. The other d values
+ *   are +0.0 and are not multiplied: a non-finite feature or logit makes the columns its pixel
+ *   touches non-finite and no others; ignored and bad pixels contribute nothing.
+ *   Never dense. The kernels compute each pixel's active values themselves; neither a kernel
+ *   nor the workspace holds a row of width O*F or O*F*3 per pixel. With N = O+1 + 4*O*F, the
+ *   number of columns of the three heads together, an image's pixels are cut into
+ *     R = 1 when N < 10, else min(8, max(1, floor(P / max(1024, 8 (K+1)))))
+ *   ranges of epos_heads_wgrad_range_pixels(P, O, F, K) = ceil(P / R) consecutive pixels, the
+ *   last one shorter: a function of its arguments only, never of B, and no range straddles two
+ *   images. The workspace holds, per pixel, S of the object row and of the fragment row (f64)
+ *   and m of the object row (f32), and, when R > 1, R partial slabs f64 [K+1, N]:
+ *     epos_heads_wgrad_workspace_bytes(B, P, O, F, K) = 20 * B * P + (R > 1 ? R * 8 * (K+1) * N : 0),
+ *   8-byte aligned, contents undefined before and after. The slabs are at most P * N bytes, a
+ *   quarter of ONE image's dense gradients, so the whole stays below the 4 * B * P * N bytes of
+ *   the dense gradients for every size.
+ *   Order of the sums (no floating-point atomics, the same bytes in every run). A workgroup
+ *   owns range r of EVERY image and adds image after image. Fragment and localisation columns
+ *   of object g: the range's pixels of class g in pixel order, one accumulator per (k, n).
+ *   Object columns: the i-th pixel of a range belongs to lane i mod 32; a lane adds its pixels
+ *   in order; the 32 lanes are added in lane order, from 0.0. The bias row is the same sum with
+ *   a feature of 1.0. With R == 1 these sums are rounded and written. With R > 1 they go to
+ *   slab r, and a closing launch adds the slabs in range order, from 0.0, and rounds. The
+ *   result depends on the batch as a whole: permuting the images changes the order.
+ *   Launches. Up to four launches on `stream` in sequence (the per-pixel S and m; the object
+ *   head; the fragment and localisation heads; the closing pass), no allocation, no host
+ *   synchronisation, capturable in a graph without parallel branches.
+ *   Refused with EPOS_E_INVALID before the first launch: the sizes epos_loss_terms refuses;
+ *   K outside 1..1024; lda < K; ld_obj < O+1; when B > 0, P > 0 and some output is wanted, a
+ *   null input (scales and workspace included; upstream may be NULL) or a workspace that is not
+ *   8-byte aligned; an output that starts at an input pointer (the workspace counts as one).
+ *   When B == 0 or P == 0 the wanted outputs are written as zeros (no input is read) and the
+ *   call returns 0. All six outputs NULL returns 0 and launches nothing.
+ *
+ * epos_momentum_step_f32: tf.train.MomentumOptimizer without Nesterov on the gradient of the
+ * reference's trainer (train.py:340-384; the l2 regulariser adds weight_decay * w, model.py:436;
+ * the whole gradient is multiplied by the variable's multiplier, train_utils.py:84-114). In
+ * place on w and accum, f32 [device], n values each; per element in fp32, each operation
+ * rounded once, no FMA:
+ *     g  = grad_mult * (grad + weight_decay * w)
+ *     a' = momentum * accum + g
+ *     w' = w - lr * a'
+ * One launch for any n and any 4-byte alignment: a 16-byte body with up to three scalar
+ * elements in front and behind where the three arrays reach a 16-byte boundary together,
+ * scalar throughout otherwise. Refused with EPOS_E_INVALID: n < 0, n > 2^38, a null pointer
+ * or a pointer that is not 4-byte aligned when n > 0. n == 0 does nothing and returns 0. */
+int64_t epos_heads_wgrad_workspace_bytes(int B, int64_t P, int num_objs, int num_frags, int K);
+int64_t epos_heads_wgrad_range_pixels(int64_t P, int num_objs, int num_frags, int K);
+int epos_heads_wgrad_f32(const float* A, int64_t lda, int K, const float* obj_logits,
+                         int64_t ld_obj, const float* frag_logits, const float* frag_loc,
+                         const int32_t* gt_obj, const int32_t* gt_frag, const float* gt_loc,
+                         const float* gt_weight, int B, int64_t P, int num_objs, int num_frags,
+                         int ignore_label, const double* scales,
+                         const double* upstream /* device [4], or NULL = {0,0,0,1} */,
+                         void* workspace, float* dW_obj, float* db_obj, float* dW_frag,
+                         float* db_frag, float* dW_loc, float* db_loc, void* stream);
+int epos_momentum_step_f32(float* w, float* accum, const float* grad, int64_t n, float lr,
+                           float momentum, float weight_decay, float grad_mult, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
