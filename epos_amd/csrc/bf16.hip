@@ -4,50 +4,18 @@
 //
 //   * pointwise GEMM (grouped, 1..8 problems per launch): the 1x1 convs, the dense convs after
 //     epos_im2col_bf16, the logits;
-//   * depthwise 3x3, im2col, bilinear resize, global mean, max-pool, subsample, add + ReLU.
+//   * depthwise 3x3, im2col, global mean (bilinear resize, max-pool, subsample, add + ReLU:
+//     glue.hip; the bf16 conversions and 16-byte packs: nhwc.h).
 #include <stdlib.h>
 
-#include "common.h"
+#include "nhwc.h"
 
 namespace epos {
 namespace {
 
 typedef short bf16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-__host__ __device__ __forceinline__ uint16_t f2bf(float f) {
-  uint32_t u;
-  __builtin_memcpy(&u, &f, 4);
-  if ((u & 0x7fffffffu) > 0x7f800000u) return static_cast<uint16_t>((u >> 16) | 0x40u);  // NaN
-  u += 0x7fffu + ((u >> 16) & 1u);
-  return static_cast<uint16_t>(u >> 16);
-}
-__device__ __forceinline__ float bf2f(uint32_t h) { return __uint_as_float(h << 16); }
-__device__ __forceinline__ uint32_t pack2(float a, float b) {
-  return static_cast<uint32_t>(f2bf(a)) | (static_cast<uint32_t>(f2bf(b)) << 16);
-}
-// 8 bf16 (16 bytes) <-> 8 floats
-__device__ __forceinline__ void ld8(const uint16_t* p, float* v) {
-  const u32x4 q = *reinterpret_cast<const u32x4*>(p);
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    v[2 * i] = __uint_as_float(q[i] << 16);
-    v[2 * i + 1] = __uint_as_float(q[i] & 0xffff0000u);
-  }
-}
-__device__ __forceinline__ void st8(uint16_t* p, const float* v) {
-  u32x4 q;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) q[i] = pack2(v[2 * i], v[2 * i + 1]);
-  *reinterpret_cast<u32x4*>(p) = q;
-}
-
-inline unsigned grid_for(int64_t total, int threads) {
-  return static_cast<unsigned>((total + threads - 1) / threads);
-}
-inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 // ---------------------------------------------------------------------------
 // Pointwise GEMM. The product is computed transposed, C^T = W^T A^T, so that the MFMA's
@@ -257,32 +225,27 @@ __global__ __launch_bounds__(256) void depthwise3x3_bf16_kernel(EposDepthwiseBf1
   EPOS_SET_PRIO(DW_PRIO);
   const int64_t id = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
   if (id >= total) return;
-  const int c = static_cast<int>(id % c8n) * 8;
-  int64_t pix = id / c8n;
-  const int xo = static_cast<int>(pix % p.Wo);
-  pix /= p.Wo;
-  const int yo = static_cast<int>(pix % p.Ho);
-  const int b = static_cast<int>(pix / p.Ho);
-  const int pad = p.rate;       // SAME (stride 1) and fixed_padding + VALID (stride 2) agree
+  const Pixel o = decode_pixel<8>(id, c8n, p.Ho, p.Wo);
+  const int pad = p.rate;      // SAME (stride 1) and fixed_padding + VALID (stride 2) agree
   float acc[8];
   {
-    const float4 b0 = *reinterpret_cast<const float4*>(p.bias + c);
-    const float4 b1 = *reinterpret_cast<const float4*>(p.bias + c + 4);
+    const float4 b0 = *reinterpret_cast<const float4*>(p.bias + o.c);
+    const float4 b1 = *reinterpret_cast<const float4*>(p.bias + o.c + 4);
     acc[0] = b0.x; acc[1] = b0.y; acc[2] = b0.z; acc[3] = b0.w;
     acc[4] = b1.x; acc[5] = b1.y; acc[6] = b1.z; acc[7] = b1.w;
   }
-  const uint16_t* xb = p.X + static_cast<int64_t>(b) * p.Hi * p.Wi * p.ldx + c;
+  const uint16_t* xb = p.X + static_cast<int64_t>(o.b) * p.Hi * p.Wi * p.ldx + o.c;
 #pragma unroll
   for (int ky = 0; ky < 3; ++ky) {
-    const int yi = yo * p.stride - pad + ky * p.rate;
+    const int yi = o.yo * p.stride - pad + ky * p.rate;
     if (yi < 0 || yi >= p.Hi) continue;
 #pragma unroll
     for (int kx = 0; kx < 3; ++kx) {
-      const int xi = xo * p.stride - pad + kx * p.rate;
+      const int xi = o.xo * p.stride - pad + kx * p.rate;
       if (xi < 0 || xi >= p.Wi) continue;
       float v[8];
       ld8(xb + (static_cast<int64_t>(yi) * p.Wi + xi) * p.ldx, v);
-      const float* w = p.w9c + (ky * 3 + kx) * p.C + c;
+      const float* w = p.w9c + (ky * 3 + kx) * p.C + o.c;
       const float4 w0 = *reinterpret_cast<const float4*>(w);
       const float4 w1 = *reinterpret_cast<const float4*>(w + 4);
       const float wv[8] = {w0.x, w0.y, w0.z, w0.w, w1.x, w1.y, w1.z, w1.w};
@@ -297,7 +260,7 @@ __global__ __launch_bounds__(256) void depthwise3x3_bf16_kernel(EposDepthwiseBf1
 #pragma unroll
     for (int e = 0; e < 8; ++e) acc[e] = fmaxf(acc[e], 0.f);
   }
-  st8(p.Y + ((static_cast<int64_t>(b) * p.Ho + yo) * p.Wo + xo) * p.ldy + c, acc);
+  st8(p.Y + pixel_offset(o, p.Ho, p.Wo, p.ldy), acc);
 }
 
 // ---------------------------------------------------------------------------
@@ -308,12 +271,9 @@ __global__ __launch_bounds__(256) void im2col_bf16_kernel(EposIm2colBf16Args p, 
                                                           int64_t total) {
   const int64_t id = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
   if (id >= total) return;
-  const int col0 = static_cast<int>(id % q) * 8;
+  const Pixel o = decode_pixel<8>(id, q, p.Ho, p.Wo);      // c = the first of the 8 columns
+  const int col0 = o.c, xo = o.xo, yo = o.yo, b = o.b;
   const int64_t m = id / q;
-  const int xo = static_cast<int>(m % p.Wo);
-  const int64_t t = m / p.Wo;
-  const int yo = static_cast<int>(t % p.Ho);
-  const int b = static_cast<int>(t / p.Ho);
   const int kkc = p.k * p.k * p.C;
   const int y0 = yo * p.stride - p.pad, x0 = xo * p.stride - p.pad;
   uint16_t* dst = p.col + m * p.ldcol + col0;
@@ -361,52 +321,6 @@ __global__ __launch_bounds__(256) void im2col_bf16_kernel(EposIm2colBf16Args p, 
   st8(dst, v);
 }
 
-// ---------------------------------------------------------------------------
-// Glue layers (8 channels per thread).
-// ---------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void resize_bilinear_bf16_kernel(
-    const void* X, int64_t ldx, int x_f32, uint16_t* Y, int64_t ldy, int Hi, int Wi, int Ho,
-    int Wo, int c8n, float sy, float sx, int64_t total) {
-  const int64_t id = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
-  if (id >= total) return;
-  const int c = static_cast<int>(id % c8n) * 8;
-  int64_t pix = id / c8n;
-  const int xo = static_cast<int>(pix % Wo);
-  pix /= Wo;
-  const int yo = static_cast<int>(pix % Ho);
-  const int b = static_cast<int>(pix / Ho);
-  // the arithmetic of resize_bilinear_kernel (layers.hip), in fp32
-  const float fy = yo * sy, fx = xo * sx;
-  const int y0 = static_cast<int>(floorf(fy)), x0 = static_cast<int>(floorf(fx));
-  const int y1 = min(static_cast<int>(ceilf(fy)), Hi - 1);
-  const int x1 = min(static_cast<int>(ceilf(fx)), Wi - 1);
-  const float ly = fy - y0, lx = fx - x0;
-  const int64_t base = static_cast<int64_t>(b) * Hi * Wi;
-  const int64_t o_tl = (base + static_cast<int64_t>(y0) * Wi + x0) * ldx + c;
-  const int64_t o_tr = (base + static_cast<int64_t>(y0) * Wi + x1) * ldx + c;
-  const int64_t o_bl = (base + static_cast<int64_t>(y1) * Wi + x0) * ldx + c;
-  const int64_t o_br = (base + static_cast<int64_t>(y1) * Wi + x1) * ldx + c;
-  float tl[8], tr[8], bl[8], br[8];
-  if (x_f32) {
-    const float* xf = static_cast<const float*>(X);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      tl[e] = xf[o_tl + e]; tr[e] = xf[o_tr + e]; bl[e] = xf[o_bl + e]; br[e] = xf[o_br + e];
-    }
-  } else {
-    const uint16_t* xh = static_cast<const uint16_t*>(X);
-    ld8(xh + o_tl, tl); ld8(xh + o_tr, tr); ld8(xh + o_bl, bl); ld8(xh + o_br, br);
-  }
-  float o[8];
-#pragma unroll
-  for (int e = 0; e < 8; ++e) {
-    const float top = tl[e] + (tr[e] - tl[e]) * lx;
-    const float bot = bl[e] + (br[e] - bl[e]) * lx;
-    o[e] = top + (bot - top) * ly;
-  }
-  st8(Y + ((static_cast<int64_t>(b) * Ho + yo) * Wo + xo) * ldy + c, o);
-}
-
 // Global mean into fp32: block = (image, 64 channels); 8 channel groups x 32 row phases;
 // fixed-order LDS reduction (deterministic).
 __global__ __launch_bounds__(256) void global_avg_pool_bf16_kernel(
@@ -433,66 +347,6 @@ __global__ __launch_bounds__(256) void global_avg_pool_bf16_kernel(
     for (int i = 1; i < 32; ++i) t += part[i][threadIdx.x];
     Y[static_cast<int64_t>(b) * C + blockIdx.x * 64 + threadIdx.x] = t / static_cast<float>(HW);
   }
-}
-
-__global__ __launch_bounds__(256) void maxpool3x3_s2_bf16_kernel(
-    const uint16_t* X, int64_t ldx, uint16_t* Y, int64_t ldy, int Hi, int Wi, int Ho, int Wo,
-    int c8n, int pad_y, int pad_x, int64_t total) {
-  const int64_t id = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
-  if (id >= total) return;
-  const int c = static_cast<int>(id % c8n) * 8;
-  int64_t pix = id / c8n;
-  const int xo = static_cast<int>(pix % Wo);
-  pix /= Wo;
-  const int yo = static_cast<int>(pix % Ho);
-  const int b = static_cast<int>(pix / Ho);
-  const uint16_t* xb = X + static_cast<int64_t>(b) * Hi * Wi * ldx + c;
-  float m[8];
-#pragma unroll
-  for (int e = 0; e < 8; ++e) m[e] = -INFINITY;
-#pragma unroll
-  for (int ky = 0; ky < 3; ++ky) {
-    const int yi = yo * 2 - pad_y + ky;
-    if (yi < 0 || yi >= Hi) continue;
-#pragma unroll
-    for (int kx = 0; kx < 3; ++kx) {
-      const int xi = xo * 2 - pad_x + kx;
-      if (xi < 0 || xi >= Wi) continue;
-      float v[8];
-      ld8(xb + (static_cast<int64_t>(yi) * Wi + xi) * ldx, v);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) m[e] = fmaxf(m[e], v[e]);
-    }
-  }
-  st8(Y + ((static_cast<int64_t>(b) * Ho + yo) * Wo + xo) * ldy + c, m);   // exact
-}
-
-__global__ __launch_bounds__(256) void subsample_bf16_kernel(
-    const uint16_t* X, int64_t ldx, uint16_t* Y, int64_t ldy, int Hi, int Wi, int Ho, int Wo,
-    int c8n, int factor, int64_t total) {
-  const int64_t id = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
-  if (id >= total) return;
-  const int c = static_cast<int>(id % c8n) * 8;
-  int64_t pix = id / c8n;
-  const int xo = static_cast<int>(pix % Wo);
-  pix /= Wo;
-  const int yo = static_cast<int>(pix % Ho);
-  const int b = static_cast<int>(pix / Ho);
-  *reinterpret_cast<u32x4*>(Y + ((static_cast<int64_t>(b) * Ho + yo) * Wo + xo) * ldy + c) =
-      *reinterpret_cast<const u32x4*>(
-          X + ((static_cast<int64_t>(b) * Hi + yo * factor) * Wi + xo * factor) * ldx + c);
-}
-
-__global__ __launch_bounds__(256) void add_relu_bf16_kernel(const uint16_t* A, const uint16_t* B,
-                                                            uint16_t* Y, int64_t n8) {
-  const int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
-  if (i >= n8) return;
-  float a[8], b[8];
-  ld8(A + 8 * i, a);
-  ld8(B + 8 * i, b);
-#pragma unroll
-  for (int e = 0; e < 8; ++e) a[e] = fmaxf(a[e] + b[e], 0.f);
-  st8(Y + 8 * i, a);
 }
 
 }  // namespace
@@ -567,7 +421,7 @@ extern "C" int epos_depthwise3x3_bf16(const EposDepthwiseBf16Args* a, void* stre
   const int c8n = a->C / 8;
   const int64_t total = static_cast<int64_t>(a->B) * a->Ho * a->Wo * c8n;
   if (total <= 0) return EPOS_OK;
-  hipLaunchKernelGGL(depthwise3x3_bf16_kernel, dim3(grid_for(total, 256)), dim3(256), 0,
+  hipLaunchKernelGGL(depthwise3x3_bf16_kernel, dim3(blocks_for(total, 256)), dim3(256), 0,
                      static_cast<hipStream_t>(stream), *a, c8n, total);
   return launch_status("depthwise3x3_bf16_kernel");
 }
@@ -588,28 +442,9 @@ extern "C" int epos_im2col_bf16(const EposIm2colBf16Args* a, void* stream) {
   const int q = static_cast<int>(a->ldcol / 8);
   const int64_t total = static_cast<int64_t>(a->B) * a->Ho * a->Wo * q;
   if (total <= 0) return EPOS_OK;
-  hipLaunchKernelGGL(im2col_bf16_kernel, dim3(grid_for(total, 256)), dim3(256), 0,
+  hipLaunchKernelGGL(im2col_bf16_kernel, dim3(blocks_for(total, 256)), dim3(256), 0,
                      static_cast<hipStream_t>(stream), *a, q, total);
   return launch_status("im2col_bf16_kernel");
-}
-
-extern "C" int epos_resize_bilinear_bf16(const void* X, int64_t ldx, int x_f32, uint16_t* Y,
-                                         int64_t ldy, int B, int Hi, int Wi, int Ho, int Wo,
-                                         int C, void* stream) {
-  EPOS_REQUIRE(X && Y, "null pointer");
-  EPOS_REQUIRE(C % 8 == 0 && ldx % 8 == 0 && ldy % 8 == 0 && al16(Y) && (x_f32 || al16(X)),
-               "C, ldx, ldy multiples of 8, 16-byte aligned");
-  EPOS_REQUIRE(B >= 1 && Hi >= 1 && Wi >= 1 && Ho >= 1 && Wo >= 1 && C >= 1, "empty map");
-  EPOS_REQUIRE(ldx >= C && ldy >= C, "ldx, ldy >= C");
-  const float sy = Ho > 1 ? static_cast<float>(Hi - 1) / (Ho - 1) : 0.f;
-  const float sx = Wo > 1 ? static_cast<float>(Wi - 1) / (Wo - 1) : 0.f;
-  const int c8n = C / 8;
-  const int64_t total = static_cast<int64_t>(B) * Ho * Wo * c8n;
-  if (total <= 0) return EPOS_OK;
-  hipLaunchKernelGGL(resize_bilinear_bf16_kernel, dim3(grid_for(total, 256)), dim3(256), 0,
-                     static_cast<hipStream_t>(stream), X, ldx, x_f32, Y, ldy, Hi, Wi, Ho, Wo,
-                     c8n, sy, sx, total);
-  return launch_status("resize_bilinear_bf16_kernel");
 }
 
 extern "C" int epos_global_avg_pool_bf16(const uint16_t* X, int64_t ldx, float* Y, int B,
@@ -618,55 +453,7 @@ extern "C" int epos_global_avg_pool_bf16(const uint16_t* X, int64_t ldx, float* 
   EPOS_REQUIRE(C % 8 == 0 && ldx % 8 == 0 && al16(X), "C, ldx multiples of 8");
   EPOS_REQUIRE(B >= 1 && HW >= 1 && C >= 1, "empty map");
   EPOS_REQUIRE(ldx >= C, "ldx >= C");
-  hipLaunchKernelGGL(global_avg_pool_bf16_kernel, dim3(grid_for(C, 64), B), dim3(256), 0,
+  hipLaunchKernelGGL(global_avg_pool_bf16_kernel, dim3(blocks_for(C, 64), B), dim3(256), 0,
                      static_cast<hipStream_t>(stream), X, ldx, Y, HW, C);
   return launch_status("global_avg_pool_bf16_kernel");
-}
-
-extern "C" int epos_maxpool3x3_s2_bf16(const uint16_t* X, int64_t ldx, uint16_t* Y,
-                                       int64_t ldy, int B, int Hi, int Wi, int C, void* stream) {
-  EPOS_REQUIRE(X && Y, "null pointer");
-  EPOS_REQUIRE(C % 8 == 0 && ldx % 8 == 0 && ldy % 8 == 0 && al16(X) && al16(Y),
-               "multiples of 8");
-  EPOS_REQUIRE(B >= 1 && Hi >= 1 && Wi >= 1 && C >= 1, "empty map");
-  EPOS_REQUIRE(ldx >= C && ldy >= C, "ldx, ldy >= C");
-  const int Ho = (Hi + 1) / 2, Wo = (Wi + 1) / 2;          // TF 'SAME'
-  const int ty = (Ho - 1) * 2 + 3 - Hi, tx = (Wo - 1) * 2 + 3 - Wi;
-  const int pad_y = ty > 0 ? ty / 2 : 0, pad_x = tx > 0 ? tx / 2 : 0;
-  const int c8n = C / 8;
-  const int64_t total = static_cast<int64_t>(B) * Ho * Wo * c8n;
-  if (total <= 0) return EPOS_OK;
-  hipLaunchKernelGGL(maxpool3x3_s2_bf16_kernel, dim3(grid_for(total, 256)), dim3(256), 0,
-                     static_cast<hipStream_t>(stream), X, ldx, Y, ldy, Hi, Wi, Ho, Wo, c8n,
-                     pad_y, pad_x, total);
-  return launch_status("maxpool3x3_s2_bf16_kernel");
-}
-
-extern "C" int epos_subsample_bf16(const uint16_t* X, int64_t ldx, uint16_t* Y, int64_t ldy,
-                                   int B, int Hi, int Wi, int C, int factor, void* stream) {
-  EPOS_REQUIRE(X && Y, "null pointer");
-  EPOS_REQUIRE(C % 8 == 0 && ldx % 8 == 0 && ldy % 8 == 0 && al16(X) && al16(Y),
-               "multiples of 8");
-  EPOS_REQUIRE(factor >= 1, "factor >= 1");
-  EPOS_REQUIRE(B >= 1 && Hi >= 1 && Wi >= 1 && C >= 1, "empty map");
-  EPOS_REQUIRE(ldx >= C && ldy >= C, "ldx, ldy >= C");
-  const int Ho = (Hi - 1) / factor + 1, Wo = (Wi - 1) / factor + 1;
-  const int c8n = C / 8;
-  const int64_t total = static_cast<int64_t>(B) * Ho * Wo * c8n;
-  if (total <= 0) return EPOS_OK;
-  hipLaunchKernelGGL(subsample_bf16_kernel, dim3(grid_for(total, 256)), dim3(256), 0,
-                     static_cast<hipStream_t>(stream), X, ldx, Y, ldy, Hi, Wi, Ho, Wo, c8n,
-                     factor, total);
-  return launch_status("subsample_bf16_kernel");
-}
-
-extern "C" int epos_add_relu_bf16(const uint16_t* A, const uint16_t* B, uint16_t* Y, int64_t n,
-                                  void* stream) {
-  EPOS_REQUIRE(A && B && Y, "null pointer");
-  EPOS_REQUIRE(n >= 0 && n % 8 == 0 && al16(A) && al16(B) && al16(Y),
-               "n % 8 == 0, 16-byte aligned");
-  if (n <= 0) return EPOS_OK;
-  hipLaunchKernelGGL(add_relu_bf16_kernel, dim3(grid_for(n / 8, 256)), dim3(256), 0,
-                     static_cast<hipStream_t>(stream), A, B, Y, n / 8);
-  return launch_status("add_relu_bf16_kernel");
 }

@@ -1,4 +1,4 @@
-// Shared host-side helpers for libepos_hip.so (gfx950 only).
+// Helpers shared by the translation units of libepos_hip.so (gfx950 only).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -22,6 +22,16 @@ inline int launch_status(const char* kernel) {
 
 inline int64_t round_up(int64_t x, int64_t m) { return (x + m - 1) / m * m; }
 inline int64_t ceil_div(int64_t x, int64_t m) { return (x + m - 1) / m; }
+// workgroups of `threads` for `total` work items
+inline unsigned blocks_for(int64_t total, int threads) {
+  return static_cast<unsigned>(ceil_div(total, threads));
+}
+inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+__device__ __forceinline__ float4 relu4(float4 v) {
+  return make_float4(fmaxf(v.x, 0.f), fmaxf(v.y, 0.f), fmaxf(v.z, 0.f),
+                     fmaxf(v.w, 0.f));
+}
 
 // Issue priority of the depthwise kernels' waves: when such a wave shares a SIMD with a GEMM
 // wave of another image in flight it gets the issue slots first -- it is short and mostly

@@ -1,26 +1,17 @@
 // HBM-bound layer kernels of the EPOS network for gfx950 (NHWC fp32):
 // depthwise 3x3 (+folded BN, ReLU before/after), im2col for the two dense 3x3
-// stem convs, global average pool, bilinear resize (align_corners) and argmax
-// (the grouped softmax: softmax.hip). All accesses are float4 along the channel axis (the
-// contiguous axis of NHWC), 16 B per lane, so a wave moves 1 KiB per instruction.
+// stem convs, global average pool, argmax, scatter and the uint8 cast (the grouped softmax:
+// softmax.hip; resize, max pool, subsample, add+ReLU: glue.hip). All accesses are float4 along
+// the channel axis (the contiguous axis of NHWC), 16 B per lane, so a wave moves 1 KiB per
+// instruction (nhwc.h).
 #include <stdlib.h>
 
-#include "common.h"
 #include "h2_scale.h"
+#include "nhwc.h"
 
 namespace epos {
 namespace {
 
-__device__ __forceinline__ float4 ld4(const float* p) {
-  return *reinterpret_cast<const float4*>(p);
-}
-__device__ __forceinline__ void st4(float* p, float4 v) {
-  *reinterpret_cast<float4*>(p) = v;
-}
-__device__ __forceinline__ float4 relu4(float4 v) {
-  return make_float4(fmaxf(v.x, 0.f), fmaxf(v.y, 0.f), fmaxf(v.z, 0.f),
-                     fmaxf(v.w, 0.f));
-}
 // fp16-pair form of four outputs (EposDepthwiseArgs.y_h2): the same 16 bytes hold
 // [hi hi hi hi | mid mid mid mid] of y * s for the fp16-pair GEMM that reads them as its A
 typedef unsigned dw_u32x4 __attribute__((ext_vector_type(4)));
@@ -65,26 +56,21 @@ __global__ __launch_bounds__(256) void depthwise3x3_kernel(EposDepthwiseArgs p,
   const bool live = id < total;
   if (__builtin_amdgcn_ballot_w64(live) == 0) return;
   id = live ? id : total - 1;
-  const int c = static_cast<int>(id % c4n) * 4;
-  int64_t pix = id / c4n;
-  const int xo = static_cast<int>(pix % p.Wo);
-  pix /= p.Wo;
-  const int yo = static_cast<int>(pix % p.Ho);
-  const int b = static_cast<int>(pix / p.Ho);
+  const Pixel o = decode_pixel<4>(id, c4n, p.Ho, p.Wo);
   const int pad = p.rate;  // SAME (stride 1) and fixed_padding (stride 2) agree
-  float4 acc = ld4(p.bias + c);
-  const float* xb = p.X + static_cast<int64_t>(b) * p.Hi * p.Wi * p.ldx + c;
+  float4 acc = ld4(p.bias + o.c);
+  const float* xb = p.X + static_cast<int64_t>(o.b) * p.Hi * p.Wi * p.ldx + o.c;
 #pragma unroll
   for (int ky = 0; ky < 3; ++ky) {
-    const int yi = yo * p.stride - pad + ky * p.rate;
+    const int yi = o.yo * p.stride - pad + ky * p.rate;
     if (yi < 0 || yi >= p.Hi) continue;
 #pragma unroll
     for (int kx = 0; kx < 3; ++kx) {
-      const int xi = xo * p.stride - pad + kx * p.rate;
+      const int xi = o.xo * p.stride - pad + kx * p.rate;
       if (xi < 0 || xi >= p.Wi) continue;
       float4 v = ld4(xb + (static_cast<int64_t>(yi) * p.Wi + xi) * p.ldx);
       if (p.relu_in) v = relu4(v);
-      acc = fma4(v, ld4(p.w9c + (ky * 3 + kx) * p.C + c), acc);
+      acc = fma4(v, ld4(p.w9c + (ky * 3 + kx) * p.C + o.c), acc);
     }
   }
   if (p.relu_out) acc = relu4(acc);
@@ -92,7 +78,7 @@ __global__ __launch_bounds__(256) void depthwise3x3_kernel(EposDepthwiseArgs p,
     float hinv;
     h2_scale_finish(am_raw, am_raw2, p.gain, p.bias0, hs, hinv);
   }
-  if (live) st4_any(p.Y + ((static_cast<int64_t>(b) * p.Ho + yo) * p.Wo + xo) * p.ldy + c, acc, h2, hs);
+  if (live) st4_any(p.Y + pixel_offset(o, p.Ho, p.Wo, p.ldy), acc, h2, hs);
 }
 
 // Stride-1 depthwise 3x3 with a SLIDING WINDOW: one thread = 4 channels x a run
@@ -498,39 +484,6 @@ __global__ __launch_bounds__(1024) void global_avg_pool_kernel(
   }
 }
 
-// --------------------------------------------------------------------------
-// Bilinear resize, align_corners=True (TF resize_bilinear arithmetic order).
-// --------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void resize_bilinear_kernel(
-    const float* X, int64_t ldx, float* Y, int64_t ldy, int Hi, int Wi, int Ho,
-    int Wo, int c4n, float sy, float sx, int64_t total) {
-  const int64_t id = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
-  if (id >= total) return;
-  const int c = static_cast<int>(id % c4n) * 4;
-  int64_t pix = id / c4n;
-  const int xo = static_cast<int>(pix % Wo);
-  pix /= Wo;
-  const int yo = static_cast<int>(pix % Ho);
-  const int b = static_cast<int>(pix / Ho);
-  const float fy = yo * sy, fx = xo * sx;
-  const int y0 = static_cast<int>(floorf(fy)), x0 = static_cast<int>(floorf(fx));
-  const int y1 = min(static_cast<int>(ceilf(fy)), Hi - 1);
-  const int x1 = min(static_cast<int>(ceilf(fx)), Wi - 1);
-  const float ly = fy - y0, lx = fx - x0;
-  const float* xb = X + static_cast<int64_t>(b) * Hi * Wi * ldx + c;
-  const float4 tl = ld4(xb + (static_cast<int64_t>(y0) * Wi + x0) * ldx);
-  const float4 tr = ld4(xb + (static_cast<int64_t>(y0) * Wi + x1) * ldx);
-  const float4 bl = ld4(xb + (static_cast<int64_t>(y1) * Wi + x0) * ldx);
-  const float4 br = ld4(xb + (static_cast<int64_t>(y1) * Wi + x1) * ldx);
-  auto lerp = [](float a, float bb, float w) { return a + (bb - a) * w; };
-  float4 o;
-  o.x = lerp(lerp(tl.x, tr.x, lx), lerp(bl.x, br.x, lx), ly);
-  o.y = lerp(lerp(tl.y, tr.y, lx), lerp(bl.y, br.y, lx), ly);
-  o.z = lerp(lerp(tl.z, tr.z, lx), lerp(bl.z, br.z, lx), ly);
-  o.w = lerp(lerp(tl.w, tr.w, lx), lerp(bl.w, br.w, lx), ly);
-  st4(Y + ((static_cast<int64_t>(b) * Ho + yo) * Wo + xo) * ldy + c, o);
-}
-
 __global__ __launch_bounds__(256) void argmax_kernel(const float* X, int64_t ldx,
                                                      int64_t* labels, int64_t P,
                                                      int C) {
@@ -578,68 +531,6 @@ __global__ __launch_bounds__(256) void u8_to_f32_kernel(const uint8_t* __restric
   } else {
     for (int64_t j = i; j < n; ++j) Y[j] = static_cast<float>(X[j]);
   }
-}
-
-// --------------------------------------------------------------------------
-// ResNet-v1-beta helpers (BASELINE config C5): 3x3 stride-2 'SAME' max pool
-// (net_resnet_v1_beta.py:190), spatial subsampling (slim resnet_utils.subsample,
-// the identity shortcut of a strided unit) and the unit's final relu(a + b)
-// where the pre-activation sum is also an end point.
-// --------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void maxpool3x3_s2_kernel(
-    const float* X, int64_t ldx, float* Y, int64_t ldy, int Hi, int Wi, int Ho,
-    int Wo, int c4n, int pad_y, int pad_x, int64_t total) {
-  const int64_t id = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
-  if (id >= total) return;
-  const int c = static_cast<int>(id % c4n) * 4;
-  int64_t pix = id / c4n;
-  const int xo = static_cast<int>(pix % Wo);
-  pix /= Wo;
-  const int yo = static_cast<int>(pix % Ho);
-  const int b = static_cast<int>(pix / Ho);
-  const float* xb = X + static_cast<int64_t>(b) * Hi * Wi * ldx + c;
-  float4 m = make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
-#pragma unroll
-  for (int ky = 0; ky < 3; ++ky) {
-    const int yi = yo * 2 - pad_y + ky;
-    if (yi < 0 || yi >= Hi) continue;
-#pragma unroll
-    for (int kx = 0; kx < 3; ++kx) {
-      const int xi = xo * 2 - pad_x + kx;
-      if (xi < 0 || xi >= Wi) continue;
-      const float4 v = ld4(xb + (static_cast<int64_t>(yi) * Wi + xi) * ldx);
-      m = make_float4(fmaxf(m.x, v.x), fmaxf(m.y, v.y), fmaxf(m.z, v.z),
-                      fmaxf(m.w, v.w));
-    }
-  }
-  st4(Y + ((static_cast<int64_t>(b) * Ho + yo) * Wo + xo) * ldy + c, m);
-}
-
-__global__ __launch_bounds__(256) void subsample_kernel(
-    const float* X, int64_t ldx, float* Y, int64_t ldy, int Hi, int Wi, int Ho,
-    int Wo, int c4n, int factor, int64_t total) {
-  const int64_t id = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
-  if (id >= total) return;
-  const int c = static_cast<int>(id % c4n) * 4;
-  int64_t pix = id / c4n;
-  const int xo = static_cast<int>(pix % Wo);
-  pix /= Wo;
-  const int yo = static_cast<int>(pix % Ho);
-  const int b = static_cast<int>(pix / Ho);
-  st4(Y + ((static_cast<int64_t>(b) * Ho + yo) * Wo + xo) * ldy + c,
-      ld4(X + ((static_cast<int64_t>(b) * Hi + yo * factor) * Wi + xo * factor) * ldx + c));
-}
-
-__global__ __launch_bounds__(256) void add_relu_kernel(const float* A, const float* B,
-                                                       float* Y, int64_t n4) {
-  const int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
-  if (i >= n4) return;
-  const float4 a = ld4(A + 4 * i), b = ld4(B + 4 * i);
-  st4(Y + 4 * i, relu4(make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w)));
-}
-
-inline unsigned blocks_for(int64_t total, int threads) {
-  return static_cast<unsigned>(ceil_div(total, threads));
 }
 
 }  // namespace
@@ -867,24 +758,6 @@ extern "C" int epos_global_avg_pool_partial_f32(const float* P, int64_t ldp, flo
   return epos::launch_status("pool_partial_kernel");
 }
 
-extern "C" int epos_resize_bilinear_f32(const float* X, int64_t ldx, float* Y,
-                                        int64_t ldy, int B, int Hi, int Wi,
-                                        int Ho, int Wo, int C, void* stream) {
-  EPOS_REQUIRE(X && Y, "null pointer");
-  EPOS_REQUIRE(C % 4 == 0 && ldx % 4 == 0 && ldy % 4 == 0, "multiples of 4");
-  EPOS_REQUIRE(B > 0 && Hi > 0 && Wi > 0 && Ho > 0 && Wo > 0 && C > 0, "empty map");
-  EPOS_REQUIRE(ldx >= C && ldy >= C, "ldx, ldy >= C");
-  const float sy = Ho > 1 ? static_cast<float>(Hi - 1) / (Ho - 1) : 0.f;
-  const float sx = Wo > 1 ? static_cast<float>(Wi - 1) / (Wo - 1) : 0.f;
-  const int c4n = C / 4;
-  const int64_t total = static_cast<int64_t>(B) * Ho * Wo * c4n;
-  if (total == 0) return EPOS_OK;
-  hipLaunchKernelGGL(resize_bilinear_kernel, dim3(blocks_for(total, 256)),
-                     dim3(256), 0, static_cast<hipStream_t>(stream), X, ldx, Y,
-                     ldy, Hi, Wi, Ho, Wo, c4n, sy, sx, total);
-  return launch_status("resize_bilinear_kernel");
-}
-
 extern "C" int epos_argmax_i64(const float* X, int64_t ldx, int64_t* labels,
                                int64_t P, int C, void* stream) {
   EPOS_REQUIRE(X && labels, "null pointer");
@@ -914,51 +787,4 @@ extern "C" int epos_u8_to_f32(const uint8_t* X, float* Y, int64_t n, void* strea
   hipLaunchKernelGGL(u8_to_f32_kernel, dim3(blocks_for((n + 15) / 16, 256)), dim3(256), 0,
                      static_cast<hipStream_t>(stream), X, Y, n);
   return launch_status("u8_to_f32_kernel");
-}
-
-extern "C" int epos_maxpool3x3_s2_f32(const float* X, int64_t ldx, float* Y,
-                                      int64_t ldy, int B, int Hi, int Wi, int C,
-                                      void* stream) {
-  EPOS_REQUIRE(X && Y, "null pointer");
-  EPOS_REQUIRE(C % 4 == 0 && ldx % 4 == 0 && ldy % 4 == 0, "multiples of 4");
-  EPOS_REQUIRE(B > 0 && Hi > 0 && Wi > 0 && C > 0, "empty map");
-  EPOS_REQUIRE(ldx >= C && ldy >= C, "ldx, ldy >= C");
-  const int Ho = (Hi + 1) / 2, Wo = (Wi + 1) / 2;          // TF 'SAME'
-  const int ty = (Ho - 1) * 2 + 3 - Hi, tx = (Wo - 1) * 2 + 3 - Wi;
-  const int pad_y = ty > 0 ? ty / 2 : 0, pad_x = tx > 0 ? tx / 2 : 0;
-  const int c4n = C / 4;
-  const int64_t total = static_cast<int64_t>(B) * Ho * Wo * c4n;
-  if (total == 0) return EPOS_OK;
-  hipLaunchKernelGGL(maxpool3x3_s2_kernel, dim3(blocks_for(total, 256)), dim3(256),
-                     0, static_cast<hipStream_t>(stream), X, ldx, Y, ldy, Hi, Wi,
-                     Ho, Wo, c4n, pad_y, pad_x, total);
-  return launch_status("maxpool3x3_s2_kernel");
-}
-
-extern "C" int epos_subsample_f32(const float* X, int64_t ldx, float* Y,
-                                  int64_t ldy, int B, int Hi, int Wi, int C,
-                                  int factor, void* stream) {
-  EPOS_REQUIRE(X && Y, "null pointer");
-  EPOS_REQUIRE(C % 4 == 0 && ldx % 4 == 0 && ldy % 4 == 0 && factor >= 1,
-               "multiples of 4");
-  EPOS_REQUIRE(B > 0 && Hi > 0 && Wi > 0 && C > 0, "empty map");
-  EPOS_REQUIRE(ldx >= C && ldy >= C, "ldx, ldy >= C");
-  const int Ho = (Hi - 1) / factor + 1, Wo = (Wi - 1) / factor + 1;
-  const int c4n = C / 4;
-  const int64_t total = static_cast<int64_t>(B) * Ho * Wo * c4n;
-  if (total == 0) return EPOS_OK;
-  hipLaunchKernelGGL(subsample_kernel, dim3(blocks_for(total, 256)), dim3(256), 0,
-                     static_cast<hipStream_t>(stream), X, ldx, Y, ldy, Hi, Wi, Ho,
-                     Wo, c4n, factor, total);
-  return launch_status("subsample_kernel");
-}
-
-extern "C" int epos_add_relu_f32(const float* A, const float* B, float* Y,
-                                 int64_t n, void* stream) {
-  EPOS_REQUIRE(A && B && Y, "null pointer");
-  EPOS_REQUIRE(n >= 0 && n % 4 == 0, "n must be a multiple of 4");
-  if (n == 0) return EPOS_OK;
-  hipLaunchKernelGGL(add_relu_kernel, dim3(blocks_for(n / 4, 256)), dim3(256), 0,
-                     static_cast<hipStream_t>(stream), A, B, Y, n / 4);
-  return launch_status("add_relu_kernel");
 }

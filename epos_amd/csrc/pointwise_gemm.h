@@ -156,10 +156,6 @@ __device__ __forceinline__ void amax_publish(unsigned* slot, float m, int lane, 
     __hip_atomic_fetch_max(slot + (salt & (EPOS_AMAX_WORDS - 1)), __float_as_uint(m),
                            __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
-__device__ __forceinline__ float4 relu4(float4 v) {
-  return make_float4(fmaxf(v.x, 0.f), fmaxf(v.y, 0.f), fmaxf(v.z, 0.f),
-                     fmaxf(v.w, 0.f));
-}
 
 // ---------------------------------------------------------------------------
 // Vectorised epilogue. The MFMA accumulator layout gives a lane ONE output column

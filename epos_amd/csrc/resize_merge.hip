@@ -1,87 +1,28 @@
 // Multi-scale inference (model.py:515-626): bilinear resize (align_corners=True) of up to
 // eight sources to one output size, merged elementwise by max or mean -- one launch per head.
 // S = 1 is a plain resize at any channel count (the per-scale input images, C = 3).
-#include "common.h"
+#include "nhwc.h"
 
 namespace epos {
 namespace {
 
 constexpr int kMaxSrc = 8;
 
-struct ResizeSrcK {
-  const float* X;
-  int64_t ldx;
-  int32_t Hi, Wi;
-  float sy, sx;
-};
-
 struct ResizeSrcsK {
-  ResizeSrcK s[kMaxSrc];
+  BilinearSrc<float> s[kMaxSrc];
 };
 
-template <int V>
-struct VecT;
-template <>
-struct VecT<1> { using T = float; };
-template <>
-struct VecT<2> { using T = float2; };
-template <>
-struct VecT<4> { using T = float4; };
-
-template <int V>
-__device__ __forceinline__ void load_v(const float* p, float* v) {
-  const typename VecT<V>::T t = *reinterpret_cast<const typename VecT<V>::T*>(p);
-  const float* f = reinterpret_cast<const float*>(&t);
-#pragma unroll
-  for (int i = 0; i < V; ++i) v[i] = f[i];
-}
-
-template <int V>
-__device__ __forceinline__ void store_v(float* p, const float* v) {
-  typename VecT<V>::T t;
-  float* f = reinterpret_cast<float*>(&t);
-#pragma unroll
-  for (int i = 0; i < V; ++i) f[i] = v[i];
-  *reinterpret_cast<typename VecT<V>::T*>(p) = t;
-}
-
-// One source's contribution at (b, yo, xo), channels [c, c + W): TF's align_corners
-// arithmetic in the order of resize_bilinear_kernel (csrc/layers.hip), no contraction.
-template <int W>
-__device__ __forceinline__ void sample(const ResizeSrcK& src, int b, int yo, int xo, int c,
-                                       float* out) {
-#pragma clang fp contract(off)
-  const float fy = static_cast<float>(yo) * src.sy;
-  const float fx = static_cast<float>(xo) * src.sx;
-  // (lo <= in - 1 always holds for in < 2^23; the min only keeps the loads in bounds)
-  const int y0 = min(static_cast<int>(floorf(fy)), src.Hi - 1);
-  const int x0 = min(static_cast<int>(floorf(fx)), src.Wi - 1);
-  const int y1 = min(static_cast<int>(ceilf(fy)), src.Hi - 1);
-  const int x1 = min(static_cast<int>(ceilf(fx)), src.Wi - 1);
-  const float ly = fy - static_cast<float>(y0), lx = fx - static_cast<float>(x0);
-  const float* xb = src.X + static_cast<int64_t>(b) * src.Hi * src.Wi * src.ldx + c;
-  float tl[W], tr[W], bl[W], br[W];
-  load_v<W>(xb + (static_cast<int64_t>(y0) * src.Wi + x0) * src.ldx, tl);
-  load_v<W>(xb + (static_cast<int64_t>(y0) * src.Wi + x1) * src.ldx, tr);
-  load_v<W>(xb + (static_cast<int64_t>(y1) * src.Wi + x0) * src.ldx, bl);
-  load_v<W>(xb + (static_cast<int64_t>(y1) * src.Wi + x1) * src.ldx, br);
-#pragma unroll
-  for (int i = 0; i < W; ++i) {
-    const float top = tl[i] + (tr[i] - tl[i]) * lx;
-    const float bot = bl[i] + (br[i] - bl[i]) * lx;
-    out[i] = top + (bot - top) * ly;
-  }
-}
-
+// One output pack: the sources' values (bilinear_sample, nhwc.h) merged in source order.
 template <int W>
 __device__ __forceinline__ void resize_merge_at(const ResizeSrcsK& srcs, int S, int merge,
                                                 float* Y, int64_t ldy, int b, int yo, int xo,
                                                 int Ho, int Wo, int c) {
 #pragma clang fp contract(off)
+  using P = F32Pack<W>;
   float acc[W], v[W];
-  sample<W>(srcs.s[0], b, yo, xo, c, acc);
+  bilinear_sample<P>(srcs.s[0], b, yo, xo, c, acc);
   for (int s = 1; s < S; ++s) {
-    sample<W>(srcs.s[s], b, yo, xo, c, v);
+    bilinear_sample<P>(srcs.s[s], b, yo, xo, c, v);
     if (merge == EPOS_MERGE_MAX) {
 #pragma unroll
       for (int i = 0; i < W; ++i) acc[i] = fmaxf(acc[i], v[i]);
@@ -95,7 +36,7 @@ __device__ __forceinline__ void resize_merge_at(const ResizeSrcsK& srcs, int S, 
 #pragma unroll
     for (int i = 0; i < W; ++i) acc[i] = acc[i] / n;
   }
-  store_v<W>(Y + ((static_cast<int64_t>(b) * Ho + yo) * Wo + xo) * ldy + c, acc);
+  P::store(Y + ((static_cast<int64_t>(b) * Ho + yo) * Wo + xo) * ldy + c, acc);
 }
 
 // Block = 256 threads on one output row (b, yo): `chunks` blocks per row, a row's pixels
@@ -147,9 +88,8 @@ extern "C" int epos_resize_merge_f32(const EposResizeSrc* srcs, int S, float* Y,
     k.s[s].ldx = src.ldx;
     k.s[s].Hi = src.Hi;
     k.s[s].Wi = src.Wi;
-    // scale = (in - 1) / (out - 1) as a float (resize_bilinear_op.cc, align_corners)
-    k.s[s].sy = Ho > 1 ? static_cast<float>(src.Hi - 1) / static_cast<float>(Ho - 1) : 0.f;
-    k.s[s].sx = Wo > 1 ? static_cast<float>(src.Wi - 1) / static_cast<float>(Wo - 1) : 0.f;
+    k.s[s].sy = align_corners_scale(src.Hi, Ho);
+    k.s[s].sx = align_corners_scale(src.Wi, Wo);
   }
   if (static_cast<int64_t>(B) * Ho * Wo == 0) return EPOS_OK;
   const int cv = C / V, tail = C % V;

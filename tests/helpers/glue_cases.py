@@ -1,6 +1,7 @@
 """Shape tables of the glue-layer and correspondence kernels (tests/test_gpu_glue_layers.py,
 tests/test_gpu_corresp_regimes.py) and, per kernel, a host-side mirror of what its launcher and
-the kernel itself branch on (epos_amd/csrc/layers.hip, softmax.hip, bf16.hip, corresp.hip), in the
+the kernel itself branch on (epos_amd/csrc/glue.hip, layers.hip, softmax.hip, bf16.hip,
+corresp.hip), in the
 style of tests/helpers/dw_regimes.py. Pure Python: tests/test_glue_cases_host.py checks without a
 GPU that every table reaches every regime its mirror distinguishes.
 

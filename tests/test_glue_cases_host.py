@@ -1,7 +1,7 @@
 """CPU-only checks of the glue-layer and correspondence test tables (tests/helpers/glue_cases.py)
 and their references (tests/helpers/glue_ref.py): the tables reach every regime the launchers and
-kernels distinguish, the mirrors give the values worked out by hand from layers.hip / bf16.hip /
-corresp.hip, the float32 restatements lie within derived bounds of float64, and the inputs have
+kernels distinguish, the mirrors give the values worked out by hand from glue.hip / layers.hip /
+bf16.hip / corresp.hip, the float32 restatements lie within derived bounds of float64, and the inputs have
 the properties that make the GPU comparisons mean something."""
 import numpy as np
 import pytest

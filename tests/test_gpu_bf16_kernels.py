@@ -1,4 +1,4 @@
-"""The bf16-mode kernels (csrc/bf16.hip) on the GPU against float64 numpy restatements on the
+"""The bf16-mode kernels (csrc/bf16.hip, csrc/glue.hip) on the GPU against float64 numpy restatements on the
 bf16-rounded operands: the grouped GEMM (every epilogue, sub = 2, column offsets, K / M / N
 tails at the plans' layer shapes, fp32 and bf16 outputs), the depthwise 3x3, the im2col, and the
 glue layers. Padding columns of A hold NaN and must not reach the output; sentinels behind C

@@ -1,5 +1,5 @@
-"""The glue-layer kernels (csrc/layers.hip, csrc/softmax.hip and the bf16 twins in csrc/bf16.hip)
-over the shape tables of tests/helpers/glue_cases.py, each through its C entry point: inputs sit
+"""The glue-layer kernels (csrc/glue.hip, csrc/layers.hip, csrc/softmax.hip, the bf16 mean in
+csrc/bf16.hip) over the shape tables of tests/helpers/glue_cases.py, each through its C entry point: inputs sit
 at their pitch and base offset inside a larger allocation whose padding holds NaN; the output
 allocation starts as a sentinel bit pattern (a NaN payload for fp32, SENT for bf16, -1 for integers) in its padding
 columns, before the base and in a guard region behind the last row, and all of that must survive.
@@ -194,6 +194,43 @@ def test_resize_bilinear_bf16(name, src_f32):
   want, (tl, tr, bl, br) = gr.resize_f32(x, c.ho, c.wo)
   mag = np.abs(tl) + np.abs(tr) + np.abs(bl) + np.abs(br)
   assert (np.abs(got - want) <= _half_ulp(want) + 2.0 ** -21 * mag).all()
+
+
+@pytest.mark.parametrize('name', _names(gc.RESIZE))
+def test_resize_entry_points_agree(name):
+  """Device against device: the three entry points that resize share one sampler (csrc/nhwc.h)
+  and must not drift apart. epos_resize_merge_f32 with one source gives the bits of
+  epos_resize_bilinear_f32; epos_resize_bilinear_bf16 gives the round-to-nearest-even bf16 of
+  the fp32 entry's output on the same input, from an fp32 source (x_f32 = 1) and from a bf16
+  source (x_f32 = 0, on an input that holds bf16 values). Out.read() holds the padding."""
+  L, lib = _lib()
+  c = gc.by_name(gc.RESIZE)[name]
+  rows = c.b * c.ho * c.wo
+
+  def f32_entry(x):
+    X, Y = In(x, c.ldx, c.xoff), Out(rows, c.c, c.ldy, c.yoff)
+    L.check(lib.epos_resize_bilinear_f32(X.ptr, c.ldx, Y.ptr, c.ldy, c.b, c.hi, c.wi, c.ho, c.wo,
+                                         c.c, _stream()), name)
+    return Y.read()
+
+  def bf16_entry(x, src_f32):
+    X, Y = In(x, c.ldx, c.xoff, bf16=not src_f32), Out(rows, c.c, c.ldy, c.yoff, 'bf16')
+    L.check(lib.epos_resize_bilinear_bf16(X.ptr, c.ldx, int(src_f32), Y.ptr, c.ldy, c.b, c.hi,
+                                          c.wi, c.ho, c.wo, c.c, _stream()), name)
+    return Y.read().view(np.uint16)
+
+  x = gr.resize_input(c)
+  want = f32_entry(x)
+  X, Y = In(x, c.ldx, c.xoff), Out(rows, c.c, c.ldy, c.yoff)
+  src = (L.ResizeSrc * 1)(L.ResizeSrc(X.ptr, c.ldx, c.hi, c.wi))
+  L.check(lib.epos_resize_merge_f32(src, 1, Y.ptr, c.ldy, c.b, c.ho, c.wo, c.c, L.MERGE_MAX,
+                                    _stream()), name)
+  assert np.array_equal(Y.read(), want)
+  if not gc.bf16_ok(c):
+    return
+  assert np.array_equal(bf16_entry(x, True), bf16_round_bits(_f32(want)))
+  xb = gr.resize_input(c, bf16=True)
+  assert np.array_equal(bf16_entry(xb, False), bf16_round_bits(_f32(f32_entry(xb))))
 
 
 # ------------------------------------------------------------------- max pool, subsample ---
