@@ -8,7 +8,7 @@
 // Not here, on purpose: the butterflies over a pixel's L lanes in loss.hip and eval.hip (L is
 // a run-time value; they walk 1 -> L/2, which loss.hip's sums pin), the arg-reductions that
 // carry a payload with the value (corresp.hip's projection, mesh_project.hip, eval.hip's
-// fragment argmax: their tie rules are their own) and reduce_scatter32 (pnp_ransac.hip: 32
+// fragment argmax: their tie rules are their own) and reduce_scatter32 (fit_lo.h: 32
 // sums at once, halving the set per level).
 #pragma once
 #include <type_traits>

@@ -4,7 +4,7 @@ reference imports (scripts/infer.py:470-488; un-vendored danini/progressive-x).
 ``find6DPoses`` keeps the reference call's keyword names, input layout (C-contiguous
 float64 ``x1y1 [n,2]`` / ``x2y2z2 [n,3]``, ``K [3,3]``) and return convention:
 ``(poses [3k,4] or None, labels, scores)``. The work runs in the HIP kernels of
-csrc/pnp_ransac.hip through the C ABI ``epos_find6d_poses``; there is no CPU path.
+csrc/pnp_ransac.hip (and the csrc/fit_*.h it includes) through the C ABI ``epos_find6d_poses``; there is no CPU path.
 
 ``solvePnPRansac`` / ``Rodrigues`` stand in for the two cv2 calls of the reference's
 alternative fitting method (``--fitting_method=opencv_ransac``, infer.py:505-528).
