@@ -196,6 +196,12 @@ class VsdPair(ctypes.Structure):
               ('diameter', ctypes.c_double)]
 
 
+class WeightPackArgs(ctypes.Structure):
+  _fields_ = [('W', vp), ('ldw', ctypes.c_int64), ('col0', ctypes.c_int64), ('bias', vp),
+              ('plain', vp), ('split', vp), ('h2', vp), ('bias_pad', vp),
+              ('K', ctypes.c_int32), ('N', ctypes.c_int32)]
+
+
 class FitParams(ctypes.Structure):
   _fields_ = [
       ('threshold', ctypes.c_double),
@@ -399,6 +405,9 @@ SYMBOLS = {
     'epos_momentum_step_f32': (ctypes.c_int, [
         vp, vp, vp, ctypes.c_int64, ctypes.c_float, ctypes.c_float, ctypes.c_float,
         ctypes.c_float, vp]),
+    # weight update: the packers on the device
+    'epos_pack_weights_device_f32': (ctypes.c_int, [
+        ctypes.POINTER(WeightPackArgs), ctypes.c_int, vp, vp]),
 }
 
 _lib = None

@@ -8,18 +8,25 @@ gradients"): the next piece of a trainer after loss.differentiable_losses.
   momentum_step       epos_momentum_step_f32: tf.train.MomentumOptimizer on the regularised,
                       multiplied gradient (train.py:340-384), in place.
   net_head_grads      from a net that has run forward_logits to checkpoint-shaped gradients.
-  HeadsOptimizer      fp32 master copies and accumulators of the six variables.
+  HeadsOptimizer      fp32 master copies and accumulators of the six variables; restores the
+                      accumulators from '<name>/Momentum' entries, so that a run can resume.
+  learning_rate       the reference's schedules (train_utils.py:117-195) in Python floats.
+  train_step          one step of the loop: forward_logits -> net_head_grads -> the optimiser
+                      step -> EposNet.set_head_weights (the device weight packer,
+                      csrc/weight_pack.hip: the updated weights reach the built net, its
+                      captured graphs included, without a round trip through the host).
 
-Out of scope here: putting updated weights back into a built EposNet (the weight packers are
-host functions: a new net, or infer.py, picks the weights up from a checkpoint written from
-HeadsOptimizer.state()), the training loop, the learning-rate schedules, backpropagation below
-the logits, bf16 mode and multi-scale nets.
+The loop itself, its checkpoints and its logging are train_heads.py. Out of scope here:
+backpropagation below the logits (everything there stays frozen), batch-norm statistics,
+augmentation, bf16 mode, multi-scale nets and more than one device.
 
 Pinned to tests/helpers/heads_wgrad_ref.py and, through loss_grad_ref.py, to torch's fp64
-autograd; parity with TensorFlow's numbers is unpinned, as for the losses. There is no CPU
-fallback: without the library or a device this raises EposError.
+autograd; parity with TensorFlow's numbers is unpinned, as for the losses -- that holds for
+learning_rate too: TensorFlow evaluates the schedules in float32, this module in Python
+floats. There is no CPU fallback: without the library or a device this raises EposError.
 """
 import ctypes
+import math
 
 from epos_amd import _lib
 from epos_amd._lib import EposError
@@ -179,12 +186,57 @@ def net_head_grads(net, gt, weights=(1.0, 1.0, 100.0), reduction='pooled', ignor
   return values, bad, grads
 
 
+def learning_rate(step, policy='poly', base_learning_rate=1e-4, decay_step=2000,
+                  decay_factor=0.1, train_steps=2000000, power=0.9, slow_start_step=0,
+                  slow_start_learning_rate=1e-4, burnin='none'):
+  """The reference's learning rate at global step `step` (train_utils.py:117-195), in Python
+  floats. 'poly': base * (1 - min(s, train_steps) / train_steps) ^ power
+  (tf.train.polynomial_decay with end_learning_rate = 0); 'step': base * decay_factor ^
+  floor(s / decay_step) (exponential_decay, staircase); s = step, or step - slow_start_step
+  when there is a burn-in. While step < slow_start_step the rate is slow_start_learning_rate
+  (burnin 'none') or rises linearly from it towards base_learning_rate ('linear')."""
+  if policy not in ('poly', 'step'):
+    raise ValueError('Unknown learning policy: %r (poly, step).' % (policy,))
+  if burnin not in ('none', 'linear'):
+    raise ValueError('Unknown burnin type: %r (none, linear).' % (burnin,))
+  s = step - slow_start_step if burnin != 'none' else step
+  if policy == 'step':
+    lr = base_learning_rate * decay_factor ** math.floor(s / decay_step)
+  else:
+    lr = base_learning_rate * (1.0 - min(s, train_steps) / train_steps) ** power
+  if step < slow_start_step:
+    lr = slow_start_learning_rate
+    if burnin == 'linear':
+      lr += (base_learning_rate - slow_start_learning_rate) * step / slow_start_step
+  return float(lr)
+
+
+def train_step(net, images, gt, opt, lr, weights=(1.0, 1.0, 100.0), reduction='pooled'):
+  """One training step of the logits layers, enqueued on the current stream without a
+  synchronisation: net.forward_logits(images, use_graph=True), net_head_grads, opt.step(grads,
+  lr), net.set_head_weights(opt.params, check=False). Returns (values f64 [4], bad i64 [B],
+  status i32): the losses of THIS step's forward (before its update) and the bad-pixel counts
+  as loss.differentiable_losses returns them, and set_head_weights' status words -- non-zero
+  when the packer refused the updated weights and the net kept the previous ones. The caller
+  reads them when it chooses."""
+  import torch
+  if not torch.cuda.is_available():
+    raise EposError('train_step needs a HIP device (there is no CPU fallback)')
+  net.forward_logits(images, use_graph=True)
+  values, bad, grads = net_head_grads(net, gt, weights, reduction)
+  opt.step(grads, lr)
+  status = net.set_head_weights(opt.params, check=False)
+  return values, bad, status
+
+
 class HeadsOptimizer(object):
   """fp32 master copies and momentum accumulators of the six logits variables on the device.
   variables: {'logits/<name>/weights': [1,1,K,N], 'logits/<name>/biases': [N]} (numpy arrays or
-  tensors; other keys are ignored). step(grads) applies momentum_step per variable as the
-  reference's trainer does: weights get the multiplier m = last_layer_gradient_multiplier and
-  the l2 decay, biases 2 * m and no decay (train_utils.py:84-114)."""
+  tensors) and, optionally, their accumulators '<variable name>/Momentum' as state() and the
+  trainer's checkpoints hold them (absent: zeros); other keys are ignored. step(grads) applies
+  momentum_step per variable as the reference's trainer does: weights get the multiplier
+  m = last_layer_gradient_multiplier and the l2 decay, biases 2 * m and no decay
+  (train_utils.py:84-114). `params` is what EposNet.set_head_weights takes."""
 
   def __init__(self, variables, lr, momentum=0.9, weight_decay=4e-5,
                last_layer_gradient_multiplier=1.0, device=None):
@@ -203,7 +255,15 @@ class HeadsOptimizer(object):
           raise KeyError('variables lack %r' % name)
         v = torch.as_tensor(variables[name]).to(device=self.device, dtype=torch.float32)
         self.params[name] = v.contiguous().clone()
-        self.accums[name] = torch.zeros_like(self.params[name])
+        slot = variables.get(name + '/Momentum')
+        if slot is None:
+          self.accums[name] = torch.zeros_like(self.params[name])
+        else:
+          a = torch.as_tensor(slot).to(device=self.device, dtype=torch.float32)
+          if a.numel() != self.params[name].numel():
+            raise ValueError('%s/Momentum holds %d values, the variable %d' % (
+                name, a.numel(), self.params[name].numel()))
+          self.accums[name] = a.reshape(self.params[name].shape).contiguous().clone()
 
   def step(self, grads, lr=None):
     """One update of every variable from grads (as net_head_grads returns them). lr overrides

@@ -258,6 +258,10 @@ class MultiScaleNet(object):
       self.run_plan()
     return self.outputs()
 
+  def set_head_weights(self, variables, check=True):
+    raise NotImplementedError('set_head_weights: multi-scale nets are not supported (as in '
+                              'heads_train)')
+
   def outputs(self):
     """The prediction dict of the LAST run (no launch)."""
     B, h, w = self.B, self.out_h, self.out_w

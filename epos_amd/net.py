@@ -726,6 +726,112 @@ class EposNet(object):
                  'softmax_slots')
     return flops
 
+  # ------------------------------------------------------ weight update ---
+  def _head_variables(self, variables):
+    """set_head_weights' argument check: [(layer, w f32 [256, N] or numpy, bias)], sorted by
+    layer. Raises before anything is uploaded or enqueued."""
+    widths = W.outputs_to_num_channels(self.num_objs, self.num_frags)
+    given = {}
+    for key, v in variables.items():
+      parts = key.split('/')
+      if (len(parts) != 3 or parts[0] != 'logits' or parts[1] not in widths or
+          parts[2] not in ('weights', 'biases')):
+        raise ValueError('%r is not a variable of the logits layers (logits/<%s>/weights, '
+                         '/biases)' % (key, '|'.join(sorted(widths))))
+      n = widths[parts[1]]
+      shapes = ((1, 1, 256, n), (256, n)) if parts[2] == 'weights' else ((n,),)
+      if isinstance(v, torch.Tensor):
+        if v.dtype != torch.float32:
+          raise TypeError('%s must be torch.float32, got %s' % (key, v.dtype))
+        if v.device != self.dev:
+          raise ValueError('%s is on %s, the net on %s (numpy arrays are uploaded)' % (
+              key, v.device, self.dev))
+        if not v.is_contiguous():
+          raise ValueError('%s must be contiguous' % key)
+      else:
+        v = np.asarray(v)
+        if v.dtype.kind != 'f':
+          raise TypeError('%s must be a floating-point array, got %s' % (key, v.dtype))
+      if tuple(v.shape) not in shapes:
+        raise ValueError('%s must have shape %s, got %s' % (
+            key, ' or '.join(str(list(s)) for s in shapes), list(v.shape)))
+      given.setdefault(parts[1], {})[parts[2]] = v
+    out = []
+    for layer in sorted(given):
+      if len(given[layer]) != 2:
+        raise ValueError('logits/%s: weights and biases are set together' % layer)
+      out.append((layer, given[layer]['weights'], given[layer]['biases']))
+    return out
+
+  def set_head_weights(self, variables, check=True):
+    """Replaces the weights of logits layers in place, on the device. variables:
+    {'logits/<name>/weights': [1,1,256,N] or [256,N], 'logits/<name>/biases': [N]} for any
+    subset of pred_obj_conf, pred_frag_conf, pred_frag_loc (a layer's two variables together);
+    values are contiguous fp32 tensors on the net's device (heads_train.HeadsOptimizer.params as
+    it is) or numpy arrays, which are uploaded. A wrong name, shape, dtype or device raises
+    ValueError / TypeError before anything is enqueued.
+
+    One grouped epos_pack_weights_device_f32 call on the current stream packs them into the very
+    tensors the plan's launch arguments point at, together with the per-object packs of the
+    sparse heads (built first if they were not): no pointer changes, so forward(),
+    forward_logits(), every graph captured before the call, the pipeline's and the stand-alone
+    object head use the new weights on their next run. A layer whose fp16-pair weights the host
+    packer refused when the plan was built gets its other layouts only. self.ckpt is NOT
+    updated (that would take a download): it keeps the weights the net was built from.
+
+    All or nothing: when the packer refuses one layer (a non-finite weight, or a column whose
+    fp16-pair scale leaves 2^+-100) nothing is written and the net holds its previous weights.
+    check=True reads the status words back (one small synchronising copy) and raises EposError
+    naming the layer; check=False does not synchronise. Returns the status tensor (int32, on
+    the device, one word per packed matrix: the layers in sorted order, then per fragment layer
+    its num_objs sparse packs; 0 = written).
+
+    Ordering is the caller's: the update is enqueued on the current stream, and a forward in
+    flight on ANOTHER stream must be ordered against it by the caller (nothing here records or
+    waits for events). fp32 single-scale nets with num_objs <= 126 only."""
+    if self.precision != 'fp32':
+      raise NotImplementedError('set_head_weights: precision=%r nets are not supported' %
+                                self.precision)
+    if self.lib is None:
+      raise _lib.EposError('set_head_weights needs a HIP device (there is no CPU fallback)')
+    layers = self._head_variables(variables)
+    O, F = self.num_objs, self.num_frags
+    if 3 + 2 * O > 256:
+      raise NotImplementedError('set_head_weights: more than 126 objects')
+    if not layers:
+      return torch.zeros(0, dtype=torch.int32, device=self.dev)
+    sparse_n = {W.PRED_FRAG_CONF: (0, F), W.PRED_FRAG_LOC: (1, 3 * F)}
+    if self._sparse_packs is None and any(l[0] in sparse_n for l in layers):
+      self._build_sparse_packs()         # from self.ckpt, while it still describes the net
+    probs, names, dense = [], [], []
+    with torch.cuda.device(self.dev):
+      for layer, w, b in layers:
+        w = torch.as_tensor(w, dtype=torch.float32).to(self.dev).reshape(256, -1)
+        b = torch.as_tensor(b, dtype=torch.float32).to(self.dev)
+        dense.append((layer, w, b))
+        probs.append(self.mode.pack_problem(self.mode.head_packs[layer], w, b, 0, w.shape[1]))
+        names.append(layer)
+      for layer, w, b in dense:
+        if layer in sparse_n:
+          kind, n = sparse_n[layer]
+          for o in range(O):
+            probs.append(self.mode.pack_problem(self._sparse_packs[o][kind], w, b, o * n, n))
+            names.append('%s (sparse pack of object %d)' % (layer, o + 1))
+      status = torch.empty(len(probs), dtype=torch.int32, device=self.dev)
+      self.mode.pack_launch(probs, status, self._stream())
+    stream = torch.cuda.current_stream(self.dev)
+    for _, w, b in dense:
+      w.record_stream(stream)            # uploaded copies outlive the call
+      b.record_stream(stream)
+    if check:
+      bad = [names[i] for i in torch.nonzero(status.cpu()).flatten().tolist()]
+      if bad:
+        raise _lib.EposError(
+            'set_head_weights: the fp16-pair packer refused logits/%s (a non-finite weight, or '
+            'a column whose scale leaves 2^+-100); nothing was written, the net still holds its '
+            'previous weights' % ', logits/'.join(bad))
+    return status
+
   def set_images(self, images):
     """images: [B,H,W,3] in [0,255] (host numpy or device tensor), float32 -- or uint8 as the
     decoder delivers them (datagen.py:435-436 casts to float32 right behind decode_image; here

@@ -101,6 +101,10 @@ class Fp32Mode(object):
     self.use_presplit = self.use_h2 and os.environ.get('EPOS_H2_PRESPLIT', '1') == '1'
     self._dw_h2 = {}           # id(depthwise output) -> its (mutable) launch arguments
     self.h2_layers, self.h2_refused, self.presplit_layers = [], [], []
+    # logits layer -> the (wp, bp, ws, wh) tensors its launch arguments point at: where
+    # EposNet.set_head_weights packs updated weights (references only; wh None = refused)
+    self.head_packs = {}
+    self.pack_device = fn('epos_pack_weights_device_f32')
     self._last_pw = None       # (C, args, foldable): the last stand-alone 1x1 launch
     self._first_im2col = None  # (op name, args, capacity in words): the plan's first im2col
 
@@ -199,6 +203,8 @@ class Fp32Mode(object):
     wp, bp, ws, wh, kpad = self._weights(name, conv, ab is not None and m > 8)
     n = conv[0].shape[1]
     assert kpad == k or (kpad > k and lda >= kpad), (name, k, kpad, lda)
+    if name.startswith('logits/'):
+      self.head_packs[name[len('logits/'):]] = (wp, bp, ws, wh)
     # A = the output of a depthwise conv that was set up to write fp16 pairs: keep that
     # only if this GEMM really runs on the fp16-pair kernel (the packer may have refused
     # the weights); the depthwise arguments are the very struct its launch passes
@@ -360,6 +366,21 @@ class Fp32Mode(object):
   def sparse_launch(self, probs, stream):
     arr = (_lib.PointwiseArgs * len(probs))(*probs)
     _lib.check(self.gemm(arr, len(probs), stream), 'sparse heads')
+
+  # ------------------------------------------------------ weight update ---
+  def pack_problem(self, pack, w, bias, col0, n):
+    """The device packer's problem that rewrites `pack` = (wp, bp, ws, wh) from the column
+    window [col0, col0 + n) of w f32 [256, ldw] and bias f32 [ldw] (device tensors)."""
+    wp, bp, ws, wh = pack
+    return _lib.WeightPackArgs(W=_ptr(w), ldw=w.shape[-1], col0=col0, bias=_ptr(bias),
+                               plain=_ptr(wp), split=_ptr(ws),
+                               h2=_ptr(wh) if wh is not None else None, bias_pad=_ptr(bp),
+                               K=w.shape[-2], N=n)
+
+  def pack_launch(self, probs, status, stream):
+    """One grouped epos_pack_weights_device_f32 call: all of probs or none of them."""
+    arr = (_lib.WeightPackArgs * len(probs))(*probs)
+    _lib.check(self.pack_device(arr, len(probs), _ptr(status), stream), 'set_head_weights')
 
   def finish(self):
     """The slot table is zeroed by the plan's first launch. Round 4: that is the im2col of the

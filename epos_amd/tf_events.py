@@ -46,6 +46,8 @@ def encode_events(scalars, step, wall_time=None):
   """The records of an event file holding `scalars` ([(tag, value)] or {tag: value}) at
   `step`: the version record, then one Event with all the values."""
   wall_time = time.time() if wall_time is None else wall_time
+  if scalars is None:                        # the version record alone (EventWriter)
+    return [_enc_event(wall_time, 0, file_version=FILE_VERSION)]
   if isinstance(scalars, dict):
     scalars = list(scalars.items())
   return [_enc_event(wall_time, 0, file_version=FILE_VERSION),
@@ -64,6 +66,22 @@ def write_scalars(log_dir, scalars, step, wall_time=None):
     path = '%s.%d' % (base, n)
   tfrecord.write_records(path, encode_events(scalars, step, wall_time))
   return path
+
+
+class EventWriter(object):
+  """One event file in log_dir that grows: the version record now, then one Event per add()
+  (a training run's scalars at its log steps)."""
+
+  def __init__(self, log_dir, wall_time=None):
+    wall_time = time.time() if wall_time is None else wall_time
+    self.path = write_scalars(log_dir, None, 0, wall_time)
+
+  def add(self, scalars, step, wall_time=None):
+    wall_time = time.time() if wall_time is None else wall_time
+    if isinstance(scalars, dict):
+      scalars = list(scalars.items())
+    tfrecord.write_records(self.path, [_enc_event(wall_time, step, scalars=scalars)],
+                           append=True)
 
 
 def decode_event(data):

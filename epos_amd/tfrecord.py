@@ -80,8 +80,8 @@ def scan_records(path, verify_crc=False):
     off += 12 + len(data) + 4
 
 
-def write_records(path, records):
-  with open(path, 'wb') as f:
+def write_records(path, records, append=False):
+  with open(path, 'ab' if append else 'wb') as f:
     for data in records:
       head = struct.pack('<Q', len(data))
       f.write(head + struct.pack('<I', _masked_crc(head)))

@@ -1261,6 +1261,54 @@ int epos_heads_wgrad_f32(const float* A, int64_t lda, int K, const float* obj_lo
 int epos_momentum_step_f32(float* w, float* accum, const float* grad, int64_t n, float lr,
                            float momentum, float weight_decay, float grad_mult, void* stream);
 
+/* Weight update (csrc/weight_pack.hip; added without an ABI version change). The three host
+ * packers above restated as device kernels, so that weights updated on the device (the momentum
+ * step) reach a built plan without a round trip through the host: a grouped call packs fp32
+ * matrices that live on the device into the buffers the plan's launches already point at.
+ *
+ * One problem = one matrix: the column window [col0, col0 + N) of W f32 [K][ldw] (row-major,
+ * the checkpoint layout [1,1,K,N'] of a logits layer; K a multiple of 4, 4..1024; N >= 1) and
+ * of bias f32 (bias[col0 + n]). Up to four destinations, each NULL = not wanted:
+ *   plain     what epos_pack_pointwise_weights writes for that K x N window,
+ *   split     what epos_pack_pointwise_weights_split writes,
+ *   h2        what epos_pack_pointwise_weights_h2 writes, the round_up(N, 128) inverse scales
+ *             behind the fragments included,
+ *   bias_pad  round_up(N, 128) floats: the bias, then zeros.
+ * Every byte of a destination is written (the zero padding of K and N too) and equals the host
+ * packer's byte for finite weights; fp32-subnormal weights and residuals are kept. The inverse
+ * scale is built from the exponent. A non-finite weight is packed only without an h2
+ * destination; the NaN payloads of its split pieces are unspecified.
+ *   Acceptance. A problem WITH an h2 destination is refused exactly when the host fp16-pair
+ *   packer returns 0 for the window: a weight that is not finite, a column maximum whose scale
+ *   2^e leaves |e| <= 100, or a weight that fails the packer's self-check
+ *   |hi + mid 2^-11 - t| <= max(2^-22 |t|, 2^-36). A problem without h2 is never refused.
+ *   All or nothing. status i32 [device, count]: 0 = written, non-zero = refused. If ANY problem
+ *   of the call is refused, no destination byte of ANY problem of the call is written. The
+ *   caller reads status when it chooses; nothing here waits for the device.
+ *   Launches. One clear of status, then per 32 problems one checking launch (only when some
+ *   problem has an h2 destination) and, behind ALL of those, one writing launch, in sequence on
+ *   `stream`: no allocation, no synchronisation, integer atomics only, the same bytes in every
+ *   run. One workgroup per (problem, 128 columns) reads its columns once for the column maxima
+ *   and once through LDS for all layouts, and stores whole 1 KB fragments.
+ *   Refused with EPOS_E_INVALID before anything is enqueued: a null table, count outside 0..256,
+ *   a null or misaligned status, K / N / ldw / col0 out of range, a null W, bias_pad without
+ *   bias, W or bias not 4-byte aligned, plain / split / h2 not 16-byte aligned (the GEMMs read
+ *   them with 16-byte loads) or bias_pad not 4-byte aligned. Source and destinations must not
+ *   overlap. count == 0 returns 0 and launches nothing. */
+typedef struct EposWeightPackArgs {
+  const float* W;          /* device f32 [K][ldw] */
+  int64_t ldw;             /* col0 + N <= ldw <= 2^31 */
+  int64_t col0;
+  const float* bias;       /* device f32, NULL allowed when bias_pad is NULL */
+  float* plain;
+  void* split;
+  void* h2;
+  float* bias_pad;
+  int32_t K, N;
+} EposWeightPackArgs;
+int epos_pack_weights_device_f32(const EposWeightPackArgs* args, int count, int32_t* status,
+                                 void* stream);
+
 #ifdef __cplusplus
 }
 #endif
