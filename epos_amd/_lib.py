@@ -408,6 +408,10 @@ SYMBOLS = {
     # weight update: the packers on the device
     'epos_pack_weights_device_f32': (ctypes.c_int, [
         ctypes.POINTER(WeightPackArgs), ctypes.c_int, vp, vp]),
+    # augmentation
+    'epos_augment_workspace_bytes': (ctypes.c_int64, [ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    'epos_augment_f32': (ctypes.c_int, [
+        vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, ctypes.c_int, vp, vp]),
 }
 
 _lib = None

@@ -18,7 +18,8 @@ gradients"): the next piece of a trainer after loss.differentiable_losses.
 
 The loop itself, its checkpoints and its logging are train_heads.py. Out of scope here:
 backpropagation below the logits (everything there stays frozen), batch-norm statistics,
-augmentation, bf16 mode, multi-scale nets and more than one device.
+bf16 mode, multi-scale nets and more than one device. Augmentation is epos_amd/augment.py;
+train_step applies it between the upload and the forward pass.
 
 Pinned to tests/helpers/heads_wgrad_ref.py and, through loss_grad_ref.py, to torch's fp64
 autograd; parity with TensorFlow's numbers is unpinned, as for the losses -- that holds for
@@ -211,10 +212,14 @@ def learning_rate(step, policy='poly', base_learning_rate=1e-4, decay_step=2000,
   return float(lr)
 
 
-def train_step(net, images, gt, opt, lr, weights=(1.0, 1.0, 100.0), reduction='pooled'):
+def train_step(net, images, gt, opt, lr, weights=(1.0, 1.0, 100.0), reduction='pooled',
+               augment=None, step=None):
   """One training step of the logits layers, enqueued on the current stream without a
   synchronisation: net.forward_logits(images, use_graph=True), net_head_grads, opt.step(grads,
-  lr), net.set_head_weights(opt.params, check=False). Returns (values f64 [4], bad i64 [B],
+  lr), net.set_head_weights(opt.params, check=False). With augment (an augment.Augmenter) the
+  images are uploaded first (net.set_images), augmented in place on the device with the draws
+  of global step `step` (augment.apply(net.images, step)) and the forward pass reads them
+  there. Returns (values f64 [4], bad i64 [B],
   status i32): the losses of THIS step's forward (before its update) and the bad-pixel counts
   as loss.differentiable_losses returns them, and set_head_weights' status words -- non-zero
   when the packer refused the updated weights and the net kept the previous ones. The caller
@@ -222,6 +227,12 @@ def train_step(net, images, gt, opt, lr, weights=(1.0, 1.0, 100.0), reduction='p
   import torch
   if not torch.cuda.is_available():
     raise EposError('train_step needs a HIP device (there is no CPU fallback)')
+  if augment is not None:
+    if step is None:
+      raise ValueError('train_step: augment needs the global step its draws are keyed by')
+    net.set_images(images)
+    augment.apply(net.images, step)
+    images = None
   net.forward_logits(images, use_graph=True)
   values, bad, grads = net_head_grads(net, gt, weights, reduction)
   opt.step(grads, lr)

@@ -1309,6 +1309,67 @@ typedef struct EposWeightPackArgs {
 int epos_pack_weights_device_f32(const EposWeightPackArgs* args, int count, int32_t* status,
                                  void* stream);
 
+/* Augmentation (csrc/augment.hip; added without an ABI version change). The seven training-time
+ * image operations of the reference (epos_lib/datagen.py:629-670, epos_lib/augment.py), in
+ * place on images f32 [device, B,h,w,3] with values in [0,255]. The table holds DRAWN values,
+ * not ranges: the call is a pure function of its arguments.
+ *
+ * ops [HOST, B][n_ops], 0 <= n_ops <= 8, is read during the call (it travels in kernel
+ * arguments) and may be reused on return. The ops of an image run in the order given, on
+ * x = value / 255 (fp32, before the first op; the result is multiplied by 255 after the last).
+ * An image whose ops are all NONE (or n_ops == 0) keeps its bytes.
+ *   NONE                   skipped
+ *   BRIGHTNESS  a = delta  clip(x + a, 0, 1)
+ *   CONTRAST    a = factor clip((x - m_c) a + m_c, 0, 1), m_c = the mean of channel c over the
+ *                          image as the preceding ops left it: fp64 sums of 64 fixed pixel
+ *                          ranges, added in their order (no floating-point atomics)
+ *   SATURATION  a = factor RGB -> HSV (hexcone; h = 0 where max = min), s = clip(s a, 0, 1),
+ *                          HSV -> RGB, clip
+ *   HUE         a = delta  RGB -> HSV, h = (h + a) mod 1 in [0,1), HSV -> RGB, clip
+ *   BLUR        a = sigma  ksize = round_half_even(8 sigma + 1) | 1, R = (ksize - 1) / 2;
+ *                          w_i = exp(-i^2 / (2 sigma^2)) / sum in fp64, rounded to fp32; rows,
+ *                          then columns, fp32 accumulation from -R to R, BORDER_REFLECT_101, no
+ *                          clip. sigma == 0 or ksize == 1: skipped. R > 32 or
+ *                          R > min(h, w) - 1: refused
+ *   NOISE       a = sigma  clip(x + a z, 0, 1); value i = (y w + x) 3 + c of the image takes
+ *                          z(i) from Philox4x32-10 at counter (i / 4, 0, 0, 0), key (key_lo,
+ *                          key_hi): u1 = ((r0 >> 8) + 0.5) 2^-24, u2 = (r1 >> 8) 2^-24,
+ *                          z(4j) = sqrt(-2 ln u1) cos(2 pi u2), z(4j+1) = ... sin(2 pi u2),
+ *                          z(4j+2), z(4j+3) the same from (r2, r3)
+ *   JPEG        a = quality (an integer, 1..100) a round trip through 8-bit baseline JPEG with
+ *                          4:2:0 chroma: v = min(255, floor(x 255.5)), the IJG 16-bit fixed-point
+ *                          colour transforms, luma padded to 16 by replication, 2x2 chroma
+ *                          means with the alternating bias (of pixels replicated to 16 columns
+ *                          and an even number of rows; below that the last chroma row is
+ *                          replicated), the 8x8 DCT in fp64, the Annex K
+ *                          tables at the IJG quality scaling, "fancy" triangle chroma
+ *                          upsampling, x = v / 255 ("Augmentation", has each step)
+ * Nothing synchronises and nothing is allocated: every launch is enqueued on `stream`, and
+ * the number of launches does not depend on B up to 8 (images go into the grid in chunks of 8).
+ * The same arguments give the same bytes in every run and at every position of a batch.
+ * work: epos_augment_workspace_bytes(B, h, w) bytes on the device, 16-byte aligned; may be NULL
+ * when no op is a CONTRAST, a BLUR or a JPEG.
+ *   Refused with EPOS_E_INVALID before the first launch: B < 0, h or w < 1, h w 3 >= 2^31,
+ *   n_ops outside 0..8, null images or ops (when B and n_ops are positive), images not 4-byte
+ *   aligned, an unknown kind, a parameter that is not finite, a negative sigma, a blur radius
+ *   out of range, a quality that is no integer in 1..100, a missing or misaligned workspace. */
+#define EPOS_AUG_NONE 0
+#define EPOS_AUG_BRIGHTNESS 1
+#define EPOS_AUG_CONTRAST 2
+#define EPOS_AUG_SATURATION 3
+#define EPOS_AUG_HUE 4
+#define EPOS_AUG_BLUR 5
+#define EPOS_AUG_NOISE 6
+#define EPOS_AUG_JPEG 7
+typedef struct EposAugmentOp {
+  int32_t kind;
+  float a, b;              /* b: reserved, ignored */
+  uint32_t key_lo, key_hi;
+} EposAugmentOp;
+int64_t epos_augment_workspace_bytes(int B, int h, int w);
+int epos_augment_f32(float* images, int B, int h, int w, const EposAugmentOp* ops, int n_ops,
+                     void* work, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,7 +8,10 @@ The part of the reference's ``scripts/train.py`` that this build has kernels for
 pred_frag_loc, tf.train.MomentumOptimizer with the l2 regulariser and the last-layer gradient
 multiplier (train.py:340-384) and the learning-rate schedules (train_utils.py:117-195).
 Everything below the logits stays frozen, as the reference does with --freeze_regex_list; no
-augmentation, no batch-norm statistics, one device, fp32, one scale.
+batch-norm statistics, one device, fp32, one scale. --data_augmentations (a mapping in the YAML
+format, on the command line or in params.yml, datagen.py:629-670) runs on the device between
+the upload of a batch and its forward pass (epos_amd/augment.py); its draws are keyed by
+(--seed, global step, image), so a resumed run augments as an uninterrupted one would.
 
   * env TF_DATA_PATH / TF_MODELS_PATH / BOP_PATH; <TF_MODELS_PATH>/<model>/params.yml overrides
     flag defaults; the flags of scripts/train.py:53-149 under their names and defaults;
@@ -98,8 +101,9 @@ def unfrozen_below_logits(regexes, args):
 
 
 def prepare(argv=None):
-  """Parses the command line, applies params.yml and refuses what this build cannot train."""
-  from epos_amd import multiscale
+  """Parses the command line, applies params.yml and refuses what this build cannot train.
+  args.data_augmentations becomes augment.parse's list."""
+  from epos_amd import augment, multiscale
   args = build_parser().parse_args(argv)
   model_dir = cli.model_dir(args)
   cli.update_flags(args, os.path.join(model_dir, cli.PARAMS_FILENAME))
@@ -113,9 +117,7 @@ def prepare(argv=None):
   if cli.str2bool(args.fine_tune_batch_norm):
     raise NotImplementedError('fine_tune_batch_norm=true: the batch-norm layers lie below the '
                               'logits and stay frozen')
-  if args.data_augmentations not in (None, '', [], {}, 'None'):
-    raise NotImplementedError('data_augmentations=%r: augmentation is not built' %
-                              (args.data_augmentations,))
+  args.data_augmentations = augment.parse(args.data_augmentations)
   if args.freeze_regex_list is not None:
     regexes = args.freeze_regex_list
     regexes = [regexes] if isinstance(regexes, str) else list(regexes)
@@ -158,7 +160,7 @@ def save(checkpoint_dir, raw, opt, step):
 def main(argv=None):
   args, model_dir = prepare(argv)
   import torch
-  from epos_amd import loss, model, ply, render, tf_checkpoint, tf_events
+  from epos_amd import augment, loss, model, ply, render, tf_checkpoint, tf_events
   from epos_amd import frames as eframes
   checkpoint_dir = os.path.join(model_dir, 'train')
   dev_index = cli.device_from_env()
@@ -191,6 +193,10 @@ def main(argv=None):
   opt = heads_train.HeadsOptimizer(
       raw, args.base_learning_rate, args.momentum, args.weight_decay,
       args.last_layer_gradient_multiplier, device=dev)
+  augmenter = None
+  if args.data_augmentations:
+    augmenter = augment.Augmenter(args.data_augmentations, args.seed, dev)
+    print('Augmentations: {}'.format(', '.join(augmenter.names)))
   weights = (args.obj_cls_loss_weight, args.frag_cls_loss_weight, args.frag_loc_loss_weight)
   todo = max(0, args.train_steps - step)
   order = [frames[(s * B + b) % len(frames)] for s in range(step, step + todo) for b in range(B)]
@@ -218,7 +224,8 @@ def main(argv=None):
                                                input_size=(w, h)) for f in chunk]
     gt = {k: torch.stack([f[k] for f in fields]) for k in loss.GT_KEYS}
     lr = schedule(args, step)
-    values, bad, status = heads_train.train_step(net, imgs, gt, opt, lr, weights)
+    values, bad, status = heads_train.train_step(net, imgs, gt, opt, lr, weights,
+                                                  augment=augmenter, step=step)
     refused.bitwise_or_(status)
     bad_pixels.add_(bad.sum())
     step += 1
