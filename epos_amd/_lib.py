@@ -405,6 +405,11 @@ SYMBOLS = {
     'epos_momentum_step_f32': (ctypes.c_int, [
         vp, vp, vp, ctypes.c_int64, ctypes.c_float, ctypes.c_float, ctypes.c_float,
         ctypes.c_float, vp]),
+    # input gradient of the logits layers
+    'epos_heads_dgrad_f32': (ctypes.c_int, [
+        vp, ctypes.c_int64, vp, vp, vp, vp, vp, vp, ctypes.c_int, ctypes.c_int64, ctypes.c_int,
+        ctypes.c_int, ctypes.c_int, vp, vp, vp, vp, vp, ctypes.c_int64, ctypes.c_int, vp,
+        ctypes.c_int64, vp, ctypes.c_int64, vp]),
     # weight update: the packers on the device
     'epos_pack_weights_device_f32': (ctypes.c_int, [
         ctypes.POINTER(WeightPackArgs), ctypes.c_int, vp, vp]),

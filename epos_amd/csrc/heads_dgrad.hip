@@ -1,0 +1,251 @@
+// The input gradient of the three logits layers: dL/d decoder_out from the raw logits and the
+// transposed weights, without ever forming the dense logit gradients (include/epos_hip.h,
+// "Input gradient"; DESIGN.md, "Losses", "Input gradient").
+//
+//   heads_dgrad_kernel  a workgroup owns DG_SHARE consecutive pixels of ONE image. Phase one is
+//                       epos_loss_grads': L lanes share a pixel's row (loss_rows.h), the pixel's
+//                       class, m and S of its two rows go to LDS. Phase two is a gather-GEMV per
+//                       pixel: a wave takes every fourth pixel of the share; its lanes compute
+//                       the pixel's active logit gradients 64 at a time, one per lane, exactly
+//                       as epos_loss_grads rounds them; each value is then broadcast from its
+//                       lane and multiplied with its row of the transposed weights, a lane
+//                       holding the fp64 sums of its own feature indices k in registers. The
+//                       row is rounded and stored once, 16 bytes per lane where the layout
+//                       allows.
+//
+// Every output row is computed by one wave from its own pixel, the weights and s_k only, one
+// accumulator per (pixel, k), the active columns in the stated order: no workspace, no atomics,
+// the same bytes in every run, at every position of every batch and for every alignment.
+// fp64 on the fp32 values, -ffp-contract=off.
+#include "loss_rows.h"
+
+namespace epos {
+namespace {
+
+constexpr int DG_MAX_K = 1024;
+constexpr int64_t DG_SHARE = 16;             // pixels per workgroup, four per wave
+constexpr int DG_WAVES = LOSS_THREADS / 64;
+
+// What phase one leaves of a share's pixels
+struct DgRows {
+  double s_obj[DG_SHARE], s_frag[DG_SHARE];  // S of the two rows
+  float m_obj[DG_SHARE], m_frag[DG_SHARE];   // m of the two rows
+  float wgt[DG_SHARE];
+  int code[DG_SHARE], frag[DG_SHARE];
+};
+
+int check_dims(const char* fn, int B, int64_t P, int num_objs, int num_frags, int K) {
+  const int rc = check_loss_dims(fn, B, P, num_objs, num_frags, DG_SHARE);
+  if (rc != EPOS_OK) return rc;
+  if (K < 1 || K > DG_MAX_K) {
+    set_error("%s: K must be in 1..1024", fn);
+    return EPOS_E_INVALID;
+  }
+  return EPOS_OK;
+}
+
+// The value lane `src` holds, in every lane; src is the same in all lanes
+__device__ __forceinline__ float from_lane(float v, int src) {
+  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), src));
+}
+
+// A lane's feature indices: k = (lane + 64 j) * KV + i, j < J, i < KV. KV == 4 needs K % 4 == 0
+// and 16-byte aligned rows, so that a quad is inside K whenever its first index is.
+template <int KV, int J>
+__device__ __forceinline__ void add_row(double (&acc)[J * KV], const float* __restrict__ row,
+                                        int K, int lane, double dv) {
+#pragma unroll
+  for (int j = 0; j < J; ++j) {
+    const int k = (lane + 64 * j) * KV;
+    if (k >= K) continue;
+    if constexpr (KV == 4) {
+      const float4 w = *reinterpret_cast<const float4*>(row + k);
+      acc[4 * j] += dv * static_cast<double>(w.x);
+      acc[4 * j + 1] += dv * static_cast<double>(w.y);
+      acc[4 * j + 2] += dv * static_cast<double>(w.z);
+      acc[4 * j + 3] += dv * static_cast<double>(w.w);
+    } else {
+      acc[j] += dv * static_cast<double>(row[k]);
+    }
+  }
+}
+
+// acc += sum_{e < n} d_e * rows[e], ascending e; lane e holds d_e (n <= 64, the same in all lanes).
+// One row per step: taking 4, 8 or 16 rows' loads ahead of their additions cost occupancy and
+// measured 1.2, 1.4 and 1.9 times the time at C2 (profiles/r24/).
+template <int KV, int J>
+__device__ __forceinline__ void add_rows(double (&acc)[J * KV], const float* __restrict__ rows,
+                                         int64_t ldwt, int n, int K, int lane, float dv) {
+  for (int e = 0; e < n; ++e)
+    add_row<KV, J>(acc, rows + e * ldwt, K, lane, static_cast<double>(from_lane(dv, e)));
+}
+
+template <int KV, int J>
+__global__ __launch_bounds__(LOSS_THREADS) void heads_dgrad_kernel(
+    const float* __restrict__ obj_logits, int64_t ld_obj, const float* __restrict__ frag_logits,
+    const float* __restrict__ frag_loc, const int32_t* __restrict__ gt_obj,
+    const int32_t* __restrict__ gt_frag, const float* __restrict__ gt_loc,
+    const float* __restrict__ gt_weight, int64_t P, int64_t blocks_per_image, int num_objs,
+    int num_frags, int ignore_label, int L, const double* __restrict__ scales,
+    const double* __restrict__ upstream, const float* __restrict__ Wt_obj,
+    const float* __restrict__ Wt_frag, const float* __restrict__ Wt_loc, int64_t ldwt, int K,
+    const float* Y, int64_t ldy, float* dX, int64_t ldx) {
+  __shared__ DgRows sh;
+  const int64_t image = blockIdx.x / blocks_per_image;
+  const int64_t p0 = (blockIdx.x % blocks_per_image) * DG_SHARE;
+  const int64_t p1 = p0 + DG_SHARE < P ? p0 + DG_SHARE : P;
+  const int n_here = static_cast<int>(p1 - p0);              // 1..DG_SHARE
+  const int64_t pix0 = image * P + p0;                       // pixel of the whole batch
+  const int O1 = num_objs + 1, F = num_frags;
+  const int sub = threadIdx.x % L;                           // L is a power of two <= 64
+  const int per_pass = LOSS_THREADS / L;
+  for (int base = 0; base < n_here; base += per_pass) {     // uniform trip count: shuffles below
+    const int i = base + threadIdx.x / L;
+    const int64_t p = pix0 + i;
+    int g = CODE_NONE, f = 0;
+    float wgt = 0.f;
+    if (i < n_here)
+      g = pixel_class(gt_obj, gt_frag, gt_weight, p, num_objs, F, ignore_label, f, wgt);
+    double m_o = 0.0, s_o = 0.0, m_f = 0.0, s_f = 0.0;
+    row_max_sum<false>(obj_logits + (g >= 0 ? p * ld_obj : 0), O1, g >= 0, sub, L, m_o, s_o);
+    const int64_t frag_row = g > 0 ? (p * num_objs + (g - 1)) * F : 0;
+    row_max_sum<false>(frag_logits + frag_row, F, g > 0, sub, L, m_f, s_f);
+    if (i < n_here && sub == 0) {
+      sh.code[i] = g;
+      sh.frag[i] = f;
+      sh.wgt[i] = wgt;
+      sh.m_obj[i] = static_cast<float>(m_o);                 // m is an fp32 value
+      sh.s_obj[i] = s_o;
+      sh.m_frag[i] = static_cast<float>(m_f);
+      sh.s_frag[i] = s_f;
+    }
+  }
+  __syncthreads();
+  // s_k = scales[b,k] * (upstream[k] + upstream[3]), one product
+  double s[3];
+  for (int k = 0; k < 3; ++k)
+    s[k] = scales[image * 3 + k] * (upstream ? upstream[k] + upstream[3] : 1.0);
+
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  for (int i = wave; i < n_here; i += DG_WAVES) {
+    const int64_t p = pix0 + i;
+    const int g = __builtin_amdgcn_readfirstlane(sh.code[i]);          // the wave's pixel
+    double acc[J * KV];
+#pragma unroll
+    for (int a = 0; a < J * KV; ++a) acc[a] = 0.0;
+    if (g >= 0) {
+      const double m = static_cast<double>(sh.m_obj[i]), S = sh.s_obj[i];
+      for (int c0 = 0; c0 < O1; c0 += 64) {                  // the object head, 64 columns a time
+        const int c = c0 + lane;
+        float dv = 0.f;
+        if (c < O1) {
+          const double x = static_cast<double>(obj_logits[p * ld_obj + c]);
+          const double pr = exp(x - m) / S;
+          dv = static_cast<float>(s[0] * (pr - (c == g ? 1.0 : 0.0)));
+        }
+        add_rows<KV, J>(acc, Wt_obj + c0 * ldwt, ldwt, O1 - c0 < 64 ? O1 - c0 : 64, K, lane, dv);
+      }
+    }
+    if (g > 0) {
+      const int f = __builtin_amdgcn_readfirstlane(sh.frag[i]);
+      const int64_t row0 = static_cast<int64_t>(g - 1) * F;  // the pixel's row of O * F
+      const double m = static_cast<double>(sh.m_frag[i]), S = sh.s_frag[i];
+      for (int c0 = 0; c0 < F; c0 += 64) {                   // the fragment head
+        const int c = c0 + lane;
+        float dv = 0.f;
+        if (c < F) {
+          const double x = static_cast<double>(frag_logits[(p * num_objs + (g - 1)) * F + c]);
+          const double pr = exp(x - m) / S;
+          dv = static_cast<float>(s[1] * (pr - (c == f ? 1.0 : 0.0)));
+        }
+        add_rows<KV, J>(acc, Wt_frag + (row0 + c0) * ldwt, ldwt, F - c0 < 64 ? F - c0 : 64, K,
+                        lane, dv);
+      }
+      float dv = 0.f;                                        // the three localisation values
+      if (lane < 3) {
+        const double q = static_cast<double>(frag_loc[((p * num_objs + (g - 1)) * F + f) * 3 + lane]);
+        const double d = q - static_cast<double>(gt_loc[p * 3 + lane]);
+        // the derivative of the Huber term, knee included: |d| <= 1 gives d
+        const double cl = d > 1.0 ? 1.0 : d < -1.0 ? -1.0 : d;
+        dv = static_cast<float>(s[2] * (static_cast<double>(sh.wgt[i]) * cl));
+      }
+      add_rows<KV, J>(acc, Wt_loc + (row0 + f) * 3 * ldwt, ldwt, 3, K, lane, dv);
+    }
+    // an ignored or bad pixel: the sums are still +0.0
+#pragma unroll
+    for (int j = 0; j < J; ++j) {
+      const int k = (lane + 64 * j) * KV;
+      if (k >= K) continue;
+      if constexpr (KV == 4) {
+        float4 v = make_float4(static_cast<float>(acc[4 * j]), static_cast<float>(acc[4 * j + 1]),
+                               static_cast<float>(acc[4 * j + 2]),
+                               static_cast<float>(acc[4 * j + 3]));
+        if (Y) {
+          const float4 y = *reinterpret_cast<const float4*>(Y + p * ldy + k);
+          if (y.x <= 0.f) v.x = 0.f;
+          if (y.y <= 0.f) v.y = 0.f;
+          if (y.z <= 0.f) v.z = 0.f;
+          if (y.w <= 0.f) v.w = 0.f;
+        }
+        *reinterpret_cast<float4*>(dX + p * ldx + k) = v;
+      } else {
+        float v = static_cast<float>(acc[j]);
+        if (Y && Y[p * ldy + k] <= 0.f) v = 0.f;
+        dX[p * ldx + k] = v;
+      }
+    }
+  }
+}
+
+}  // namespace
+}  // namespace epos
+
+using namespace epos;
+
+extern "C" int epos_heads_dgrad_f32(const float* obj_logits, int64_t ld_obj,
+                                    const float* frag_logits, const float* frag_loc,
+                                    const int32_t* gt_obj, const int32_t* gt_frag,
+                                    const float* gt_loc, const float* gt_weight, int B, int64_t P,
+                                    int num_objs, int num_frags, int ignore_label,
+                                    const double* scales, const double* upstream,
+                                    const float* Wt_obj, const float* Wt_frag,
+                                    const float* Wt_loc, int64_t ldwt, int K, const float* Y,
+                                    int64_t ldy, float* dX, int64_t ldx, void* stream) {
+  const int rc = check_dims(__func__, B, P, num_objs, num_frags, K);
+  if (rc != EPOS_OK) return rc;
+  EPOS_REQUIRE(ldx >= K, "ldx must be >= K");
+  EPOS_REQUIRE(ldwt >= K, "ldwt must be >= K");
+  EPOS_REQUIRE(!Y || ldy >= K, "ldy must be >= K");
+  EPOS_REQUIRE(ld_obj >= num_objs + 1, "ld_obj must be >= num_objs + 1");
+  if (B == 0 || P == 0) return EPOS_OK;
+  EPOS_REQUIRE(obj_logits && frag_logits && frag_loc && gt_obj && gt_frag && gt_loc &&
+               gt_weight && scales && Wt_obj && Wt_frag && Wt_loc && dX, "null pointer");
+  const void* inputs[] = {obj_logits, frag_logits, frag_loc, gt_obj, gt_frag, gt_loc, gt_weight,
+                          scales, upstream, Wt_obj, Wt_frag, Wt_loc, Y};
+  for (const void* in : inputs)
+    EPOS_REQUIRE(in != dX, "the output buffer starts at an input pointer");
+  const int64_t per_image = ceil_div(P, DG_SHARE);
+  const int L = loss_lanes(num_frags);            // 1..64 lanes per pixel, as epos_loss_grads
+  // 16 bytes per lane where every row of the weights, of Y and of dX starts on a 16-byte boundary
+  const bool vec = K % 4 == 0 && ldwt % 4 == 0 && ldx % 4 == 0 && al16(Wt_obj) &&
+                   al16(Wt_frag) && al16(Wt_loc) && al16(dX) && (!Y || (ldy % 4 == 0 && al16(Y)));
+  const int groups = static_cast<int>(ceil_div(K, vec ? 256 : 64));   // of 64 lanes
+  const dim3 grid(static_cast<unsigned>(B * per_image));
+  hipStream_t s = static_cast<hipStream_t>(stream);
+#define EPOS_DGRAD_LAUNCH(KV, J)                                                               \
+  hipLaunchKernelGGL((heads_dgrad_kernel<KV, J>), grid, dim3(LOSS_THREADS), 0, s, obj_logits,  \
+                     ld_obj, frag_logits, frag_loc, gt_obj, gt_frag, gt_loc, gt_weight, P,     \
+                     per_image, num_objs, num_frags, ignore_label, L, scales, upstream,        \
+                     Wt_obj, Wt_frag, Wt_loc, ldwt, K, Y, ldy, dX, ldx)
+  if (vec) {
+    if (groups <= 1) EPOS_DGRAD_LAUNCH(4, 1);
+    else if (groups <= 2) EPOS_DGRAD_LAUNCH(4, 2);
+    else EPOS_DGRAD_LAUNCH(4, 4);
+  } else {
+    if (groups <= 1) EPOS_DGRAD_LAUNCH(1, 1);
+    else if (groups <= 4) EPOS_DGRAD_LAUNCH(1, 4);
+    else EPOS_DGRAD_LAUNCH(1, 16);
+  }
+#undef EPOS_DGRAD_LAUNCH
+  return launch_status("heads_dgrad_kernel");
+}

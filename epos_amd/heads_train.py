@@ -5,9 +5,13 @@ gradients"): the next piece of a trainer after loss.differentiable_losses.
   heads_weight_grads  epos_heads_wgrad_f32: dW and db of logits/pred_obj_conf, pred_frag_conf
                       and pred_frag_loc from EposNet.decoder_out and the raw logits, without the
                       dense logit gradients.
+  heads_input_grad    epos_heads_dgrad_f32 (csrc/heads_dgrad.hip; "Input gradient"): the gradient
+                      at EposNet.decoder_out, or behind its ReLU, from the raw logits and the
+                      three weight matrices, without the dense logit gradients.
   momentum_step       epos_momentum_step_f32: tf.train.MomentumOptimizer on the regularised,
                       multiplied gradient (train.py:340-384), in place.
   net_head_grads      from a net that has run forward_logits to checkpoint-shaped gradients.
+  net_feature_grad    from such a net to the gradient at its decoder output.
   HeadsOptimizer      fp32 master copies and accumulators of the six variables; restores the
                       accumulators from '<name>/Momentum' entries, so that a run can resume.
   learning_rate       the reference's schedules (train_utils.py:117-195) in Python floats.
@@ -17,7 +21,8 @@ gradients"): the next piece of a trainer after loss.differentiable_losses.
                       captured graphs included, without a round trip through the host).
 
 The loop itself, its checkpoints and its logging are train_heads.py. Out of scope here:
-backpropagation below the logits (everything there stays frozen), batch-norm statistics,
+backpropagation from decoder_conv1_pointwise down (heads_input_grad is where it would start;
+train_step keeps everything below the logits frozen), batch-norm statistics and gradients,
 bf16 mode, multi-scale nets and more than one device. Augmentation is epos_amd/augment.py;
 train_step applies it between the upload and the forward pass.
 
@@ -136,6 +141,113 @@ def heads_weight_grads(features, logits, gt, scales, upstream=None, ignore_label
   return result
 
 
+def heads_input_grad(logits, gt, scales, head_weights, upstream=None, relu_of=None,
+                     ignore_label=255, out=None, workspace=None):
+  """epos_heads_dgrad_f32 over one batch: the gradient of the losses with respect to the tensor
+  the logits layers read (EposNet.decoder_out), without the dense logit gradients. logits, gt,
+  scales, upstream as loss.loss_grads takes them; head_weights = {variable name: tensor or
+  array} with 'logits/<name>/weights' in the checkpoint layout [1,1,K,N] (or [K,N]), as
+  HeadsOptimizer.params and state() hold them (other keys are ignored). The kernel reads the
+  matrices transposed, [N,K]: they are transposed here, with torch, on the current stream, into
+  `workspace` (a contiguous float32 tensor of at least (O+1 + 4*O*F) * K values) or a new
+  tensor. relu_of: the forward activation f32 [B,h,w,K] or [B*P,K], rows a constant stride
+  apart (it may be the features themselves): the result is +0.0 wherever it is <= 0, the
+  gradient with respect to the pre-activation. Returns dX f32 [B*P, K], or `out` (f32 [..., K],
+  rows a constant stride apart, B*P of them; its padding columns are kept). Every element is
+  written. Enqueues on the current stream; does not synchronise."""
+  import torch
+  lib = _lib.load()
+  obj, frag, loc = (logits[k] for k in HEADS)
+  if not obj.is_cuda:
+    raise EposError('the input gradient needs a HIP device (there is no CPU fallback)')
+  dev = obj.device
+  if frag.dim() < 3 or obj.dim() < 2:
+    raise ValueError('pred_frag_conf must be [..., O, F] and pred_obj_conf [..., O+1]')
+  O, F = int(frag.shape[-2]), int(frag.shape[-1])
+  if obj.shape[-1] != O + 1:
+    raise ValueError('pred_obj_conf has %d channels, pred_frag_conf %d objects' % (
+        obj.shape[-1], O))
+  gt_obj = gt['obj_label']
+  B = int(gt_obj.shape[0]) if gt_obj.dim() > 1 else 1
+  n = gt_obj.numel()
+  if B == 0 or n % B:
+    raise ValueError('obj_label must be [B, ...] with B >= 1')
+  P = n // B
+  if obj.dtype != torch.float32:
+    raise TypeError('pred_obj_conf must be torch.float32, got %s' % obj.dtype)
+  widths = (O + 1, O * F, O * F * 3)
+  mats, K = [], None
+  for head, width in zip(HEADS, widths):
+    wname = variable_names(head)[0]
+    if wname not in head_weights:
+      raise KeyError('head_weights lack %r' % wname)
+    m = torch.as_tensor(head_weights[wname])
+    if m.dim() < 2 or m.shape[-1] != width or m.numel() != m.shape[-2] * width:
+      raise ValueError('%s must be [1, 1, K, %d], got %s' % (wname, width, tuple(m.shape)))
+    if K is None:
+      K = int(m.shape[-2])
+    elif m.shape[-2] != K:
+      raise ValueError('%s has %d input channels, expected %d' % (wname, m.shape[-2], K))
+    mats.append(m.reshape(K, width))
+  rows = sum(widths)
+  if workspace is None:
+    wt = torch.empty((rows, K), dtype=torch.float32, device=dev)
+  else:
+    if (workspace.device != dev or workspace.dtype != torch.float32 or
+        not workspace.is_contiguous() or workspace.numel() < rows * K):
+      raise ValueError('workspace must be a contiguous float32 tensor of at least %d values '
+                       'on %s' % (rows * K, dev))
+    wt = workspace.view(-1)[:rows * K].view(rows, K)
+  r0 = 0
+  for m, width in zip(mats, widths):
+    wt[r0:r0 + width].copy_(m.t())                 # to the device and to float32 where needed
+    r0 += width
+  obj2, ld = L._rows(obj, O + 1)
+  if obj2.shape[0] != n:
+    raise ValueError('pred_obj_conf holds %d rows, expected %d' % (obj2.shape[0], n))
+  ins = [obj2,
+         L._flat(frag, dev, torch.float32, n * O * F, 'pred_frag_conf'),
+         L._flat(loc, dev, torch.float32, n * O * F * 3, 'pred_frag_loc'),
+         L._flat(gt_obj, dev, torch.int32, n, 'obj_label'),
+         L._flat(gt['frag_label'], dev, torch.int32, n, 'frag_label'),
+         L._flat(gt['frag_loc'], dev, torch.float32, n * 3, 'frag_loc'),
+         L._flat(gt['frag_weight'], dev, torch.float32, n, 'frag_weight'),
+         L._flat(scales, dev, torch.float64, B * 3, 'scales')]
+  up = None
+  if upstream is not None:
+    up = L._flat(upstream, dev, torch.float64, 4, 'upstream')
+    ins.append(up)
+  y2, ldy = None, K
+  if relu_of is not None:
+    if relu_of.device != dev:
+      raise EposError('relu_of is on %s, the logits on %s' % (relu_of.device, dev))
+    if relu_of.dtype != torch.float32 or relu_of.shape[-1] != K:
+      raise TypeError('relu_of must be torch.float32 [..., %d], got %s %s' % (
+          K, relu_of.dtype, tuple(relu_of.shape)))
+    y2, ldy = L._rows(relu_of, K)
+    if y2.shape[0] != n:
+      raise ValueError('relu_of holds %d rows, expected %d' % (y2.shape[0], n))
+    ins.append(y2)
+  if out is None:
+    out = torch.empty((n, K), dtype=torch.float32, device=dev)
+  elif out.device != dev or out.dtype != torch.float32 or out.shape[-1] != K:
+    raise ValueError('out must be a float32 tensor [..., %d] on %s' % (K, dev))
+  out2, ldx = L._rows(out, K)
+  if out2.data_ptr() != out.data_ptr() or out2.shape[0] != n:
+    raise ValueError('out: %d rows of dX must lie a constant stride apart' % n)
+  stream = torch.cuda.current_stream(dev)
+  with torch.cuda.device(dev):
+    _lib.check(lib.epos_heads_dgrad_f32(
+        L._ptr(ins[0]), ld, L._ptr(ins[1]), L._ptr(ins[2]), L._ptr(ins[3]), L._ptr(ins[4]),
+        L._ptr(ins[5]), L._ptr(ins[6]), B, P, O, F, int(ignore_label), L._ptr(ins[7]),
+        L._ptr(up), L._ptr(wt[:widths[0]]), L._ptr(wt[widths[0]:widths[0] + widths[1]]),
+        L._ptr(wt[widths[0] + widths[1]:]), K, K, L._ptr(y2), ldy, L._ptr(out2), ldx,
+        ctypes.c_void_p(stream.cuda_stream)), 'epos_heads_dgrad_f32')
+  for t in ins + [wt]:
+    t.record_stream(stream)           # temporaries and dense copies made here outlive the call
+  return out
+
+
 def momentum_step(param, accum, grad, lr, momentum=0.9, weight_decay=0.0, grad_mult=1.0):
   """epos_momentum_step_f32, in place on param and accum (f32, contiguous, on the device):
   g = grad_mult * (grad + weight_decay * param); accum = momentum * accum + g;
@@ -185,6 +297,33 @@ def net_head_grads(net, gt, weights=(1.0, 1.0, 100.0), reduction='pooled', ignor
     grads[wname] = dW.view(1, 1, dW.shape[0], dW.shape[1])
     grads[bname] = db
   return values, bad, grads
+
+
+def net_feature_grad(net, gt, head_weights, weights=(1.0, 1.0, 100.0), reduction='pooled',
+                     relu=False, ignore_label=255):
+  """From a running network to the gradient at its decoder output: call after
+  net.forward_logits(). Runs loss_terms -> loss_values -> heads_input_grad on the net's logits
+  with head_weights (the six logits variables the net was built from, or
+  HeadsOptimizer.params). Returns (values f64 [4], bad i64 [B], dX f32 [B*P, K]): values and
+  bad as loss.differentiable_losses returns them, dX the gradient with respect to
+  net.decoder_out or, with relu=True, masked with net.decoder_out: with respect to the
+  pre-activation of decoder_conv1_pointwise (batch norm folded). fp32 single-scale nets only.
+  Does not synchronise."""
+  import torch
+  feats = net.decoder_out
+  if feats.dtype != torch.float32:
+    raise TypeError('features must be torch.float32, got %s (a bf16 decoder_out is not '
+                    'supported: run the net with precision=\'fp32\')' % feats.dtype)
+  B, h, w = int(feats.shape[0]), int(feats.shape[1]), int(feats.shape[2])
+  O, F = int(net.num_objs), int(net.num_frags)
+  logits = {W.PRED_OBJ_CONF: net.logits[W.PRED_OBJ_CONF],
+            W.PRED_FRAG_CONF: net.logits[W.PRED_FRAG_CONF].view(B, h, w, O, F),
+            W.PRED_FRAG_LOC: net.logits[W.PRED_FRAG_LOC].view(B, h, w, O, F, 3)}
+  sums, counts, bad = L.loss_terms(logits, gt, ignore_label)
+  values, scales = L.loss_values(sums, counts, weights, reduction)
+  dX = heads_input_grad(logits, gt, scales, head_weights, relu_of=feats if relu else None,
+                        ignore_label=ignore_label)
+  return values, bad, dX
 
 
 def learning_rate(step, policy='poly', base_learning_rate=1e-4, decay_step=2000,

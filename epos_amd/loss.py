@@ -22,6 +22,10 @@ derivative with respect to the three logit tensors, and differentiable_losses pu
 a torch.autograd.Function, so that an optimiser and torch's own conv backward can fine-tune the
 logits layers on EposNet.decoder_out. Pinned to tests/helpers/loss_grad_ref.py and, through it,
 to torch's fp64 autograd; parity with TensorFlow's gradients is unpinned.
+differentiable_losses_from_features is the same behind the logits layers: a function of the
+features those layers read and of their six variables, whose backward is the input gradient
+(csrc/heads_dgrad.hip) and the weight gradients (csrc/heads_wgrad.hip) of
+epos_amd/heads_train.py; DESIGN.md, "Losses", "Input gradient".
 
 There is no CPU fallback: without the library or a device this raises EposError.
 """
@@ -441,6 +445,122 @@ def _losses_function():
 
   _function = EposLosses
   return _function
+
+
+HEAD_VARIABLES = tuple('logits/%s/%s' % (head, kind)
+                       for head in (W.PRED_OBJ_CONF, W.PRED_FRAG_CONF, W.PRED_FRAG_LOC)
+                       for kind in ('weights', 'biases'))
+
+
+def logits_from_features(features, head_weights):
+  """The three logit tensors of features f32 [..., K] under the six logits variables
+  (HEAD_VARIABLES; weights [1,1,K,N] or [K,N], biases [N]; device tensors): plain torch,
+  features.reshape(-1, K) @ W + b in fp32 per head -- NOT the net's grouped heads launch, whose
+  rounding differs. Returns the dict loss_terms takes: pred_obj_conf [n,O+1], pred_frag_conf
+  [n,O,F], pred_frag_loc [n,O,F,3]."""
+  K = int(features.shape[-1])
+  x = features.reshape(-1, K)
+  n = x.shape[0]
+  flat = [x @ head_weights[HEAD_VARIABLES[2 * k]].reshape(K, -1) +
+          head_weights[HEAD_VARIABLES[2 * k + 1]] for k in range(3)]
+  O = int(flat[0].shape[1]) - 1
+  if O < 1 or flat[1].shape[1] % O or flat[2].shape[1] != 3 * flat[1].shape[1]:
+    raise ValueError('the logits variables have %d, %d and %d columns: not O+1, O*F and O*F*3' %
+                     tuple(t.shape[1] for t in flat))
+  F = int(flat[1].shape[1]) // O
+  return {W.PRED_OBJ_CONF: flat[0], W.PRED_FRAG_CONF: flat[1].view(n, O, F),
+          W.PRED_FRAG_LOC: flat[2].view(n, O, F, 3)}
+
+
+_features_function = None
+
+
+def _features_losses_function():
+  """The torch.autograd.Function behind differentiable_losses_from_features, defined at first
+  use: this module imports without torch."""
+  global _features_function
+  if _features_function is not None:
+    return _features_function
+  import torch
+  from torch.autograd.function import once_differentiable
+
+  class EposLossesFromFeatures(torch.autograd.Function):
+
+    @staticmethod
+    def forward(ctx, features, w_obj, b_obj, w_frag, b_frag, w_loc, b_loc, gt_obj, gt_frag,
+                gt_loc, gt_weight, weights, reduction, ignore_label):
+      variables = (w_obj, b_obj, w_frag, b_frag, w_loc, b_loc)
+      logits = logits_from_features(features, dict(zip(HEAD_VARIABLES, variables)))
+      gt = dict(zip(GT_KEYS, (gt_obj, gt_frag, gt_loc, gt_weight)))
+      sums, counts, bad = loss_terms(logits, gt, ignore_label)
+      values, scales = loss_values(sums, counts, weights, reduction)
+      ctx.save_for_backward(features, w_obj, w_frag, w_loc, logits[W.PRED_OBJ_CONF],
+                            logits[W.PRED_FRAG_CONF], logits[W.PRED_FRAG_LOC], gt_obj, gt_frag,
+                            gt_loc, gt_weight, scales)
+      ctx.ignore_label = ignore_label
+      ctx.shapes = tuple(v.shape for v in variables)
+      ctx.mark_non_differentiable(bad)
+      return values, bad
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_values, grad_bad):
+      from epos_amd import heads_train
+      (features, w_obj, w_frag, w_loc, obj, frag, loc, gt_obj, gt_frag, gt_loc, gt_weight,
+       scales) = ctx.saved_tensors
+      logits = {W.PRED_OBJ_CONF: obj, W.PRED_FRAG_CONF: frag, W.PRED_FRAG_LOC: loc}
+      gt = dict(zip(GT_KEYS, (gt_obj, gt_frag, gt_loc, gt_weight)))
+      up = grad_values.to(torch.float64)
+      d_feat = None
+      if ctx.needs_input_grad[0]:
+        d_feat = heads_train.heads_input_grad(
+            logits, gt, scales, dict(zip(HEAD_VARIABLES[0::2], (w_obj, w_frag, w_loc))),
+            upstream=up, ignore_label=ctx.ignore_label).view(features.shape)
+      need = tuple(ctx.needs_input_grad[1 + 2 * k] or ctx.needs_input_grad[2 + 2 * k]
+                   for k in range(3))
+      grads = [None] * 6
+      if any(need):
+        raw = heads_train.heads_weight_grads(features, logits, gt, scales, upstream=up,
+                                             ignore_label=ctx.ignore_label, need=need)
+        for k, head in enumerate(heads_train.HEADS):
+          if need[k]:
+            grads[2 * k] = raw[head][0].view(ctx.shapes[2 * k])
+            grads[2 * k + 1] = raw[head][1].view(ctx.shapes[2 * k + 1])
+      return (d_feat,) + tuple(grads) + (None,) * 7
+
+  _features_function = EposLossesFromFeatures
+  return _features_function
+
+
+def differentiable_losses_from_features(features, head_weights, gt, weights=(1.0, 1.0, 100.0),
+                                        reduction='mean', ignore_label=255):
+  """The three losses of one batch as a differentiable function of the FEATURES the logits
+  layers read and of the six logits variables: with it a torch.nn restatement of the decoder,
+  or any module that produces [B,h,w,K] features, trains against these losses with
+  loss.backward(). features f32 [B,h,w,K] or [B*P,K] on the device; head_weights =
+  {HEAD_VARIABLES: device tensor} in the checkpoint layout (HeadsOptimizer.params); gt as
+  loss_terms takes it. Forward: the logits by plain torch matmuls in fp32
+  (logits_from_features), then loss_terms and loss_values: (values f64 [4], bad i64 [B]),
+  bit-equal to differentiable_losses on those logits. Backward, once differentiable: d features
+  through epos_heads_dgrad_f32 (heads_train.heads_input_grad), dW and db of the six variables
+  through epos_heads_wgrad_f32 (heads_train.heads_weight_grads), each only where a gradient is
+  needed; the dense logit gradients are never formed. The logits themselves are kept for the
+  backward pass. Nothing synchronises."""
+  import torch
+  _lib.load()
+  if not torch.cuda.is_available() or not features.is_cuda:
+    raise EposError('the losses need a HIP device (there is no CPU fallback)')
+  if reduction not in REDUCTIONS:
+    raise ValueError("reduction must be 'mean' or 'pooled', got %r" % (reduction,))
+  if features.dtype != torch.float32:
+    raise TypeError('features must be torch.float32, got %s (a bf16 decoder_out is not '
+                    'supported: run the net with precision=\'fp32\')' % features.dtype)
+  for name in HEAD_VARIABLES:
+    if name not in head_weights:
+      raise KeyError('head_weights lack %r' % name)
+  return _features_losses_function().apply(
+      features, *(head_weights[name] for name in HEAD_VARIABLES), *(gt[k] for k in GT_KEYS),
+      tuple(float(w) for w in weights), reduction, int(ignore_label))
 
 
 def differentiable_losses(logits, gt, weights=(1.0, 1.0, 100.0), reduction='mean',

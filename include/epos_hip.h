@@ -1261,6 +1261,54 @@ int epos_heads_wgrad_f32(const float* A, int64_t lda, int K, const float* obj_lo
 int epos_momentum_step_f32(float* w, float* accum, const float* grad, int64_t n, float lr,
                            float momentum, float weight_decay, float grad_mult, void* stream);
 
+/* Input gradient (csrc/heads_dgrad.hip; added without an ABI version change). The gradient of
+ * the losses with respect to the tensor the three logits layers read (EposNet.decoder_out),
+ * dL/dX: what backpropagation below the logits starts from. Taken WITHOUT forming the dense
+ * logit gradients. tests/helpers/heads_dgrad_ref.py restates it in numpy.
+ *
+ * epos_heads_dgrad_f32. The first sixteen arguments are exactly the inputs of epos_loss_grads,
+ * under the same rules. Wt_obj f32 [O+1, K], Wt_frag f32 [O*F, K], Wt_loc f32 [O*F*3, K]
+ * [device]: the three weight matrices TRANSPOSED (the checkpoint holds [1,1,K,N]; a pixel's
+ * active columns n become contiguous rows of K values), all three with row stride ldwt >= K,
+ * 1 <= K <= 1024. Y f32 [device] with row stride ldy >= K, or NULL: the forward activation, for
+ * the ReLU mask. dX f32 [device]: B*P rows of K values with row stride ldx >= K.
+ *   Definition. Let d_obj, d_frag, d_loc be the f32 values epos_loss_grads is specified to
+ *   write for the same inputs (the fl32-rounded values, with its m, its S and its butterfly
+ *   over the L lanes of a row). Then
+ *     dX[p,k] = fl32( sum_h sum_{n active at p} (double)d_h[p,n] * (double)Wt_h[n,k] )
+ *   accumulated in fp64 (the product of two fp32 values is exact in fp64) from 0.0 in a FIXED
+ *   order -- the heads in the order obj, frag, loc, ascending n within a head, one accumulator
+ *   per (p, k) -- and rounded to f32 once, at the end. ACTIVE as for epos_heads_wgrad_f32: the
+ *   O+1 object values of a pixel that is neither ignored nor bad, the F values of the row g-1
+ *   and the three values at (g-1, f) of a foreground pixel: at most O+1 + F + 3 of the
+ *   O+1 + 4*O*F columns. The other d values are +0.0 and are not multiplied. An ignored or bad
+ *   pixel gets a row of +0.0 and nothing of it but its labels is read. A non-finite logit or
+ *   weight makes its own pixel's row non-finite (a weight: the rows of the pixels for which its
+ *   column is active) and no others; that is not an error.
+ *   ReLU mask. With Y non-NULL, dX[p,k] is written as +0.0 wherever Y[p,k] <= 0 (-0.0 counts,
+ *   a NaN does not): the gradient with respect to the pre-activation of the layer that
+ *   produced X (decoder_conv1_pointwise with its batch norm folded). With Y NULL it is the
+ *   gradient with respect to X itself. Y may be the buffer of the features.
+ *   EVERY element of dX is WRITTEN, not added; the ldx - K padding columns are not touched.
+ *   Never dense, and no workspace: a wave computes a pixel's active d values itself, 64 at a
+ *   time, one per lane; neither a kernel nor a buffer holds a row of width O*F or O*F*3.
+ *   One launch on `stream`, a workgroup per 16 consecutive pixels of one image: no allocation,
+ *   no host synchronisation, no atomics, capturable in a graph; the same bytes in every run,
+ *   for an image alone and at any position of a batch, and for every alignment of the buffers.
+ *   Refused with EPOS_E_INVALID before the launch: the sizes epos_loss_terms refuses; K outside
+ *   1..1024; ldx or ldwt < K, ldy < K when Y is given; ld_obj < O+1; when B > 0 and P > 0, a
+ *   null pointer (upstream and Y may be NULL); dX starting at an input pointer, Y included: the
+ *   mask is read while other lanes write the row. B == 0 or P == 0 writes nothing and
+ *   returns 0. */
+int epos_heads_dgrad_f32(const float* obj_logits, int64_t ld_obj, const float* frag_logits,
+                         const float* frag_loc, const int32_t* gt_obj, const int32_t* gt_frag,
+                         const float* gt_loc, const float* gt_weight, int B, int64_t P,
+                         int num_objs, int num_frags, int ignore_label, const double* scales,
+                         const double* upstream /* device [4], or NULL = {0,0,0,1} */,
+                         const float* Wt_obj, const float* Wt_frag, const float* Wt_loc,
+                         int64_t ldwt, int K, const float* Y /* or NULL */, int64_t ldy,
+                         float* dX, int64_t ldx, void* stream);
+
 /* Weight update (csrc/weight_pack.hip; added without an ABI version change). The three host
  * packers above restated as device kernels, so that weights updated on the device (the momentum
  * step) reach a built plan without a round trip through the host: a grouped call packs fp32
