@@ -3,15 +3,15 @@
 // "Input gradient"; DESIGN.md, "Losses", "Input gradient").
 //
 //   heads_dgrad_kernel  a workgroup owns DG_SHARE consecutive pixels of ONE image. Phase one is
-//                       epos_loss_grads': L lanes share a pixel's row (loss_rows.h), the pixel's
-//                       class, m and S of its two rows go to LDS. Phase two is a gather-GEMV per
-//                       pixel: a wave takes every fourth pixel of the share; its lanes compute
-//                       the pixel's active logit gradients 64 at a time, one per lane, exactly
-//                       as epos_loss_grads rounds them; each value is then broadcast from its
-//                       lane and multiplied with its row of the transposed weights, a lane
-//                       holding the fp64 sums of its own feature indices k in registers. The
-//                       row is rounded and stored once, 16 bytes per lane where the layout
-//                       allows.
+//                       epos_loss_grads' (loss_rows.h, pixel_rows): the pixel's class, m and S
+//                       of its two rows go to LDS. Phase two is a gather-GEMV per pixel: a wave
+//                       takes every fourth pixel of the share; its lanes compute the pixel's
+//                       active logit gradients 64 at a time, one per lane, with the functions
+//                       epos_loss_grads rounds them with (loss_rows.h, softmax_grad and
+//                       huber_grad); each value is then broadcast from its lane and multiplied
+//                       with its row of the transposed weights, a lane holding the fp64 sums of
+//                       its own feature indices k in registers. The row is rounded and stored
+//                       once, 16 bytes per lane where the layout allows.
 //
 // Every output row is computed by one wave from its own pixel, the weights and s_k only, one
 // accumulator per (pixel, k), the active columns in the stated order: no workspace, no atomics,
@@ -22,26 +22,11 @@
 namespace epos {
 namespace {
 
-constexpr int DG_MAX_K = 1024;
 constexpr int64_t DG_SHARE = 16;             // pixels per workgroup, four per wave
 constexpr int DG_WAVES = LOSS_THREADS / 64;
 
-// What phase one leaves of a share's pixels
-struct DgRows {
-  double s_obj[DG_SHARE], s_frag[DG_SHARE];  // S of the two rows
-  float m_obj[DG_SHARE], m_frag[DG_SHARE];   // m of the two rows
-  float wgt[DG_SHARE];
-  int code[DG_SHARE], frag[DG_SHARE];
-};
-
 int check_dims(const char* fn, int B, int64_t P, int num_objs, int num_frags, int K) {
-  const int rc = check_loss_dims(fn, B, P, num_objs, num_frags, DG_SHARE);
-  if (rc != EPOS_OK) return rc;
-  if (K < 1 || K > DG_MAX_K) {
-    set_error("%s: K must be in 1..1024", fn);
-    return EPOS_E_INVALID;
-  }
-  return EPOS_OK;
+  return check_heads_dims(fn, B, P, num_objs, num_frags, DG_SHARE, K);
 }
 
 // The value lane `src` holds, in every lane; src is the same in all lanes
@@ -90,7 +75,7 @@ __global__ __launch_bounds__(LOSS_THREADS) void heads_dgrad_kernel(
     const double* __restrict__ upstream, const float* __restrict__ Wt_obj,
     const float* __restrict__ Wt_frag, const float* __restrict__ Wt_loc, int64_t ldwt, int K,
     const float* Y, int64_t ldy, float* dX, int64_t ldx) {
-  __shared__ DgRows sh;
+  __shared__ ShareRows<DG_SHARE> sh;
   const int64_t image = blockIdx.x / blocks_per_image;
   const int64_t p0 = (blockIdx.x % blocks_per_image) * DG_SHARE;
   const int64_t p1 = p0 + DG_SHARE < P ? p0 + DG_SHARE : P;
@@ -101,30 +86,14 @@ __global__ __launch_bounds__(LOSS_THREADS) void heads_dgrad_kernel(
   const int per_pass = LOSS_THREADS / L;
   for (int base = 0; base < n_here; base += per_pass) {     // uniform trip count: shuffles below
     const int i = base + threadIdx.x / L;
-    const int64_t p = pix0 + i;
-    int g = CODE_NONE, f = 0;
-    float wgt = 0.f;
-    if (i < n_here)
-      g = pixel_class(gt_obj, gt_frag, gt_weight, p, num_objs, F, ignore_label, f, wgt);
-    double m_o = 0.0, s_o = 0.0, m_f = 0.0, s_f = 0.0;
-    row_max_sum<false>(obj_logits + (g >= 0 ? p * ld_obj : 0), O1, g >= 0, sub, L, m_o, s_o);
-    const int64_t frag_row = g > 0 ? (p * num_objs + (g - 1)) * F : 0;
-    row_max_sum<false>(frag_logits + frag_row, F, g > 0, sub, L, m_f, s_f);
-    if (i < n_here && sub == 0) {
-      sh.code[i] = g;
-      sh.frag[i] = f;
-      sh.wgt[i] = wgt;
-      sh.m_obj[i] = static_cast<float>(m_o);                 // m is an fp32 value
-      sh.s_obj[i] = s_o;
-      sh.m_frag[i] = static_cast<float>(m_f);
-      sh.s_frag[i] = s_f;
-    }
+    const PixelRows r = pixel_rows<false, false>(obj_logits, ld_obj, frag_logits, gt_obj, gt_frag,
+                                                 gt_weight, pix0 + i, i < n_here, num_objs, F,
+                                                 ignore_label, true, true, sub, L);
+    if (i < n_here && sub == 0) sh.put(i, r);
   }
   __syncthreads();
-  // s_k = scales[b,k] * (upstream[k] + upstream[3]), one product
   double s[3];
-  for (int k = 0; k < 3; ++k)
-    s[k] = scales[image * 3 + k] * (upstream ? upstream[k] + upstream[3] : 1.0);
+  for (int k = 0; k < 3; ++k) s[k] = task_factor(scales, image, k, upstream_factor(upstream, k));
 
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   for (int i = wave; i < n_here; i += DG_WAVES) {
@@ -138,37 +107,26 @@ __global__ __launch_bounds__(LOSS_THREADS) void heads_dgrad_kernel(
       for (int c0 = 0; c0 < O1; c0 += 64) {                  // the object head, 64 columns a time
         const int c = c0 + lane;
         float dv = 0.f;
-        if (c < O1) {
-          const double x = static_cast<double>(obj_logits[p * ld_obj + c]);
-          const double pr = exp(x - m) / S;
-          dv = static_cast<float>(s[0] * (pr - (c == g ? 1.0 : 0.0)));
-        }
+        if (c < O1) dv = softmax_grad(obj_logits[p * ld_obj + c], m, S, c == g, s[0]);
         add_rows<KV, J>(acc, Wt_obj + c0 * ldwt, ldwt, O1 - c0 < 64 ? O1 - c0 : 64, K, lane, dv);
       }
     }
     if (g > 0) {
       const int f = __builtin_amdgcn_readfirstlane(sh.frag[i]);
       const int64_t row0 = static_cast<int64_t>(g - 1) * F;  // the pixel's row of O * F
+      const int64_t frag_row = frag_row_offset(p, num_objs, g, F);
       const double m = static_cast<double>(sh.m_frag[i]), S = sh.s_frag[i];
       for (int c0 = 0; c0 < F; c0 += 64) {                   // the fragment head
         const int c = c0 + lane;
         float dv = 0.f;
-        if (c < F) {
-          const double x = static_cast<double>(frag_logits[(p * num_objs + (g - 1)) * F + c]);
-          const double pr = exp(x - m) / S;
-          dv = static_cast<float>(s[1] * (pr - (c == f ? 1.0 : 0.0)));
-        }
+        if (c < F) dv = softmax_grad(frag_logits[frag_row + c], m, S, c == f, s[1]);
         add_rows<KV, J>(acc, Wt_frag + (row0 + c0) * ldwt, ldwt, F - c0 < 64 ? F - c0 : 64, K,
                         lane, dv);
       }
       float dv = 0.f;                                        // the three localisation values
-      if (lane < 3) {
-        const double q = static_cast<double>(frag_loc[((p * num_objs + (g - 1)) * F + f) * 3 + lane]);
-        const double d = q - static_cast<double>(gt_loc[p * 3 + lane]);
-        // the derivative of the Huber term, knee included: |d| <= 1 gives d
-        const double cl = d > 1.0 ? 1.0 : d < -1.0 ? -1.0 : d;
-        dv = static_cast<float>(s[2] * (static_cast<double>(sh.wgt[i]) * cl));
-      }
+      if (lane < 3)
+        dv = huber_grad(frag_loc[(frag_row + f) * 3 + lane], gt_loc[p * 3 + lane], sh.wgt[i],
+                        s[2]);
       add_rows<KV, J>(acc, Wt_loc + (row0 + f) * 3 * ldwt, ldwt, 3, K, lane, dv);
     }
     // an ignored or bad pixel: the sums are still +0.0
@@ -220,10 +178,10 @@ extern "C" int epos_heads_dgrad_f32(const float* obj_logits, int64_t ld_obj,
   if (B == 0 || P == 0) return EPOS_OK;
   EPOS_REQUIRE(obj_logits && frag_logits && frag_loc && gt_obj && gt_frag && gt_loc &&
                gt_weight && scales && Wt_obj && Wt_frag && Wt_loc && dX, "null pointer");
-  const void* inputs[] = {obj_logits, frag_logits, frag_loc, gt_obj, gt_frag, gt_loc, gt_weight,
-                          scales, upstream, Wt_obj, Wt_frag, Wt_loc, Y};
-  for (const void* in : inputs)
-    EPOS_REQUIRE(in != dX, "the output buffer starts at an input pointer");
+  const int alias = check_no_alias(__func__, {obj_logits, frag_logits, frag_loc, gt_obj, gt_frag,
+                                              gt_loc, gt_weight, scales, upstream, Wt_obj, Wt_frag,
+                                              Wt_loc, Y}, {dX});
+  if (alias != EPOS_OK) return alias;
   const int64_t per_image = ceil_div(P, DG_SHARE);
   const int L = loss_lanes(num_frags);            // 1..64 lanes per pixel, as epos_loss_grads
   // 16 bytes per lane where every row of the weights, of Y and of dX starts on a 16-byte boundary

@@ -3,9 +3,9 @@
 // (include/epos_hip.h, "Weight gradients"; DESIGN.md, "Losses", "Weight gradients").
 //
 //   wgrad_rows_kernel   pixel-parallel: S of the object row and of the foreground pixel's
-//                       fragment row, and m of the object row, exactly as epos_loss_grads takes
-//                       them (loss_rows.h: L lanes share a row, butterfly), to the workspace:
-//                       20 bytes per pixel.
+//                       fragment row, and m of the object row, from the function epos_loss_grads
+//                       takes them with (loss_rows.h, pixel_rows), to the workspace: 20 bytes per
+//                       pixel.
 //   wgrad_frag_kernel   a workgroup owns (object g, a slice of ks feature indices, a pixel
 //                       range) of the fragment and the localisation head. It walks its range of
 //                       every image, compacts the pixels of class g with ballots, and takes them
@@ -26,14 +26,15 @@
 // to slab r of the workspace [R][K+1][N], N = O+1 + 4*O*F; small images have R = 1 and no
 // slabs: the head kernels round and write the outputs themselves. Every sum is that of one
 // thread, or of a fixed sequence of threads and slabs, in a fixed order -- no atomics, the same
-// bytes in every run. fp64 on the fp32 values, -ffp-contract=off.
+// bytes in every run. fp64 on the fp32 values, -ffp-contract=off; the logit gradients that are
+// multiplied with the features are softmax_grad and huber_grad of loss_rows.h, the functions
+// epos_loss_grads writes its outputs with.
 #include "loss_rows.h"
 
 namespace epos {
 namespace {
 
 constexpr int WG_KS = 16;                    // feature indices per slice (fewer for F > 64)
-constexpr int WG_MAX_K = 1024;
 constexpr int WG_BATCH = 64;                 // pixels per batch, at most
 constexpr int WG_DF = 4096;                  // floats of a batch's fragment gradients
 constexpr int WG_LOC = 3072;                 // doubles of the localisation table: ks * F * 3
@@ -44,11 +45,15 @@ constexpr int OBJ_COLS = 8, OBJ_LANES = LOSS_THREADS / OBJ_COLS, OBJ_UNROLL = 4;
 constexpr int WG_MAX_RANGES = 8;             // ranges per image, at most
 constexpr int64_t WG_MIN_RANGE = 1024;       // pixels per range, at least, when there are two
 
+// N = O+1 + 4*O*F, the columns of a slab row: those of the object, the fragment and the
+// localisation head
+__host__ __device__ inline int64_t slab_cols(int64_t O1, int64_t OF) { return O1 + 4 * OF; }
+
 // Ranges per image: up to 8 of at least max(1024, 8 (K+1)) pixels -- the R slabs of
 // 8 (K+1) N bytes then stay below a quarter of the dense gradients' 4 P N -- and one range for
 // the smallest heads (N < 10), where 20 bytes per pixel are most of the dense size already.
 inline int wgrad_ranges(int64_t P, int num_objs, int num_frags, int K) {
-  const int64_t N = num_objs + 1 + int64_t(4) * num_objs * num_frags;
+  const int64_t N = slab_cols(num_objs + 1, int64_t(num_objs) * num_frags);
   const int64_t least = 8 * (int64_t(K) + 1) > WG_MIN_RANGE ? 8 * (int64_t(K) + 1) : WG_MIN_RANGE;
   const int64_t R = N < 10 ? 1 : P / least;
   return R < 1 ? 1 : R > WG_MAX_RANGES ? WG_MAX_RANGES : static_cast<int>(R);
@@ -63,13 +68,28 @@ inline int frag_batch(int num_frags) {
 }
 
 int check_dims(const char* fn, int B, int64_t P, int num_objs, int num_frags, int K) {
-  const int rc = check_loss_dims(fn, B, P, num_objs, num_frags, WG_ROWS_PIXELS);
-  if (rc != EPOS_OK) return rc;
-  if (K < 1 || K > WG_MAX_K) {
-    set_error("%s: K must be in 1..1024", fn);
-    return EPOS_E_INVALID;
+  return check_heads_dims(fn, B, P, num_objs, num_frags, WG_ROWS_PIXELS, K);
+}
+
+// Where the sum of feature row kq (kq == K: the bias row) and column col of a head of `width`
+// columns goes when there are no slabs: dW[kq, col] or db[col]; null for kq > K and for an
+// output that is not asked for
+__device__ __forceinline__ float* out_cell(int64_t kq, int K, float* dW, float* db,
+                                           int64_t width, int64_t col) {
+  if (kq < K) return dW ? dW + kq * width + col : nullptr;
+  return kq == K && db ? db + col : nullptr;
+}
+
+// One finished sum: to cell [kq][n0 + col] of the workgroup's slab of N columns when there are
+// slabs, else rounded to its output
+__device__ __forceinline__ void store_sum(double sum, int64_t kq, int K, double* slab, int64_t N,
+                                          int64_t n0, float* dW, float* db, int64_t width,
+                                          int64_t col) {
+  if (slab) {
+    if (kq <= K) slab[kq * N + n0 + col] = sum;
+  } else if (float* out = out_cell(kq, K, dW, db, width, col)) {
+    *out = static_cast<float>(sum);
   }
-  return EPOS_OK;
 }
 
 __global__ __launch_bounds__(LOSS_THREADS) void wgrad_rows_kernel(
@@ -83,24 +103,15 @@ __global__ __launch_bounds__(LOSS_THREADS) void wgrad_rows_kernel(
   const int64_t p0 = blockIdx.x * WG_ROWS_PIXELS;
   for (int base = 0; base < WG_ROWS_PIXELS; base += per_pass) {   // uniform: shuffles below
     const int64_t p = p0 + base + threadIdx.x / L;
-    int g = CODE_NONE, f = 0;
-    float wgt = 0.f;
-    if (p < n_pix)
-      g = pixel_class(gt_obj, gt_frag, gt_weight, p, num_objs, num_frags, ignore_label, f, wgt);
-    double m_o = 0.0, s_o = 0.0, m_f = 0.0, s_f = 0.0;
-    if (want_obj)
-      row_max_sum<false>(obj_logits + (g >= 0 ? p * ld_obj : 0), num_objs + 1, g >= 0, sub, L,
-                         m_o, s_o);
-    if (want_frag) {
-      const int64_t frag_row = g > 0 ? (p * num_objs + (g - 1)) * num_frags : 0;
-      row_max_sum<false>(frag_logits + frag_row, num_frags, g > 0, sub, L, m_f, s_f);
-    }
+    const PixelRows r = pixel_rows<false, false>(obj_logits, ld_obj, frag_logits, gt_obj, gt_frag,
+                                                 gt_weight, p, p < n_pix, num_objs, num_frags,
+                                                 ignore_label, want_obj, want_frag, sub, L);
     if (p < n_pix && sub == 0) {
       if (want_obj) {
-        s_obj[p] = s_o;
-        m_obj[p] = static_cast<float>(m_o);                  // m is an fp32 value
+        s_obj[p] = r.s_obj;
+        m_obj[p] = static_cast<float>(r.m_obj);              // m is an fp32 value
       }
-      if (want_frag) s_frag[p] = s_f;
+      if (want_frag) s_frag[p] = r.s_frag;
     }
   }
 }
@@ -143,14 +154,12 @@ __global__ __launch_bounds__(LOSS_THREADS) void wgrad_frag_kernel(
   double acc[4] = {0.0, 0.0, 0.0, 0.0};
   if (want_loc)
     for (int e = t; e < ks * F * 3; e += LOSS_THREADS) sh.loc[e] = 0.0;
-  const double u1 = upstream ? upstream[1] + upstream[3] : 1.0;
-  const double u2 = upstream ? upstream[2] + upstream[3] : 1.0;
+  const double u1 = upstream_factor(upstream, 1), u2 = upstream_factor(upstream, 2);
   __syncthreads();
 
   for (int b = 0; b < B; ++b) {
     const int64_t img = static_cast<int64_t>(b) * P;
-    // s_k = scales[b,k] * (upstream[k] + upstream[3]), one product
-    const double s1 = scales[b * 3 + 1] * u1, s2 = scales[b * 3 + 2] * u2;
+    const double s1 = task_factor(scales, b, 1, u1), s2 = task_factor(scales, b, 2, u2);
     uint32_t head = 0, tail = 0;                             // uniform
     for (int64_t base = r0;; base += WG_SCAN * LOSS_THREADS) {
       const bool more = base < r1;
@@ -194,7 +203,7 @@ __global__ __launch_bounds__(LOSS_THREADS) void wgrad_frag_kernel(
           if (valid) {
             p = img + sh.ring[(head + i) % WG_RING];
             if (want_frag) {
-              const float* row = frag_logits + (p * num_objs + (g - 1)) * F;
+              const float* row = frag_logits + frag_row_offset(p, num_objs, g, F);
               for (int c = sub; c < F; c += 4) m = fmaxf(m, row[c]);
             }
           }
@@ -212,22 +221,18 @@ __global__ __launch_bounds__(LOSS_THREADS) void wgrad_frag_kernel(
         if (want_frag) {
           for (int e = t; e < n * F; e += LOSS_THREADS) {
             const int i = e / F, c = e - i * F;
-            const double x = static_cast<double>(
-                frag_logits[(sh.pixel[i] * num_objs + (g - 1)) * F + c]);
-            const double pr = exp(x - static_cast<double>(sh.m_frag[i])) / sh.s_frag[i];
-            sh.df[e] = static_cast<float>(s1 * (pr - (c == sh.frag[i] ? 1.0 : 0.0)));
+            sh.df[e] = softmax_grad(frag_logits[frag_row_offset(sh.pixel[i], num_objs, g, F) + c],
+                                    static_cast<double>(sh.m_frag[i]), sh.s_frag[i],
+                                    c == sh.frag[i], s1);
           }
         }
         if (want_loc) {
           for (int e = t; e < n * 3; e += LOSS_THREADS) {
             const int i = e / 3, c = e - i * 3;
             const int64_t p = sh.pixel[i];
-            const double q = static_cast<double>(
-                frag_loc[((p * num_objs + (g - 1)) * F + sh.frag[i]) * 3 + c]);
-            const double d = q - static_cast<double>(gt_loc[p * 3 + c]);
-            // the derivative of the Huber term, knee included: |d| <= 1 gives d
-            const double cd = d > 1.0 ? 1.0 : d < -1.0 ? -1.0 : d;
-            sh.dl[e] = static_cast<float>(s2 * (static_cast<double>(sh.wgt[i]) * cd));
+            sh.dl[e] = huber_grad(
+                frag_loc[(frag_row_offset(p, num_objs, g, F) + sh.frag[i]) * 3 + c],
+                gt_loc[p * 3 + c], sh.wgt[i], s2);
           }
         }
         for (int e = t; e < n * ks; e += LOSS_THREADS) {
@@ -263,7 +268,7 @@ __global__ __launch_bounds__(LOSS_THREADS) void wgrad_frag_kernel(
 
   const int kq = k0 + k;
   const int64_t OF = static_cast<int64_t>(num_objs) * F;
-  const int64_t N = num_objs + 1 + 4 * OF;                   // columns of a slab row
+  const int64_t N = slab_cols(num_objs + 1, OF);
   double* __restrict__ slab = slabs ? slabs + blockIdx.z * (static_cast<int64_t>(K) + 1) * N
                                     : nullptr;
   if (want_frag) {
@@ -271,14 +276,8 @@ __global__ __launch_bounds__(LOSS_THREADS) void wgrad_frag_kernel(
     for (int j = 0; j < 4; ++j) {
       const int c = cl + lanes * j;
       if (c >= F) continue;
-      const int64_t col = static_cast<int64_t>(g - 1) * F + c;
-      if (slab) {
-        if (kq <= K) slab[kq * N + (num_objs + 1) + col] = acc[j];
-      } else if (kq < K) {
-        if (dW_frag) dW_frag[kq * OF + col] = static_cast<float>(acc[j]);
-      } else if (kq == K && db_frag) {
-        db_frag[col] = static_cast<float>(acc[j]);
-      }
+      store_sum(acc[j], kq, K, slab, N, num_objs + 1, dW_frag, db_frag, OF,
+                static_cast<int64_t>(g - 1) * F + c);
     }
   }
   if (want_loc) {
@@ -286,6 +285,8 @@ __global__ __launch_bounds__(LOSS_THREADS) void wgrad_frag_kernel(
     for (int e = t; e < ks * F * 3; e += LOSS_THREADS) {
       const int fc = e / ks, kk = k0 + (e - fc * ks);
       const int64_t col = static_cast<int64_t>(g - 1) * F * 3 + fc;
+      // store_sum's cases written out: the sum lies in LDS and is read only where it is stored
+      // (taken by value it is read for every cell; profiles/r25/)
       if (slab) {
         if (kk <= K) slab[kk * N + (num_objs + 1) + OF + col] = sh.loc[e];
       } else if (kk < K) {
@@ -311,7 +312,7 @@ __global__ __launch_bounds__(LOSS_THREADS) void wgrad_obj_kernel(
   const int O1 = num_objs + 1;
   const int c = blockIdx.y * OBJ_COLS + cc;
   const int k0 = (slice0 + blockIdx.x) * WG_KS;              // k == K is the bias row
-  const double u0 = upstream ? upstream[0] + upstream[3] : 1.0;
+  const double u0 = upstream_factor(upstream, 0);
   // range blockIdx.z of every image
   const int64_t r0 = blockIdx.z * range;
   const int64_t r1 = r0 + range < P ? r0 + range : P;
@@ -320,7 +321,7 @@ __global__ __launch_bounds__(LOSS_THREADS) void wgrad_obj_kernel(
   for (int kk = 0; kk < WG_KS; ++kk) acc[kk] = 0.0;
   for (int b = 0; b < B; ++b) {
     const int64_t img = static_cast<int64_t>(b) * P;
-    const double s0 = scales[b * 3] * u0;
+    const double s0 = task_factor(scales, b, 0, u0);
     for (int64_t base = r0; base < r1; base += OBJ_LANES * OBJ_UNROLL) {
       int code[OBJ_UNROLL];
       float x[OBJ_UNROLL], m[OBJ_UNROLL];
@@ -349,9 +350,8 @@ __global__ __launch_bounds__(LOSS_THREADS) void wgrad_obj_kernel(
       for (int j = 0; j < OBJ_UNROLL; ++j) {
         if (code[j] < 0) continue;
         const int64_t p = img + base + j * OBJ_LANES + pl;
-        const double pr = exp(static_cast<double>(x[j]) - static_cast<double>(m[j])) / s[j];
         const double dv = static_cast<double>(
-            static_cast<float>(s0 * (pr - (c == code[j] ? 1.0 : 0.0))));
+            softmax_grad(x[j], static_cast<double>(m[j]), s[j], c == code[j], s0));
         const float* __restrict__ a = A + p * lda;
 #pragma unroll
         for (int kk = 0; kk < WG_KS; ++kk) {
@@ -371,14 +371,9 @@ __global__ __launch_bounds__(LOSS_THREADS) void wgrad_obj_kernel(
     double sum = 0.0;
     for (int l = 0; l < OBJ_LANES; ++l) sum += part[l][oc][kk];       // lanes in order
     if (col < O1) {
-      if (slabs) {
-        const int64_t N = O1 + int64_t(4) * num_objs * num_frags;
-        if (kq <= K) slabs[(blockIdx.z * (static_cast<int64_t>(K) + 1) + kq) * N + col] = sum;
-      } else if (kq < K) {
-        if (dW_obj) dW_obj[static_cast<int64_t>(kq) * O1 + col] = static_cast<float>(sum);
-      } else if (kq == K && db_obj) {
-        db_obj[col] = static_cast<float>(sum);
-      }
+      const int64_t N = slab_cols(O1, int64_t(num_objs) * num_frags);
+      double* slab = slabs ? slabs + blockIdx.z * (static_cast<int64_t>(K) + 1) * N : nullptr;
+      store_sum(sum, kq, K, slab, N, 0, dW_obj, db_obj, O1, col);
     }
   }
 }
@@ -389,7 +384,7 @@ __global__ __launch_bounds__(LOSS_THREADS) void wgrad_close_kernel(
     const double* __restrict__ slabs, int R, int K, int O1, int64_t OF,
     float* __restrict__ dW_obj, float* __restrict__ db_obj, float* __restrict__ dW_frag,
     float* __restrict__ db_frag, float* __restrict__ dW_loc, float* __restrict__ db_loc) {
-  const int64_t N = O1 + 4 * OF;
+  const int64_t N = slab_cols(O1, OF);
   const int64_t e = static_cast<int64_t>(blockIdx.x) * LOSS_THREADS + threadIdx.x;
   if (e >= (static_cast<int64_t>(K) + 1) * N) return;
   const int64_t k = e / N, n = e - k * N;
@@ -399,7 +394,7 @@ __global__ __launch_bounds__(LOSS_THREADS) void wgrad_close_kernel(
   if (n < O1) { dW = dW_obj; db = db_obj; col = n; width = O1; }
   else if (n < O1 + OF) { dW = dW_frag; db = db_frag; col = n - O1; width = OF; }
   else { dW = dW_loc; db = db_loc; col = n - O1 - OF; width = 3 * OF; }
-  float* out = k < K ? (dW ? dW + k * width + col : nullptr) : (db ? db + col : nullptr);
+  float* out = out_cell(k, K, dW, db, width, col);
   if (!out) return;                               // not asked for: its slab columns hold nothing
   double sum = 0.0;
   for (int r = 0; r < R; ++r) sum += slabs[(r * (static_cast<int64_t>(K) + 1)) * N + e];
@@ -453,7 +448,7 @@ extern "C" int64_t epos_heads_wgrad_workspace_bytes(int B, int64_t P, int num_ob
                                                     int num_frags, int K) {
   if (check_dims(__func__, B, P, num_objs, num_frags, K) != EPOS_OK) return EPOS_E_INVALID;
   const int R = wgrad_ranges(P, num_objs, num_frags, K);
-  const int64_t N = num_objs + 1 + int64_t(4) * num_objs * num_frags;
+  const int64_t N = slab_cols(num_objs + 1, int64_t(num_objs) * num_frags);
   return 20 * (static_cast<int64_t>(B) * P) + (R > 1 ? R * 8 * (int64_t(K) + 1) * N : 0);
 }
 
@@ -470,7 +465,6 @@ extern "C" int epos_heads_wgrad_f32(const float* A, int64_t lda, int K, const fl
   if (rc != EPOS_OK) return rc;
   EPOS_REQUIRE(lda >= K, "lda must be >= K");
   EPOS_REQUIRE(ld_obj >= num_objs + 1, "ld_obj must be >= num_objs + 1");
-  float* const outs[] = {dW_obj, db_obj, dW_frag, db_frag, dW_loc, db_loc};
   const bool want_obj = dW_obj || db_obj, want_frag = dW_frag || db_frag,
              want_loc = dW_loc || db_loc;
   if (!want_obj && !want_frag && !want_loc) return EPOS_OK;
@@ -481,11 +475,10 @@ extern "C" int epos_heads_wgrad_f32(const float* A, int64_t lda, int K, const fl
     EPOS_REQUIRE(reinterpret_cast<uintptr_t>(workspace) % 8 == 0,
                  "workspace must be 8-byte aligned");
   }
-  const void* inputs[] = {A, obj_logits, frag_logits, frag_loc, gt_obj, gt_frag, gt_loc,
-                          gt_weight, scales, upstream, workspace};
-  for (const void* in : inputs)
-    for (const float* out : outs)
-      EPOS_REQUIRE(!in || !out || in != out, "an output buffer starts at an input pointer");
+  const int alias = check_no_alias(__func__, {A, obj_logits, frag_logits, frag_loc, gt_obj, gt_frag,
+                                              gt_loc, gt_weight, scales, upstream, workspace},
+                                   {dW_obj, db_obj, dW_frag, db_frag, dW_loc, db_loc});
+  if (alias != EPOS_OK) return alias;
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (n_pix == 0) B = 0;                          // no pixel: the kernels write zeros
   // workspace: the R slabs f64 [R][K+1][N] when R > 1, S of the object rows f64 [B*P], S of the
@@ -493,9 +486,10 @@ extern "C" int epos_heads_wgrad_f32(const float* A, int64_t lda, int K, const fl
   const int R = B ? wgrad_ranges(P, num_objs, num_frags, K) : 1;
   const int64_t range = ceil_div(P, R);
   const int64_t OF = static_cast<int64_t>(num_objs) * num_frags;
+  const int64_t cells = (int64_t(K) + 1) * slab_cols(num_objs + 1, OF);      // of a slab
   double* slabs = R > 1 ? static_cast<double*>(workspace) : nullptr;
   double* s_obj = static_cast<double*>(workspace);
-  if (slabs) s_obj += R * (int64_t(K) + 1) * (num_objs + 1 + 4 * OF);
+  if (slabs) s_obj += R * cells;
   double* s_frag = s_obj ? s_obj + n_pix : nullptr;
   float* m_obj = s_obj ? reinterpret_cast<float*>(s_frag + n_pix) : nullptr;
   if (n_pix > 0 && (want_obj || want_frag)) {
@@ -532,7 +526,6 @@ extern "C" int epos_heads_wgrad_f32(const float* A, int64_t lda, int K, const fl
     if (st != EPOS_OK) return st;
   }
   if (slabs) {
-    const int64_t cells = (int64_t(K) + 1) * (num_objs + 1 + 4 * OF);
     hipLaunchKernelGGL(wgrad_close_kernel, dim3(static_cast<unsigned>(ceil_div(cells,
                        LOSS_THREADS))), dim3(LOSS_THREADS), 0, s, slabs, R, K, num_objs + 1, OF,
                        dW_obj, db_obj, dW_frag, db_frag, dW_loc, db_loc);

@@ -15,6 +15,8 @@
 //
 // fp64 on the fp32 values, -ffp-contract=off (no FMA). Background, ignored and bad pixels read
 // no fragment value; a foreground pixel reads its object's F logits and 3 localisation values.
+// The class of a pixel, m and S of a row and the Huber term are loss_rows.h's, next to their
+// derivatives.
 #include "loss_rows.h"
 
 namespace epos {
@@ -49,11 +51,6 @@ __device__ __forceinline__ double row_cross_entropy(const float* __restrict__ ro
   return log(s) + (md - static_cast<double>(row[target]));
 }
 
-__device__ __forceinline__ double huber1(double d) {
-  const double a = fabs(d);
-  return a <= 1.0 ? 0.5 * d * d : a - 0.5;
-}
-
 template <bool VEC_OBJ, bool VEC_FRAG>
 __global__ __launch_bounds__(LOSS_THREADS) void loss_terms_kernel(
     const float* __restrict__ obj_logits, int64_t ld_obj, const float* __restrict__ frag_logits,
@@ -78,7 +75,7 @@ __global__ __launch_bounds__(LOSS_THREADS) void loss_terms_kernel(
       g = pixel_class(gt_obj, gt_frag, gt_weight, p, num_objs, num_frags, ignore_label, f, wgt);
     const double ce_obj = row_cross_entropy<VEC_OBJ>(obj_logits + p * ld_obj, num_objs + 1, g,
                                                      g >= 0, sub, L);
-    const int64_t frag_row = g > 0 ? (p * num_objs + (g - 1)) * num_frags : 0;
+    const int64_t frag_row = g > 0 ? frag_row_offset(p, num_objs, g, num_frags) : 0;
     const double ce_frag = row_cross_entropy<VEC_FRAG>(frag_logits + frag_row, num_frags, f,
                                                        g > 0, sub, L);
     if (i < n_here && sub == 0) {

@@ -6,7 +6,7 @@
 //                       per object (pooled) in rounds of 256, one thread adds each round's
 //                       results in index order.
 //   loss_grads_kernel   a workgroup owns a contiguous share of the pixels of ONE image.
-//                       Phase one is the forward's: L lanes share a pixel's row; the pixel's
+//                       Phase one is the forward's (loss_rows.h, pixel_rows): the pixel's
 //                       class, m and S of its two rows and where its active rows start go to
 //                       LDS. Phase two streams the share's contiguous spans of d_frag and d_loc
 //                       in 16-byte nontemporal stores: zeros, except for the quads that touch a
@@ -14,7 +14,8 @@
 //
 // Every output element is written by exactly one thread from values that depend on its own
 // pixel only: no atomics, the same bytes in every run and at every position of every batch.
-// fp64 on the fp32 values, -ffp-contract=off (no FMA).
+// fp64 on the fp32 values, -ffp-contract=off (no FMA): an element's value is softmax_grad or
+// huber_grad of loss_rows.h, which heads_wgrad.hip and heads_dgrad.hip call as well.
 #include "loss_rows.h"
 
 namespace epos {
@@ -145,13 +146,9 @@ __global__ __launch_bounds__(REDUCE_THREADS) void loss_reduce_kernel(
   for (int64_t j = t; j < int64_t(3) * B; j += REDUCE_THREADS) scales[j] = pooled[j % 3];
 }
 
-// What phase one leaves of a share's pixels
-struct ShareRows {
-  double s_obj[GRAD_SHARE_MAX], s_frag[GRAD_SHARE_MAX];    // S of the two rows
-  float m_obj[GRAD_SHARE_MAX], m_frag[GRAD_SHARE_MAX];     // m of the two rows
-  float wgt[GRAD_SHARE_MAX];
-  int code[GRAD_SHARE_MAX], frag[GRAD_SHARE_MAX];
-  // where the pixel's active row starts inside its O * F (O * F * 3) values, or NO_ROW
+// What phase one leaves of a share's pixels, and where each pixel's active row starts inside
+// its O * F (O * F * 3) values, or NO_ROW: the `start` of fill_span
+struct GradRows : ShareRows<GRAD_SHARE_MAX> {
   int row_frag[GRAD_SHARE_MAX], row_loc[GRAD_SHARE_MAX];
 };
 
@@ -211,7 +208,7 @@ __global__ __launch_bounds__(LOSS_THREADS) void loss_grads_kernel(
     int num_objs, int num_frags, int ignore_label, int L, const double* __restrict__ scales,
     const double* __restrict__ upstream, float* __restrict__ d_obj, int64_t ld_dobj,
     float* __restrict__ d_frag, float* __restrict__ d_loc) {
-  __shared__ ShareRows sh;
+  __shared__ GradRows sh;
   const int64_t image = blockIdx.x / blocks_per_image;
   const int64_t p0 = (blockIdx.x % blocks_per_image) * share;
   const int64_t p1 = p0 + share < P ? p0 + share : P;
@@ -219,50 +216,32 @@ __global__ __launch_bounds__(LOSS_THREADS) void loss_grads_kernel(
   const int64_t pix0 = image * P + p0;                       // pixel of the whole batch
   const int O1 = num_objs + 1;
   const uint32_t OF = static_cast<uint32_t>(num_objs) * num_frags;
-  const bool rows_frag = d_frag != nullptr;                  // nothing else needs m, S of it
   const int sub = threadIdx.x % L;                           // L is a power of two <= 64
   const int per_pass = LOSS_THREADS / L;
   for (int base = 0; base < n_here; base += per_pass) {     // uniform trip count: shuffles below
     const int i = base + threadIdx.x / L;
-    const int64_t p = pix0 + i;
-    int g = CODE_NONE, f = 0;
-    float wgt = 0.f;
-    if (i < n_here)
-      g = pixel_class(gt_obj, gt_frag, gt_weight, p, num_objs, num_frags, ignore_label, f, wgt);
-    double m_o = 0.0, s_o = 0.0, m_f = 0.0, s_f = 0.0;
-    if (d_obj) row_max_sum<VEC_OBJ>(obj_logits + p * ld_obj, O1, g >= 0, sub, L, m_o, s_o);
-    if (rows_frag) {
-      const int64_t frag_row = g > 0 ? (p * num_objs + (g - 1)) * num_frags : 0;
-      row_max_sum<VEC_FRAG>(frag_logits + frag_row, num_frags, g > 0, sub, L, m_f, s_f);
-    }
+    // nothing but d_frag needs m, S of the fragment row
+    const PixelRows r = pixel_rows<VEC_OBJ, VEC_FRAG>(
+        obj_logits, ld_obj, frag_logits, gt_obj, gt_frag, gt_weight, pix0 + i, i < n_here,
+        num_objs, num_frags, ignore_label, d_obj != nullptr, d_frag != nullptr, sub, L);
     if (i < n_here && sub == 0) {
-      sh.code[i] = g;
-      sh.frag[i] = f;
-      sh.wgt[i] = wgt;
-      sh.m_obj[i] = static_cast<float>(m_o);                 // m is an fp32 value
-      sh.s_obj[i] = s_o;
-      sh.m_frag[i] = static_cast<float>(m_f);
-      sh.s_frag[i] = s_f;
-      sh.row_frag[i] = g > 0 ? (g - 1) * num_frags : NO_ROW;
-      sh.row_loc[i] = g > 0 ? 3 * ((g - 1) * num_frags + f) : NO_ROW;
+      sh.put(i, r);
+      sh.row_frag[i] = r.code > 0 ? (r.code - 1) * num_frags : NO_ROW;
+      sh.row_loc[i] = r.code > 0 ? 3 * ((r.code - 1) * num_frags + r.frag) : NO_ROW;
     }
   }
   __syncthreads();
-  // s_k = scales[b,k] * (upstream[k] + upstream[3]), one product
   double s[3];
-  for (int k = 0; k < 3; ++k)
-    s[k] = scales[image * 3 + k] * (upstream ? upstream[k] + upstream[3] : 1.0);
+  for (int k = 0; k < 3; ++k) s[k] = task_factor(scales, image, k, upstream_factor(upstream, k));
 
   if (d_obj) {
     for (int t = threadIdx.x; t < n_here * O1; t += LOSS_THREADS) {
       const int i = t / O1, c = t - i * O1;
       const int g = sh.code[i];
       float v = 0.f;
-      if (g >= 0) {
-        const double x = static_cast<double>(obj_logits[(pix0 + i) * ld_obj + c]);
-        const double pr = exp(x - static_cast<double>(sh.m_obj[i])) / sh.s_obj[i];
-        v = static_cast<float>(s[0] * (pr - (c == g ? 1.0 : 0.0)));
-      }
+      if (g >= 0)
+        v = softmax_grad(obj_logits[(pix0 + i) * ld_obj + c], static_cast<double>(sh.m_obj[i]),
+                         sh.s_obj[i], c == g, s[0]);
       d_obj[(pix0 + i) * ld_dobj + c] = v;
     }
   }
@@ -270,22 +249,18 @@ __global__ __launch_bounds__(LOSS_THREADS) void loss_grads_kernel(
     const int64_t span = pix0 * OF;
     fill_span(d_frag + span, static_cast<uint32_t>(n_here) * OF, OF, sh.row_frag, num_frags,
               [&](uint32_t i, int c) {
-                const double x = static_cast<double>(
-                    frag_logits[span + static_cast<int64_t>(i) * OF + sh.row_frag[i] + c]);
-                const double pr = exp(x - static_cast<double>(sh.m_frag[i])) / sh.s_frag[i];
-                return static_cast<float>(s[1] * (pr - (c == sh.frag[i] ? 1.0 : 0.0)));
+                return softmax_grad(
+                    frag_logits[span + static_cast<int64_t>(i) * OF + sh.row_frag[i] + c],
+                    static_cast<double>(sh.m_frag[i]), sh.s_frag[i], c == sh.frag[i], s[1]);
               });
   }
   if (d_loc) {
     const int64_t span = pix0 * OF * 3;
     fill_span(d_loc + span, static_cast<uint32_t>(n_here) * OF * 3, OF * 3, sh.row_loc, 3,
               [&](uint32_t i, int k) {
-                const double q = static_cast<double>(
-                    frag_loc[span + static_cast<int64_t>(i) * OF * 3 + sh.row_loc[i] + k]);
-                const double d = q - static_cast<double>(gt_loc[(pix0 + i) * 3 + k]);
-                // the derivative of the Huber term, knee included: |d| <= 1 gives d
-                const double cl = d > 1.0 ? 1.0 : d < -1.0 ? -1.0 : d;
-                return static_cast<float>(s[2] * (static_cast<double>(sh.wgt[i]) * cl));
+                return huber_grad(
+                    frag_loc[span + static_cast<int64_t>(i) * OF * 3 + sh.row_loc[i] + k],
+                    gt_loc[(pix0 + i) * 3 + k], sh.wgt[i], s[2]);
               });
   }
 }
@@ -330,11 +305,10 @@ extern "C" int epos_loss_grads(const float* obj_logits, int64_t ld_obj, const fl
   EPOS_REQUIRE(obj_logits && frag_logits && frag_loc && gt_obj && gt_frag && gt_loc &&
                gt_weight && scales, "null pointer");
   if (!d_obj && !d_frag && !d_loc) return EPOS_OK;
-  const void* inputs[] = {obj_logits, frag_logits, frag_loc, gt_obj, gt_frag, gt_loc, gt_weight,
-                          scales, upstream};
-  for (const void* in : inputs)
-    EPOS_REQUIRE(!in || (in != d_obj && in != d_frag && in != d_loc),
-                 "an output buffer starts at an input pointer");
+  const int alias = check_no_alias(__func__, {obj_logits, frag_logits, frag_loc, gt_obj, gt_frag,
+                                              gt_loc, gt_weight, scales, upstream},
+                                   {d_obj, d_frag, d_loc});
+  if (alias != EPOS_OK) return alias;
   const int64_t share = grad_share(P);
   const int64_t per_image = ceil_div(P, share);
   const int L = loss_lanes(num_frags);            // 1..64 lanes per pixel

@@ -1,8 +1,13 @@
-// What the loss reduction (loss.hip) and its gradient (loss_grad.hip) share: the limits, the
-// class of a pixel, and the row scheme -- L lanes share a pixel's row, each lane adds its own
-// values in index order, the lanes' partial sums are added in a butterfly.
+// What the loss reduction (loss.hip), its gradient (loss_grad.hip) and the logits layers' weight
+// and input gradients (heads_wgrad.hip, heads_dgrad.hip) share, each rule stated once: the
+// limits and entry checks, the class of a pixel, the row scheme -- L lanes share a pixel's row,
+// each lane adds its own values in index order, the lanes' partial sums are added in a
+// butterfly --, what phase one leaves of a pixel, and the value of one gradient element: fp64
+// on the fp32 values, one product for s_k, rounded to float last.
 #pragma once
 #include <math.h>
+
+#include <initializer_list>
 
 #include "common.h"
 
@@ -12,6 +17,7 @@ constexpr int LOSS_THREADS = 256;
 constexpr int LOSS_MAX_OBJS = 4095, LOSS_MAX_FRAGS = 256;
 constexpr int64_t LOSS_MAX_PIXELS = int64_t(1) << 31;
 constexpr int64_t LOSS_MAX_BLOCKS = (int64_t(1) << 31) - 1;
+constexpr int HEADS_MAX_K = 1024;            // feature channels of the logits layers
 
 // classes of a pixel slot in LDS besides 0..O
 constexpr int CODE_IGNORED = -1, CODE_BAD = -2, CODE_NONE = -3;
@@ -37,6 +43,31 @@ inline int check_loss_dims(const char* fn, int B, int64_t P, int num_objs, int n
   if (!msg) return EPOS_OK;
   set_error("%s: %s", fn, msg);
   return EPOS_E_INVALID;
+}
+
+// check_loss_dims and the limit of K, for the entries that read or write the features
+inline int check_heads_dims(const char* fn, int B, int64_t P, int num_objs, int num_frags,
+                            int64_t share, int K) {
+  const int rc = check_loss_dims(fn, B, P, num_objs, num_frags, share);
+  if (rc != EPOS_OK) return rc;
+  if (K < 1 || K > HEADS_MAX_K) {
+    set_error("%s: K must be in 1..1024", fn);
+    return EPOS_E_INVALID;
+  }
+  return EPOS_OK;
+}
+
+// EPOS_E_INVALID when an output starts at an input pointer; null pointers are skipped
+inline int check_no_alias(const char* fn, std::initializer_list<const void*> inputs,
+                          std::initializer_list<const void*> outputs) {
+  for (const void* in : inputs)
+    for (const void* out : outputs)
+      if (in && in == out) {
+        set_error("%s: %s output buffer starts at an input pointer", fn,
+                  outputs.size() == 1 ? "the" : "an");
+        return EPOS_E_INVALID;
+      }
+  return EPOS_OK;
 }
 
 // The class of pixel p: 0..O, CODE_IGNORED or CODE_BAD; the ignore rule first. f and wgt are
@@ -93,6 +124,93 @@ __device__ __forceinline__ void row_max_sum(const float* __restrict__ row, int n
                          [&](float v) { acc += exp(static_cast<double>(v) - mm); });
   for (int d = 1; d < L; d <<= 1) acc += __shfl_xor(acc, d);
   s = acc;
+}
+
+// Where the F fragment logits of foreground pixel p (of the whole batch) and object g start;
+// three times that, its localisation values
+__device__ __forceinline__ int64_t frag_row_offset(int64_t p, int num_objs, int g,
+                                                   int num_frags) {
+  return (p * num_objs + (g - 1)) * num_frags;
+}
+
+// What phase one leaves of a pixel: its class, fragment and weight (pixel_class), m and S of
+// its object row (class >= 0) and of its fragment row (class > 0)
+struct PixelRows {
+  int code, frag;
+  float wgt;
+  double m_obj, s_obj, m_frag, s_frag;       // m is an fp32 value
+};
+
+// Phase one of pixel p for the L lanes that share it (all of them call, `valid` or not: the
+// shuffles of row_max_sum); a row that is not wanted is not read and leaves m = S = 0.
+template <bool VEC_OBJ, bool VEC_FRAG>
+__device__ __forceinline__ PixelRows pixel_rows(
+    const float* __restrict__ obj_logits, int64_t ld_obj, const float* __restrict__ frag_logits,
+    const int32_t* __restrict__ gt_obj, const int32_t* __restrict__ gt_frag,
+    const float* __restrict__ gt_weight, int64_t p, bool valid, int num_objs, int num_frags,
+    int ignore_label, bool want_obj, bool want_frag, int sub, int L) {
+  PixelRows r = {CODE_NONE, 0, 0.f, 0.0, 0.0, 0.0, 0.0};
+  if (valid)
+    r.code = pixel_class(gt_obj, gt_frag, gt_weight, p, num_objs, num_frags, ignore_label,
+                         r.frag, r.wgt);
+  if (want_obj)
+    row_max_sum<VEC_OBJ>(obj_logits + (r.code >= 0 ? p * ld_obj : 0), num_objs + 1, r.code >= 0,
+                         sub, L, r.m_obj, r.s_obj);
+  if (want_frag)
+    row_max_sum<VEC_FRAG>(
+        frag_logits + (r.code > 0 ? frag_row_offset(p, num_objs, r.code, num_frags) : 0),
+        num_frags, r.code > 0, sub, L, r.m_frag, r.s_frag);
+  return r;
+}
+
+// Phase one of a share of N pixels at most, in LDS
+template <int N>
+struct ShareRows {
+  double s_obj[N], s_frag[N];                // S of the two rows
+  float m_obj[N], m_frag[N];                 // m of the two rows
+  float wgt[N];
+  int code[N], frag[N];
+
+  __device__ __forceinline__ void put(int i, const PixelRows& r) {
+    code[i] = r.code;
+    frag[i] = r.frag;
+    wgt[i] = r.wgt;
+    m_obj[i] = static_cast<float>(r.m_obj);
+    s_obj[i] = r.s_obj;
+    m_frag[i] = static_cast<float>(r.m_frag);
+    s_frag[i] = r.s_frag;
+  }
+};
+
+// u_k: what arrives at loss k, directly and through the total; 1.0 without upstream
+__device__ __forceinline__ double upstream_factor(const double* __restrict__ upstream, int k) {
+  return upstream ? upstream[k] + upstream[3] : 1.0;
+}
+
+// s_k of image b = scales[b,k] * u_k, one product
+__device__ __forceinline__ double task_factor(const double* __restrict__ scales, int64_t b,
+                                              int k, double u_k) {
+  return scales[b * 3 + k] * u_k;
+}
+
+// d loss / d x of one element of a softmax row with maximum m and sum S
+__device__ __forceinline__ float softmax_grad(float x, double m, double S, bool target,
+                                              double s_k) {
+  const double pr = exp(static_cast<double>(x) - m) / S;
+  return static_cast<float>(s_k * (pr - (target ? 1.0 : 0.0)));
+}
+
+// The Huber term of one localisation component, d = q - t ...
+__device__ __forceinline__ double huber1(double d) {
+  const double a = fabs(d);
+  return a <= 1.0 ? 0.5 * d * d : a - 0.5;
+}
+
+// ... and its derivative, knee included: |d| <= 1 gives d
+__device__ __forceinline__ float huber_grad(float q, float t, float wgt, double s_2) {
+  const double d = static_cast<double>(q) - static_cast<double>(t);
+  const double cl = d > 1.0 ? 1.0 : d < -1.0 ? -1.0 : d;
+  return static_cast<float>(s_2 * (static_cast<double>(wgt) * cl));
 }
 
 }  // namespace epos

@@ -39,12 +39,7 @@ from epos_amd._lib import EposError
 from epos_amd import loss as L
 from epos_amd import weights as W
 
-HEADS = (W.PRED_OBJ_CONF, W.PRED_FRAG_CONF, W.PRED_FRAG_LOC)
-
-
-def variable_names(head):
-  """(weights, biases): the checkpoint variable names of a logits layer."""
-  return 'logits/%s/weights' % head, 'logits/%s/biases' % head
+HEADS, variable_names = L.HEADS, L.variable_names
 
 
 def heads_weight_grads(features, logits, gt, scales, upstream=None, ignore_label=255,
@@ -59,48 +54,15 @@ def heads_weight_grads(features, logits, gt, scales, upstream=None, ignore_label
   written. Enqueues on the current stream; does not synchronise."""
   import torch
   lib = _lib.load()
-  obj, frag, loc = (logits[k] for k in HEADS)
-  if not obj.is_cuda:
-    raise EposError('the weight gradients need a HIP device (there is no CPU fallback)')
-  dev = obj.device
-  if frag.dim() < 3 or obj.dim() < 2:
-    raise ValueError('pred_frag_conf must be [..., O, F] and pred_obj_conf [..., O+1]')
-  O, F = int(frag.shape[-2]), int(frag.shape[-1])
-  if obj.shape[-1] != O + 1:
-    raise ValueError('pred_obj_conf has %d channels, pred_frag_conf %d objects' % (
-        obj.shape[-1], O))
-  gt_obj = gt['obj_label']
-  B = int(gt_obj.shape[0]) if gt_obj.dim() > 1 else 1
-  n = gt_obj.numel()
-  if B == 0 or n % B:
-    raise ValueError('obj_label must be [B, ...] with B >= 1')
-  P = n // B
+  bt = L._Batch(logits, gt, 'the weight gradients need', scales, upstream)
+  dev, B, P, O, F, n = bt.dev, bt.B, bt.P, bt.O, bt.F, bt.n
   if features.device != dev:
     raise EposError('features are on %s, the logits on %s' % (features.device, dev))
-  if features.dtype != torch.float32:
-    raise TypeError('features must be torch.float32, got %s (a bf16 decoder_out is not '
-                    'supported: run the net with precision=\'fp32\')' % features.dtype)
-  if obj.dtype != torch.float32:
-    raise TypeError('pred_obj_conf must be torch.float32, got %s' % obj.dtype)
+  L._need_fp32(features)
   K = int(features.shape[-1])
   feat2, lda = L._rows(features, K)
   if feat2.shape[0] != n:
     raise ValueError('features hold %d rows, expected %d' % (feat2.shape[0], n))
-  obj2, ld = L._rows(obj, O + 1)
-  if obj2.shape[0] != n:
-    raise ValueError('pred_obj_conf holds %d rows, expected %d' % (obj2.shape[0], n))
-  ins = [feat2, obj2,
-         L._flat(frag, dev, torch.float32, n * O * F, 'pred_frag_conf'),
-         L._flat(loc, dev, torch.float32, n * O * F * 3, 'pred_frag_loc'),
-         L._flat(gt_obj, dev, torch.int32, n, 'obj_label'),
-         L._flat(gt['frag_label'], dev, torch.int32, n, 'frag_label'),
-         L._flat(gt['frag_loc'], dev, torch.float32, n * 3, 'frag_loc'),
-         L._flat(gt['frag_weight'], dev, torch.float32, n, 'frag_weight'),
-         L._flat(scales, dev, torch.float64, B * 3, 'scales')]
-  up = None
-  if upstream is not None:
-    up = L._flat(upstream, dev, torch.float64, 4, 'upstream')
-    ins.append(up)
   widths = (O + 1, O * F, O * F * 3)
   result, ptrs = {}, []
   for k, head in enumerate(HEADS):
@@ -132,11 +94,9 @@ def heads_weight_grads(features, logits, gt, scales, upstream=None, ignore_label
   stream = torch.cuda.current_stream(dev)
   with torch.cuda.device(dev):
     _lib.check(lib.epos_heads_wgrad_f32(
-        L._ptr(ins[0]), lda, K, L._ptr(ins[1]), ld, L._ptr(ins[2]), L._ptr(ins[3]),
-        L._ptr(ins[4]), L._ptr(ins[5]), L._ptr(ins[6]), L._ptr(ins[7]), B, P, O, F,
-        int(ignore_label), L._ptr(ins[8]), L._ptr(up), L._ptr(ws), *[L._ptr(t) for t in ptrs],
-        ctypes.c_void_p(stream.cuda_stream)), 'epos_heads_wgrad_f32')
-  for t in ins + [ws]:
+        L._ptr(feat2), lda, K, *bt.grad_args(ignore_label), L._ptr(ws),
+        *[L._ptr(t) for t in ptrs], ctypes.c_void_p(stream.cuda_stream)), 'epos_heads_wgrad_f32')
+  for t in bt.keep + [feat2, ws]:
     t.record_stream(stream)           # temporaries and dense copies made here outlive the call
   return result
 
@@ -157,24 +117,8 @@ def heads_input_grad(logits, gt, scales, head_weights, upstream=None, relu_of=No
   written. Enqueues on the current stream; does not synchronise."""
   import torch
   lib = _lib.load()
-  obj, frag, loc = (logits[k] for k in HEADS)
-  if not obj.is_cuda:
-    raise EposError('the input gradient needs a HIP device (there is no CPU fallback)')
-  dev = obj.device
-  if frag.dim() < 3 or obj.dim() < 2:
-    raise ValueError('pred_frag_conf must be [..., O, F] and pred_obj_conf [..., O+1]')
-  O, F = int(frag.shape[-2]), int(frag.shape[-1])
-  if obj.shape[-1] != O + 1:
-    raise ValueError('pred_obj_conf has %d channels, pred_frag_conf %d objects' % (
-        obj.shape[-1], O))
-  gt_obj = gt['obj_label']
-  B = int(gt_obj.shape[0]) if gt_obj.dim() > 1 else 1
-  n = gt_obj.numel()
-  if B == 0 or n % B:
-    raise ValueError('obj_label must be [B, ...] with B >= 1')
-  P = n // B
-  if obj.dtype != torch.float32:
-    raise TypeError('pred_obj_conf must be torch.float32, got %s' % obj.dtype)
+  bt = L._Batch(logits, gt, 'the input gradient needs', scales, upstream)
+  dev, O, F, n = bt.dev, bt.O, bt.F, bt.n
   widths = (O + 1, O * F, O * F * 3)
   mats, K = [], None
   for head, width in zip(HEADS, widths):
@@ -202,21 +146,6 @@ def heads_input_grad(logits, gt, scales, head_weights, upstream=None, relu_of=No
   for m, width in zip(mats, widths):
     wt[r0:r0 + width].copy_(m.t())                 # to the device and to float32 where needed
     r0 += width
-  obj2, ld = L._rows(obj, O + 1)
-  if obj2.shape[0] != n:
-    raise ValueError('pred_obj_conf holds %d rows, expected %d' % (obj2.shape[0], n))
-  ins = [obj2,
-         L._flat(frag, dev, torch.float32, n * O * F, 'pred_frag_conf'),
-         L._flat(loc, dev, torch.float32, n * O * F * 3, 'pred_frag_loc'),
-         L._flat(gt_obj, dev, torch.int32, n, 'obj_label'),
-         L._flat(gt['frag_label'], dev, torch.int32, n, 'frag_label'),
-         L._flat(gt['frag_loc'], dev, torch.float32, n * 3, 'frag_loc'),
-         L._flat(gt['frag_weight'], dev, torch.float32, n, 'frag_weight'),
-         L._flat(scales, dev, torch.float64, B * 3, 'scales')]
-  up = None
-  if upstream is not None:
-    up = L._flat(upstream, dev, torch.float64, 4, 'upstream')
-    ins.append(up)
   y2, ldy = None, K
   if relu_of is not None:
     if relu_of.device != dev:
@@ -227,7 +156,6 @@ def heads_input_grad(logits, gt, scales, head_weights, upstream=None, relu_of=No
     y2, ldy = L._rows(relu_of, K)
     if y2.shape[0] != n:
       raise ValueError('relu_of holds %d rows, expected %d' % (y2.shape[0], n))
-    ins.append(y2)
   if out is None:
     out = torch.empty((n, K), dtype=torch.float32, device=dev)
   elif out.device != dev or out.dtype != torch.float32 or out.shape[-1] != K:
@@ -238,12 +166,11 @@ def heads_input_grad(logits, gt, scales, head_weights, upstream=None, relu_of=No
   stream = torch.cuda.current_stream(dev)
   with torch.cuda.device(dev):
     _lib.check(lib.epos_heads_dgrad_f32(
-        L._ptr(ins[0]), ld, L._ptr(ins[1]), L._ptr(ins[2]), L._ptr(ins[3]), L._ptr(ins[4]),
-        L._ptr(ins[5]), L._ptr(ins[6]), B, P, O, F, int(ignore_label), L._ptr(ins[7]),
-        L._ptr(up), L._ptr(wt[:widths[0]]), L._ptr(wt[widths[0]:widths[0] + widths[1]]),
-        L._ptr(wt[widths[0] + widths[1]:]), K, K, L._ptr(y2), ldy, L._ptr(out2), ldx,
-        ctypes.c_void_p(stream.cuda_stream)), 'epos_heads_dgrad_f32')
-  for t in ins + [wt]:
+        *bt.grad_args(ignore_label), L._ptr(wt[:widths[0]]),
+        L._ptr(wt[widths[0]:widths[0] + widths[1]]), L._ptr(wt[widths[0] + widths[1]:]), K, K,
+        L._ptr(y2), ldy, L._ptr(out2), ldx, ctypes.c_void_p(stream.cuda_stream)),
+               'epos_heads_dgrad_f32')
+  for t in bt.keep + [wt] + ([y2] if y2 is not None else []):
     t.record_stream(stream)           # temporaries and dense copies made here outlive the call
   return out
 
@@ -272,24 +199,33 @@ def momentum_step(param, accum, grad, lr, momentum=0.9, weight_decay=0.0, grad_m
   return param
 
 
+def net_logits(net):
+  """The logits of a net that has run forward_logits, as loss.loss_terms takes them: views
+  [B,h,w,O+1], [B,h,w,O,F] and [B,h,w,O,F,3] of the net's own buffers."""
+  B, h, w = (int(d) for d in net.decoder_out.shape[:3])
+  O, F = int(net.num_objs), int(net.num_frags)
+  return {W.PRED_OBJ_CONF: net.logits[W.PRED_OBJ_CONF],
+          W.PRED_FRAG_CONF: net.logits[W.PRED_FRAG_CONF].view(B, h, w, O, F),
+          W.PRED_FRAG_LOC: net.logits[W.PRED_FRAG_LOC].view(B, h, w, O, F, 3)}
+
+
+def _net_losses(net, gt, weights, reduction, ignore_label):
+  """loss_terms -> loss_values on an fp32 net's logits: (logits, values, bad, scales)."""
+  L._need_fp32(net.decoder_out)
+  logits = net_logits(net)
+  sums, counts, bad = L.loss_terms(logits, gt, ignore_label)
+  values, scales = L.loss_values(sums, counts, weights, reduction)
+  return logits, values, bad, scales
+
+
 def net_head_grads(net, gt, weights=(1.0, 1.0, 100.0), reduction='pooled', ignore_label=255):
   """From a running network to checkpoint-shaped gradients: call after net.forward_logits().
   Runs loss_terms -> loss_values -> heads_weight_grads on net.decoder_out and the net's logits.
   Returns (values f64 [4], bad i64 [B], grads): values and bad as loss.differentiable_losses
   returns them, grads = {'logits/<name>/weights': f32 [1,1,K,N], 'logits/<name>/biases': f32
   [N]} on the device. fp32 single-scale nets only. Does not synchronise."""
-  import torch
-  feats = net.decoder_out
-  if feats.dtype != torch.float32:
-    raise TypeError('net_head_grads needs an fp32 net: decoder_out is %s' % feats.dtype)
-  B, h, w = int(feats.shape[0]), int(feats.shape[1]), int(feats.shape[2])
-  O, F = int(net.num_objs), int(net.num_frags)
-  logits = {W.PRED_OBJ_CONF: net.logits[W.PRED_OBJ_CONF],
-            W.PRED_FRAG_CONF: net.logits[W.PRED_FRAG_CONF].view(B, h, w, O, F),
-            W.PRED_FRAG_LOC: net.logits[W.PRED_FRAG_LOC].view(B, h, w, O, F, 3)}
-  sums, counts, bad = L.loss_terms(logits, gt, ignore_label)
-  values, scales = L.loss_values(sums, counts, weights, reduction)
-  raw = heads_weight_grads(feats, logits, gt, scales, ignore_label=ignore_label)
+  logits, values, bad, scales = _net_losses(net, gt, weights, reduction, ignore_label)
+  raw = heads_weight_grads(net.decoder_out, logits, gt, scales, ignore_label=ignore_label)
   grads = {}
   for head in HEADS:
     dW, db = raw[head]
@@ -309,20 +245,9 @@ def net_feature_grad(net, gt, head_weights, weights=(1.0, 1.0, 100.0), reduction
   net.decoder_out or, with relu=True, masked with net.decoder_out: with respect to the
   pre-activation of decoder_conv1_pointwise (batch norm folded). fp32 single-scale nets only.
   Does not synchronise."""
-  import torch
-  feats = net.decoder_out
-  if feats.dtype != torch.float32:
-    raise TypeError('features must be torch.float32, got %s (a bf16 decoder_out is not '
-                    'supported: run the net with precision=\'fp32\')' % feats.dtype)
-  B, h, w = int(feats.shape[0]), int(feats.shape[1]), int(feats.shape[2])
-  O, F = int(net.num_objs), int(net.num_frags)
-  logits = {W.PRED_OBJ_CONF: net.logits[W.PRED_OBJ_CONF],
-            W.PRED_FRAG_CONF: net.logits[W.PRED_FRAG_CONF].view(B, h, w, O, F),
-            W.PRED_FRAG_LOC: net.logits[W.PRED_FRAG_LOC].view(B, h, w, O, F, 3)}
-  sums, counts, bad = L.loss_terms(logits, gt, ignore_label)
-  values, scales = L.loss_values(sums, counts, weights, reduction)
-  dX = heads_input_grad(logits, gt, scales, head_weights, relu_of=feats if relu else None,
-                        ignore_label=ignore_label)
+  logits, values, bad, scales = _net_losses(net, gt, weights, reduction, ignore_label)
+  dX = heads_input_grad(logits, gt, scales, head_weights,
+                        relu_of=net.decoder_out if relu else None, ignore_label=ignore_label)
   return values, bad, dX
 
 

@@ -57,6 +57,13 @@ def _flat(t, device, dtype, numel, what):
   return t
 
 
+def _need_fp32(features):
+  import torch
+  if features.dtype != torch.float32:
+    raise TypeError('features must be torch.float32, got %s (a bf16 decoder_out is not '
+                    'supported: run the net with precision=\'fp32\')' % features.dtype)
+
+
 def _rows(t, width):
   """(tensor, row stride) of obj logits [..., width]: a view whose rows lie a constant stride
   apart is taken as it is (a slice of a wider head buffer), anything else is made dense."""
@@ -70,6 +77,78 @@ def _rows(t, width):
   return t.contiguous().view(-1, width), width
 
 
+HEADS = (W.PRED_OBJ_CONF, W.PRED_FRAG_CONF, W.PRED_FRAG_LOC)
+
+
+def variable_names(head):
+  """(weights, biases): the checkpoint variable names of a logits layer."""
+  return 'logits/%s/weights' % head, 'logits/%s/biases' % head
+
+
+HEAD_VARIABLES = tuple(name for head in HEADS for name in variable_names(head))
+
+
+def _head_dicts(obj, frag, loc, gt_obj, gt_frag, gt_loc, gt_weight):
+  """(logits, gt) as loss_terms takes them, from the seven tensors."""
+  return (dict(zip(HEADS, (obj, frag, loc))),
+          dict(zip(GT_KEYS, (gt_obj, gt_frag, gt_loc, gt_weight))))
+
+
+class _Batch(object):
+  """A batch of logits and ground truth as the C entries take it: dev, B, P, O, F, n = B * P;
+  shapes of the three logit tensors; ins = [obj rows, frag, loc, obj_label, frag_label, frag_loc,
+  frag_weight] flattened, in ABI order, with ld the row stride of the first; scales and upstream
+  flattened (or None); keep = what to record_stream after the launch."""
+
+  def __init__(self, logits, gt, who, scales=None, upstream=None):
+    import torch
+    obj, frag, loc = (logits[k] for k in HEADS)
+    if not obj.is_cuda:
+      raise EposError('%s a HIP device (there is no CPU fallback)' % who)
+    dev = obj.device
+    if frag.dim() < 3 or obj.dim() < 2:
+      raise ValueError('pred_frag_conf must be [..., O, F] and pred_obj_conf [..., O+1]')
+    O, F = int(frag.shape[-2]), int(frag.shape[-1])
+    if obj.shape[-1] != O + 1:
+      raise ValueError('pred_obj_conf has %d channels, pred_frag_conf %d objects' % (
+          obj.shape[-1], O))
+    gt_obj = gt['obj_label']
+    B = int(gt_obj.shape[0]) if gt_obj.dim() > 1 else 1
+    n = gt_obj.numel()
+    if B == 0 or n % B:
+      raise ValueError('obj_label must be [B, ...] with B >= 1')
+    if obj.dtype != torch.float32:
+      raise TypeError('pred_obj_conf must be torch.float32, got %s' % obj.dtype)
+    obj2, self.ld = _rows(obj, O + 1)
+    if obj2.shape[0] != n:
+      raise ValueError('pred_obj_conf holds %d rows, expected %d' % (obj2.shape[0], n))
+    self.dev, self.B, self.P, self.O, self.F, self.n = dev, B, n // B, O, F, n
+    self.shapes = (obj.shape, frag.shape, loc.shape)
+    self.ins = [obj2,
+                _flat(frag, dev, torch.float32, n * O * F, 'pred_frag_conf'),
+                _flat(loc, dev, torch.float32, n * O * F * 3, 'pred_frag_loc'),
+                _flat(gt_obj, dev, torch.int32, n, 'obj_label'),
+                _flat(gt['frag_label'], dev, torch.int32, n, 'frag_label'),
+                _flat(gt['frag_loc'], dev, torch.float32, n * 3, 'frag_loc'),
+                _flat(gt['frag_weight'], dev, torch.float32, n, 'frag_weight')]
+    self.scales = self.upstream = None
+    if scales is not None:
+      self.scales = _flat(scales, dev, torch.float64, B * 3, 'scales')
+    if upstream is not None:
+      self.upstream = _flat(upstream, dev, torch.float64, 4, 'upstream')
+    self.keep = self.ins + [t for t in (self.scales, self.upstream) if t is not None]
+
+  def args(self, ignore_label):
+    """The arguments every entry shares: obj, ld_obj, frag, loc, the four ground-truth fields,
+    B, P, O, F, ignore_label."""
+    i = [_ptr(t) for t in self.ins]
+    return (i[0], self.ld) + tuple(i[1:]) + (self.B, self.P, self.O, self.F, int(ignore_label))
+
+  def grad_args(self, ignore_label):
+    """args, then scales and upstream (NULL without)."""
+    return self.args(ignore_label) + (_ptr(self.scales), _ptr(self.upstream))
+
+
 def loss_terms(logits, gt, ignore_label=255, out=None):
   """epos_loss_terms over one batch. logits: the dict of EposNet.forward_logits --
   pred_obj_conf f32 [B,h,w,O+1], pred_frag_conf f32 [B,h,w,O,F], pred_frag_loc f32
@@ -79,33 +158,8 @@ def loss_terms(logits, gt, ignore_label=255, out=None):
   larger table) to write into. Enqueues on the current stream; does not synchronise."""
   import torch
   lib = _lib.load()
-  obj, frag, loc = (logits[k] for k in (W.PRED_OBJ_CONF, W.PRED_FRAG_CONF, W.PRED_FRAG_LOC))
-  if not obj.is_cuda:
-    raise EposError('the losses need a HIP device (there is no CPU fallback)')
-  dev = obj.device
-  if frag.dim() < 3 or obj.dim() < 2:
-    raise ValueError('pred_frag_conf must be [..., O, F] and pred_obj_conf [..., O+1]')
-  O, F = int(frag.shape[-2]), int(frag.shape[-1])
-  if obj.shape[-1] != O + 1:
-    raise ValueError('pred_obj_conf has %d channels, pred_frag_conf %d objects' % (
-        obj.shape[-1], O))
-  gt_obj = gt['obj_label']
-  B = int(gt_obj.shape[0]) if gt_obj.dim() > 1 else 1
-  n = gt_obj.numel()
-  if B == 0 or n % B:
-    raise ValueError('obj_label must be [B, ...] with B >= 1')
-  P = n // B
-  if obj.dtype != torch.float32 or obj.device != dev:
-    raise TypeError('pred_obj_conf must be torch.float32, got %s' % obj.dtype)
-  obj2, ld = _rows(obj, O + 1)
-  if obj2.shape[0] != n:
-    raise ValueError('pred_obj_conf holds %d rows, expected %d' % (obj2.shape[0], n))
-  frag = _flat(frag, dev, torch.float32, n * O * F, 'pred_frag_conf')
-  loc = _flat(loc, dev, torch.float32, n * O * F * 3, 'pred_frag_loc')
-  g_obj = _flat(gt_obj, dev, torch.int32, n, 'obj_label')
-  g_frag = _flat(gt['frag_label'], dev, torch.int32, n, 'frag_label')
-  g_loc = _flat(gt['frag_loc'], dev, torch.float32, n * 3, 'frag_loc')
-  g_w = _flat(gt['frag_weight'], dev, torch.float32, n, 'frag_weight')
+  bt = _Batch(logits, gt, 'the losses need')
+  dev, B, P, O, F = bt.dev, bt.B, bt.P, bt.O, bt.F
   if out is None:
     out = (torch.empty((B, O + 1, 3), dtype=torch.float64, device=dev),
            torch.empty((B, O + 1, 2), dtype=torch.int64, device=dev),
@@ -123,10 +177,9 @@ def loss_terms(logits, gt, ignore_label=255, out=None):
   stream = torch.cuda.current_stream(dev)
   with torch.cuda.device(dev):
     _lib.check(lib.epos_loss_terms(
-        _ptr(obj2), ld, _ptr(frag), _ptr(loc), _ptr(g_obj), _ptr(g_frag), _ptr(g_loc),
-        _ptr(g_w), B, P, O, F, int(ignore_label), _ptr(ws), _ptr(sums), _ptr(counts),
-        _ptr(bad), ctypes.c_void_p(stream.cuda_stream)), 'epos_loss_terms')
-  for t in (obj2, frag, loc, g_obj, g_frag, g_loc, g_w, ws):
+        *bt.args(ignore_label), _ptr(ws), _ptr(sums), _ptr(counts), _ptr(bad),
+        ctypes.c_void_p(stream.cuda_stream)), 'epos_loss_terms')
+  for t in bt.keep + [ws]:
     t.record_stream(stream)           # temporaries and dense copies made here outlive the call
   return sums, counts, bad
 
@@ -348,39 +401,9 @@ def loss_grads(logits, gt, scales, upstream=None, ignore_label=255, need=(True, 
   pixels get zero gradient. Enqueues on the current stream; does not synchronise."""
   import torch
   lib = _lib.load()
-  obj, frag, loc = (logits[k] for k in (W.PRED_OBJ_CONF, W.PRED_FRAG_CONF, W.PRED_FRAG_LOC))
-  if not obj.is_cuda:
-    raise EposError('the losses need a HIP device (there is no CPU fallback)')
-  dev = obj.device
-  if frag.dim() < 3 or obj.dim() < 2:
-    raise ValueError('pred_frag_conf must be [..., O, F] and pred_obj_conf [..., O+1]')
-  O, F = int(frag.shape[-2]), int(frag.shape[-1])
-  if obj.shape[-1] != O + 1:
-    raise ValueError('pred_obj_conf has %d channels, pred_frag_conf %d objects' % (
-        obj.shape[-1], O))
-  gt_obj = gt['obj_label']
-  B = int(gt_obj.shape[0]) if gt_obj.dim() > 1 else 1
-  n = gt_obj.numel()
-  if B == 0 or n % B:
-    raise ValueError('obj_label must be [B, ...] with B >= 1')
-  P = n // B
-  if obj.dtype != torch.float32:
-    raise TypeError('pred_obj_conf must be torch.float32, got %s' % obj.dtype)
-  obj2, ld = _rows(obj, O + 1)
-  if obj2.shape[0] != n:
-    raise ValueError('pred_obj_conf holds %d rows, expected %d' % (obj2.shape[0], n))
-  ins = [obj2,
-         _flat(frag, dev, torch.float32, n * O * F, 'pred_frag_conf'),
-         _flat(loc, dev, torch.float32, n * O * F * 3, 'pred_frag_loc'),
-         _flat(gt_obj, dev, torch.int32, n, 'obj_label'),
-         _flat(gt['frag_label'], dev, torch.int32, n, 'frag_label'),
-         _flat(gt['frag_loc'], dev, torch.float32, n * 3, 'frag_loc'),
-         _flat(gt['frag_weight'], dev, torch.float32, n, 'frag_weight'),
-         _flat(scales, dev, torch.float64, B * 3, 'scales')]
-  if upstream is not None:
-    ins.append(_flat(upstream, dev, torch.float64, 4, 'upstream'))
+  bt = _Batch(logits, gt, 'the losses need', scales, upstream)
+  dev, O, shapes = bt.dev, bt.O, bt.shapes
   outs = list(out) if out is not None else [None, None, None]
-  shapes = (obj.shape, frag.shape, loc.shape)
   for k in range(3):
     if not need[k]:
       outs[k] = None
@@ -398,11 +421,9 @@ def loss_grads(logits, gt, scales, upstream=None, ignore_label=255, need=(True, 
   stream = torch.cuda.current_stream(dev)
   with torch.cuda.device(dev):
     _lib.check(lib.epos_loss_grads(
-        _ptr(ins[0]), ld, _ptr(ins[1]), _ptr(ins[2]), _ptr(ins[3]), _ptr(ins[4]), _ptr(ins[5]),
-        _ptr(ins[6]), B, P, O, F, int(ignore_label), _ptr(ins[7]),
-        _ptr(ins[8]) if upstream is not None else None, _ptr(d_obj2), ld_d, _ptr(outs[1]),
-        _ptr(outs[2]), ctypes.c_void_p(stream.cuda_stream)), 'epos_loss_grads')
-  for t in ins:
+        *bt.grad_args(ignore_label), _ptr(d_obj2), ld_d, _ptr(outs[1]), _ptr(outs[2]),
+        ctypes.c_void_p(stream.cuda_stream)), 'epos_loss_grads')
+  for t in bt.keep:
     t.record_stream(stream)           # temporaries and dense copies made here outlive the call
   return tuple(outs)
 
@@ -424,8 +445,7 @@ def _losses_function():
     @staticmethod
     def forward(ctx, obj, frag, loc, gt_obj, gt_frag, gt_loc, gt_weight, weights, reduction,
                 ignore_label):
-      logits = {W.PRED_OBJ_CONF: obj, W.PRED_FRAG_CONF: frag, W.PRED_FRAG_LOC: loc}
-      gt = dict(zip(GT_KEYS, (gt_obj, gt_frag, gt_loc, gt_weight)))
+      logits, gt = _head_dicts(obj, frag, loc, gt_obj, gt_frag, gt_loc, gt_weight)
       sums, counts, bad = loss_terms(logits, gt, ignore_label)
       values, scales = loss_values(sums, counts, weights, reduction)
       ctx.save_for_backward(obj, frag, loc, gt_obj, gt_frag, gt_loc, gt_weight, scales)
@@ -437,19 +457,13 @@ def _losses_function():
     @once_differentiable
     def backward(ctx, grad_values, grad_bad):
       obj, frag, loc, gt_obj, gt_frag, gt_loc, gt_weight, scales = ctx.saved_tensors
-      logits = {W.PRED_OBJ_CONF: obj, W.PRED_FRAG_CONF: frag, W.PRED_FRAG_LOC: loc}
-      gt = dict(zip(GT_KEYS, (gt_obj, gt_frag, gt_loc, gt_weight)))
+      logits, gt = _head_dicts(obj, frag, loc, gt_obj, gt_frag, gt_loc, gt_weight)
       grads = loss_grads(logits, gt, scales, upstream=grad_values.to(torch.float64),
                          ignore_label=ctx.ignore_label, need=tuple(ctx.needs_input_grad[:3]))
       return grads + (None,) * 7
 
   _function = EposLosses
   return _function
-
-
-HEAD_VARIABLES = tuple('logits/%s/%s' % (head, kind)
-                       for head in (W.PRED_OBJ_CONF, W.PRED_FRAG_CONF, W.PRED_FRAG_LOC)
-                       for kind in ('weights', 'biases'))
 
 
 def logits_from_features(features, head_weights):
@@ -468,8 +482,7 @@ def logits_from_features(features, head_weights):
     raise ValueError('the logits variables have %d, %d and %d columns: not O+1, O*F and O*F*3' %
                      tuple(t.shape[1] for t in flat))
   F = int(flat[1].shape[1]) // O
-  return {W.PRED_OBJ_CONF: flat[0], W.PRED_FRAG_CONF: flat[1].view(n, O, F),
-          W.PRED_FRAG_LOC: flat[2].view(n, O, F, 3)}
+  return dict(zip(HEADS, (flat[0], flat[1].view(n, O, F), flat[2].view(n, O, F, 3))))
 
 
 _features_function = None
@@ -490,13 +503,12 @@ def _features_losses_function():
     def forward(ctx, features, w_obj, b_obj, w_frag, b_frag, w_loc, b_loc, gt_obj, gt_frag,
                 gt_loc, gt_weight, weights, reduction, ignore_label):
       variables = (w_obj, b_obj, w_frag, b_frag, w_loc, b_loc)
-      logits = logits_from_features(features, dict(zip(HEAD_VARIABLES, variables)))
-      gt = dict(zip(GT_KEYS, (gt_obj, gt_frag, gt_loc, gt_weight)))
+      made = logits_from_features(features, dict(zip(HEAD_VARIABLES, variables)))
+      logits, gt = _head_dicts(*(made[k] for k in HEADS), gt_obj, gt_frag, gt_loc, gt_weight)
       sums, counts, bad = loss_terms(logits, gt, ignore_label)
       values, scales = loss_values(sums, counts, weights, reduction)
-      ctx.save_for_backward(features, w_obj, w_frag, w_loc, logits[W.PRED_OBJ_CONF],
-                            logits[W.PRED_FRAG_CONF], logits[W.PRED_FRAG_LOC], gt_obj, gt_frag,
-                            gt_loc, gt_weight, scales)
+      ctx.save_for_backward(features, w_obj, w_frag, w_loc, *(logits[k] for k in HEADS),
+                            gt_obj, gt_frag, gt_loc, gt_weight, scales)
       ctx.ignore_label = ignore_label
       ctx.shapes = tuple(v.shape for v in variables)
       ctx.mark_non_differentiable(bad)
@@ -508,8 +520,7 @@ def _features_losses_function():
       from epos_amd import heads_train
       (features, w_obj, w_frag, w_loc, obj, frag, loc, gt_obj, gt_frag, gt_loc, gt_weight,
        scales) = ctx.saved_tensors
-      logits = {W.PRED_OBJ_CONF: obj, W.PRED_FRAG_CONF: frag, W.PRED_FRAG_LOC: loc}
-      gt = dict(zip(GT_KEYS, (gt_obj, gt_frag, gt_loc, gt_weight)))
+      logits, gt = _head_dicts(obj, frag, loc, gt_obj, gt_frag, gt_loc, gt_weight)
       up = grad_values.to(torch.float64)
       d_feat = None
       if ctx.needs_input_grad[0]:
@@ -522,7 +533,7 @@ def _features_losses_function():
       if any(need):
         raw = heads_train.heads_weight_grads(features, logits, gt, scales, upstream=up,
                                              ignore_label=ctx.ignore_label, need=need)
-        for k, head in enumerate(heads_train.HEADS):
+        for k, head in enumerate(HEADS):
           if need[k]:
             grads[2 * k] = raw[head][0].view(ctx.shapes[2 * k])
             grads[2 * k + 1] = raw[head][1].view(ctx.shapes[2 * k + 1])
@@ -552,9 +563,7 @@ def differentiable_losses_from_features(features, head_weights, gt, weights=(1.0
     raise EposError('the losses need a HIP device (there is no CPU fallback)')
   if reduction not in REDUCTIONS:
     raise ValueError("reduction must be 'mean' or 'pooled', got %r" % (reduction,))
-  if features.dtype != torch.float32:
-    raise TypeError('features must be torch.float32, got %s (a bf16 decoder_out is not '
-                    'supported: run the net with precision=\'fp32\')' % features.dtype)
+  _need_fp32(features)
   for name in HEAD_VARIABLES:
     if name not in head_weights:
       raise KeyError('head_weights lack %r' % name)

@@ -12,6 +12,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 from tests.helpers import loss_cases, pack_cases   # noqa: E402
+from tests.helpers.loss_device import KEYS as HEADS, gt_tensors   # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -119,7 +120,6 @@ def test_refusals_are_the_host_packers_and_all_or_nothing(lib, what, where):
 
 # --------------------------------------------------------------------- net ---
 H, W, O, F, B = 96, 128, 3, 64, 2
-HEADS = ('pred_obj_conf', 'pred_frag_conf', 'pred_frag_loc')
 
 
 def six(ckpt):
@@ -261,11 +261,7 @@ def test_refusal_through_the_net_and_argument_checks(ckpts, images, net_upd):
 
 # -------------------------------------------------------------- train_step ---
 def gt_fields(h, w, seed):
-  c = loss_cases.make_case(B, h * w, O, F, seed=seed)
-  return {'obj_label': torch.from_numpy(c['gt_obj']).cuda().view(B, h, w),
-          'frag_label': torch.from_numpy(c['gt_frag']).cuda().view(B, h, w),
-          'frag_loc': torch.from_numpy(c['gt_loc']).cuda().view(B, h, w, 3),
-          'frag_weight': torch.from_numpy(c['gt_weight']).cuda().view(B, h, w)}
+  return gt_tensors(loss_cases.make_case(B, h * w, O, F, seed=seed), h, w)
 
 
 def test_train_step_equals_its_parts(ckpts, images, net_a):

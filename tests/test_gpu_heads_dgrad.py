@@ -5,7 +5,6 @@ inputs (pinned by test_gpu_loss_grad.py), fed to tests/helpers/heads_dgrad_ref.p
 comparison is about the fp64 sum over a pixel's active columns only, to heads_dgrad_ref.bound.
 dX is pre-filled with a sentinel: every element must be written, zeros as +0.0 bytes, and the
 padding columns untouched."""
-import ctypes
 import os
 import sys
 
@@ -17,30 +16,15 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 from tests.helpers import (heads_dgrad_ref as ref, heads_wgrad_ref, loss_cases,      # noqa: E402
-                           loss_grad_ref, loss_ref)
+                           loss_device, loss_grad_ref)
+from tests.helpers.loss_device import (IGNORE, KEYS, MEAN, NET_B, NET_F, NET_H,   # noqa: E402,F401
+                                       NET_O, NET_W, POOLED, SENTINEL, UPSTREAM, WEIGHTS, _lib,
+                                       _p, _stream, gt_tensors, net_logits, ref_counts,
+                                       small_net, tensors)
 
 pytestmark = pytest.mark.gpu
 
-IGNORE = loss_cases.IGNORE
-SENTINEL = 0x7FA55A5A                      # a NaN no kernel produces
-WEIGHTS = (0.7, 1.3, 100.0)
-UPSTREAM = [0.3, -1.0, 2.0, 0.5]
-MEAN, POOLED = 0, 1
 INVALID = -1                               # EPOS_E_INVALID
-KEYS = ('pred_obj_conf', 'pred_frag_conf', 'pred_frag_loc')
-
-
-def _p(t):
-  return ctypes.c_void_p(t.data_ptr()) if t is not None else None
-
-
-def _stream():
-  return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _lib():
-  from epos_amd import _lib as binding
-  return binding.load()
 
 
 def _dev(a, dtype=torch.float32):
@@ -58,10 +42,6 @@ def head_matrices(O, F, K, seed):
   """The three weight matrices in the checkpoint layout, f32 [K, N]."""
   rng = np.random.RandomState(seed)
   return [(0.5 * rng.randn(K, n)).astype(np.float32) for n in (O + 1, O * F, O * F * 3)]
-
-
-def ref_counts(c, ignore=IGNORE):
-  return loss_cases.ref_terms(loss_ref, c, 64, ignore)[1]
 
 
 class Device(object):
@@ -89,16 +69,7 @@ class Device(object):
     self._ref = None
 
   def logit_grads(self):
-    lib = _lib()
-    B, P, O, F = self.B, self.P, self.O, self.F
-    d = [torch.empty(B * P * n, dtype=torch.float32, device='cuda')
-         for n in (O + 1, O * F, O * F * 3)]
-    rc = lib.epos_loss_grads(_p(self.obj), self.ld_obj, _p(self.frag), _p(self.loc),
-                             _p(self.g_obj), _p(self.g_frag), _p(self.g_loc), _p(self.g_w), B, P,
-                             O, F, self.ignore, _p(self.sc), _p(self.up), _p(d[0]), O + 1,
-                             _p(d[1]), _p(d[2]), _stream())
-    assert rc == 0, lib.epos_last_error()
-    return d
+    return loss_device.logit_grads(self)
 
   def reference(self):
     """(sums, abs_sums, n_active) of heads_dgrad_ref.dgrad on the device's own d, computed once."""
@@ -345,6 +316,38 @@ def test_upstream():
   assert bits.tobytes() != none.tobytes()
 
 
+@pytest.mark.parametrize('O,F', [(2, 3), (3, 5)])
+def test_identity_weights_give_the_logit_gradients_themselves(O, F):
+  # K = N = O+1 + 4*O*F and the three weight matrices the row blocks of the N x N identity:
+  # dX[p, k] has exactly one non-zero term, so dX is [d_obj | d_frag | d_loc] of epos_loss_grads
+  # on the same inputs, element for element (as fp32 values: a sum that starts at +0.0 turns a
+  # -0.0 into +0.0). That holds only while both kernels round an element with the same
+  # function. N = 27: one k per lane; N = 64: the 16-byte path. P = 19: one full share of 16
+  # pixels and a tail of three.
+  B, P, N = 2, 19, O + 1 + 4 * O * F
+
+  def edit(c):
+    fg = np.nonzero((c['gt_obj'][1] >= 1) & (c['gt_obj'][1] <= O))[0]
+    c['gt_obj'][1, fg[0]] = O + 1                          # two bad pixels
+    c['gt_weight'][1, fg[1]] = 0.0
+
+  def edit_w(Ws):
+    r0 = 0
+    for W in Ws:
+      W[:] = np.eye(N, dtype=np.float32)[:, r0:r0 + W.shape[1]]
+      r0 += W.shape[1]
+  dev = make(B, P, O, F, N, seed=60 + F, edit=edit, edit_w=edit_w)
+  cls = heads_wgrad_ref.classes(dev.c, IGNORE)[0]
+  assert (cls == 0).any() and (cls > 0).any()              # background, foreground,
+  assert (dev.c['gt_obj'] == IGNORE).any()                 # ignored
+  assert ((cls < 0) & (dev.c['gt_obj'].reshape(-1) != IGNORE)).sum() == 2      # and bad pixels
+  got = dev.run().view(np.float32)
+  d = np.concatenate([t.cpu().numpy().reshape(B * P, -1) for t in dev.logit_grads()], axis=1)
+  assert d.shape == got.shape == (B * P, N)
+  assert np.isfinite(d).all() and d[cls >= 0].any(axis=1).all() and not d[cls < 0].any()
+  assert (got == d).all(), np.argwhere(got != d)[:5]
+
+
 def test_refusals_leave_dx_untouched():
   dev = make(2, 30, 3, 5, 8, seed=46)
   O, F, K = dev.O, dev.F, dev.K
@@ -394,23 +397,6 @@ def test_refusals_leave_dx_untouched():
 
 
 # ---------------------------------------------------------------- through Python ---
-def gt_tensors(c, h, w):
-  B = c['gt_obj'].shape[0]
-  return {'obj_label': torch.from_numpy(c['gt_obj']).cuda().view(B, h, w),
-          'frag_label': torch.from_numpy(c['gt_frag']).cuda().view(B, h, w),
-          'frag_loc': torch.from_numpy(c['gt_loc']).cuda().view(B, h, w, 3),
-          'frag_weight': torch.from_numpy(c['gt_weight']).cuda().view(B, h, w)}
-
-
-def tensors(c, h, w):
-  B = c['gt_obj'].shape[0]
-  O, F = c['frag_logits'].shape[2:4]
-  logits = {'pred_obj_conf': torch.from_numpy(c['obj_logits']).cuda().view(B, h, w, O + 1),
-            'pred_frag_conf': torch.from_numpy(c['frag_logits']).cuda().view(B, h, w, O, F),
-            'pred_frag_loc': torch.from_numpy(c['frag_loc']).cuda().view(B, h, w, O, F, 3)}
-  return logits, gt_tensors(c, h, w)
-
-
 def variables(Ws, seed=0, device='cuda'):
   """{variable name: tensor} of the six logits variables in the checkpoint layout."""
   rng = np.random.RandomState(seed)
@@ -537,28 +523,6 @@ def test_differentiable_losses_from_features():
   assert abs(got[0, p, k] - fd) <= 1e-4 * np.abs(auto).max()
 
 
-NET_H, NET_W, NET_O, NET_F, NET_B = 96, 128, 3, 8, 2
-
-
-@pytest.fixture(scope='module')
-def small_net():
-  """xception_65 at a 128 x 96 crop (the net of test_gpu_heads_wgrad.py), 3 objects x 8
-  fragments, after one forward_logits; with labels of a seeded case on its 24 x 32 heads."""
-  from epos_amd import model, synthetic, weights
-  ckpt = weights.random_init('xception_65', num_objs=NET_O, num_frags=NET_F, seed=5,
-                             randomize_bn=True)
-  mo = model.ModelOptions(model.get_outputs_to_num_channels(NET_O, NET_F),
-                          crop_size=(NET_W, NET_H))
-  net = model.get_net(ckpt, NET_B, NET_H, NET_W, NET_O, NET_F, mo, 'cuda:0')
-  imgs = np.stack([synthetic.image(i, NET_H, NET_W) for i in range(NET_B)]).astype(np.float32)
-  net.forward_logits(imgs)
-  torch.cuda.synchronize()
-  h, w = net.out_h, net.out_w
-  c = loss_cases.make_case(NET_B, h * w, NET_O, NET_F, seed=33)
-  yield net, ckpt, mo, c, gt_tensors(c, h, w)
-  model._NETS.clear()
-
-
 def test_net_feature_grad_on_a_real_net(small_net):
   from epos_amd import heads_train, loss, model, synthetic
   net, ckpt, mo, c, gt = small_net
@@ -568,9 +532,7 @@ def test_net_feature_grad_on_a_real_net(small_net):
   assert values.shape == (4,) and values.dtype == torch.float64 and bad.tolist() == [0] * B
   assert dX.dtype == torch.float32 and tuple(dX.shape) == (B * h * w, K)
   # the same as the three calls by hand
-  logits = {'pred_obj_conf': net.logits['pred_obj_conf'],
-            'pred_frag_conf': net.logits['pred_frag_conf'].view(B, h, w, O, F),
-            'pred_frag_loc': net.logits['pred_frag_loc'].view(B, h, w, O, F, 3)}
+  logits = net_logits(net)
   sums, counts, _ = loss.loss_terms(logits, gt)
   values2, scales = loss.loss_values(sums, counts, WEIGHTS, 'pooled')
   assert torch.equal(values, values2)

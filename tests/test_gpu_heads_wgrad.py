@@ -4,7 +4,6 @@ the device's own epos_loss_grads output on the same inputs (pinned by test_gpu_l
 fed to tests/helpers/heads_wgrad_ref.py: the comparison is about the fp64 summation only, to
 heads_wgrad_ref.bound. Outputs are pre-filled with a sentinel: every element must be written,
 zeros as +0.0 bytes, and a skipped output untouched."""
-import ctypes
 import itertools
 import os
 import sys
@@ -16,46 +15,16 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-from tests.helpers import heads_wgrad_ref as ref, loss_cases, loss_grad_ref, loss_ref  # noqa: E402
+from tests.helpers import heads_wgrad_ref as ref, loss_cases, loss_grad_ref      # noqa: E402
+from tests.helpers import loss_device                                            # noqa: E402
+from tests.helpers.loss_device import (IGNORE, KEYS, MEAN, NET_B, NET_F, NET_O,  # noqa: E402,F401
+                                       POOLED, SENTINEL, UPSTREAM, WEIGHTS, _lib, _off, _out, _p,
+                                       _stream, net_logits, ref_counts, small_net, tensors)
 
 pytestmark = pytest.mark.gpu
 
-IGNORE = loss_cases.IGNORE
-SENTINEL = 0x7FA55A5A                      # a NaN no kernel produces
-WEIGHTS = (0.7, 1.3, 100.0)
-UPSTREAM = [0.3, -1.0, 2.0, 0.5]
-MEAN, POOLED = 0, 1
 HEADS = ref.HEADS
 OUTS = [(h, j) for h in HEADS for j in (0, 1)]          # dW_obj, db_obj, dW_frag, ...
-
-
-def _p(t):
-  return ctypes.c_void_p(t.data_ptr()) if t is not None else None
-
-
-def _stream():
-  return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _lib():
-  from epos_amd import _lib as binding
-  return binding.load()
-
-
-def _off(a, offset, dtype=torch.float32):
-  """The array on the device, `offset` elements behind a 16-byte boundary."""
-  a = np.ascontiguousarray(a).reshape(-1)
-  flat = torch.empty(a.size + offset, dtype=dtype, device='cuda')
-  assert flat.data_ptr() % 16 == 0
-  view = flat[offset:]
-  view.copy_(torch.from_numpy(a))
-  return view
-
-
-def _out(numel, offset):
-  flat = torch.full((numel + offset,), SENTINEL, dtype=torch.int32, device='cuda')
-  assert flat.data_ptr() % 16 == 0
-  return flat[offset:].view(torch.float32)
 
 
 def features(n_pix, K, seed, lda=None):
@@ -69,10 +38,6 @@ def features(n_pix, K, seed, lda=None):
   return A, padded
 
 
-def ref_counts(c, ignore=IGNORE):
-  return loss_cases.ref_terms(loss_ref, c, 64, ignore)[1]
-
-
 class Device(object):
   """A host case on the device, with the logit gradients epos_loss_grads writes for it."""
 
@@ -80,7 +45,7 @@ class Device(object):
     self.c, self.K, self.ignore = c, K, ignore
     self.B, self.P, O1 = c['obj_logits'].shape
     self.O, self.F = c['frag_logits'].shape[2:4]
-    self.lda = A_padded.shape[1]
+    self.lda, self.ld_obj = A_padded.shape[1], O1
     self.A = _off(A_padded, in_off[0])
     self.obj = _off(c['obj_logits'], in_off[1])
     self.frag = _off(c['frag_logits'], in_off[2])
@@ -96,16 +61,7 @@ class Device(object):
     self._ref = None
 
   def logit_grads(self):
-    lib = _lib()
-    B, P, O, F = self.B, self.P, self.O, self.F
-    d = [torch.empty(B * P * n, dtype=torch.float32, device='cuda')
-         for n in (O + 1, O * F, O * F * 3)]
-    rc = lib.epos_loss_grads(_p(self.obj), O + 1, _p(self.frag), _p(self.loc), _p(self.g_obj),
-                             _p(self.g_frag), _p(self.g_loc), _p(self.g_w), B, P, O, F,
-                             self.ignore, _p(self.sc), _p(self.up), _p(d[0]), O + 1, _p(d[1]),
-                             _p(d[2]), _stream())
-    assert rc == 0, lib.epos_last_error()
-    return d
+    return loss_device.logit_grads(self)
 
   def reference(self):
     """(sums, abs_sums, n_terms) of heads_wgrad_ref.wgrads on the device's own d."""
@@ -394,6 +350,30 @@ def test_against_the_dense_route_on_the_device():
       assert ok, (h, j, w)
 
 
+@pytest.mark.parametrize('O,F,K,fg', [(3, 8, 24, False), (3, 8, 24, True), (2, 65, 5, True)])
+def test_one_pixel_gives_the_logit_gradients_themselves(O, F, K, fg):
+  # B = P = 1: every sum has a single term, and with features that are powers of two,
+  # A[k] = 2^(k % 5 - 2), that term is exact: dW[k, col] == A[k] * d[col] and db[col] == d[col]
+  # for d = epos_loss_grads' output on the same inputs, for all six outputs (as fp32 values).
+  # That holds only while both round an element with the same function. A background pixel, a
+  # foreground pixel, and one at F > 64: four feature indices per slice, fragment 64.
+  def edit(c, A):
+    A[0, :K] = 2.0 ** (np.arange(K) % 5 - 2)
+    if fg:
+      c['gt_obj'][0, 0], c['gt_frag'][0, 0], c['gt_weight'][0, 0] = O, F - 1, 0.75
+    else:
+      c['gt_obj'][0, 0], c['gt_frag'][0, 0], c['gt_weight'][0, 0] = 0, -1, 0.0
+  dev = make(1, 1, O, F, K, seed=70 + F, lda=K + 3, edit=edit)
+  assert ref.classes(dev.c, IGNORE)[0].tolist() == [O if fg else 0]
+  got = dev.run()
+  A = dev.A.cpu().numpy().reshape(1, dev.lda)[0, :K]
+  for h, t in zip(HEADS, dev.logit_grads()):
+    d = t.cpu().numpy()
+    assert np.isfinite(d).all() and d.any() == (fg or h == 'obj')
+    dW, db = got[(h, 0)].view(np.float32), got[(h, 1)].view(np.float32)
+    assert (dW == A[:, None] * d[None, :]).all() and (db == d).all(), h
+
+
 # ---------------------------------------------------------------- momentum step ---
 HYPER = [(0.01, 0.9, 4e-5, 1.0), (0.5, 0.0, 0.0, 1.0), (0.003, 0.9, 0.0, 2.0),
          (0.1, 0.5, 0.01, 2.0)]
@@ -421,26 +401,6 @@ def test_momentum_step_bytes(n):
 
 
 # ---------------------------------------------------------------- through Python ---
-def tensors(c, h, w):
-  B = c['gt_obj'].shape[0]
-  O, F = c['frag_logits'].shape[2:4]
-  logits = {'pred_obj_conf': torch.from_numpy(c['obj_logits']).cuda().view(B, h, w, O + 1),
-            'pred_frag_conf': torch.from_numpy(c['frag_logits']).cuda().view(B, h, w, O, F),
-            'pred_frag_loc': torch.from_numpy(c['frag_loc']).cuda().view(B, h, w, O, F, 3)}
-  return logits, gt_tensors(c, h, w)
-
-
-def gt_tensors(c, h, w):
-  B = c['gt_obj'].shape[0]
-  return {'obj_label': torch.from_numpy(c['gt_obj']).cuda().view(B, h, w),
-          'frag_label': torch.from_numpy(c['gt_frag']).cuda().view(B, h, w),
-          'frag_loc': torch.from_numpy(c['gt_loc']).cuda().view(B, h, w, 3),
-          'frag_weight': torch.from_numpy(c['gt_weight']).cuda().view(B, h, w)}
-
-
-KEYS = ('pred_obj_conf', 'pred_frag_conf', 'pred_frag_loc')
-
-
 def test_heads_weight_grads_entry():
   from epos_amd import heads_train, loss
   B, h, w, O, F, K = 2, 9, 11, 3, 8, 24
@@ -477,38 +437,9 @@ def test_heads_weight_grads_entry():
   assert loss.REDUCTIONS == {'mean': 0, 'pooled': 1}
 
 
-NET_H, NET_W, NET_O, NET_F, NET_B = 96, 128, 3, 8, 2
-
-
-@pytest.fixture(scope='module')
-def small_net():
-  """xception_65 at a 128 x 96 crop (the net of test_gpu_loss_net.py), 3 objects x 8
-  fragments, after one forward_logits; with labels of a seeded case on its 24 x 32 heads."""
-  from epos_amd import model, synthetic, weights
-  ckpt = weights.random_init('xception_65', num_objs=NET_O, num_frags=NET_F, seed=5,
-                             randomize_bn=True)
-  mo = model.ModelOptions(model.get_outputs_to_num_channels(NET_O, NET_F),
-                          crop_size=(NET_W, NET_H))
-  net = model.get_net(ckpt, NET_B, NET_H, NET_W, NET_O, NET_F, mo, 'cuda:0')
-  imgs = np.stack([synthetic.image(i, NET_H, NET_W) for i in range(NET_B)]).astype(np.float32)
-  net.forward_logits(imgs)
-  torch.cuda.synchronize()
-  h, w = net.out_h, net.out_w
-  c = loss_cases.make_case(NET_B, h * w, NET_O, NET_F, seed=33)
-  yield net, ckpt, c, gt_tensors(c, h, w)
-  model._NETS.clear()
-
-
-def net_logits(net):
-  B, h, w = NET_B, net.out_h, net.out_w
-  return {'pred_obj_conf': net.logits['pred_obj_conf'],
-          'pred_frag_conf': net.logits['pred_frag_conf'].view(B, h, w, NET_O, NET_F),
-          'pred_frag_loc': net.logits['pred_frag_loc'].view(B, h, w, NET_O, NET_F, 3)}
-
-
 def test_net_head_grads_on_a_real_net(small_net):
   from epos_amd import heads_train, loss
-  net, ckpt, c, gt = small_net
+  net, ckpt, _, c, gt = small_net
   B, h, w, O, F = NET_B, net.out_h, net.out_w, NET_O, NET_F
   K = int(net.decoder_out.shape[-1])
   values, bad, grads = heads_train.net_head_grads(net, gt, WEIGHTS, 'pooled')
@@ -566,7 +497,7 @@ def test_descent_and_checkpoint(small_net, tmp_path):
   # 1/(2L) on the weights and, with the biases' multiplier 2, 1/L on the biases stays below 2/L,
   # so it must decrease the total strictly while the gradient is not zero.
   from epos_amd import heads_train, loss, tf_checkpoint
-  net, ckpt, c, gt = small_net
+  net, ckpt, _, c, gt = small_net
   B, h, w, O, F = NET_B, net.out_h, net.out_w, NET_O, NET_F
   P = h * w
   A = net.decoder_out.reshape(B * P, -1).clone()

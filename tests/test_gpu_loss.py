@@ -2,7 +2,6 @@
 counts, bad-pixel counts and localisation sums exactly, cross-entropy sums to the derived
 bound; head views, extreme logits, the Huber knee, the bad-pixel rules, determinism, refusals,
 and LossEval over the launcher."""
-import ctypes
 import os
 import sys
 
@@ -14,33 +13,11 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 from tests.helpers import loss_cases, loss_ref      # noqa: E402
+from tests.helpers.loss_device import IGNORE, _lib, _off, _p, _stream      # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-IGNORE = loss_cases.IGNORE
 SENTINEL = -7
-
-
-def _p(t):
-  return ctypes.c_void_p(t.data_ptr()) if t is not None else None
-
-
-def _stream():
-  return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _lib():
-  from epos_amd import _lib as binding
-  return binding.load()
-
-
-def _off(a, offset):
-  """The array on the device, `offset` floats behind a 16-byte boundary."""
-  flat = torch.empty(a.size + offset, dtype=torch.float32, device='cuda')
-  assert flat.data_ptr() % 16 == 0
-  view = flat[offset:]
-  view.copy_(torch.from_numpy(np.ascontiguousarray(a).reshape(-1)))
-  return view
 
 
 def run_terms(c, ignore=IGNORE, ld_obj=None, offsets=(0, 0, 0), outputs=None):

@@ -4,7 +4,6 @@ gradients to the derived bound; every launch regime, views and alignment, null o
 extreme and non-finite logits, the Huber knee, the pixel rules, determinism and position; the
 reduction of the tables against loss.summarize; differentiable_losses through autograd, a
 descent on the logits, and a captured graph."""
-import ctypes
 import itertools
 import os
 import sys
@@ -16,44 +15,14 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-from tests.helpers import loss_cases, loss_grad_ref, loss_ref      # noqa: E402
+from tests.helpers import loss_cases, loss_grad_ref, loss_ref                     # noqa: E402
+from tests.helpers.loss_device import (IGNORE, KEYS, MEAN, POOLED, UPSTREAM,      # noqa: E402
+                                       WEIGHTS, _lib, _off, _out, _p, _stream, ref_counts,
+                                       tensors)
 
 pytestmark = pytest.mark.gpu
 
-IGNORE = loss_cases.IGNORE
 SENTINEL = 0x7fc12345                     # the bits of a NaN no kernel produces
-WEIGHTS = (0.7, 1.3, 100.0)
-UPSTREAM = [0.3, -1.0, 2.0, 0.5]
-MEAN, POOLED = 0, 1
-
-
-def _p(t):
-  return ctypes.c_void_p(t.data_ptr()) if t is not None else None
-
-
-def _stream():
-  return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _lib():
-  from epos_amd import _lib as binding
-  return binding.load()
-
-
-def _off(a, offset):
-  """The array on the device, `offset` floats behind a 16-byte boundary."""
-  flat = torch.empty(a.size + offset, dtype=torch.float32, device='cuda')
-  assert flat.data_ptr() % 16 == 0
-  view = flat[offset:]
-  view.copy_(torch.from_numpy(np.ascontiguousarray(a).reshape(-1)))
-  return view
-
-
-def _out(numel, offset):
-  """A sentinel-filled output of `numel` floats, `offset` floats behind a 16-byte boundary."""
-  flat = torch.full((numel + offset,), SENTINEL, dtype=torch.int32, device='cuda')
-  assert flat.data_ptr() % 16 == 0
-  return flat[offset:].view(torch.float32)
 
 
 def share_of(P, O, F):
@@ -64,10 +33,6 @@ def share_of(P, O, F):
 
 def take(c, images):
   return {k: np.ascontiguousarray(v[list(images)]) for k, v in c.items()}
-
-
-def ref_counts(c, ignore=IGNORE):
-  return loss_cases.ref_terms(loss_ref, c, 64, ignore)[1]
 
 
 def run_grads(c, scale, upstream=None, ignore=IGNORE, ld_obj=None, ld_dobj=None,
@@ -91,8 +56,8 @@ def run_grads(c, scale, upstream=None, ignore=IGNORE, ld_obj=None, ld_dobj=None,
   g_w = torch.from_numpy(np.ascontiguousarray(c['gt_weight'], np.float32)).cuda()
   sc = torch.from_numpy(np.ascontiguousarray(scale, np.float64)).cuda()
   up = None if upstream is None else torch.tensor(upstream, dtype=torch.float64, device='cuda')
-  bufs = [_out(B * P * ldd, out_off[0]), _out(B * P * O * F, out_off[1]),
-          _out(B * P * O * F * 3, out_off[2])]
+  bufs = [_out(B * P * ldd, out_off[0], SENTINEL), _out(B * P * O * F, out_off[1], SENTINEL),
+          _out(B * P * O * F * 3, out_off[2], SENTINEL)]
   ptrs = [_p(b) if n else None for b, n in zip(bufs, need)]
   rc = lib.epos_loss_grads(_p(obj), ld, _p(frag), _p(loc), _p(g_obj), _p(g_frag), _p(g_loc),
                            _p(g_w), B, P, O, F, ignore, _p(sc), _p(up), ptrs[0], ldd, ptrs[1],
@@ -426,22 +391,6 @@ def test_determinism_and_position(O, F):
 
 
 # ---------------------------------------------------------------- through Python ---
-def tensors(c, h, w):
-  B = c['gt_obj'].shape[0]
-  O, F = c['frag_logits'].shape[2:4]
-  logits = {'pred_obj_conf': torch.from_numpy(c['obj_logits']).cuda().view(B, h, w, O + 1),
-            'pred_frag_conf': torch.from_numpy(c['frag_logits']).cuda().view(B, h, w, O, F),
-            'pred_frag_loc': torch.from_numpy(c['frag_loc']).cuda().view(B, h, w, O, F, 3)}
-  gt = {'obj_label': torch.from_numpy(c['gt_obj']).cuda().view(B, h, w),
-        'frag_label': torch.from_numpy(c['gt_frag']).cuda().view(B, h, w),
-        'frag_loc': torch.from_numpy(c['gt_loc']).cuda().view(B, h, w, 3),
-        'frag_weight': torch.from_numpy(c['gt_weight']).cuda().view(B, h, w)}
-  return logits, gt
-
-
-KEYS = ('pred_obj_conf', 'pred_frag_conf', 'pred_frag_loc')
-
-
 @pytest.mark.parametrize('reduction', ['mean', 'pooled'])
 def test_differentiable_losses(reduction):
   from epos_amd import loss
