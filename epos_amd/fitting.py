@@ -56,10 +56,11 @@ def find6DPoses(x1y1, x2y2z2, K, threshold=4.0, neighborhood_ball_radius=20.0,
                 proposal_engine_conf=1.0, min_coverage=0.5,
                 min_triangle_area=0.0, min_point_number=6, max_model_number=1,
                 max_model_number_for_optimization=5, use_prosac=False, log=False,
-                seed=0, max_poses=16, gc_sweeps=None, pearl_iters=None):
+                seed=0, max_poses=16, gc_sweeps=None, pearl_iters=None, lo_iters=8):
   """Same contract as pyprogressivex.find6DPoses (infer.py:470-488). Extra
   keyword ``seed`` selects the (counter-based) random stream; ``max_poses`` caps
-  the number of instances when max_model_number == -1."""
+  the number of instances when max_model_number == -1; ``lo_iters``, ``gc_sweeps``
+  and ``pearl_iters`` are the build's own knobs (see fit_params)."""
   del log
   xy = np.ascontiguousarray(x1y1, np.float64)
   xyz = np.ascontiguousarray(x2y2z2, np.float64)
@@ -72,8 +73,8 @@ def find6DPoses(x1y1, x2y2z2, K, threshold=4.0, neighborhood_ball_radius=20.0,
                  scaling_from_millimeters, max_tanimoto_similarity, max_iters,
                  conf, proposal_engine_conf, min_coverage, min_triangle_area,
                  min_point_number, max_model_number,
-                 max_model_number_for_optimization, use_prosac, gc_sweeps=gc_sweeps,
-                 pearl_iters=pearl_iters)
+                 max_model_number_for_optimization, use_prosac, lo_iters=lo_iters,
+                 gc_sweeps=gc_sweeps, pearl_iters=pearl_iters)
   max_k = max_poses if max_model_number < 0 else max(1, min(max_model_number,
                                                             max_poses))
   poses = np.zeros((max_k, 12), np.float64)

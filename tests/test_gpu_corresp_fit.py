@@ -283,8 +283,10 @@ def test_two_close_instances_of_a_symmetric_object():
       mine = lab[(src == j) & (kind < 2)]
       assert (mine >= 0).mean() > 0.4
   # the joint refinement (PEARL's role) off / on / restricted by
-  # max_model_number_for_optimization: each identical to the oracle (the greedy result
-  # of this scene is already a fixed point of it or within its energy check)
+  # max_model_number_for_optimization: each identical to the oracle. (With TWO instances the
+  # greedy result of this scene is a fixed point of it; with four it moves poses and labels: cases
+  # pearl_iters / max_model_number_for_optimization / joint_* of helpers/fit_decision_cases.py,
+  # compared on the device by test_gpu_fit_decisions.py)
   off = _same_as_oracle(xy, xyz, 5, max_k=5, max_model_number=2, pearl_iters=0)
   on = _same_as_oracle(xy, xyz, 5, max_k=5, max_model_number=2, pearl_iters=2)
   capped = _same_as_oracle(xy, xyz, 5, max_k=5, max_model_number=2,
