@@ -202,6 +202,15 @@ class WeightPackArgs(ctypes.Structure):
               ('K', ctypes.c_int32), ('N', ctypes.c_int32)]
 
 
+class PointwiseWgradArgs(ctypes.Structure):
+  _fields_ = [('A', vp), ('lda', ctypes.c_int64), ('G', vp), ('ldg', ctypes.c_int64),
+              ('M', ctypes.c_int64), ('K', ctypes.c_int32), ('N', ctypes.c_int32),
+              ('a_presplit', ctypes.c_int32), ('reserved0', ctypes.c_int32),
+              ('a_amax', vp), ('a_amax2', vp),
+              ('a_gain', ctypes.c_float), ('a_bias', ctypes.c_float),
+              ('S', vp), ('g', vp), ('workspace', vp)]
+
+
 class FitParams(ctypes.Structure):
   _fields_ = [
       ('threshold', ctypes.c_double),
@@ -410,6 +419,14 @@ SYMBOLS = {
         vp, ctypes.c_int64, vp, vp, vp, vp, vp, vp, ctypes.c_int, ctypes.c_int64, ctypes.c_int,
         ctypes.c_int, ctypes.c_int, vp, vp, vp, vp, vp, ctypes.c_int64, ctypes.c_int, vp,
         ctypes.c_int64, vp, ctypes.c_int64, vp]),
+    # weight and batch-norm gradients of a 1x1 conv layer
+    'epos_pointwise_wgrad_workspace_bytes': (ctypes.c_int64, [
+        ctypes.c_int64, ctypes.c_int, ctypes.c_int]),
+    'epos_pointwise_wgrad_range_rows': (ctypes.c_int64, [
+        ctypes.c_int64, ctypes.c_int, ctypes.c_int]),
+    'epos_pointwise_wgrad_f32': (ctypes.c_int, [ctypes.POINTER(PointwiseWgradArgs), vp]),
+    'epos_pointwise_wgrad_close_f32': (ctypes.c_int, [
+        vp, vp, vp, ctypes.c_int, ctypes.c_int, vp, vp, vp, ctypes.c_double, vp, vp, vp, vp]),
     # weight update: the packers on the device
     'epos_pack_weights_device_f32': (ctypes.c_int, [
         ctypes.POINTER(WeightPackArgs), ctypes.c_int, vp, vp]),

@@ -20,11 +20,13 @@ gradients"): the next piece of a trainer after loss.differentiable_losses.
                       csrc/weight_pack.hip: the updated weights reach the built net, its
                       captured graphs included, without a round trip through the host).
 
-The loop itself, its checkpoints and its logging are train_heads.py. Out of scope here:
-backpropagation from decoder_conv1_pointwise down (heads_input_grad is where it would start;
-train_step keeps everything below the logits frozen), batch-norm statistics and gradients,
-bf16 mode, multi-scale nets and more than one device. Augmentation is epos_amd/augment.py;
-train_step applies it between the upload and the forward pass.
+The loop itself, its checkpoints and its logging are train_heads.py. train_step keeps
+everything below the logits frozen; the layer below them, decoder_conv1_pointwise, is trained by
+epos_amd/decoder_train.py (its weight and batch-norm gradients from heads_input_grad's output,
+DecoderOptimizer, train_step_decoder). Not built: backpropagation from decoder_conv1_depthwise
+down, which starts with the input gradient G W^T of decoder_conv1_pointwise; batch-norm
+statistics, bf16 mode, multi-scale nets and more than one device. Augmentation is
+epos_amd/augment.py; train_step applies it between the upload and the forward pass.
 
 Pinned to tests/helpers/heads_wgrad_ref.py and, through loss_grad_ref.py, to torch's fp64
 autograd; parity with TensorFlow's numbers is unpinned, as for the losses -- that holds for

@@ -138,6 +138,7 @@ class EposNet(object):
     self._n_trunk_ops = 0        # the ops in front of the logits (sparse-head mode)
     self._obj_head_op, self._obj_head_flops = None, 0
     self._sparse_packs = None
+    self._layer_consts = {}      # trainable layer -> (moving_mean, moving_variance) on the device
     self._decoder_x = None
     self.mode = MODES[precision](self)
     self.act_dtype = self.mode.dtype
@@ -795,42 +796,165 @@ class EposNet(object):
     if self.lib is None:
       raise _lib.EposError('set_head_weights needs a HIP device (there is no CPU fallback)')
     layers = self._head_variables(variables)
-    O, F = self.num_objs, self.num_frags
-    if 3 + 2 * O > 256:
+    if 3 + 2 * self.num_objs > 256:
       raise NotImplementedError('set_head_weights: more than 126 objects')
     if not layers:
       return torch.zeros(0, dtype=torch.int32, device=self.dev)
+    with torch.cuda.device(self.dev):
+      probs, names, keep = self._head_pack_problems(layers)
+    return self._pack(probs, names, keep, check, 'set_head_weights', 'logits/')
+
+  def _head_pack_problems(self, layers):
+    """(problems, names, tensors to keep alive) of the device packer for logits layers as
+    _head_variables returns them: the dense packs in sorted order, then per fragment layer its
+    num_objs sparse packs."""
+    O, F = self.num_objs, self.num_frags
     sparse_n = {W.PRED_FRAG_CONF: (0, F), W.PRED_FRAG_LOC: (1, 3 * F)}
     if self._sparse_packs is None and any(l[0] in sparse_n for l in layers):
       self._build_sparse_packs()         # from self.ckpt, while it still describes the net
-    probs, names, dense = [], [], []
+    probs, names, dense, keep = [], [], [], []
+    for layer, w, b in layers:
+      w = torch.as_tensor(w, dtype=torch.float32).to(self.dev).reshape(256, -1)
+      b = torch.as_tensor(b, dtype=torch.float32).to(self.dev)
+      dense.append((layer, w, b))
+      keep += [w, b]
+      probs.append(self.mode.pack_problem(self.mode.head_packs[layer], w, b, 0, w.shape[1]))
+      names.append(layer)
+    for layer, w, b in dense:
+      if layer in sparse_n:
+        kind, n = sparse_n[layer]
+        for o in range(O):
+          probs.append(self.mode.pack_problem(self._sparse_packs[o][kind], w, b, o * n, n))
+          names.append('%s (sparse pack of object %d)' % (layer, o + 1))
+    return probs, names, keep
+
+  def _pack(self, probs, names, keep, check, what, prefix):
+    """One grouped call of the device packer on the current stream: all of probs or none.
+    Returns the status tensor; with check, reads it back and raises naming the refused."""
     with torch.cuda.device(self.dev):
-      for layer, w, b in layers:
-        w = torch.as_tensor(w, dtype=torch.float32).to(self.dev).reshape(256, -1)
-        b = torch.as_tensor(b, dtype=torch.float32).to(self.dev)
-        dense.append((layer, w, b))
-        probs.append(self.mode.pack_problem(self.mode.head_packs[layer], w, b, 0, w.shape[1]))
-        names.append(layer)
-      for layer, w, b in dense:
-        if layer in sparse_n:
-          kind, n = sparse_n[layer]
-          for o in range(O):
-            probs.append(self.mode.pack_problem(self._sparse_packs[o][kind], w, b, o * n, n))
-            names.append('%s (sparse pack of object %d)' % (layer, o + 1))
       status = torch.empty(len(probs), dtype=torch.int32, device=self.dev)
-      self.mode.pack_launch(probs, status, self._stream())
+      self.mode.pack_launch(probs, status, self._stream(), what)
     stream = torch.cuda.current_stream(self.dev)
-    for _, w, b in dense:
-      w.record_stream(stream)            # uploaded copies outlive the call
-      b.record_stream(stream)
+    for t in keep:
+      t.record_stream(stream)            # uploaded copies outlive the call
     if check:
       bad = [names[i] for i in torch.nonzero(status.cpu()).flatten().tolist()]
       if bad:
         raise _lib.EposError(
-            'set_head_weights: the fp16-pair packer refused logits/%s (a non-finite weight, or '
+            '%s: the fp16-pair packer refused %s%s (a non-finite weight, or '
             'a column whose scale leaves 2^+-100); nothing was written, the net still holds its '
-            'previous weights' % ', logits/'.join(bad))
+            'previous weights' % (what, prefix, (', ' + prefix).join(bad)))
     return status
+
+  # ------------------------------------------- the layer below the logits ---
+  def _need_fp32_plan(self, what):
+    if self.precision != 'fp32':
+      raise NotImplementedError('%s: precision=%r nets are not supported' % (
+          what, self.precision))
+    if self.lib is None:
+      raise _lib.EposError('%s needs a HIP device (there is no CPU fallback)' % what)
+
+  def pointwise_operand(self, name=W.DECODER_CONV1_POINTWISE):
+    """What the backward pass of a trainable 1x1 conv layer needs of the plan, as it was
+    recorded while the plan was built: {'a': the layer's input, the depthwise output buffer
+    [B,h,w,lda] the net keeps alive; 'lda', 'm', 'k', 'n'; 'presplit': whether that buffer holds
+    fp16 pairs (the default; EPOS_H2_PRESPLIT=0, EPOS_GEMM_H2=0 or fp16-pair weights the host
+    packer refused give fp32); 'a_h2': None for an fp32 A, else (slot words, second slot's words
+    or None, gain, bias), the very values the layer's PointwiseArgs carry; 'packs': the (plain,
+    bias, split, fp16-pair) weight tensors its launch points at; 'eps': the batch norm's}."""
+    self._need_fp32_plan('pointwise_operand')
+    if name not in self.mode.layer_operands:
+      raise ValueError('%r is not a trainable layer (%s)' % (
+          name, ', '.join(W.TRAINABLE_POINTWISE)))
+    a, lda, m, k, n, args, packs, ab = self.mode.layer_operands[name]
+    presplit = bool(args.a_presplit)
+    a_h2 = None
+    if presplit:
+      a_h2 = (self.mode.slot_words(ab[0]), self.mode.slot_words(ab[1]), float(args.a_gain),
+              float(args.a_bias))
+    return {'a': a, 'lda': lda, 'm': m, 'k': k, 'n': n, 'presplit': presplit, 'a_h2': a_h2,
+            'packs': packs, 'eps': HEAD_BN_EPS}
+
+  def layer_constants(self, name=W.DECODER_CONV1_POINTWISE):
+    """(moving_mean, moving_variance) of a trainable layer's batch norm on the device, f32 [N],
+    uploaded from the checkpoint once: training never changes them."""
+    if name not in self._layer_consts:
+      self._layer_consts[name] = tuple(
+          torch.from_numpy(np.ascontiguousarray(self.ckpt[name + '/BatchNorm/' + v],
+                                                np.float32)).to(self.dev)
+          for v in ('moving_mean', 'moving_variance'))
+    return self._layer_consts[name]
+
+  def _layer_variables(self, variables, name):
+    """set_layer_weights' argument check for the layer's three variables: (w f32 [K,N], gamma,
+    beta) on the device, or None when none of them is given."""
+    _, _, _, k, n, _, _, _ = self.mode.layer_operands[name]
+    keys = (name + '/weights', name + '/BatchNorm/gamma', name + '/BatchNorm/beta')
+    given = [key for key in keys if key in variables]
+    if not given:
+      return None
+    if len(given) != 3:
+      raise ValueError('%s: weights, BatchNorm/gamma and BatchNorm/beta are set together' % name)
+    out = []
+    for key, shapes in zip(keys, (((1, 1, k, n), (k, n)), ((n,),), ((n,),))):
+      v = variables[key]
+      if isinstance(v, torch.Tensor):
+        if v.dtype != torch.float32:
+          raise TypeError('%s must be torch.float32, got %s' % (key, v.dtype))
+        if v.device != self.dev:
+          raise ValueError('%s is on %s, the net on %s (numpy arrays are uploaded)' % (
+              key, v.device, self.dev))
+        if not v.is_contiguous():
+          raise ValueError('%s must be contiguous' % key)
+      else:
+        v = np.asarray(v)
+        if v.dtype.kind != 'f':
+          raise TypeError('%s must be a floating-point array, got %s' % (key, v.dtype))
+      if tuple(v.shape) not in shapes:
+        raise ValueError('%s must have shape %s, got %s' % (
+            key, ' or '.join(str(list(s)) for s in shapes), list(v.shape)))
+      out.append(torch.as_tensor(v, dtype=torch.float32).to(self.dev))
+    return out[0].reshape(k, n), out[1], out[2]
+
+  def set_layer_weights(self, variables, check=True):
+    """set_head_weights for decoder/decoder_conv1_pointwise, alone or together with logits
+    layers. variables: the layer's '<scope>/weights' [1,1,K,N] or [K,N], '<scope>/BatchNorm/gamma'
+    and '<scope>/BatchNorm/beta' [N] (the three together; decoder_train.DecoderOptimizer.params
+    as it is) and any of the logits variables set_head_weights takes; contiguous fp32 tensors on
+    the net's device, or numpy arrays. The moving statistics are the checkpoint's: inputs,
+    never changed.
+
+    The batch norm is folded on the device, bit for bit as weights.fold_bn and the plan's host
+    fold do (scale = gamma / sqrt(var + eps) and bias = beta - mean * scale in fp64, each
+    operation rounded once, both rounded to fp32; the matrix is weights * scale in fp32), and
+    the folded matrix and bias go through the device packer into the very tensors the layer's
+    launch points at, in ONE grouped call with the logits layers' packs: all or nothing, for
+    the layer and the logits layers together. Captured graphs see the new weights. Returns the
+    status tensor: set_head_weights' words for the logits layers given, then one for the layer.
+    check and ordering as for set_head_weights."""
+    self._need_fp32_plan('set_layer_weights')
+    name = W.DECODER_CONV1_POINTWISE
+    heads = {k: v for k, v in variables.items() if not k.startswith(name + '/')}
+    layers = self._head_variables(heads)
+    if 3 + 2 * self.num_objs + 1 > 256:
+      raise NotImplementedError('set_layer_weights: more than 126 objects')
+    layer = self._layer_variables(variables, name)
+    if not layers and layer is None:
+      return torch.zeros(0, dtype=torch.int32, device=self.dev)
+    with torch.cuda.device(self.dev):
+      probs, names, keep = self._head_pack_problems(layers) if layers else ([], [], [])
+      names = ['logits/' + n for n in names]
+      if layer is not None:
+        w, gamma, beta = layer
+        mean, var = self.layer_constants(name)
+        scale = gamma.double() / torch.sqrt(var.double() + HEAD_BN_EPS)
+        bias = (beta.double() - mean.double() * scale).float()
+        folded = (w * scale.float()[None, :]).contiguous()
+        probs.append(self.mode.pack_problem(self.mode.layer_operands[name][6], folded, bias, 0,
+                                            folded.shape[1]))
+        names.append(name)
+        keep += [folded, bias]
+    return self._pack(probs, names, keep, check, 'set_layer_weights', '')
 
   def set_images(self, images):
     """images: [B,H,W,3] in [0,255] (host numpy or device tensor), float32 -- or uint8 as the

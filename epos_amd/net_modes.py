@@ -104,6 +104,9 @@ class Fp32Mode(object):
     # logits layer -> the (wp, bp, ws, wh) tensors its launch arguments point at: where
     # EposNet.set_head_weights packs updated weights (references only; wh None = refused)
     self.head_packs = {}
+    # trainable layer below the logits -> what its backward pass and its weight update need:
+    # (A buffer, lda, M, K, N, the launch's PointwiseArgs, (wp, bp, ws, wh), A's bound or None)
+    self.layer_operands = {}
     self.pack_device = fn('epos_pack_weights_device_f32')
     self._last_pw = None       # (C, args, foldable): the last stand-alone 1x1 launch
     self._first_im2col = None  # (op name, args, capacity in words): the plan's first im2col
@@ -227,6 +230,9 @@ class Fp32Mode(object):
         a_amax2=self._slot_ptr(ab[1]) if h else None,
         a_gain=ab[2] if h else 0.0, a_bias=ab[3] if h else 0.0,
         a_presplit=int(presplit), c_amax=self._slot_ptr(cslot))
+    if name in W.TRAINABLE_POINTWISE:
+      assert a_off == 0 and sub == 1 and res is None and kpad == k, name
+      self.layer_operands[name] = (a, lda, m, k, n, args, (wp, bp, ws, wh), ab if h else None)
     # fp32 activations in and out, weights once (4 B each: what the layer IS; the
     # split kernel streams 6 B per weight), residual once
     nbytes = 4 * (m * k + k * n + m * n + (m * n if res is not None else 0))
@@ -377,10 +383,16 @@ class Fp32Mode(object):
                                h2=_ptr(wh) if wh is not None else None, bias_pad=_ptr(bp),
                                K=w.shape[-2], N=n)
 
-  def pack_launch(self, probs, status, stream):
+  def pack_launch(self, probs, status, stream, what='set_head_weights'):
     """One grouped epos_pack_weights_device_f32 call: all of probs or none of them."""
     arr = (_lib.WeightPackArgs * len(probs))(*probs)
-    _lib.check(self.pack_device(arr, len(probs), _ptr(status), stream), 'set_head_weights')
+    _lib.check(self.pack_device(arr, len(probs), _ptr(status), stream), what)
+
+  def slot_words(self, i):
+    """The words of absmax slot i as a view of the table (None for None)."""
+    if i is None:
+      return None
+    return self._amax_table[i * _lib.AMAX_WORDS:(i + 1) * _lib.AMAX_WORDS]
 
   def finish(self):
     """The slot table is zeroed by the plan's first launch. Round 4: that is the im2col of the

@@ -93,6 +93,9 @@ PRED_OBJ_CONF = 'pred_obj_conf'    # common.py:24-27
 PRED_OBJ_LABEL = 'pred_obj_label'
 PRED_FRAG_CONF = 'pred_frag_conf'
 PRED_FRAG_LOC = 'pred_frag_loc'
+# the 1x1 conv layers below the logits that can be trained (epos_amd/decoder_train.py)
+DECODER_CONV1_POINTWISE = 'decoder/decoder_conv1_pointwise'
+TRAINABLE_POINTWISE = (DECODER_CONV1_POINTWISE,)
 
 
 def outputs_to_num_channels(num_objs, num_frags):

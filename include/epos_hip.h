@@ -1309,6 +1309,82 @@ int epos_heads_dgrad_f32(const float* obj_logits, int64_t ld_obj, const float* f
                          int64_t ldwt, int K, const float* Y /* or NULL */, int64_t ldy,
                          float* dX, int64_t ldx, void* stream);
 
+/* Pointwise weight gradient (csrc/pointwise_wgrad.hip; added without an ABI version change). The
+ * gradients of a 1x1 conv layer with a FROZEN batch norm -- decoder/decoder_conv1_pointwise,
+ * the layer below the logits -- from its input A and the gradient G at its pre-activation
+ * (epos_heads_dgrad_f32 with Y given writes G). tests/helpers/pointwise_wgrad_ref.py restates
+ * it in numpy.
+ *
+ * The layer's forward is y = relu(scale (.) (A W) + bias) with, per output channel c,
+ *     scale_c = fl32(gamma_c / sqrt(var_c + eps))   (the quotient in fp64, rounded once)
+ *     bias_c  = beta_c - mean_c scale_c
+ * A [M,K] the layer's input, W [K,N] the checkpoint's `weights`; mean and var are the moving
+ * statistics and are constants (the reference's fine_tune_batch_norm=False), gamma and beta are
+ * variables. With G [M,N] = dL/d(pre-activation), S = A^T G [K,N] and g_c = sum_p G[p,c]:
+ *     dW[k,c]   = scale_c S[k,c]
+ *     dbeta_c   = g_c
+ *     dgamma_c  = rstd_c (sum_k W[k,c] S[k,c] - mean_c g_c),    rstd_c = 1 / sqrt(var_c + eps)
+ * (sum_p G[p,c] z[p,c] = sum_k W[k,c] S[k,c] for z = A W: z is never stored, and nothing is
+ * divided by gamma.) One GEMM and one column sum give all three.
+ *
+ * epos_pointwise_wgrad_f32: S f64 [K,N] and g f64 [N] [device], every element WRITTEN.
+ *   A: M rows with row stride lda (in units of 4 bytes), either fp32, or with a_presplit != 0
+ *   the fp16 pairs EposDepthwiseArgs.y_h2 writes: per 16 bytes [hi(c..c+3) | mid(c..c+3)], the
+ *   scale s from a_amax / a_amax2 / a_gain / a_bias exactly as EposPointwiseArgs derives it; the
+ *   value summed is the one the forward GEMM multiplied, (hi + mid 2^-11) / s, exact in fp64.
+ *   G: fp32, M rows with row stride ldg. The padding columns of A and G are never read.
+ *   Arithmetic. Every product is exact in fp64; the sums over rows are fp64 from +0.0 on the
+ *   matrix pipe (v_mfma_f64_16x16x4_f64). The result is within (M + 16) 2^-52 sum_p |A||G| of
+ *   the exact sum whatever the order. A non-finite value of A or G reaches, by IEEE rules, the
+ *   elements of S and g that depend on it and no others.
+ *   Order of the sums (no floating-point atomics, the same bytes in every run). M is cut into
+ *   ranges of epos_pointwise_wgrad_range_rows(M, K, N) consecutive rows, the last one shorter: a
+ *   function of its arguments only. With one range the sums are written to S and g. With more,
+ *   range r writes its sums to slab r of the workspace, f64 [K*N + N], and a closing launch adds
+ *   the slabs in range order, from +0.0. Within a range, S[k,c] adds the rows four at a time in
+ *   ascending order (the matrix pipe's order within four); g_c adds every fourth row, then the
+ *   four partial sums in their order.
+ *   workspace [device]: epos_pointwise_wgrad_workspace_bytes(M, K, N) bytes (0 with one range:
+ *   it may then be NULL), 8-byte aligned, contents undefined before and after.
+ *   Launches: one, or two with more than one range, on `stream`; no allocation, no host
+ *   synchronisation, capturable in a graph.
+ *   Refused with EPOS_E_INVALID before the launch, nothing written: null args, A, G, S or g; M,
+ *   K or N < 1; lda < K; ldg < N; A or G not 4-byte, S or g not 8-byte aligned; a missing or
+ *   misaligned workspace when one is needed; a pre-split A without a_amax, or with K % 4 != 0,
+ *   lda % 4 != 0 or A not 16-byte aligned.
+ *
+ * epos_pointwise_wgrad_close_f32: the checkpoint-shaped fp32 gradients from S and g. W f32
+ * [K,N] contiguous; gamma, moving_mean, moving_variance f32 [N]; dW f32 [K,N], dgamma and
+ * dbeta f32 [N] [device]. The three formulas above, each operation in fp64 and rounded once (no
+ * FMA), sum_k in sixteen partial sums (k mod 16, ascending) added in their order, the result
+ * rounded to fp32 once; a result of -0.0 is written as +0.0. With gamma NULL (a conv with
+ * biases and no batch norm; moving_mean, moving_variance and dgamma must then be NULL, W is
+ * not read): dW = fl32(S), dbeta = fl32(g) is the gradient of `biases`. One launch.
+ *   Refused with EPOS_E_INVALID: K or N < 1; a null S, g, dW or dbeta; with gamma, a null W,
+ *   moving_mean, moving_variance or dgamma, or an eps that is negative or NaN; without gamma, a
+ *   non-null moving_mean, moving_variance or dgamma; a misaligned pointer. */
+typedef struct EposPointwiseWgradArgs {
+  const void* A; int64_t lda;
+  const float* G; int64_t ldg;
+  int64_t M;
+  int32_t K, N;
+  int32_t a_presplit;
+  int32_t reserved0;        /* 0 */
+  const uint32_t* a_amax;   /* as in EposPointwiseArgs; read only with a_presplit */
+  const uint32_t* a_amax2;
+  float a_gain, a_bias;
+  double* S;
+  double* g;
+  void* workspace;
+} EposPointwiseWgradArgs;
+int64_t epos_pointwise_wgrad_workspace_bytes(int64_t M, int K, int N);
+int64_t epos_pointwise_wgrad_range_rows(int64_t M, int K, int N);
+int epos_pointwise_wgrad_f32(const EposPointwiseWgradArgs* args, void* stream);
+int epos_pointwise_wgrad_close_f32(const double* S, const double* g, const float* W, int K, int N,
+                                   const float* gamma, const float* moving_mean,
+                                   const float* moving_variance, double eps, float* dW,
+                                   float* dgamma, float* dbeta, void* stream);
+
 /* Weight update (csrc/weight_pack.hip; added without an ABI version change). The three host
  * packers above restated as device kernels, so that weights updated on the device (the momentum
  * step) reach a built plan without a round trip through the host: a grouped call packs fp32

@@ -1,5 +1,6 @@
 #!/usr/bin/env python
-"""Fine-tunes the three logits layers of an EPOS checkpoint on MI355X.
+"""Fine-tunes the three logits layers of an EPOS checkpoint on MI355X and, when
+--freeze_regex_list leaves it free, decoder/decoder_conv1_pointwise below them.
 
     python train_heads.py --model=<model_name> --train_tfrecord_names=<n> --dataset <d> [flags]
 
@@ -7,7 +8,11 @@ The part of the reference's ``scripts/train.py`` that this build has kernels for
 (epos_lib/loss.py:99-303), the gradients of logits/pred_obj_conf, pred_frag_conf and
 pred_frag_loc, tf.train.MomentumOptimizer with the l2 regulariser and the last-layer gradient
 multiplier (train.py:340-384) and the learning-rate schedules (train_utils.py:117-195).
-Everything below the logits stays frozen, as the reference does with --freeze_regex_list; no
+By default everything below the logits stays frozen, as the reference does with
+--freeze_regex_list. A list that leaves variables of decoder/decoder_conv1_pointwise trainable
+(its weights, BatchNorm/gamma, BatchNorm/beta: --freeze_regex_list
+'^(?!logits|decoder/decoder_conv1_pointwise)') trains them too, with the batch-norm statistics
+frozen (epos_amd/decoder_train.py); any other unfrozen scope is refused. No
 batch-norm statistics, one device, fp32, one scale. --data_augmentations (a mapping in the YAML
 format, on the command line or in params.yml, datagen.py:629-670) runs on the device between
 the upload of a batch and its forward pass (epos_amd/augment.py); its draws are keyed by
@@ -23,8 +28,9 @@ the upload of a batch and its forward pass (epos_amd/augment.py); its draws are 
     whole: its '/Momentum' slots and global_step too, so a run started again on a folder this
     script wrote into resumes where the last checkpoint stopped;
   * output: <model>/train/model.ckpt-<global_step> (.index, .data-00000-of-00001) with every
-    variable of the loaded checkpoint, the six logits variables replaced, their six
-    '/Momentum' slots and an int64 global_step, every --save_interval_steps and at the end;
+    variable of the loaded checkpoint, the six logits variables (and the trained variables of
+    decoder/decoder_conv1_pointwise) replaced, their '/Momentum' slots and an int64
+    global_step, every --save_interval_steps and at the end;
     the ``checkpoint`` state file names the newest; one TensorBoard event file per run with
     train/obj_cls_loss, train/frag_cls_loss, train/frag_loc_loss and train/total_loss every
     --log_steps, and one line per log step on stdout.
@@ -45,7 +51,7 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 if ROOT not in sys.path:
   sys.path.insert(0, ROOT)
 
-from epos_amd import cli, eval_utils, heads_train   # noqa: E402
+from epos_amd import cli, decoder_train, eval_utils, heads_train   # noqa: E402
 
 
 def build_parser():
@@ -68,8 +74,8 @@ def build_parser():
   a('--frag_cls_loss_weight', type=float, default=1.0)
   a('--frag_loc_loss_weight', type=float, default=100.0)
   a('--freeze_regex_list', action='append', default=None,
-    help='accepted when it freezes every variable below the logits (this script trains '
-         'nothing else); default: exactly that')
+    help='accepted when every variable it leaves trainable below the logits belongs to '
+         'decoder/decoder_conv1_pointwise; default: everything below the logits frozen')
   a('--learning_policy', default='poly', choices=['poly', 'step'])
   a('--base_learning_rate', type=float, default=0.0001)
   a('--learning_rate_decay_factor', type=float, default=0.1)
@@ -82,6 +88,7 @@ def build_parser():
   a('--train_max_height_before_crop', type=int, default=480)
   a('--train_crop_size', default='640,480')
   a('--last_layer_gradient_multiplier', type=float, default=1.0)
+  a('--last_layers_contain_logits_only', type=cli.str2bool, default=False)
   a('--slow_start_step', type=int, default=0)
   a('--slow_start_learning_rate', type=float, default=0.0001)
   a('--fine_tune_batch_norm', type=cli.str2bool, default=False)
@@ -90,14 +97,24 @@ def build_parser():
   return ap
 
 
+TRAINABLE_OF_KIND = {'conv': ('weights', 'BatchNorm/gamma', 'BatchNorm/beta'),
+                     'dw': ('depthwise_weights', 'BatchNorm/gamma', 'BatchNorm/beta')}
+
+
 def unfrozen_below_logits(regexes, args):
-  """The first variable scope below the logits that none of `regexes` freezes, or None."""
+  """The trainable variables below the logits that none of `regexes` freezes, in the network's
+  order: the reference filters per variable name (train.py:369-371)."""
   from epos_amd import weights
-  for _, scope, _, _ in weights.variable_specs(
+  names = []
+  for kind, scope, _, _ in weights.variable_specs(
       args.model_variant, 1, args.num_frags, tuple(cli.as_list(args.atrous_rates, int))):
-    if not scope.startswith('logits/') and not any(re.search(r, scope) for r in regexes):
-      return scope
-  return None
+    if scope.startswith('logits/'):
+      continue
+    for v in TRAINABLE_OF_KIND[kind]:
+      name = scope + '/' + v
+      if not any(re.search(r, name) for r in regexes):
+        names.append(name)
+  return names
 
 
 def prepare(argv=None):
@@ -118,14 +135,17 @@ def prepare(argv=None):
     raise NotImplementedError('fine_tune_batch_norm=true: the batch-norm layers lie below the '
                               'logits and stay frozen')
   args.data_augmentations = augment.parse(args.data_augmentations)
+  args.layer_trainable = ()          # the variables of decoder_conv1_pointwise to train
   if args.freeze_regex_list is not None:
     regexes = args.freeze_regex_list
     regexes = [regexes] if isinstance(regexes, str) else list(regexes)
-    scope = unfrozen_below_logits(regexes, args)
-    if scope is not None:
+    free = unfrozen_below_logits(regexes, args)
+    other = [n for n in free if n not in decoder_train.LAYER_VARIABLES]
+    if other:
       raise NotImplementedError(
           'freeze_regex_list=%r leaves %s trainable: train_heads.py trains the logits layers '
-          'only' % (regexes, scope))
+          'and %s only' % (regexes, other[0], decoder_train.LAYER))
+    args.layer_trainable = tuple(free)
   if not (args.dataset and os.environ.get('BOP_PATH')):
     raise ValueError('train_heads.py needs --dataset and $BOP_PATH (object models)')
   if args.train_batch_size < 1:
@@ -190,9 +210,18 @@ def main(argv=None):
   net = model.get_net(ckpt, B, h, w, num_objs, args.num_frags,
                       cli.model_options(args, num_objs, w, h, None), dev)
   out_size = (net.out_w, net.out_h)
-  opt = heads_train.HeadsOptimizer(
-      raw, args.base_learning_rate, args.momentum, args.weight_decay,
-      args.last_layer_gradient_multiplier, device=dev)
+  if args.layer_trainable:
+    opt = decoder_train.DecoderOptimizer(
+        raw, args.base_learning_rate, args.momentum, args.weight_decay,
+        args.last_layer_gradient_multiplier, cli.str2bool(args.last_layers_contain_logits_only),
+        trainable=loss.HEAD_VARIABLES + args.layer_trainable, device=dev)
+    train_step = decoder_train.train_step_decoder
+    print('Training below the logits: {}'.format(', '.join(args.layer_trainable)))
+  else:
+    opt = heads_train.HeadsOptimizer(
+        raw, args.base_learning_rate, args.momentum, args.weight_decay,
+        args.last_layer_gradient_multiplier, device=dev)
+    train_step = heads_train.train_step
   augmenter = None
   if args.data_augmentations:
     augmenter = augment.Augmenter(args.data_augmentations, args.seed, dev)
@@ -204,7 +233,8 @@ def main(argv=None):
   feed = eframes.Prefetcher(order, B, h, w, workers=args.decode_threads or None,
                             ahead=max(1, args.prefetch), inflight=held_max)
   # what the steps since the last look left behind, on the device
-  refused = torch.zeros(3 + 2 * num_objs, dtype=torch.int32, device=dev)
+  refused = torch.zeros(3 + 2 * num_objs + bool(args.layer_trainable), dtype=torch.int32,
+                        device=dev)
   bad_pixels = torch.zeros((), dtype=torch.int64, device=dev)
   events = tf_events.EventWriter(checkpoint_dir) if todo else None
 
@@ -224,8 +254,8 @@ def main(argv=None):
                                                input_size=(w, h)) for f in chunk]
     gt = {k: torch.stack([f[k] for f in fields]) for k in loss.GT_KEYS}
     lr = schedule(args, step)
-    values, bad, status = heads_train.train_step(net, imgs, gt, opt, lr, weights,
-                                                  augment=augmenter, step=step)
+    values, bad, status = train_step(net, imgs, gt, opt, lr, weights, augment=augmenter,
+                                     step=step)
     refused.bitwise_or_(status)
     bad_pixels.add_(bad.sum())
     step += 1
