@@ -6,14 +6,9 @@
                           and dbeta of a 1x1 conv layer with a frozen batch norm (or dW and db
                           of one with biases) from its input A -- fp32 or the fp16 pairs the
                           depthwise kernel wrote -- and the gradient G at its pre-activation.
-  net_decoder_grads       from a net that has run forward_logits to the gradients of the nine
-                          variables: the six of the logits layers and the layer's weights,
-                          BatchNorm/gamma and BatchNorm/beta.
-  gradient_rule           the reference's multiplier and decay of a variable, in Python.
-  DecoderOptimizer        heads_train.HeadsOptimizer's contract over the nine variables, any
-                          subset of them trainable.
-  train_step_decoder      heads_train.train_step with the layer unfrozen: forward_logits ->
-                          net_decoder_grads -> the optimiser step -> EposNet.set_layer_weights.
+
+The nine variables' gradients from a running net, the optimiser and the training step are
+epos_amd/trainer.py; the in-place weight update is EposNet.set_weights.
 
 The batch-norm statistics are frozen (the reference's fine_tune_batch_norm=False): moving_mean
 and moving_variance are inputs. Not built: the input gradient of this layer, G W^T, and with it
@@ -25,19 +20,14 @@ import ctypes
 
 from epos_amd import _lib
 from epos_amd._lib import EposError
-from epos_amd import heads_train as HT
 from epos_amd import loss as L
 from epos_amd import weights as W
 
 LAYER = W.DECODER_CONV1_POINTWISE
-LAYER_VARIABLES = (LAYER + '/weights', LAYER + '/BatchNorm/gamma', LAYER + '/BatchNorm/beta')
+LAYER_VARIABLES = W.trainable_variables((LAYER,))
 LAYER_CONSTANTS = (LAYER + '/BatchNorm/moving_mean', LAYER + '/BatchNorm/moving_variance')
-VARIABLES = L.HEAD_VARIABLES + LAYER_VARIABLES
-BN_EPS = 1e-5                    # model.py:307-312, the decoder's batch norms
-# model.py: get_extra_layer_scopes(last_layers_contain_logits_only=False) -- every scope above
-# the backbone counts as a last layer (train_utils.py:84-114 tests `scope in variable name`)
-LAST_LAYER_SCOPES = ('logits', 'image_pooling', 'aspp', 'concat_projection', 'decoder',
-                     'meta_architecture')
+VARIABLES = W.trainable_variables()
+BN_EPS = W.TRAINABLE_LAYERS[LAYER]
 
 
 def workspace_words(M, K, N):
@@ -84,8 +74,7 @@ def pointwise_weight_grads(a, g, weights, bn=None, eps=BN_EPS, a_h2=None, out=No
     raise ValueError('a holds %d rows, g %d' % (M, g2.shape[0]))
   if a_h2 is not None and a2.data_ptr() != a.data_ptr():
     raise ValueError('a pre-split a must have rows a constant stride apart')
-  names = ('weights', 'BatchNorm/gamma', 'BatchNorm/beta') if bn is not None else \
-      ('weights', 'biases')
+  names = W.CONV_VARIABLES[bn is not None]
   consts = [None, None, None]
   if bn is not None:
     if len(bn) != 3:
@@ -109,32 +98,16 @@ def pointwise_weight_grads(a, g, weights, bn=None, eps=BN_EPS, a_h2=None, out=No
       raise ValueError('a_h2: a pre-split a needs its absmax slot')
   result = {}
   for name in names:
-    shape = (1, 1, K, N) if name == 'weights' else (N,)
-    t = (out or {}).get(name)
-    if t is None:
-      t = torch.empty(shape, dtype=torch.float32, device=dev)
-    elif (t.device != dev or t.dtype != torch.float32 or not t.is_contiguous() or
-          t.numel() != (K * N if name == 'weights' else N)):
-      raise ValueError('out[%r] must be a contiguous float32 tensor of shape %s on %s' % (
-          name, shape, dev))
-    result[name] = t
-  words = workspace_words(M, K, N)
-  if workspace is None:
-    ws = torch.empty((words,), dtype=torch.int64, device=dev)
-  else:
-    ws = workspace
-    if (ws.device != dev or ws.dtype != torch.int64 or not ws.is_contiguous() or
-        ws.numel() < words):
-      raise ValueError('workspace must be a contiguous int64 tensor of at least %d values on '
-                       '%s' % (words, dev))
+    result[name] = L._out((out or {}).get(name), dev, torch.float32,
+                          W.variable_shapes(name, K, N)[0], 'out[%r]' % name, flat=True)
+  ws = L._workspace(workspace, dev, 8 * workspace_words(M, K, N), torch.int64)
   S, gsum, slabs = ws[:K * N], ws[K * N:K * N + N], ws[K * N + N:]
   args = _lib.PointwiseWgradArgs(
       A=L._ptr(a2), lda=lda, G=L._ptr(g2), ldg=ldg, M=M, K=K, N=N,
       a_presplit=int(a_h2 is not None), a_amax=L._ptr(slots[0]), a_amax2=L._ptr(slots[1]),
       a_gain=gain, a_bias=bias, S=L._ptr(S), g=L._ptr(gsum),
       workspace=L._ptr(slabs) if slabs.numel() else None)
-  stream = torch.cuda.current_stream(dev)
-  sp = ctypes.c_void_p(stream.cuda_stream)
+  stream, sp = L._stream_handle(dev)
   with torch.cuda.device(dev):
     _lib.check(lib.epos_pointwise_wgrad_f32(ctypes.byref(args), sp), 'epos_pointwise_wgrad_f32')
     _lib.check(lib.epos_pointwise_wgrad_close_f32(
@@ -163,142 +136,3 @@ def _layer_inputs(net, variables):
   w, gamma = (torch.as_tensor(variables[n], dtype=torch.float32).to(net.dev).contiguous()
               for n in LAYER_VARIABLES[:2])
   return w, (gamma, mean.contiguous(), var.contiguous())
-
-
-def net_decoder_grads(net, gt, variables, weights=(1.0, 1.0, 100.0), reduction='pooled',
-                      ignore_label=255):
-  """From a running network to the gradients of the nine variables: call after
-  net.forward_logits(). variables: the nine variables the net currently runs on (as
-  DecoderOptimizer.params holds them; the logits weights give the input gradient, the layer's
-  weights and gamma its own gradients). Runs loss_terms -> loss_values once, then
-  heads_weight_grads, heads_input_grad(relu_of=net.decoder_out) and pointwise_weight_grads on
-  the net's own A (EposNet.pointwise_operand: fp16 pairs by default). Returns (values f64 [4],
-  bad i64 [B], grads): values and bad as loss.differentiable_losses returns them, grads = the
-  six entries of heads_train.net_head_grads and 'decoder/decoder_conv1_pointwise/weights' f32
-  [1,1,256,256], '/BatchNorm/gamma' and '/BatchNorm/beta' f32 [256], on the device. fp32
-  single-scale nets only. Does not synchronise."""
-  op = net.pointwise_operand(LAYER)
-  logits, values, bad, scales = HT._net_losses(net, gt, weights, reduction, ignore_label)
-  raw = HT.heads_weight_grads(net.decoder_out, logits, gt, scales, ignore_label=ignore_label)
-  grads = {}
-  for head in HT.HEADS:
-    dW, db = raw[head]
-    wname, bname = HT.variable_names(head)
-    grads[wname] = dW.view(1, 1, dW.shape[0], dW.shape[1])
-    grads[bname] = db
-  G = HT.heads_input_grad(logits, gt, scales, variables, relu_of=net.decoder_out,
-                          ignore_label=ignore_label)
-  w, bn = _layer_inputs(net, variables)
-  a = op['a'].view(-1, op['a'].shape[-1])[:, :op['k']] if op['lda'] != op['k'] else op['a']
-  layer = pointwise_weight_grads(a, G, w, bn=bn, eps=op['eps'], a_h2=op['a_h2'])
-  for short, t in layer.items():
-    grads[LAYER + '/' + short] = t
-  return values, bad, grads
-
-
-def gradient_rule(name, last_layer_gradient_multiplier=1.0, weight_decay=4e-5,
-                  last_layers_contain_logits_only=False):
-  """(gradient multiplier, l2 decay) of a variable by its name, as the reference's trainer sets
-  them and heads_train.HeadsOptimizer applies them to the logits layers: variables of a last
-  layer get m = last_layer_gradient_multiplier, its biases 2 m, other biases 2, everything else
-  1 (train_utils.py:84-114); with last_layers_contain_logits_only=False, the reference's
-  default, every scope above the backbone -- `decoder` among them -- is a last layer, with True
-  the logits only. The l2 regulariser is on `weights` alone (model.py:96): gamma, beta and
-  biases carry none."""
-  m = float(last_layer_gradient_multiplier)
-  scopes = ('logits',) if last_layers_contain_logits_only else LAST_LAYER_SCOPES
-  last = any(s in name for s in scopes)
-  mult = (m if last else 1.0) * (2.0 if 'biases' in name else 1.0)
-  return mult, (float(weight_decay) if name.endswith('/weights') else 0.0)
-
-
-class DecoderOptimizer(object):
-  """heads_train.HeadsOptimizer's contract over the nine variables: fp32 master copies on the
-  device of the six logits variables and of decoder/decoder_conv1_pointwise/{weights,
-  BatchNorm/gamma, BatchNorm/beta}, momentum accumulators of the trainable ones, restored from
-  '<name>/Momentum' entries when present (absent: zeros). trainable: the names that step()
-  updates (default: all nine) -- --freeze_regex_list filters per variable name
-  (train.py:369-371); a frozen variable keeps its bytes and has no accumulator.
-  step(grads) applies heads_train.momentum_step per trainable variable with gradient_rule's
-  multiplier and decay. `params` is what EposNet.set_layer_weights takes."""
-
-  def __init__(self, variables, lr, momentum=0.9, weight_decay=4e-5,
-               last_layer_gradient_multiplier=1.0, last_layers_contain_logits_only=False,
-               trainable=None, device=None):
-    import torch
-    if not torch.cuda.is_available():
-      raise EposError('the optimiser needs a HIP device (there is no CPU fallback)')
-    _lib.load()
-    self.device = torch.device(device if device is not None else 'cuda:0')
-    self.lr, self.momentum = float(lr), float(momentum)
-    self.trainable = tuple(n for n in VARIABLES if trainable is None or n in trainable)
-    unknown = sorted(set(trainable or ()) - set(VARIABLES))
-    if unknown:
-      raise ValueError('not a variable this optimiser holds: %s' % ', '.join(unknown))
-    self.rules = {n: gradient_rule(n, last_layer_gradient_multiplier, weight_decay,
-                                   last_layers_contain_logits_only) for n in VARIABLES}
-    self.params, self.accums = {}, {}
-    for name in VARIABLES:
-      if name not in variables:
-        raise KeyError('variables lack %r' % name)
-      v = torch.as_tensor(variables[name]).to(device=self.device, dtype=torch.float32)
-      self.params[name] = v.contiguous().clone()
-      if name not in self.trainable:
-        continue
-      slot = variables.get(name + '/Momentum')
-      if slot is None:
-        self.accums[name] = torch.zeros_like(self.params[name])
-      else:
-        a = torch.as_tensor(slot).to(device=self.device, dtype=torch.float32)
-        if a.numel() != self.params[name].numel():
-          raise ValueError('%s/Momentum holds %d values, the variable %d' % (
-              name, a.numel(), self.params[name].numel()))
-        self.accums[name] = a.reshape(self.params[name].shape).contiguous().clone()
-
-  def step(self, grads, lr=None):
-    """One update of every trainable variable from grads (as net_decoder_grads returns them).
-    lr overrides the constructor's for this step."""
-    lr = self.lr if lr is None else float(lr)
-    for name in self.trainable:
-      param, g = self.params[name], grads[name]
-      if g.numel() != param.numel():
-        raise ValueError('%s: gradient of %d values, variable of %d' % (
-            name, g.numel(), param.numel()))
-      mult, decay = self.rules[name]
-      HT.momentum_step(param, self.accums[name], g.contiguous().view(param.shape), lr,
-                       self.momentum, decay, mult)
-
-  def state(self, with_slots=True):
-    """{variable name: numpy array} for tf_checkpoint.write_checkpoint: the nine variables and,
-    with_slots, the '<name>/Momentum' accumulators of the trainable ones. Synchronises."""
-    out = {name: p.cpu().numpy() for name, p in self.params.items()}
-    if with_slots:
-      for name, a in self.accums.items():
-        out[name + '/Momentum'] = a.cpu().numpy()
-    return out
-
-
-def train_step_decoder(net, images, gt, opt, lr, weights=(1.0, 1.0, 100.0), reduction='pooled',
-                       augment=None, step=None):
-  """heads_train.train_step with decoder/decoder_conv1_pointwise unfrozen, enqueued on the
-  current stream without a synchronisation: net.forward_logits(images, use_graph=True),
-  net_decoder_grads with opt.params (the weights that forward ran on), opt.step(grads, lr),
-  net.set_layer_weights(opt.params, check=False) -- one grouped pack call for the logits layers
-  and the layer. augment and step as for train_step. Returns (values f64 [4], bad i64 [B],
-  status i32): the losses of THIS step's forward and the bad-pixel counts, and
-  set_layer_weights' status words -- non-zero when the packer refused the updated weights and
-  the net kept ALL its previous ones."""
-  import torch
-  if not torch.cuda.is_available():
-    raise EposError('train_step_decoder needs a HIP device (there is no CPU fallback)')
-  if augment is not None:
-    if step is None:
-      raise ValueError('train_step_decoder: augment needs the global step its draws are keyed by')
-    net.set_images(images)
-    augment.apply(net.images, step)
-    images = None
-  net.forward_logits(images, use_graph=True)
-  values, bad, grads = net_decoder_grads(net, gt, opt.params, weights, reduction)
-  opt.step(grads, lr)
-  status = net.set_layer_weights(opt.params, check=False)
-  return values, bad, status

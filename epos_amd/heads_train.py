@@ -10,32 +10,17 @@ gradients"): the next piece of a trainer after loss.differentiable_losses.
                       three weight matrices, without the dense logit gradients.
   momentum_step       epos_momentum_step_f32: tf.train.MomentumOptimizer on the regularised,
                       multiplied gradient (train.py:340-384), in place.
-  net_head_grads      from a net that has run forward_logits to checkpoint-shaped gradients.
+  net_logits          the logits of a net that has run forward_logits, as the losses take them.
   net_feature_grad    from such a net to the gradient at its decoder output.
-  HeadsOptimizer      fp32 master copies and accumulators of the six variables; restores the
-                      accumulators from '<name>/Momentum' entries, so that a run can resume.
-  learning_rate       the reference's schedules (train_utils.py:117-195) in Python floats.
-  train_step          one step of the loop: forward_logits -> net_head_grads -> the optimiser
-                      step -> EposNet.set_head_weights (the device weight packer,
-                      csrc/weight_pack.hip: the updated weights reach the built net, its
-                      captured graphs included, without a round trip through the host).
 
-The loop itself, its checkpoints and its logging are train_heads.py. train_step keeps
-everything below the logits frozen; the layer below them, decoder_conv1_pointwise, is trained by
-epos_amd/decoder_train.py (its weight and batch-norm gradients from heads_input_grad's output,
-DecoderOptimizer, train_step_decoder). Not built: backpropagation from decoder_conv1_depthwise
-down, which starts with the input gradient G W^T of decoder_conv1_pointwise; batch-norm
-statistics, bf16 mode, multi-scale nets and more than one device. Augmentation is
-epos_amd/augment.py; train_step applies it between the upload and the forward pass.
+What stands above these kernels -- the optimiser, the training step, the learning-rate schedules
+-- is epos_amd/trainer.py; the layer below the logits, decoder_conv1_pointwise, gets its weight
+and batch-norm gradients from heads_input_grad's output in epos_amd/decoder_train.py.
 
 Pinned to tests/helpers/heads_wgrad_ref.py and, through loss_grad_ref.py, to torch's fp64
-autograd; parity with TensorFlow's numbers is unpinned, as for the losses -- that holds for
-learning_rate too: TensorFlow evaluates the schedules in float32, this module in Python
-floats. There is no CPU fallback: without the library or a device this raises EposError.
+autograd; parity with TensorFlow's numbers is unpinned, as for the losses. There is no CPU
+fallback: without the library or a device this raises EposError.
 """
-import ctypes
-import math
-
 from epos_amd import _lib
 from epos_amd._lib import EposError
 from epos_amd import loss as L
@@ -72,32 +57,19 @@ def heads_weight_grads(features, logits, gt, scales, upstream=None, ignore_label
     if need[k]:
       given = (out or {}).get(head)
       for j, shape in enumerate(((K, widths[k]), (widths[k],))):
-        if given is None:
-          pair[j] = torch.empty(shape, dtype=torch.float32, device=dev)
-        elif given[j] is not None:
-          t = given[j]
-          if (t.device != dev or t.dtype != torch.float32 or tuple(t.shape) != shape or
-              not t.is_contiguous()):
-            raise ValueError('out[%r][%d] must be a contiguous float32 tensor of shape %s on '
-                             '%s' % (head, j, shape, dev))
-          pair[j] = t
+        if given is None or given[j] is not None:
+          pair[j] = L._out(given and given[j], dev, torch.float32, shape,
+                           'out[%r][%d]' % (head, j))
     ptrs += pair
     result[head] = tuple(pair) if need[k] else None
   nbytes = lib.epos_heads_wgrad_workspace_bytes(B, P, O, F, K)
   _lib.check(nbytes, 'epos_heads_wgrad_workspace_bytes')
-  if workspace is None:
-    ws = torch.empty(((nbytes + 7) // 8 or 1,), dtype=torch.int64, device=dev)
-  else:
-    ws = workspace
-    if (ws.device != dev or not ws.is_contiguous() or
-        ws.numel() * ws.element_size() < nbytes):
-      raise ValueError('workspace must be a contiguous tensor of at least %d bytes on %s' % (
-          nbytes, dev))
-  stream = torch.cuda.current_stream(dev)
+  ws = L._workspace(workspace, dev, nbytes)
+  stream, sp = L._stream_handle(dev)
   with torch.cuda.device(dev):
     _lib.check(lib.epos_heads_wgrad_f32(
         L._ptr(feat2), lda, K, *bt.grad_args(ignore_label), L._ptr(ws),
-        *[L._ptr(t) for t in ptrs], ctypes.c_void_p(stream.cuda_stream)), 'epos_heads_wgrad_f32')
+        *[L._ptr(t) for t in ptrs], sp), 'epos_heads_wgrad_f32')
   for t in bt.keep + [feat2, ws]:
     t.record_stream(stream)           # temporaries and dense copies made here outlive the call
   return result
@@ -109,7 +81,7 @@ def heads_input_grad(logits, gt, scales, head_weights, upstream=None, relu_of=No
   the logits layers read (EposNet.decoder_out), without the dense logit gradients. logits, gt,
   scales, upstream as loss.loss_grads takes them; head_weights = {variable name: tensor or
   array} with 'logits/<name>/weights' in the checkpoint layout [1,1,K,N] (or [K,N]), as
-  HeadsOptimizer.params and state() hold them (other keys are ignored). The kernel reads the
+  trainer.Optimizer.params and state() hold them (other keys are ignored). The kernel reads the
   matrices transposed, [N,K]: they are transposed here, with torch, on the current stream, into
   `workspace` (a contiguous float32 tensor of at least (O+1 + 4*O*F) * K values) or a new
   tensor. relu_of: the forward activation f32 [B,h,w,K] or [B*P,K], rows a constant stride
@@ -136,14 +108,7 @@ def heads_input_grad(logits, gt, scales, head_weights, upstream=None, relu_of=No
       raise ValueError('%s has %d input channels, expected %d' % (wname, m.shape[-2], K))
     mats.append(m.reshape(K, width))
   rows = sum(widths)
-  if workspace is None:
-    wt = torch.empty((rows, K), dtype=torch.float32, device=dev)
-  else:
-    if (workspace.device != dev or workspace.dtype != torch.float32 or
-        not workspace.is_contiguous() or workspace.numel() < rows * K):
-      raise ValueError('workspace must be a contiguous float32 tensor of at least %d values '
-                       'on %s' % (rows * K, dev))
-    wt = workspace.view(-1)[:rows * K].view(rows, K)
+  wt = L._workspace(workspace, dev, 4 * rows * K, torch.float32).view(-1)[:rows * K].view(rows, K)
   r0 = 0
   for m, width in zip(mats, widths):
     wt[r0:r0 + width].copy_(m.t())                 # to the device and to float32 where needed
@@ -158,20 +123,16 @@ def heads_input_grad(logits, gt, scales, head_weights, upstream=None, relu_of=No
     y2, ldy = L._rows(relu_of, K)
     if y2.shape[0] != n:
       raise ValueError('relu_of holds %d rows, expected %d' % (y2.shape[0], n))
-  if out is None:
-    out = torch.empty((n, K), dtype=torch.float32, device=dev)
-  elif out.device != dev or out.dtype != torch.float32 or out.shape[-1] != K:
-    raise ValueError('out must be a float32 tensor [..., %d] on %s' % (K, dev))
+  out = L._out(out, dev, torch.float32, (n, K), 'out', rows=True)
   out2, ldx = L._rows(out, K)
   if out2.data_ptr() != out.data_ptr() or out2.shape[0] != n:
     raise ValueError('out: %d rows of dX must lie a constant stride apart' % n)
-  stream = torch.cuda.current_stream(dev)
+  stream, sp = L._stream_handle(dev)
   with torch.cuda.device(dev):
     _lib.check(lib.epos_heads_dgrad_f32(
         *bt.grad_args(ignore_label), L._ptr(wt[:widths[0]]),
         L._ptr(wt[widths[0]:widths[0] + widths[1]]), L._ptr(wt[widths[0] + widths[1]:]), K, K,
-        L._ptr(y2), ldy, L._ptr(out2), ldx, ctypes.c_void_p(stream.cuda_stream)),
-               'epos_heads_dgrad_f32')
+        L._ptr(y2), ldy, L._ptr(out2), ldx, sp), 'epos_heads_dgrad_f32')
   for t in bt.keep + [wt] + ([y2] if y2 is not None else []):
     t.record_stream(stream)           # temporaries and dense copies made here outlive the call
   return out
@@ -192,11 +153,10 @@ def momentum_step(param, accum, grad, lr, momentum=0.9, weight_decay=0.0, grad_m
         not t.is_contiguous()):
       raise ValueError('%s must be a contiguous float32 tensor of %d values on %s' % (
           what, n, param.device))
-  stream = torch.cuda.current_stream(param.device)
   with torch.cuda.device(param.device):
     _lib.check(lib.epos_momentum_step_f32(
         L._ptr(param), L._ptr(accum), L._ptr(grad), n, float(lr), float(momentum),
-        float(weight_decay), float(grad_mult), ctypes.c_void_p(stream.cuda_stream)),
+        float(weight_decay), float(grad_mult), L._stream_handle(param.device)[1]),
                'epos_momentum_step_f32')
   return param
 
@@ -220,29 +180,12 @@ def _net_losses(net, gt, weights, reduction, ignore_label):
   return logits, values, bad, scales
 
 
-def net_head_grads(net, gt, weights=(1.0, 1.0, 100.0), reduction='pooled', ignore_label=255):
-  """From a running network to checkpoint-shaped gradients: call after net.forward_logits().
-  Runs loss_terms -> loss_values -> heads_weight_grads on net.decoder_out and the net's logits.
-  Returns (values f64 [4], bad i64 [B], grads): values and bad as loss.differentiable_losses
-  returns them, grads = {'logits/<name>/weights': f32 [1,1,K,N], 'logits/<name>/biases': f32
-  [N]} on the device. fp32 single-scale nets only. Does not synchronise."""
-  logits, values, bad, scales = _net_losses(net, gt, weights, reduction, ignore_label)
-  raw = heads_weight_grads(net.decoder_out, logits, gt, scales, ignore_label=ignore_label)
-  grads = {}
-  for head in HEADS:
-    dW, db = raw[head]
-    wname, bname = variable_names(head)
-    grads[wname] = dW.view(1, 1, dW.shape[0], dW.shape[1])
-    grads[bname] = db
-  return values, bad, grads
-
-
 def net_feature_grad(net, gt, head_weights, weights=(1.0, 1.0, 100.0), reduction='pooled',
                      relu=False, ignore_label=255):
   """From a running network to the gradient at its decoder output: call after
   net.forward_logits(). Runs loss_terms -> loss_values -> heads_input_grad on the net's logits
   with head_weights (the six logits variables the net was built from, or
-  HeadsOptimizer.params). Returns (values f64 [4], bad i64 [B], dX f32 [B*P, K]): values and
+  trainer.Optimizer.params). Returns (values f64 [4], bad i64 [B], dX f32 [B*P, K]): values and
   bad as loss.differentiable_losses returns them, dX the gradient with respect to
   net.decoder_out or, with relu=True, masked with net.decoder_out: with respect to the
   pre-activation of decoder_conv1_pointwise (batch norm folded). fp32 single-scale nets only.
@@ -251,116 +194,3 @@ def net_feature_grad(net, gt, head_weights, weights=(1.0, 1.0, 100.0), reduction
   dX = heads_input_grad(logits, gt, scales, head_weights,
                         relu_of=net.decoder_out if relu else None, ignore_label=ignore_label)
   return values, bad, dX
-
-
-def learning_rate(step, policy='poly', base_learning_rate=1e-4, decay_step=2000,
-                  decay_factor=0.1, train_steps=2000000, power=0.9, slow_start_step=0,
-                  slow_start_learning_rate=1e-4, burnin='none'):
-  """The reference's learning rate at global step `step` (train_utils.py:117-195), in Python
-  floats. 'poly': base * (1 - min(s, train_steps) / train_steps) ^ power
-  (tf.train.polynomial_decay with end_learning_rate = 0); 'step': base * decay_factor ^
-  floor(s / decay_step) (exponential_decay, staircase); s = step, or step - slow_start_step
-  when there is a burn-in. While step < slow_start_step the rate is slow_start_learning_rate
-  (burnin 'none') or rises linearly from it towards base_learning_rate ('linear')."""
-  if policy not in ('poly', 'step'):
-    raise ValueError('Unknown learning policy: %r (poly, step).' % (policy,))
-  if burnin not in ('none', 'linear'):
-    raise ValueError('Unknown burnin type: %r (none, linear).' % (burnin,))
-  s = step - slow_start_step if burnin != 'none' else step
-  if policy == 'step':
-    lr = base_learning_rate * decay_factor ** math.floor(s / decay_step)
-  else:
-    lr = base_learning_rate * (1.0 - min(s, train_steps) / train_steps) ** power
-  if step < slow_start_step:
-    lr = slow_start_learning_rate
-    if burnin == 'linear':
-      lr += (base_learning_rate - slow_start_learning_rate) * step / slow_start_step
-  return float(lr)
-
-
-def train_step(net, images, gt, opt, lr, weights=(1.0, 1.0, 100.0), reduction='pooled',
-               augment=None, step=None):
-  """One training step of the logits layers, enqueued on the current stream without a
-  synchronisation: net.forward_logits(images, use_graph=True), net_head_grads, opt.step(grads,
-  lr), net.set_head_weights(opt.params, check=False). With augment (an augment.Augmenter) the
-  images are uploaded first (net.set_images), augmented in place on the device with the draws
-  of global step `step` (augment.apply(net.images, step)) and the forward pass reads them
-  there. Returns (values f64 [4], bad i64 [B],
-  status i32): the losses of THIS step's forward (before its update) and the bad-pixel counts
-  as loss.differentiable_losses returns them, and set_head_weights' status words -- non-zero
-  when the packer refused the updated weights and the net kept the previous ones. The caller
-  reads them when it chooses."""
-  import torch
-  if not torch.cuda.is_available():
-    raise EposError('train_step needs a HIP device (there is no CPU fallback)')
-  if augment is not None:
-    if step is None:
-      raise ValueError('train_step: augment needs the global step its draws are keyed by')
-    net.set_images(images)
-    augment.apply(net.images, step)
-    images = None
-  net.forward_logits(images, use_graph=True)
-  values, bad, grads = net_head_grads(net, gt, weights, reduction)
-  opt.step(grads, lr)
-  status = net.set_head_weights(opt.params, check=False)
-  return values, bad, status
-
-
-class HeadsOptimizer(object):
-  """fp32 master copies and momentum accumulators of the six logits variables on the device.
-  variables: {'logits/<name>/weights': [1,1,K,N], 'logits/<name>/biases': [N]} (numpy arrays or
-  tensors) and, optionally, their accumulators '<variable name>/Momentum' as state() and the
-  trainer's checkpoints hold them (absent: zeros); other keys are ignored. step(grads) applies
-  momentum_step per variable as the reference's trainer does: weights get the multiplier
-  m = last_layer_gradient_multiplier and the l2 decay, biases 2 * m and no decay
-  (train_utils.py:84-114). `params` is what EposNet.set_head_weights takes."""
-
-  def __init__(self, variables, lr, momentum=0.9, weight_decay=4e-5,
-               last_layer_gradient_multiplier=1.0, device=None):
-    import torch
-    if not torch.cuda.is_available():
-      raise EposError('the optimiser needs a HIP device (there is no CPU fallback)')
-    _lib.load()
-    self.device = torch.device(device if device is not None else 'cuda:0')
-    self.lr, self.momentum = float(lr), float(momentum)
-    self.weight_decay = float(weight_decay)
-    self.multiplier = float(last_layer_gradient_multiplier)
-    self.params, self.accums = {}, {}
-    for head in HEADS:
-      for name in variable_names(head):
-        if name not in variables:
-          raise KeyError('variables lack %r' % name)
-        v = torch.as_tensor(variables[name]).to(device=self.device, dtype=torch.float32)
-        self.params[name] = v.contiguous().clone()
-        slot = variables.get(name + '/Momentum')
-        if slot is None:
-          self.accums[name] = torch.zeros_like(self.params[name])
-        else:
-          a = torch.as_tensor(slot).to(device=self.device, dtype=torch.float32)
-          if a.numel() != self.params[name].numel():
-            raise ValueError('%s/Momentum holds %d values, the variable %d' % (
-                name, a.numel(), self.params[name].numel()))
-          self.accums[name] = a.reshape(self.params[name].shape).contiguous().clone()
-
-  def step(self, grads, lr=None):
-    """One update of every variable from grads (as net_head_grads returns them). lr overrides
-    the constructor's for this step (the schedules are the caller's)."""
-    lr = self.lr if lr is None else float(lr)
-    for name, param in self.params.items():
-      g = grads[name]
-      if g.numel() != param.numel():
-        raise ValueError('%s: gradient of %d values, variable of %d' % (
-            name, g.numel(), param.numel()))
-      bias = name.endswith('/biases')
-      momentum_step(param, self.accums[name], g.contiguous().view(param.shape), lr,
-                    self.momentum, 0.0 if bias else self.weight_decay,
-                    2.0 * self.multiplier if bias else self.multiplier)
-
-  def state(self, with_slots=True):
-    """{variable name: numpy array} for tf_checkpoint.write_checkpoint: the six variables and,
-    with_slots, their '<name>/Momentum' accumulators. Synchronises."""
-    out = {name: p.cpu().numpy() for name, p in self.params.items()}
-    if with_slots:
-      for name, a in self.accums.items():
-        out[name + '/Momentum'] = a.cpu().numpy()
-    return out

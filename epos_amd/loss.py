@@ -77,15 +77,57 @@ def _rows(t, width):
   return t.contiguous().view(-1, width), width
 
 
+def _out(t, device, dtype, shape, what, flat=False, rows=False):
+  """The output tensor t after its check, or a new one for None: a contiguous `dtype` tensor of
+  `shape` on `device` -- flat: of as many values in any shape; rows: [..., shape[-1]], which the
+  caller passes through _rows -- else ValueError."""
+  import torch
+  if t is None:
+    return torch.empty(shape, dtype=dtype, device=device)
+  if rows:
+    fits = t.shape[-1] == shape[-1]
+  elif flat:
+    fits = t.is_contiguous() and t.numel() == torch.Size(shape).numel()
+  else:
+    fits = t.is_contiguous() and tuple(t.shape) == tuple(shape)
+  if t.device != device or t.dtype != dtype or not fits:
+    raise ValueError('%s must be a %s%s tensor of shape %s on %s' % (
+        what, '' if rows else 'contiguous ', dtype,
+        '[..., %d]' % shape[-1] if rows else tuple(shape), device))
+  return t
+
+
+def _workspace(t, device, nbytes, dtype=None):
+  """The workspace tensor t after its check, or a new one for None: contiguous, on `device`, of
+  at least nbytes bytes and, where one is given, of `dtype` (a new one: int64), else
+  ValueError."""
+  import torch
+  if t is None:
+    new = dtype or torch.int64
+    return torch.empty((max(-(-nbytes // new.itemsize), 1),), dtype=new, device=device)
+  if (t.device != device or not t.is_contiguous() or (dtype is not None and t.dtype != dtype) or
+      t.numel() * t.element_size() < nbytes):
+    raise ValueError('workspace must be a contiguous %stensor of at least %d bytes on %s' % (
+        '%s ' % dtype if dtype else '', nbytes, device))
+  return t
+
+
+def _stream_handle(device):
+  """(the current torch stream of `device`, its hipStream_t as the C entries take it)."""
+  import torch
+  stream = torch.cuda.current_stream(device)
+  return stream, ctypes.c_void_p(stream.cuda_stream)
+
+
 HEADS = (W.PRED_OBJ_CONF, W.PRED_FRAG_CONF, W.PRED_FRAG_LOC)
 
 
 def variable_names(head):
   """(weights, biases): the checkpoint variable names of a logits layer."""
-  return 'logits/%s/weights' % head, 'logits/%s/biases' % head
+  return W.trainable_variables(('logits/' + head,))
 
 
-HEAD_VARIABLES = tuple(name for head in HEADS for name in variable_names(head))
+HEAD_VARIABLES = W.trainable_variables(W.LOGITS_LAYERS)
 
 
 def _head_dicts(obj, frag, loc, gt_obj, gt_frag, gt_loc, gt_weight):
@@ -160,25 +202,18 @@ def loss_terms(logits, gt, ignore_label=255, out=None):
   lib = _lib.load()
   bt = _Batch(logits, gt, 'the losses need')
   dev, B, P, O, F = bt.dev, bt.B, bt.P, bt.O, bt.F
-  if out is None:
-    out = (torch.empty((B, O + 1, 3), dtype=torch.float64, device=dev),
-           torch.empty((B, O + 1, 2), dtype=torch.int64, device=dev),
-           torch.empty((B,), dtype=torch.int64, device=dev))
-  sums, counts, bad = out
-  for t, dtype, numel, what in ((sums, torch.float64, B * (O + 1) * 3, 'sums'),
-                                (counts, torch.int64, B * (O + 1) * 2, 'counts'),
-                                (bad, torch.int64, B, 'bad')):
-    if t.device != dev or t.dtype != dtype or t.numel() != numel or not t.is_contiguous():
-      raise ValueError('out: %s must be a contiguous %s tensor of %d values on %s' % (
-          what, dtype, numel, dev))
+  sums, counts, bad = (
+      _out(t, dev, dtype, shape, 'out: ' + what, flat=True) for t, dtype, shape, what in zip(
+          out or (None, None, None), (torch.float64, torch.int64, torch.int64),
+          ((B, O + 1, 3), (B, O + 1, 2), (B,)), ('sums', 'counts', 'bad')))
   nbytes = lib.epos_loss_workspace_bytes(B, P, O, F)
   _lib.check(nbytes, 'epos_loss_workspace_bytes')
   ws = torch.empty((max(nbytes // 8, 1),), dtype=torch.int64, device=dev)
-  stream = torch.cuda.current_stream(dev)
+  stream, sp = _stream_handle(dev)
   with torch.cuda.device(dev):
     _lib.check(lib.epos_loss_terms(
-        *bt.args(ignore_label), _ptr(ws), _ptr(sums), _ptr(counts), _ptr(bad),
-        ctypes.c_void_p(stream.cuda_stream)), 'epos_loss_terms')
+        *bt.args(ignore_label), _ptr(ws), _ptr(sums), _ptr(counts), _ptr(bad), sp),
+               'epos_loss_terms')
   for t in bt.keep + [ws]:
     t.record_stream(stream)           # temporaries and dense copies made here outlive the call
   return sums, counts, bad
@@ -381,11 +416,10 @@ def loss_values(sums, counts, weights, reduction='mean', out=None):
       raise ValueError('%s must be a contiguous %s tensor of %d values on %s' % (
           what, dtype, numel, dev))
   w_obj, w_cls, w_loc = (float(w) for w in weights)
-  stream = torch.cuda.current_stream(dev)
   with torch.cuda.device(dev):
     _lib.check(lib.epos_loss_reduce(
         _ptr(sums), _ptr(counts), B, O1 - 1, w_obj, w_cls, w_loc, REDUCTIONS[reduction],
-        _ptr(values), _ptr(scales), ctypes.c_void_p(stream.cuda_stream)), 'epos_loss_reduce')
+        _ptr(values), _ptr(scales), _stream_handle(dev)[1]), 'epos_loss_reduce')
   return values, scales
 
 
@@ -418,11 +452,11 @@ def loss_grads(logits, gt, scales, upstream=None, ignore_label=255, need=(True, 
     d_obj2, ld_d = _rows(outs[0], O + 1)
     if d_obj2.data_ptr() != outs[0].data_ptr():
       raise ValueError('out[0]: the rows of d_obj must lie a constant stride apart')
-  stream = torch.cuda.current_stream(dev)
+  stream, sp = _stream_handle(dev)
   with torch.cuda.device(dev):
     _lib.check(lib.epos_loss_grads(
-        *bt.grad_args(ignore_label), _ptr(d_obj2), ld_d, _ptr(outs[1]), _ptr(outs[2]),
-        ctypes.c_void_p(stream.cuda_stream)), 'epos_loss_grads')
+        *bt.grad_args(ignore_label), _ptr(d_obj2), ld_d, _ptr(outs[1]), _ptr(outs[2]), sp),
+               'epos_loss_grads')
   for t in bt.keep:
     t.record_stream(stream)           # temporaries and dense copies made here outlive the call
   return tuple(outs)
@@ -549,7 +583,7 @@ def differentiable_losses_from_features(features, head_weights, gt, weights=(1.0
   layers read and of the six logits variables: with it a torch.nn restatement of the decoder,
   or any module that produces [B,h,w,K] features, trains against these losses with
   loss.backward(). features f32 [B,h,w,K] or [B*P,K] on the device; head_weights =
-  {HEAD_VARIABLES: device tensor} in the checkpoint layout (HeadsOptimizer.params); gt as
+  {HEAD_VARIABLES: device tensor} in the checkpoint layout (trainer.Optimizer.params); gt as
   loss_terms takes it. Forward: the logits by plain torch matmuls in fp32
   (logits_from_features), then loss_terms and loss_values: (values f64 [4], bad i64 [B]),
   bit-equal to differentiable_losses on those logits. Backward, once differentiable: d features

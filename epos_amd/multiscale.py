@@ -258,9 +258,9 @@ class MultiScaleNet(object):
       self.run_plan()
     return self.outputs()
 
-  def set_head_weights(self, variables, check=True):
-    raise NotImplementedError('set_head_weights: multi-scale nets are not supported (as in '
-                              'heads_train)')
+  def set_weights(self, variables, check=True):
+    raise NotImplementedError('set_weights: multi-scale nets are not supported (as in '
+                              'trainer)')
 
   def outputs(self):
     """The prediction dict of the LAST run (no launch)."""

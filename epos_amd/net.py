@@ -728,19 +728,25 @@ class EposNet(object):
     return flops
 
   # ------------------------------------------------------ weight update ---
-  def _head_variables(self, variables):
-    """set_head_weights' argument check: [(layer, w f32 [256, N] or numpy, bias)], sorted by
-    layer. Raises before anything is uploaded or enqueued."""
-    widths = W.outputs_to_num_channels(self.num_objs, self.num_frags)
+  def _need_fp32_plan(self, what, device=True):
+    if self.precision != 'fp32':
+      raise NotImplementedError('%s: precision=%r nets are not supported' % (
+          what, self.precision))
+    if device and self.lib is None:
+      raise _lib.EposError('%s needs a HIP device (there is no CPU fallback)' % what)
+
+  def _checked_variables(self, variables):
+    """set_weights' argument check against weights.TRAINABLE_LAYERS: [(scope, [the layer's
+    variables in weights.layer_variables' order, as given])], the logits layers first, sorted,
+    then the others in the table's order. Raises before anything is uploaded or enqueued."""
     given = {}
     for key, v in variables.items():
-      parts = key.split('/')
-      if (len(parts) != 3 or parts[0] != 'logits' or parts[1] not in widths or
-          parts[2] not in ('weights', 'biases')):
-        raise ValueError('%r is not a variable of the logits layers (logits/<%s>/weights, '
-                         '/biases)' % (key, '|'.join(sorted(widths))))
-      n = widths[parts[1]]
-      shapes = ((1, 1, 256, n), (256, n)) if parts[2] == 'weights' else ((n,),)
+      if key not in W.TRAINABLE_VARIABLES:
+        raise ValueError('%r is not a variable whose weights can be replaced (%s)' % (
+            key, ', '.join(W.TRAINABLE_VARIABLES)))
+      scope, short = W.TRAINABLE_VARIABLES[key]
+      k, n, _ = self.mode.packs[scope]
+      shapes = W.variable_shapes(short, k, n)
       if isinstance(v, torch.Tensor):
         if v.dtype != torch.float32:
           raise TypeError('%s must be torch.float32, got %s' % (key, v.dtype))
@@ -756,104 +762,106 @@ class EposNet(object):
       if tuple(v.shape) not in shapes:
         raise ValueError('%s must have shape %s, got %s' % (
             key, ' or '.join(str(list(s)) for s in shapes), list(v.shape)))
-      given.setdefault(parts[1], {})[parts[2]] = v
+      given.setdefault(scope, {})[short] = v
     out = []
-    for layer in sorted(given):
-      if len(given[layer]) != 2:
-        raise ValueError('logits/%s: weights and biases are set together' % layer)
-      out.append((layer, given[layer]['weights'], given[layer]['biases']))
+    for scope in sorted(s for s in given if s in W.LOGITS_LAYERS) + [
+        s for s in W.TRAINABLE_LAYERS if s in given and s not in W.LOGITS_LAYERS]:
+      shorts = W.layer_variables(scope)
+      if len(given[scope]) != len(shorts):
+        raise ValueError('%s: %s and %s are set together' % (
+            scope, ', '.join(shorts[:-1]), shorts[-1]))
+      out.append((scope, [given[scope][short] for short in shorts]))
     return out
 
-  def set_head_weights(self, variables, check=True):
-    """Replaces the weights of logits layers in place, on the device. variables:
-    {'logits/<name>/weights': [1,1,256,N] or [256,N], 'logits/<name>/biases': [N]} for any
-    subset of pred_obj_conf, pred_frag_conf, pred_frag_loc (a layer's two variables together);
-    values are contiguous fp32 tensors on the net's device (heads_train.HeadsOptimizer.params as
-    it is) or numpy arrays, which are uploaded. A wrong name, shape, dtype or device raises
-    ValueError / TypeError before anything is enqueued.
+  def set_weights(self, variables, check=True):
+    """Replaces the weights of layers of weights.TRAINABLE_LAYERS in place, on the device.
+    variables: {'<scope>/weights': [1,1,K,N] or [K,N], '<scope>/biases': [N]} for any subset of
+    logits/pred_obj_conf, pred_frag_conf and pred_frag_loc, and '<scope>/weights',
+    '<scope>/BatchNorm/gamma' and '<scope>/BatchNorm/beta' [N] of decoder/decoder_conv1_pointwise
+    (a layer's variables together); values are contiguous fp32 tensors on the net's device
+    (trainer.Optimizer.params as it is) or numpy arrays, which are uploaded. A wrong name, shape,
+    dtype or device raises ValueError / TypeError before anything is enqueued. The moving
+    statistics of a batch norm are the checkpoint's: inputs, never changed.
 
-    One grouped epos_pack_weights_device_f32 call on the current stream packs them into the very
-    tensors the plan's launch arguments point at, together with the per-object packs of the
-    sparse heads (built first if they were not): no pointer changes, so forward(),
+    A batch norm is folded on the device, bit for bit as weights.fold_bn and the plan's host
+    fold do (scale = gamma / sqrt(var + eps) and bias = beta - mean * scale in fp64, each
+    operation rounded once, both rounded to fp32; the matrix is weights * scale in fp32). One
+    grouped epos_pack_weights_device_f32 call on the current stream then packs every matrix
+    into the very tensors the plan's launch arguments point at, together with the per-object
+    packs of the sparse heads (built first if they were not): no pointer changes, so forward(),
     forward_logits(), every graph captured before the call, the pipeline's and the stand-alone
     object head use the new weights on their next run. A layer whose fp16-pair weights the host
     packer refused when the plan was built gets its other layouts only. self.ckpt is NOT
     updated (that would take a download): it keeps the weights the net was built from.
 
-    All or nothing: when the packer refuses one layer (a non-finite weight, or a column whose
-    fp16-pair scale leaves 2^+-100) nothing is written and the net holds its previous weights.
-    check=True reads the status words back (one small synchronising copy) and raises EposError
-    naming the layer; check=False does not synchronise. Returns the status tensor (int32, on
-    the device, one word per packed matrix: the layers in sorted order, then per fragment layer
-    its num_objs sparse packs; 0 = written).
+    All or nothing, for all the layers given together: when the packer refuses one (a
+    non-finite weight, or a column whose fp16-pair scale leaves 2^+-100) nothing is written and
+    the net holds its previous weights. check=True reads the status words back (one small
+    synchronising copy) and raises EposError naming the layer; check=False does not
+    synchronise. Returns the status tensor (int32, on the device, one word per packed matrix:
+    the logits layers in sorted order, then per fragment layer its num_objs sparse packs, then
+    one word per batch-norm layer; 0 = written).
 
     Ordering is the caller's: the update is enqueued on the current stream, and a forward in
     flight on ANOTHER stream must be ordered against it by the caller (nothing here records or
     waits for events). fp32 single-scale nets with num_objs <= 126 only."""
-    if self.precision != 'fp32':
-      raise NotImplementedError('set_head_weights: precision=%r nets are not supported' %
-                                self.precision)
-    if self.lib is None:
-      raise _lib.EposError('set_head_weights needs a HIP device (there is no CPU fallback)')
-    layers = self._head_variables(variables)
-    if 3 + 2 * self.num_objs > 256:
-      raise NotImplementedError('set_head_weights: more than 126 objects')
+    self._need_fp32_plan('set_weights', device=False)
+    layers = self._checked_variables(variables)
+    self._need_fp32_plan('set_weights')
+    if len(W.TRAINABLE_LAYERS) + 2 * self.num_objs > 256:
+      raise NotImplementedError('set_weights: more than 126 objects')
     if not layers:
       return torch.zeros(0, dtype=torch.int32, device=self.dev)
     with torch.cuda.device(self.dev):
-      probs, names, keep = self._head_pack_problems(layers)
-    return self._pack(probs, names, keep, check, 'set_head_weights', 'logits/')
-
-  def _head_pack_problems(self, layers):
-    """(problems, names, tensors to keep alive) of the device packer for logits layers as
-    _head_variables returns them: the dense packs in sorted order, then per fragment layer its
-    num_objs sparse packs."""
-    O, F = self.num_objs, self.num_frags
-    sparse_n = {W.PRED_FRAG_CONF: (0, F), W.PRED_FRAG_LOC: (1, 3 * F)}
-    if self._sparse_packs is None and any(l[0] in sparse_n for l in layers):
-      self._build_sparse_packs()         # from self.ckpt, while it still describes the net
-    probs, names, dense, keep = [], [], [], []
-    for layer, w, b in layers:
-      w = torch.as_tensor(w, dtype=torch.float32).to(self.dev).reshape(256, -1)
-      b = torch.as_tensor(b, dtype=torch.float32).to(self.dev)
-      dense.append((layer, w, b))
-      keep += [w, b]
-      probs.append(self.mode.pack_problem(self.mode.head_packs[layer], w, b, 0, w.shape[1]))
-      names.append(layer)
-    for layer, w, b in dense:
-      if layer in sparse_n:
-        kind, n = sparse_n[layer]
-        for o in range(O):
-          probs.append(self.mode.pack_problem(self._sparse_packs[o][kind], w, b, o * n, n))
-          names.append('%s (sparse pack of object %d)' % (layer, o + 1))
-    return probs, names, keep
-
-  def _pack(self, probs, names, keep, check, what, prefix):
-    """One grouped call of the device packer on the current stream: all of probs or none.
-    Returns the status tensor; with check, reads it back and raises naming the refused."""
-    with torch.cuda.device(self.dev):
-      status = torch.empty(len(probs), dtype=torch.int32, device=self.dev)
-      self.mode.pack_launch(probs, status, self._stream(), what)
+      packed, keep = self._pack_problems(layers)
+      status = torch.empty(len(packed), dtype=torch.int32, device=self.dev)
+      self.mode.pack_launch([p[0] for p in packed], status, self._stream())
     stream = torch.cuda.current_stream(self.dev)
     for t in keep:
       t.record_stream(stream)            # uploaded copies outlive the call
     if check:
-      bad = [names[i] for i in torch.nonzero(status.cpu()).flatten().tolist()]
+      bad = [packed[i][1:] for i in torch.nonzero(status.cpu()).flatten().tolist()]
+      bad = ['%s (sparse pack of object %d)' % b if b[1] else b[0] for b in bad]
       if bad:
         raise _lib.EposError(
-            '%s: the fp16-pair packer refused %s%s (a non-finite weight, or '
+            'set_weights: the fp16-pair packer refused %s (a non-finite weight, or '
             'a column whose scale leaves 2^+-100); nothing was written, the net still holds its '
-            'previous weights' % (what, prefix, (', ' + prefix).join(bad)))
+            'previous weights' % ', '.join(bad))
     return status
 
-  # ------------------------------------------- the layer below the logits ---
-  def _need_fp32_plan(self, what):
-    if self.precision != 'fp32':
-      raise NotImplementedError('%s: precision=%r nets are not supported' % (
-          what, self.precision))
-    if self.lib is None:
-      raise _lib.EposError('%s needs a HIP device (there is no CPU fallback)' % what)
+  def _pack_problems(self, layers):
+    """([(problem, scope, object id of a sparse pack or 0)], tensors to keep alive) of the
+    device packer for layers as _checked_variables returns them: the logits layers' packs, then
+    per fragment layer its num_objs sparse packs, then the folded batch-norm layers' packs."""
+    O, F = self.num_objs, self.num_frags
+    sparse_n = {'logits/' + W.PRED_FRAG_CONF: (0, F), 'logits/' + W.PRED_FRAG_LOC: (1, 3 * F)}
+    if self._sparse_packs is None and any(scope in sparse_n for scope, _ in layers):
+      self._build_sparse_packs()         # from self.ckpt, while it still describes the net
+    dense, sparse, folded, keep = [], [], [], []
+    for scope, values in layers:
+      k, n, pack = self.mode.packs[scope]
+      w, *rest = (torch.as_tensor(v, dtype=torch.float32).to(self.dev) for v in values)
+      w = w.reshape(k, n)
+      eps = W.TRAINABLE_LAYERS[scope]
+      if eps is None:
+        b = rest[0]
+      else:
+        gamma, beta = rest
+        mean, var = self.layer_constants(scope)
+        scale = gamma.double() / torch.sqrt(var.double() + eps)
+        b = (beta.double() - mean.double() * scale).float()
+        w = (w * scale.float()[None, :]).contiguous()
+      keep += [w, b]
+      (dense if eps is None else folded).append(
+          (self.mode.pack_problem(pack, w, b, 0, n), scope, 0))
+      if scope in sparse_n:
+        kind, width = sparse_n[scope]
+        for o in range(O):
+          sparse.append((self.mode.pack_problem(self._sparse_packs[o][kind], w, b, o * width,
+                                                width), scope, o + 1))
+    return dense + sparse + folded, keep
 
+  # ------------------------------------------- the layer below the logits ---
   def pointwise_operand(self, name=W.DECODER_CONV1_POINTWISE):
     """What the backward pass of a trainable 1x1 conv layer needs of the plan, as it was
     recorded while the plan was built: {'a': the layer's input, the depthwise output buffer
@@ -865,15 +873,15 @@ class EposNet(object):
     self._need_fp32_plan('pointwise_operand')
     if name not in self.mode.layer_operands:
       raise ValueError('%r is not a trainable layer (%s)' % (
-          name, ', '.join(W.TRAINABLE_POINTWISE)))
-    a, lda, m, k, n, args, packs, ab = self.mode.layer_operands[name]
+          name, ', '.join(self.mode.layer_operands)))
+    a, lda, m, k, n, args, ab = self.mode.layer_operands[name]
     presplit = bool(args.a_presplit)
     a_h2 = None
     if presplit:
       a_h2 = (self.mode.slot_words(ab[0]), self.mode.slot_words(ab[1]), float(args.a_gain),
               float(args.a_bias))
     return {'a': a, 'lda': lda, 'm': m, 'k': k, 'n': n, 'presplit': presplit, 'a_h2': a_h2,
-            'packs': packs, 'eps': HEAD_BN_EPS}
+            'packs': self.mode.packs[name][2], 'eps': W.TRAINABLE_LAYERS[name]}
 
   def layer_constants(self, name=W.DECODER_CONV1_POINTWISE):
     """(moving_mean, moving_variance) of a trainable layer's batch norm on the device, f32 [N],
@@ -884,77 +892,6 @@ class EposNet(object):
                                                 np.float32)).to(self.dev)
           for v in ('moving_mean', 'moving_variance'))
     return self._layer_consts[name]
-
-  def _layer_variables(self, variables, name):
-    """set_layer_weights' argument check for the layer's three variables: (w f32 [K,N], gamma,
-    beta) on the device, or None when none of them is given."""
-    _, _, _, k, n, _, _, _ = self.mode.layer_operands[name]
-    keys = (name + '/weights', name + '/BatchNorm/gamma', name + '/BatchNorm/beta')
-    given = [key for key in keys if key in variables]
-    if not given:
-      return None
-    if len(given) != 3:
-      raise ValueError('%s: weights, BatchNorm/gamma and BatchNorm/beta are set together' % name)
-    out = []
-    for key, shapes in zip(keys, (((1, 1, k, n), (k, n)), ((n,),), ((n,),))):
-      v = variables[key]
-      if isinstance(v, torch.Tensor):
-        if v.dtype != torch.float32:
-          raise TypeError('%s must be torch.float32, got %s' % (key, v.dtype))
-        if v.device != self.dev:
-          raise ValueError('%s is on %s, the net on %s (numpy arrays are uploaded)' % (
-              key, v.device, self.dev))
-        if not v.is_contiguous():
-          raise ValueError('%s must be contiguous' % key)
-      else:
-        v = np.asarray(v)
-        if v.dtype.kind != 'f':
-          raise TypeError('%s must be a floating-point array, got %s' % (key, v.dtype))
-      if tuple(v.shape) not in shapes:
-        raise ValueError('%s must have shape %s, got %s' % (
-            key, ' or '.join(str(list(s)) for s in shapes), list(v.shape)))
-      out.append(torch.as_tensor(v, dtype=torch.float32).to(self.dev))
-    return out[0].reshape(k, n), out[1], out[2]
-
-  def set_layer_weights(self, variables, check=True):
-    """set_head_weights for decoder/decoder_conv1_pointwise, alone or together with logits
-    layers. variables: the layer's '<scope>/weights' [1,1,K,N] or [K,N], '<scope>/BatchNorm/gamma'
-    and '<scope>/BatchNorm/beta' [N] (the three together; decoder_train.DecoderOptimizer.params
-    as it is) and any of the logits variables set_head_weights takes; contiguous fp32 tensors on
-    the net's device, or numpy arrays. The moving statistics are the checkpoint's: inputs,
-    never changed.
-
-    The batch norm is folded on the device, bit for bit as weights.fold_bn and the plan's host
-    fold do (scale = gamma / sqrt(var + eps) and bias = beta - mean * scale in fp64, each
-    operation rounded once, both rounded to fp32; the matrix is weights * scale in fp32), and
-    the folded matrix and bias go through the device packer into the very tensors the layer's
-    launch points at, in ONE grouped call with the logits layers' packs: all or nothing, for
-    the layer and the logits layers together. Captured graphs see the new weights. Returns the
-    status tensor: set_head_weights' words for the logits layers given, then one for the layer.
-    check and ordering as for set_head_weights."""
-    self._need_fp32_plan('set_layer_weights')
-    name = W.DECODER_CONV1_POINTWISE
-    heads = {k: v for k, v in variables.items() if not k.startswith(name + '/')}
-    layers = self._head_variables(heads)
-    if 3 + 2 * self.num_objs + 1 > 256:
-      raise NotImplementedError('set_layer_weights: more than 126 objects')
-    layer = self._layer_variables(variables, name)
-    if not layers and layer is None:
-      return torch.zeros(0, dtype=torch.int32, device=self.dev)
-    with torch.cuda.device(self.dev):
-      probs, names, keep = self._head_pack_problems(layers) if layers else ([], [], [])
-      names = ['logits/' + n for n in names]
-      if layer is not None:
-        w, gamma, beta = layer
-        mean, var = self.layer_constants(name)
-        scale = gamma.double() / torch.sqrt(var.double() + HEAD_BN_EPS)
-        bias = (beta.double() - mean.double() * scale).float()
-        folded = (w * scale.float()[None, :]).contiguous()
-        probs.append(self.mode.pack_problem(self.mode.layer_operands[name][6], folded, bias, 0,
-                                            folded.shape[1]))
-        names.append(name)
-        keep += [folded, bias]
-    return self._pack(probs, names, keep, check, 'set_layer_weights', '')
 
   def set_images(self, images):
     """images: [B,H,W,3] in [0,255] (host numpy or device tensor), float32 -- or uint8 as the

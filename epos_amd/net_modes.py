@@ -101,11 +101,12 @@ class Fp32Mode(object):
     self.use_presplit = self.use_h2 and os.environ.get('EPOS_H2_PRESPLIT', '1') == '1'
     self._dw_h2 = {}           # id(depthwise output) -> its (mutable) launch arguments
     self.h2_layers, self.h2_refused, self.presplit_layers = [], [], []
-    # logits layer -> the (wp, bp, ws, wh) tensors its launch arguments point at: where
-    # EposNet.set_head_weights packs updated weights (references only; wh None = refused)
-    self.head_packs = {}
-    # trainable layer below the logits -> what its backward pass and its weight update need:
-    # (A buffer, lda, M, K, N, the launch's PointwiseArgs, (wp, bp, ws, wh), A's bound or None)
+    # layer of weights.TRAINABLE_LAYERS -> (K, N, the (wp, bp, ws, wh) tensors its launch
+    # arguments point at): where EposNet.set_weights packs updated weights (references only;
+    # wh None = refused)
+    self.packs = {}
+    # trainable layer below the logits -> what its backward pass needs:
+    # (A buffer, lda, M, K, N, the launch's PointwiseArgs, A's bound or None)
     self.layer_operands = {}
     self.pack_device = fn('epos_pack_weights_device_f32')
     self._last_pw = None       # (C, args, foldable): the last stand-alone 1x1 launch
@@ -206,8 +207,9 @@ class Fp32Mode(object):
     wp, bp, ws, wh, kpad = self._weights(name, conv, ab is not None and m > 8)
     n = conv[0].shape[1]
     assert kpad == k or (kpad > k and lda >= kpad), (name, k, kpad, lda)
-    if name.startswith('logits/'):
-      self.head_packs[name[len('logits/'):]] = (wp, bp, ws, wh)
+    if name in W.TRAINABLE_LAYERS:
+      assert kpad == k, name
+      self.packs[name] = (k, n, (wp, bp, ws, wh))
     # A = the output of a depthwise conv that was set up to write fp16 pairs: keep that
     # only if this GEMM really runs on the fp16-pair kernel (the packer may have refused
     # the weights); the depthwise arguments are the very struct its launch passes
@@ -230,9 +232,9 @@ class Fp32Mode(object):
         a_amax2=self._slot_ptr(ab[1]) if h else None,
         a_gain=ab[2] if h else 0.0, a_bias=ab[3] if h else 0.0,
         a_presplit=int(presplit), c_amax=self._slot_ptr(cslot))
-    if name in W.TRAINABLE_POINTWISE:
-      assert a_off == 0 and sub == 1 and res is None and kpad == k, name
-      self.layer_operands[name] = (a, lda, m, k, n, args, (wp, bp, ws, wh), ab if h else None)
+    if name in W.TRAINABLE_LAYERS and name not in W.LOGITS_LAYERS:
+      assert a_off == 0 and sub == 1 and res is None, name
+      self.layer_operands[name] = (a, lda, m, k, n, args, ab if h else None)
     # fp32 activations in and out, weights once (4 B each: what the layer IS; the
     # split kernel streams 6 B per weight), residual once
     nbytes = 4 * (m * k + k * n + m * n + (m * n if res is not None else 0))
@@ -383,7 +385,7 @@ class Fp32Mode(object):
                                h2=_ptr(wh) if wh is not None else None, bias_pad=_ptr(bp),
                                K=w.shape[-2], N=n)
 
-  def pack_launch(self, probs, status, stream, what='set_head_weights'):
+  def pack_launch(self, probs, status, stream, what='set_weights'):
     """One grouped epos_pack_weights_device_f32 call: all of probs or none of them."""
     arr = (_lib.WeightPackArgs * len(probs))(*probs)
     _lib.check(self.pack_device(arr, len(probs), _ptr(status), stream), what)

@@ -93,9 +93,42 @@ PRED_OBJ_CONF = 'pred_obj_conf'    # common.py:24-27
 PRED_OBJ_LABEL = 'pred_obj_label'
 PRED_FRAG_CONF = 'pred_frag_conf'
 PRED_FRAG_LOC = 'pred_frag_loc'
-# the 1x1 conv layers below the logits that can be trained (epos_amd/decoder_train.py)
 DECODER_CONV1_POINTWISE = 'decoder/decoder_conv1_pointwise'
-TRAINABLE_POINTWISE = (DECODER_CONV1_POINTWISE,)
+# The 1x1 conv layers whose weights a built net replaces in place (EposNet.set_weights) and the
+# trainer holds (epos_amd/trainer.py), in the trainer's order: scope -> None for a layer with
+# `biases`, or the eps of its frozen batch norm (gamma and beta trained, the statistics inputs;
+# model.py:307-312). A layer with a batch norm is folded before it is packed.
+TRAINABLE_LAYERS = {
+    'logits/' + PRED_OBJ_CONF: None,
+    'logits/' + PRED_FRAG_CONF: None,
+    'logits/' + PRED_FRAG_LOC: None,
+    DECODER_CONV1_POINTWISE: 1e-5,
+}
+LOGITS_LAYERS = tuple(s for s in TRAINABLE_LAYERS if s.startswith('logits/'))
+# a 1x1 conv layer's trained variables by whether it has a batch norm, `weights` first: what is
+# given together to EposNet.set_weights and what a gradient wrapper's result is keyed by
+CONV_VARIABLES = {False: ('weights', 'biases'),
+                  True: ('weights', 'BatchNorm/gamma', 'BatchNorm/beta')}
+
+
+def layer_variables(scope):
+  """The short names of a TRAINABLE_LAYERS layer's variables."""
+  return CONV_VARIABLES[TRAINABLE_LAYERS[scope] is not None]
+
+
+# checkpoint name -> (scope, short name) of every variable of TRAINABLE_LAYERS
+TRAINABLE_VARIABLES = {s + '/' + v: (s, v) for s in TRAINABLE_LAYERS for v in layer_variables(s)}
+
+
+def trainable_variables(scopes=None):
+  """The checkpoint names of the variables of `scopes` (default: every TRAINABLE_LAYERS layer),
+  in the table's order."""
+  return tuple(n for n, (s, _) in TRAINABLE_VARIABLES.items() if scopes is None or s in scopes)
+
+
+def variable_shapes(short, k, n):
+  """The shapes a variable of a K -> N layer may have."""
+  return ((1, 1, k, n), (k, n)) if short == 'weights' else ((n,),)
 
 
 def outputs_to_num_channels(num_objs, num_frags):

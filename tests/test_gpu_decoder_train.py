@@ -1,5 +1,5 @@
-"""Training decoder/decoder_conv1_pointwise on the device (epos_amd/decoder_train.py,
-EposNet.pointwise_operand and set_layer_weights, train_heads.py with the layer unfrozen) on the
+"""Training decoder/decoder_conv1_pointwise on the device (epos_amd/decoder_train.py and
+trainer.py, EposNet.pointwise_operand and set_weights, train_heads.py with the layer unfrozen) on the
 small net of tests/helpers/loss_device.py: the gradients against their parts and against
 tests/helpers/pointwise_wgrad_ref.py fed the net's own A bytes and the device's own G, the
 in-place weight update against a freshly built net, a training step against its parts, and the
@@ -59,17 +59,19 @@ def same_bytes(a, b):
 
 # ------------------------------------------------------------- gradients ---
 def check_grads(net, ckpt, gt, presplit):
-  """net_decoder_grads after a forward_logits: byte-equal to its parts called by hand, and the
+  """net_grads of all nine variables after a forward_logits: byte-equal to its parts called by hand, and the
   layer's three gradients within bound of the restatement on the net's own A bytes and the
   device's own G."""
-  from epos_amd import decoder_train as DT, heads_train as HT, loss as L
+  from epos_amd import decoder_train as DT, heads_train as HT, loss as L, trainer
+  from epos_amd import weights as W
   op = net.pointwise_operand()
   assert op['presplit'] is presplit and (op['a_h2'] is not None) == presplit
   assert (op['k'], op['n'], op['lda']) == (256, 256, 256)
   assert op['m'] == NET_B * net.out_h * net.out_w
   assert (DT.LAYER in net.presplit_layers) == presplit
   variables = on_device(nine(ckpt))
-  values, bad, grads = DT.net_decoder_grads(net, gt, variables, LOSS_WEIGHTS, 'pooled')
+  values, bad, grads = trainer.net_grads(net, gt, variables, tuple(W.TRAINABLE_LAYERS),
+                                         LOSS_WEIGHTS, 'pooled')
   assert sorted(grads) == sorted(DT.VARIABLES) and bad.tolist() == [0] * NET_B
   assert tuple(grads[DT.LAYER + '/weights'].shape) == (1, 1, 256, 256)
   # the parts, by hand
@@ -119,7 +121,7 @@ def check_grads(net, ckpt, gt, presplit):
   return host(grads)
 
 
-def test_net_decoder_grads_equal_their_parts_and_the_restatement(small_net, images, monkeypatch):
+def test_net_grads_equal_their_parts_and_the_restatement(small_net, images, monkeypatch):
   net, ckpt, mo, c, gt = small_net
   net.forward_logits(images)
   pairs = check_grads(net, ckpt, gt, presplit=True)
@@ -137,7 +139,7 @@ def test_net_decoder_grads_equal_their_parts_and_the_restatement(small_net, imag
 
 
 def test_python_layer_argument_checks(small_net):
-  from epos_amd import decoder_train as DT
+  from epos_amd import decoder_train as DT, trainer
   net = small_net[0]
   a = torch.zeros(10, 8, device='cuda')
   g = torch.zeros(10, 4, device='cuda')
@@ -162,7 +164,7 @@ def test_python_layer_argument_checks(small_net):
   with pytest.raises(ValueError, match='not a trainable layer'):
     net.pointwise_operand('decoder/decoder_conv0_pointwise')
   with pytest.raises(ValueError, match='not a variable this optimiser holds'):
-    DT.DecoderOptimizer(nine(small_net[1]), 1e-3, trainable=('logits/other/weights',))
+    trainer.Optimizer(nine(small_net[1]), 1e-3, trainable=('logits/other/weights',))
 
 
 # ---------------------------------------------------------- weight update ---
@@ -183,7 +185,7 @@ def assert_same(got, want, tag):
       assert got[run][k].tobytes() == want[run][k].tobytes(), (tag, run, k)
 
 
-def test_set_layer_weights_equals_a_freshly_built_net(small_net, images):
+def test_set_weights_of_the_layer_equals_a_freshly_built_net(small_net, images):
   from epos_amd import decoder_train as DT, weights
   from epos_amd._lib import EposError
   a = small_net[1]
@@ -200,25 +202,25 @@ def test_set_layer_weights_equals_a_freshly_built_net(small_net, images):
   want_ab = all_runs(build(ab, instance=3), images)
   assert_same(all_runs(upd, images), want_a, 'before')
   # all nine, tensors on the device: one grouped pack call
-  status = upd.set_layer_weights(on_device(nine(ab)))
+  status = upd.set_weights(on_device(nine(ab)))
   assert status.dtype == torch.int32 and status.tolist() == [0] * (3 + 2 * NET_O + 1)
   assert_same(all_runs(upd, images), want_ab, 'nine')
   assert (upd._graph, upd._graph_logits) == graphs
   # back to a, then the layer alone, numpy arrays with [K, N] weights
-  upd.set_layer_weights(nine(a))
+  upd.set_weights(nine(a))
   assert_same(all_runs(upd, images), want_a, 'back')
   lay = {n: np.asarray(b[n]) for n in DT.LAYER_VARIABLES}
   lay[DT.LAYER + '/weights'] = lay[DT.LAYER + '/weights'].reshape(256, 256)
-  assert upd.set_layer_weights(lay).tolist() == [0]
+  assert upd.set_weights(lay).tolist() == [0]
   want_layer = all_runs(upd, images)          # the layer of b under the logits layers of a
   for run in want_layer:
     for k in ('pred_obj_conf', 'pred_frag_conf', 'pred_frag_loc'):
       assert want_layer[run][k].tobytes() != want_a[run][k].tobytes(), (run, k)
       assert want_layer[run][k].tobytes() != want_ab[run][k].tobytes(), (run, k)
-  # ... and the logits layers of b on top of it, through set_head_weights: all nine of b
-  upd.set_head_weights({n: b[n] for n in loss_names()})
+  # ... and the logits layers of b on top of it, in a call of their own: all nine of b
+  upd.set_weights({n: b[n] for n in loss_names()})
   assert_same(all_runs(upd, images), want_ab, 'layer, then heads')
-  upd.set_head_weights({n: a[n] for n in loss_names()})
+  upd.set_weights({n: a[n] for n in loss_names()})
   assert_same(all_runs(upd, images), want_layer, 'layer')
   # a refused update leaves everything as it was: the layer and the logits layers together
   bad = nine(a)
@@ -226,10 +228,10 @@ def test_set_layer_weights_equals_a_freshly_built_net(small_net, images):
   w[0, 0, 17, 100] = np.nan
   bad[DT.LAYER + '/weights'] = w
   with pytest.raises(EposError,
-                     match=r'set_layer_weights.*refused %s.*previous weights' % DT.LAYER):
-    upd.set_layer_weights(bad)
+                     match=r'set_weights.*refused %s.*previous weights' % DT.LAYER):
+    upd.set_weights(bad)
   assert_same(all_runs(upd, images), want_layer, 'refused')
-  status = upd.set_layer_weights(bad, check=False)
+  status = upd.set_weights(bad, check=False)
   assert torch.nonzero(status).flatten().tolist() == [3 + 2 * NET_O]
   assert_same(all_runs(upd, images), want_layer, 'refused, unchecked')
   # argument checks: before anything is enqueued
@@ -241,35 +243,37 @@ def test_set_layer_weights_equals_a_freshly_built_net(small_net, images):
                          ({name: good[name]}, ValueError),
                          (dict(good, **{'decoder/other/weights': good[name]}), ValueError)):
     with pytest.raises(exc):
-      upd.set_layer_weights(variables)
+      upd.set_weights(variables)
   assert_same(all_runs(upd, images), want_layer, 'after the argument checks')
-  assert upd.set_layer_weights({}).numel() == 0
+  assert upd.set_weights({}).numel() == 0
 
 
 # -------------------------------------------------------------- train step ---
-def test_train_step_decoder_equals_its_parts(small_net, images):
-  from epos_amd import decoder_train as DT, loss
+def test_train_step_with_the_layer_equals_its_parts(small_net, images):
+  from epos_amd import decoder_train as DT, loss, trainer
+  from epos_amd import weights as W
   a = small_net[1]
-  lr, kw = 1e-3, dict(momentum=0.9, weight_decay=4e-5, last_layer_gradient_multiplier=3.0)
+  lr, kw = 1e-3, dict(momentum=0.9, weight_decay=4e-5, last_layer_gradient_multiplier=3.0,
+                      trainable=DT.VARIABLES)
   c = loss_cases.make_case(NET_B, small_net[0].out_h * small_net[0].out_w, NET_O, NET_F, seed=41)
   gt = gt_tensors(c, small_net[0].out_h, small_net[0].out_w)
   # by hand, on one net (the plan of the update test, put back to a)
-  hand, ref_opt = build(a, instance=1), DT.DecoderOptimizer(a, lr=lr, **kw)
-  hand.set_layer_weights(nine(a))
+  hand, ref_opt = build(a, instance=1), trainer.Optimizer(a, lr=lr, **kw)
+  hand.set_weights(nine(a))
   ref_values = []
   for _ in range(2):
     hand.forward_logits(images)
-    values, bad, grads = DT.net_decoder_grads(hand, gt, ref_opt.params)
+    values, bad, grads = trainer.net_grads(hand, gt, ref_opt.params, ref_opt.layers)
     ref_values.append(values.cpu().numpy().copy())
     ref_opt.step(grads, lr)
-    assert hand.set_layer_weights(ref_opt.params).tolist() == [0] * (3 + 2 * NET_O + 1)
+    assert hand.set_weights(ref_opt.params).tolist() == [0] * (3 + 2 * NET_O + 1)
   ref_state = ref_opt.state()
-  hand.set_layer_weights(nine(a))             # the cached plan as it was built
+  hand.set_weights(nine(a))             # the cached plan as it was built
   # two train steps on another
-  trainee, opt = small_net[0], DT.DecoderOptimizer(a, lr=lr, **kw)
+  trainee, opt = small_net[0], trainer.Optimizer(a, lr=lr, **kw)
   got_values = []
   for _ in range(2):
-    values, bad, status = DT.train_step_decoder(trainee, images, gt, opt, lr)
+    values, bad, status = trainer.train_step(trainee, images, gt, opt, lr)
     got_values.append(values.cpu().numpy().copy())
     assert bad.tolist() == [0] * NET_B and status.tolist() == [0] * (3 + 2 * NET_O + 1)
   for step in range(2):
@@ -284,24 +288,24 @@ def test_train_step_decoder_equals_its_parts(small_net, images):
   # the update follows the rule: one momentum step by hand on gamma, from the first gradients
   from tests.helpers import heads_wgrad_ref
   name = DT.LAYER + '/BatchNorm/gamma'
-  check_opt = DT.DecoderOptimizer(a, lr=lr, **kw)
+  check_opt = trainer.Optimizer(a, lr=lr, **kw)
   hand.forward_logits(images)
-  _, _, grads = DT.net_decoder_grads(hand, gt, check_opt.params)
+  _, _, grads = trainer.net_grads(hand, gt, check_opt.params, tuple(W.TRAINABLE_LAYERS))
   g0 = grads[name].cpu().numpy()
   w1, a1 = heads_wgrad_ref.momentum_step(a[name], np.zeros(256, np.float32), g0, lr, 0.9, 0.0, 3.0)
   check_opt.step(grads, lr)
   assert check_opt.params[name].cpu().numpy().tobytes() == w1.tobytes()
   assert check_opt.accums[name].cpu().numpy().tobytes() == a1.tobytes()
   # resuming: an optimiser restored from the state continues with the same bytes
-  resumed = DT.DecoderOptimizer(state, lr=lr, **kw)
+  resumed = trainer.Optimizer(state, lr=lr, **kw)
   for k in state:
     t = resumed.accums[k[:-9]] if k.endswith('/Momentum') else resumed.params[k]
     assert t.cpu().numpy().tobytes() == state[k].tobytes(), k
   # gamma and beta frozen: their bytes stay, they have no accumulator, the weights move
-  frozen = DT.DecoderOptimizer(a, lr=lr, trainable=loss.HEAD_VARIABLES + (DT.LAYER + '/weights',),
-                               **kw)
-  trainee.set_layer_weights(nine(a))
-  DT.train_step_decoder(trainee, images, gt, frozen, lr)
+  frozen = trainer.Optimizer(a, lr=lr, **dict(
+      kw, trainable=loss.HEAD_VARIABLES + (DT.LAYER + '/weights',)))
+  trainee.set_weights(nine(a))
+  trainer.train_step(trainee, images, gt, frozen, lr)
   st = frozen.state()
   assert len(st) == 9 + 7
   for short in ('BatchNorm/gamma', 'BatchNorm/beta'):
@@ -309,7 +313,71 @@ def test_train_step_decoder_equals_its_parts(small_net, images):
     assert st[n].tobytes() == np.asarray(a[n], np.float32).tobytes() and n + '/Momentum' not in st
   n = DT.LAYER + '/weights'
   assert st[n].tobytes() != np.asarray(a[n], np.float32).tobytes() and n + '/Momentum' in st
-  trainee.set_layer_weights(nine(a))
+  trainee.set_weights(nine(a))
+
+
+def test_logits_only_step_leaves_the_layer_alone(small_net, images, monkeypatch):
+  from epos_amd import decoder_train as DT, heads_train as HT, loss, trainer
+  net, a, _, _, gt = small_net
+  net.set_weights(nine(a))
+  calls = {'pointwise_weight_grads': 0, 'heads_input_grad': 0}
+
+  def count(module, name):
+    real = getattr(module, name)
+
+    def counted(*args, **kwargs):
+      calls[name] += 1
+      return real(*args, **kwargs)
+    monkeypatch.setattr(module, name, counted)
+  count(DT, 'pointwise_weight_grads')
+  count(HT, 'heads_input_grad')
+  packs = net.pointwise_operand()['packs']
+  assert len(packs) == 4 and None not in packs
+  torch.cuda.synchronize()
+  before = [t.clone() for t in packs]
+  opt = trainer.Optimizer(a, lr=1e-3)
+  values, bad, status = trainer.train_step(net, images, gt, opt, 1e-3)
+  assert calls == {'pointwise_weight_grads': 0, 'heads_input_grad': 0}
+  assert status.tolist() == [0] * (3 + 2 * NET_O) and bad.tolist() == [0] * NET_B
+  for t, was in zip(packs, before):
+    assert same_bytes(t, was)
+  state = opt.state()
+  assert sorted(state) == sorted(loss.HEAD_VARIABLES +
+                                 tuple(n + '/Momentum' for n in loss.HEAD_VARIABLES))
+  assert len(state) == 12
+  for n in loss.HEAD_VARIABLES:                # the step itself was a step
+    assert state[n].tobytes() != np.asarray(a[n], np.float32).tobytes(), n
+  # the counters do count: the same step with the layer trained calls each once
+  net.set_weights(nine(a))
+  trainer.train_step(net, images, gt, trainer.Optimizer(a, lr=1e-3, trainable=DT.VARIABLES), 1e-3)
+  assert calls == {'pointwise_weight_grads': 1, 'heads_input_grad': 1}
+  net.set_weights(nine(a))
+
+
+def test_one_method_same_words(small_net, images):
+  from epos_amd import decoder_train as DT, weights
+  a = small_net[1]
+  b = weights.random_init('xception_65', num_objs=NET_O, num_frags=NET_F, seed=6,
+                          randomize_bn=True)
+  upd = build(a, instance=1)                  # the plan of the update test
+  upd.set_weights(nine(a))
+  want_a = all_runs(upd, images)
+  # the logits layers of b, then the layer of b ...
+  logits_status = upd.set_weights({n: b[n] for n in loss_names()})
+  layer_status = upd.set_weights({n: b[n] for n in DT.LAYER_VARIABLES})
+  in_two = all_runs(upd, images)
+  for run in in_two:
+    for k in ('pred_obj_conf', 'pred_frag_conf', 'pred_frag_loc'):
+      assert in_two[run][k].tobytes() != want_a[run][k].tobytes(), (run, k)
+  # ... and all nine in one call, from a again
+  upd.set_weights(nine(a))
+  assert_same(all_runs(upd, images), want_a, 'back')
+  all_status = upd.set_weights(nine(b))
+  assert_same(all_runs(upd, images), in_two, 'one call')
+  for status, words in ((logits_status, 3 + 2 * NET_O), (layer_status, 1),
+                        (all_status, 3 + 2 * NET_O + 1)):
+    assert status.dtype == torch.int32 and status.tolist() == [0] * words
+  upd.set_weights(nine(a))
 
 
 # ------------------------------------------------------------ command line ---
@@ -335,8 +403,8 @@ def _run(model_root, bop, fdir, *extra):
 
 
 def test_train_heads_cli_with_the_layer_unfrozen(tmp_path, gpu_children):
-  from epos_amd import cli, decoder_train as DT, eval_utils, frames as eframes, heads_train
-  from epos_amd import loss, model, ply, render, synthetic, tf_checkpoint, weights
+  from epos_amd import cli, decoder_train as DT, eval_utils, frames as eframes, loss, model
+  from epos_amd import ply, render, synthetic, tf_checkpoint, trainer, weights
   store = synthetic.ModelStore(O, F, seed=0)           # the store --synthetic builds
   bop = tmp_path / 'bop'
   (bop / 'lm' / 'models_eval').mkdir(parents=True)
@@ -394,20 +462,20 @@ def test_train_heads_cli_with_the_layer_unfrozen(tmp_path, gpu_children):
   frag_pool = render.pool_fragments(store.frag_centers, store.frag_sizes, O)
   frames = eframes.frames_from_dir(str(fdir), meta, H, W)
 
-  def steps(n, opt, step_fn, instance, status_words):
+  def steps(n, opt, instance, status_words):
     net = model.get_net(ckpt, 1, H, W, O, F, mo, 'cuda:0', instance=instance)
     for s in range(n):
       gt = eval_utils.gt_loss_fields_device(ren, frames[s % 2], (W // 4, H // 4), frag_pool,
                                             'lm', input_size=(W, H))
-      lr = heads_train.learning_rate(s, policy='step')
-      values, bad, status = step_fn(net, torch.from_numpy(images[s % 2][None]),
-                                    {k: gt[k][None] for k in loss.GT_KEYS}, opt, lr)
+      lr = trainer.learning_rate(s, policy='step')
+      values, bad, status = trainer.train_step(net, torch.from_numpy(images[s % 2][None]),
+                                               {k: gt[k][None] for k in loss.GT_KEYS}, opt, lr)
       assert bad.tolist() == [0] and status.tolist() == [0] * status_words
     return opt.state()
 
-  state = steps(3, DT.DecoderOptimizer(ckpt, 1e-4, momentum=0.9, weight_decay=4e-5,
-                                       last_layer_gradient_multiplier=2.0),
-                DT.train_step_decoder, 0, 3 + 2 * O + 1)
+  state = steps(3, trainer.Optimizer(ckpt, 1e-4, momentum=0.9, weight_decay=4e-5,
+                                     last_layer_gradient_multiplier=2.0, trainable=DT.VARIABLES),
+                0, 3 + 2 * O + 1)
   assert len(state) == 18 and int(whole['global_step']) == 3 and int(resumed['global_step']) == 3
   assert sorted(whole) == sorted(resumed) == sorted(
       list(ckpt) + [n + '/Momentum' for n in DT.VARIABLES] + ['global_step'])
@@ -419,9 +487,8 @@ def test_train_heads_cli_with_the_layer_unfrozen(tmp_path, gpu_children):
   for name in ckpt:
     moved = whole[name].tobytes() != np.asarray(ckpt[name]).tobytes()
     assert moved == (name in DT.VARIABLES), name       # the statistics and all else stay
-  # the default: the logits layers only, the bytes heads_train.train_step gives
-  plain = steps(1, heads_train.HeadsOptimizer(ckpt, 1e-4, momentum=0.9, weight_decay=4e-5),
-                heads_train.train_step, 1, 3 + 2 * O)
+  # the default: the logits layers only, the bytes the default Optimizer's train_step gives
+  plain = steps(1, trainer.Optimizer(ckpt, 1e-4, momentum=0.9, weight_decay=4e-5), 1, 3 + 2 * O)
   assert len(plain) == 12
   assert sorted(default) == sorted(list(ckpt) + [n + '/Momentum' for n in loss.HEAD_VARIABLES] +
                                    ['global_step'])

@@ -1,6 +1,6 @@
 """The weight update on the device: epos_pack_weights_device_f32 against the three host packers
-byte for byte, its refusals (all or nothing), EposNet.set_head_weights against a freshly built
-net (eager, captured graphs, sparse heads) and heads_train.train_step against its parts."""
+byte for byte, its refusals (all or nothing), EposNet.set_weights against a freshly built
+net (eager, captured graphs, sparse heads) and trainer.train_step against its parts."""
 import os
 import sys
 
@@ -200,12 +200,11 @@ def assert_same(got, want, tag):
 
 
 @pytest.mark.parametrize('packs', ['built_before', 'built_after'])
-def test_set_head_weights_equals_a_freshly_built_net(ckpts, images, net_a, net_b, net_upd,
-                                                     packs):
+def test_set_weights_equals_a_freshly_built_net(ckpts, images, net_a, net_b, net_upd, packs):
   a, ab = ckpts
   graphs = (net_upd._graph, net_upd._graph_logits)
   assert None not in graphs
-  net_upd.set_head_weights(six(a))                 # whatever an earlier test left
+  net_upd.set_weights(six(a))                 # whatever an earlier test left
   if packs == 'built_before':
     sparse_bytes(net_upd, images)
     assert net_upd._sparse_packs is not None
@@ -214,15 +213,15 @@ def test_set_head_weights_equals_a_freshly_built_net(ckpts, images, net_a, net_b
   want_a, want_b = all_runs(net_a, images), all_runs(net_b, images)
   assert want_a['logits_eager']['pred_obj_conf'].tobytes() != \
       want_b['logits_eager']['pred_obj_conf'].tobytes()
-  status = net_upd.set_head_weights(
+  status = net_upd.set_weights(
       {k: torch.from_numpy(v).cuda() for k, v in six(ab).items()})
   assert status.dtype == torch.int32 and status.tolist() == [0] * (3 + 2 * O)
   assert_same(all_runs(net_upd, images), want_b, packs)
   assert (net_upd._graph, net_upd._graph_logits) == graphs       # the graphs from before
   # one layer only (numpy arrays, [256, N] weights): the other two heads keep their bytes
   name = 'logits/pred_frag_conf/'
-  net_upd.set_head_weights({name + 'weights': a[name + 'weights'].reshape(256, -1),
-                            name + 'biases': a[name + 'biases']})
+  net_upd.set_weights({name + 'weights': a[name + 'weights'].reshape(256, -1),
+                       name + 'biases': a[name + 'biases']})
   got = all_runs(net_upd, images)
   for run in ('logits_eager', 'logits_graph', 'sparse'):
     assert got[run]['pred_frag_conf'].tobytes() == want_a[run]['pred_frag_conf'].tobytes(), run
@@ -233,18 +232,18 @@ def test_set_head_weights_equals_a_freshly_built_net(ckpts, images, net_a, net_b
 def test_refusal_through_the_net_and_argument_checks(ckpts, images, net_upd):
   from epos_amd._lib import EposError
   a, ab = ckpts
-  net_upd.set_head_weights(six(a))
+  net_upd.set_weights(six(a))
   before = host(net_upd.forward_logits(images))
   bad = six(ab)
   w = bad['logits/pred_frag_loc/weights'].copy()
   w[0, 0, 17, 100] = np.nan
   bad['logits/pred_frag_loc/weights'] = w
   with pytest.raises(EposError, match=r'refused logits/pred_frag_loc.*previous weights'):
-    net_upd.set_head_weights(bad)
+    net_upd.set_weights(bad)
   after = host(net_upd.forward_logits(images))
   for k in before:
     assert after[k].tobytes() == before[k].tobytes(), k
-  status = net_upd.set_head_weights(bad, check=False)
+  status = net_upd.set_weights(bad, check=False)
   # sorted layers: frag_conf, frag_loc, obj_conf; then 3 + 3 sparse packs: column 100 of
   # pred_frag_loc lies in the pack of object 1
   assert torch.nonzero(status).flatten().tolist() == [1, 6]
@@ -256,7 +255,7 @@ def test_refusal_through_the_net_and_argument_checks(ckpts, images, net_upd):
                          (dict(good, **{'logits/other/weights': good[name]}), ValueError),
                          ({name: good[name]}, ValueError)):
     with pytest.raises(exc):
-      net_upd.set_head_weights(variables)
+      net_upd.set_weights(variables)
 
 
 # -------------------------------------------------------------- train_step ---
@@ -265,16 +264,16 @@ def gt_fields(h, w, seed):
 
 
 def test_train_step_equals_its_parts(ckpts, images, net_a):
-  from epos_amd import heads_train
+  from epos_amd import trainer
   a = ckpts[0]
   lr, kw = 1e-3, dict(momentum=0.9, weight_decay=4e-5)
   gt = gt_fields(net_a.out_h, net_a.out_w, seed=41)
   # what the parent commit allows: gradients and the step on one net, then a NEW net built by
   # the host packers from the optimiser's state for the second step
-  ref_opt = heads_train.HeadsOptimizer(a, lr=lr, **kw)
+  ref_opt = trainer.Optimizer(a, lr=lr, **kw)
   ref_values = []
   net_a.forward_logits(images)
-  values, bad, grads = heads_train.net_head_grads(net_a, gt)
+  values, bad, grads = trainer.net_grads(net_a, gt, ref_opt.params)
   ref_values.append(values.cpu().numpy().copy())
   ref_opt.step(grads, lr)
   state = ref_opt.state()
@@ -282,16 +281,16 @@ def test_train_step_equals_its_parts(ckpts, images, net_a):
   second.update({k: v for k, v in state.items() if not k.endswith('/Momentum')})
   net2 = build(second)
   net2.forward_logits(images)
-  values, bad, grads = heads_train.net_head_grads(net2, gt)
+  values, bad, grads = trainer.net_grads(net2, gt, ref_opt.params)
   ref_values.append(values.cpu().numpy().copy())
   ref_opt.step(grads, lr)
   ref_state = ref_opt.state()
   # two train_steps on ONE net
   trainee = build(a)
-  opt = heads_train.HeadsOptimizer(a, lr=lr, **kw)
+  opt = trainer.Optimizer(a, lr=lr, **kw)
   got_values = []
   for _ in range(2):
-    values, bad, status = heads_train.train_step(trainee, images, gt, opt, lr)
+    values, bad, status = trainer.train_step(trainee, images, gt, opt, lr)
     got_values.append(values.cpu().numpy().copy())
     assert bad.tolist() == [0] * B and status.tolist() == [0] * (3 + 2 * O)
   for step in range(2):
@@ -304,7 +303,7 @@ def test_train_step_equals_its_parts(ckpts, images, net_a):
   for k in ref_state:
     assert got_state[k].tobytes() == ref_state[k].tobytes(), k
   # resuming: an optimiser restored from that state continues with the same bytes
-  resumed = heads_train.HeadsOptimizer(got_state, lr=lr, **kw)
+  resumed = trainer.Optimizer(got_state, lr=lr, **kw)
   for k in got_state:
     t = resumed.accums[k[:-9]] if k.endswith('/Momentum') else resumed.params[k]
     assert t.cpu().numpy().tobytes() == got_state[k].tobytes(), k

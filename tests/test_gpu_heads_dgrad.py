@@ -419,7 +419,7 @@ def test_heads_input_grad_entry_and_graph_capture():
   dX = heads_train.heads_input_grad(logits, gt, dev.sc, hw, upstream=up)
   assert dX.dtype == torch.float32 and tuple(dX.shape) == (B * h * w, K)
   assert dX.cpu().numpy().tobytes() == exp.tobytes()
-  # host arrays as HeadsOptimizer.state() holds them; out as a view of a wider buffer; workspace
+  # host arrays as trainer.Optimizer.state() holds them; out as a view of a wider buffer; workspace
   state = {k: v.cpu().numpy() for k, v in hw.items()}
   wide = torch.full((B, h, w, K + 8), -7.0, device='cuda')
   ws = torch.empty(((O + 1 + 4 * O * F) * K + 5,), device='cuda')

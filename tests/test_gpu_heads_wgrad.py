@@ -437,12 +437,12 @@ def test_heads_weight_grads_entry():
   assert loss.REDUCTIONS == {'mean': 0, 'pooled': 1}
 
 
-def test_net_head_grads_on_a_real_net(small_net):
-  from epos_amd import heads_train, loss
+def test_net_grads_of_the_logits_layers_on_a_real_net(small_net):
+  from epos_amd import heads_train, loss, trainer
   net, ckpt, _, c, gt = small_net
   B, h, w, O, F = NET_B, net.out_h, net.out_w, NET_O, NET_F
   K = int(net.decoder_out.shape[-1])
-  values, bad, grads = heads_train.net_head_grads(net, gt, WEIGHTS, 'pooled')
+  values, bad, grads = trainer.net_grads(net, gt, {}, weights=WEIGHTS, reduction='pooled')
   assert values.shape == (4,) and values.dtype == torch.float64 and bad.tolist() == [0] * B
   widths = dict(zip(KEYS, (O + 1, O * F, O * F * 3)))
   assert set(grads) == {n for k in KEYS for n in heads_train.variable_names(k)}
@@ -496,7 +496,7 @@ def test_descent_and_checkpoint(small_net, tmp_path):
   # is <= 1/2, the Huber term's <= 1; test_gpu_loss_grad.test_descent_on_the_logits). A step of
   # 1/(2L) on the weights and, with the biases' multiplier 2, 1/L on the biases stays below 2/L,
   # so it must decrease the total strictly while the gradient is not zero.
-  from epos_amd import heads_train, loss, tf_checkpoint
+  from epos_amd import heads_train, loss, tf_checkpoint, trainer
   net, ckpt, _, c, gt = small_net
   B, h, w, O, F = NET_B, net.out_h, net.out_w, NET_O, NET_F
   P = h * w
@@ -511,7 +511,7 @@ def test_descent_and_checkpoint(small_net, tmp_path):
             weights[2] * w_max / (3 * n_min)) / B
   A1 = torch.cat([A.double(), torch.ones((B * P, 1), dtype=torch.float64, device='cuda')], dim=1)
   lam = float(np.linalg.eigvalsh((A1.t() @ A1).cpu().numpy())[-1])
-  opt = heads_train.HeadsOptimizer(ckpt, lr=0.5 / (lip * lam), momentum=0.0, weight_decay=0.0)
+  opt = trainer.Optimizer(ckpt, lr=0.5 / (lip * lam), momentum=0.0, weight_decay=0.0)
   shapes = {'pred_obj_conf': (B, h, w, O + 1), 'pred_frag_conf': (B, h, w, O, F),
             'pred_frag_loc': (B, h, w, O, F, 3)}
   totals = []
@@ -554,7 +554,7 @@ def test_descent_and_checkpoint(small_net, tmp_path):
 
 
 def test_optimizer_multipliers():
-  from epos_amd import heads_train
+  from epos_amd import heads_train, trainer
   rng = np.random.RandomState(3)
   K, O, F = 5, 2, 3
   variables, grads = {}, {}
@@ -562,8 +562,8 @@ def test_optimizer_multipliers():
     wname, bname = heads_train.variable_names(k)
     variables[wname] = rng.randn(1, 1, K, n).astype(np.float32)
     variables[bname] = rng.randn(n).astype(np.float32)
-  opt = heads_train.HeadsOptimizer(variables, lr=0.01, momentum=0.9, weight_decay=4e-5,
-                                   last_layer_gradient_multiplier=10.0)
+  opt = trainer.Optimizer(variables, lr=0.01, momentum=0.9, weight_decay=4e-5,
+                          last_layer_gradient_multiplier=10.0)
   exp = {n: (v.copy(), np.zeros_like(v)) for n, v in variables.items()}
   for step in range(2):
     for n in variables:

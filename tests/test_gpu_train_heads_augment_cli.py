@@ -48,8 +48,8 @@ def _run(model_root, bop, fdir, *extra):
 
 
 def test_train_heads_cli_with_augmentations(tmp_path, gpu_children):
-  from epos_amd import augment, eval_utils, frames as eframes, heads_train, loss, model, ply
-  from epos_amd import render, synthetic, tf_checkpoint, weights
+  from epos_amd import augment, eval_utils, frames as eframes, loss, model, ply
+  from epos_amd import render, synthetic, tf_checkpoint, trainer, weights
   store = synthetic.ModelStore(O, F, seed=0)           # the store --synthetic builds
   bop = tmp_path / 'bop'
   (bop / 'lm' / 'models_eval').mkdir(parents=True)
@@ -105,12 +105,12 @@ def test_train_heads_cli_with_augmentations(tmp_path, gpu_children):
       ren.add_model(o, m)
     frag_pool = render.pool_fragments(store.frag_centers, store.frag_sizes, O)
     frames = eframes.frames_from_dir(str(fdir), meta, H, W)
-    opt = heads_train.HeadsOptimizer(ckpt, 1e-4, momentum=0.9, weight_decay=4e-5)
+    opt = trainer.Optimizer(ckpt, 1e-4, momentum=0.9, weight_decay=4e-5)
     for s in range(4):
       gt = eval_utils.gt_loss_fields_device(ren, frames[s % 2], (W // 4, H // 4), frag_pool,
                                             'lm', input_size=(W, H))
-      lr = heads_train.learning_rate(s, policy='step')
-      values, bad, status = heads_train.train_step(
+      lr = trainer.learning_rate(s, policy='step')
+      values, bad, status = trainer.train_step(
           net, torch.from_numpy(images[s % 2][None]), {k: gt[k][None] for k in loss.GT_KEYS},
           opt, lr, augment=augmenter, step=s)
       assert bad.tolist() == [0] and status.tolist() == [0] * (3 + 2 * O)

@@ -36,8 +36,8 @@ def _run(model_root, bop, fdir, *extra):
 
 
 def test_train_heads_cli(tmp_path, gpu_children):
-  from epos_amd import cli, eval_utils, frames as eframes, heads_train, loss, model, ply, render
-  from epos_amd import synthetic, tf_checkpoint, tf_events, weights
+  from epos_amd import cli, eval_utils, frames as eframes, loss, model, ply, render
+  from epos_amd import synthetic, tf_checkpoint, tf_events, trainer, weights
   store = synthetic.ModelStore(O, F, seed=0)           # the store --synthetic builds
   bop = tmp_path / 'bop'
   (bop / 'lm' / 'models_eval').mkdir(parents=True)
@@ -101,14 +101,14 @@ def test_train_heads_cli(tmp_path, gpu_children):
     ren.add_model(o, m)
   frag_pool = render.pool_fragments(store.frag_centers, store.frag_sizes, O)
   frames = eframes.frames_from_dir(str(fdir), meta, H, W)
-  opt = heads_train.HeadsOptimizer(ckpt, 1e-4, momentum=0.9, weight_decay=4e-5)
+  opt = trainer.Optimizer(ckpt, 1e-4, momentum=0.9, weight_decay=4e-5)
   totals = []
   for s in range(4):
     frame = frames[s % 2]
     gt = eval_utils.gt_loss_fields_device(ren, frame, (W // 4, H // 4), frag_pool, 'lm',
                                           input_size=(W, H))
-    lr = heads_train.learning_rate(s, train_steps=2 if s < 2 else 4)
-    values, bad, status = heads_train.train_step(
+    lr = trainer.learning_rate(s, train_steps=2 if s < 2 else 4)
+    values, bad, status = trainer.train_step(
         net, torch.from_numpy(images[s % 2][None]), {k: gt[k][None] for k in loss.GT_KEYS},
         opt, lr)
     assert bad.tolist() == [0] and status.tolist() == [0] * (3 + 2 * O)

@@ -1,5 +1,5 @@
 """The weight update without a device: the binding of epos_pack_weights_device_f32 and its
-host-side refusals, heads_train.learning_rate against hand-computed values, what
+host-side refusals, trainer.learning_rate against hand-computed values, what
 train_heads.prepare refuses, and the entries' behaviour on a machine without a GPU."""
 import ctypes
 import os
@@ -101,7 +101,7 @@ def test_host_side_refusals_of_epos_pack_weights_device_f32():
 
 
 def test_learning_rate_against_hand_computed_values():
-  from epos_amd.heads_train import learning_rate as lr
+  from epos_amd.trainer import learning_rate as lr
   T = 1000
   close = lambda a, b: abs(a - b) <= 4 * 2.0 ** -53 * abs(b)        # noqa: E731
   # poly, end_learning_rate = 0, the step clipped to train_steps
@@ -175,14 +175,15 @@ def test_train_heads_prepare_refuses_by_name(tmp_path, monkeypatch):
 
 def test_heads_train_still_imports_without_torch():
   code = ('import sys; sys.modules["torch"] = None\n'
-          'from epos_amd import heads_train\n'
-          'assert heads_train.learning_rate(0) == 1e-4\n'
+          'from epos_amd import heads_train, trainer\n'
+          'assert callable(heads_train.heads_weight_grads)\n'
+          'assert trainer.learning_rate(0) == 1e-4\n'
           'assert "torch" not in [m for m in sys.modules if sys.modules[m] is not None]\n')
   subprocess.check_call([sys.executable, '-c', code], cwd=ROOT)
 
 
 def test_entries_without_a_device(monkeypatch):
-  from epos_amd import heads_train, net, weights
+  from epos_amd import heads_train, net, trainer, weights
   from epos_amd._lib import EposError
   monkeypatch.setattr(torch.cuda, 'is_available', lambda: False)
   ckpt = weights.random_init('xception_65', num_objs=2, num_frags=4, seed=0)
@@ -191,9 +192,9 @@ def test_entries_without_a_device(monkeypatch):
     net.EposNet(ckpt, 1, 64, 64, 2, 4)
   plan = net.EposNet(ckpt, 1, 64, 64, 2, 4, dry_run=True)
   with pytest.raises(EposError, match='no CPU fallback'):
-    plan.set_head_weights(six)
+    plan.set_weights(six)
   with pytest.raises(EposError, match='no CPU fallback'):
-    heads_train.train_step(plan, None, None, None, 1e-4)
+    trainer.train_step(plan, None, None, None, 1e-4)
 
 
 def test_nets_out_of_scope_say_so():
@@ -202,10 +203,53 @@ def test_nets_out_of_scope_say_so():
   six = {n: ckpt[n] for h in heads_train.HEADS for n in heads_train.variable_names(h)}
   plan = net.EposNet(ckpt, 1, 64, 64, 2, 4, dry_run=True, precision='bf16')
   with pytest.raises(NotImplementedError, match='bf16'):
-    plan.set_head_weights(six)
+    plan.set_weights(six)
   with pytest.raises(NotImplementedError, match='multi-scale'):
-    multiscale.MultiScaleNet.set_head_weights(None, six)
+    multiscale.MultiScaleNet.set_weights(None, six)
   # the plan keeps references to the logits layers' weight tensors, and nothing else changed
   plan = net.EposNet(ckpt, 1, 64, 64, 2, 4, dry_run=True)
-  assert sorted(plan.mode.head_packs) == sorted(heads_train.HEADS)
-  assert np.all([len(v) == 4 for v in plan.mode.head_packs.values()])
+  assert sorted(plan.mode.packs) == sorted(weights.TRAINABLE_LAYERS)
+  assert sorted(s[len('logits/'):] for s in weights.LOGITS_LAYERS) == sorted(heads_train.HEADS)
+  assert np.all([len(packs) == 4 for _, _, packs in plan.mode.packs.values()])
+
+
+NINE = ('logits/pred_obj_conf/weights', 'logits/pred_obj_conf/biases',
+        'logits/pred_frag_conf/weights', 'logits/pred_frag_conf/biases',
+        'logits/pred_frag_loc/weights', 'logits/pred_frag_loc/biases',
+        'decoder/decoder_conv1_pointwise/weights',
+        'decoder/decoder_conv1_pointwise/BatchNorm/gamma',
+        'decoder/decoder_conv1_pointwise/BatchNorm/beta')
+
+
+def test_gradient_rule_gives_the_logits_variables_the_literals_of_the_logits_only_step():
+  """The optimiser of the logits layers alone hard-coded (m, decay) for weights and (2 m, 0)
+  for biases; gradient_rule gives the six variables the same under both scope settings."""
+  from epos_amd.trainer import gradient_rule
+  wd = 4e-5
+  table = {1.0: {'weights': (1.0, 4e-5), 'biases': (2.0, 0.0)},
+           3.0: {'weights': (3.0, 4e-5), 'biases': (6.0, 0.0)}}
+  for m, want in table.items():
+    for logits_only in (False, True):
+      for name in NINE[:6]:
+        assert gradient_rule(name, m, wd, logits_only) == want[name.rsplit('/', 1)[1]], (
+            name, m, logits_only)
+
+
+def test_the_table_is_the_only_source_of_names():
+  from epos_amd import decoder_train, loss, net, trainer, weights
+  assert loss.HEAD_VARIABLES == NINE[:6]
+  assert trainer.VARIABLES == NINE and decoder_train.VARIABLES == NINE
+  assert decoder_train.LAYER_VARIABLES == NINE[6:]
+  assert weights.trainable_variables() == NINE
+  # what set_weights accepts: a name alone is an incomplete layer, any other name is unknown
+  ckpt = weights.random_init('xception_65', num_objs=2, num_frags=4, seed=0)
+  plan = net.EposNet(ckpt, 1, 64, 64, 2, 4, dry_run=True)
+  accepted = []
+  for name in sorted(set(ckpt) | set(NINE)) + ['logits/pred_obj_conf/weights/Momentum']:
+    with pytest.raises(ValueError) as err:
+      plan.set_weights({name: np.zeros((1,), np.float32) if name not in ckpt else ckpt[name]})
+    if 'are set together' in str(err.value):
+      accepted.append(name)
+    else:
+      assert 'is not a variable' in str(err.value), name
+  assert len(ckpt) > 100 and sorted(accepted) == sorted(NINE)

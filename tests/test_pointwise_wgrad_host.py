@@ -262,7 +262,8 @@ def test_train_heads_prepare_accepts_the_layer(tmp_path, monkeypatch):
 
 
 def test_multiplier_and_decay_table():
-  from epos_amd.decoder_train import LAYER, VARIABLES, gradient_rule
+  from epos_amd.decoder_train import LAYER, VARIABLES
+  from epos_amd.trainer import gradient_rule
   assert len(VARIABLES) == 9 and VARIABLES[6:] == (
       LAYER + '/weights', LAYER + '/BatchNorm/gamma', LAYER + '/BatchNorm/beta')
   m, wd = 10.0, 4e-5
@@ -287,12 +288,12 @@ def test_multiplier_and_decay_table():
 
 def test_module_imports_without_torch_and_entries_need_a_device(monkeypatch):
   code = ('import sys; sys.modules["torch"] = None\n'
-          'from epos_amd import decoder_train\n'
+          'from epos_amd import decoder_train, trainer\n'
           'assert callable(decoder_train.pointwise_weight_grads)\n'
-          'assert decoder_train.gradient_rule("logits/x/biases", 3.0) == (6.0, 0.0)\n'
+          'assert trainer.gradient_rule("logits/x/biases", 3.0) == (6.0, 0.0)\n'
           'assert "torch" not in [m for m in sys.modules if sys.modules[m] is not None]\n')
   subprocess.check_call([sys.executable, '-c', code], cwd=ROOT)
-  from epos_amd import decoder_train, net, weights
+  from epos_amd import decoder_train, net, trainer, weights
   from epos_amd._lib import EposError
   with pytest.raises(EposError, match='no CPU fallback'):
     decoder_train.pointwise_weight_grads(torch.zeros(4, 8), torch.zeros(4, 8),
@@ -300,21 +301,23 @@ def test_module_imports_without_torch_and_entries_need_a_device(monkeypatch):
   monkeypatch.setattr(torch.cuda, 'is_available', lambda: False)
   ckpt = weights.random_init('xception_65', num_objs=2, num_frags=4, seed=0)
   with pytest.raises(EposError, match='no CPU fallback'):
-    decoder_train.DecoderOptimizer(ckpt, 1e-4)
+    trainer.Optimizer(ckpt, 1e-4, trainable=decoder_train.VARIABLES)
   with pytest.raises(EposError, match='no CPU fallback'):
-    decoder_train.train_step_decoder(None, None, None, None, 1e-4)
+    trainer.train_step(None, None, None, None, 1e-4)
   plan = net.EposNet(ckpt, 1, 64, 64, 2, 4, dry_run=True)
   nine = {n: ckpt[n] for n in decoder_train.VARIABLES}
   with pytest.raises(EposError, match='no CPU fallback'):
-    plan.set_layer_weights(nine)
+    plan.set_weights(nine)
   with pytest.raises(EposError, match='no CPU fallback'):
     plan.pointwise_operand()
   # the plan recorded the layer while it was built: A is the depthwise output, K = N = 256
-  a, lda, m, k, n, args, packs, ab = plan.mode.layer_operands[decoder_train.LAYER]
+  a, lda, m, k, n, args, ab = plan.mode.layer_operands[decoder_train.LAYER]
+  packs = plan.mode.packs[decoder_train.LAYER][2]
+  assert plan.mode.packs[decoder_train.LAYER][:2] == (k, n)
   assert (lda, k, n) == (256, 256, 256) and m == 16 * 16 and tuple(a.shape) == (1, 16, 16, 256)
   assert args.M == m and args.K == k and args.N == n and len(packs) == 4
   bf16 = net.EposNet(ckpt, 1, 64, 64, 2, 4, dry_run=True, precision='bf16')
   with pytest.raises(NotImplementedError, match='bf16'):
-    bf16.set_layer_weights(nine)
+    bf16.set_weights(nine)
   with pytest.raises(NotImplementedError, match='bf16'):
     bf16.pointwise_operand()

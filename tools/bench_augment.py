@@ -14,7 +14,7 @@ At B = 1 and B = 8 images of 640 x 480 with the seven-op chain in the reference'
       table that holds that stage's ops alone;
   (d) the host route: the same ops through numpy, scipy (the blur) and PIL (the round trip),
       one image per thread, 16 threads at most; wall clock, upload and download not counted;
-  (e) B = 1: heads_train.train_step with and without the augmenter, interleaved.
+  (e) B = 1: trainer.train_step with and without the augmenter, interleaved.
 Before timing, one full-size image is validated against tests/helpers/augment_ref.py: the six
 ops in front of the round trip to 2e-3 on [0,255], the levels entering the round trip as
 tests/test_gpu_augment.py compares them, and the round trip alone by the share of equal levels
@@ -86,7 +86,7 @@ def host_image(img, ops):
 
 def main():
   import torch
-  from epos_amd import augment, heads_train, net as enet, synthetic, weights
+  from epos_amd import augment, net as enet, synthetic, trainer, weights
   ap = argparse.ArgumentParser()
   ap.add_argument('--repeats', type=int, default=30)
   ap.add_argument('--host_repeats', type=int, default=3)
@@ -195,7 +195,7 @@ def main():
   # ---- (e) inside a training step, B = 1
   ckpt = weights.random_init('xception_65', num_objs=O, num_frags=F, seed=0, randomize_bn=True)
   net = enet.EposNet(ckpt, 1, H, W, O, F, device='cuda:0')
-  opt = heads_train.HeadsOptimizer(ckpt, lr=1e-4)
+  opt = trainer.Optimizer(ckpt, lr=1e-4)
   images = torch.from_numpy(synthetic.image(0, H, W)[None].astype(np.uint8)).cuda()
   gt_h, _ = label_maps(1, 1)
   gt_h[:, :6] = IGNORE
@@ -205,10 +205,10 @@ def main():
         'frag_weight': torch.ones((1, H // 4, W // 4), device='cuda')}
 
   def plain():
-    heads_train.train_step(net, images, gt, opt, 0.0)
+    trainer.train_step(net, images, gt, opt, 0.0)
 
   def augmented():
-    heads_train.train_step(net, images, gt, opt, 0.0, augment=aug, step=0)
+    trainer.train_step(net, images, gt, opt, 0.0, augment=aug, step=0)
 
   p_ms, s_ms = interleaved((plain, augmented))
   say('B=1, %dx%d: train_step %.4f ms; with the augmenter %.4f ms; augmentation adds %.4f ms '

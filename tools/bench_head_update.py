@@ -1,5 +1,5 @@
 """Times the weight update of the logits layers (csrc/weight_pack.hip through
-EposNet.set_head_weights) on the device, warm, with HIP events, next to the route the host
+EposNet.set_weights) on the device, warm, with HIP events, next to the route the host
 packers allow and next to the floor of anything that reads the weights and writes the packs.
 
     python tools/bench_head_update.py [--repeats 30] [--out profiles/r22/head_update_bench.txt]
@@ -7,16 +7,15 @@ packers allow and next to the floor of anything that reads the weights and write
 At the workload's size -- K = 256, 21 objects, 64 fragments: the three layers (22, 1344 and
 4032 columns) plus the 42 per-object packs of the sparse heads, 45 matrices, 2.8 M packed
 weights in four layouts -- on a 640 x 480 net at B = 1:
-  (a) net.set_head_weights(opt.params, check=False): one grouped device call;
+  (a) net.set_weights(opt.params, check=False): one grouped device call;
   (b) the route without the device packer, for the same effect on the same buffers: download
       the six tensors, net_modes._fold and the three host packers per matrix, copy_ into the
       plan's tensors;
   (c) the floor: device-to-device copies of every source tensor and, from scratch tensors of
       the same sizes, into every destination.
 (a), (b) and (c) are timed INTERLEAVED -- one call of each per round, each between its own two
-events -- and the medians of the rounds are reported. Then one heads_train.train_step against
-its parts (forward_logits from its graph, net_head_grads, HeadsOptimizer.step), interleaved the
-same way: the difference is what the update adds to a step.
+events -- and the medians of the rounds are reported. Then one trainer.train_step against its
+parts (forward_logits from its graph, net_grads, Optimizer.step), interleaved the same way: the difference is what the update adds to a step.
 Before timing, the bytes (a) leaves in the plan's tensors are compared with (b)'s.
 """
 import argparse
@@ -36,7 +35,7 @@ IGNORE = 255
 
 def main():
   import torch
-  from epos_amd import heads_train, net as enet, net_modes, synthetic, weights
+  from epos_amd import net as enet, net_modes, synthetic, trainer, weights
   ap = argparse.ArgumentParser()
   ap.add_argument('--repeats', type=int, default=30)
   ap.add_argument('--out', default=None)
@@ -45,21 +44,21 @@ def main():
   ckpt = weights.random_init('xception_65', num_objs=O, num_frags=F, seed=0, randomize_bn=True)
   net = enet.EposNet(ckpt, 1, H, W, O, F, device='cuda:0')
   mode = net.mode
-  opt = heads_train.HeadsOptimizer(ckpt, lr=1e-4)
+  opt = trainer.Optimizer(ckpt, lr=1e-4)
   net._build_sparse_packs()
-  layers = sorted(mode.head_packs)
+  layers = sorted(weights.outputs_to_num_channels(O, F))
   sparse = {'pred_frag_conf': (0, F), 'pred_frag_loc': (1, 3 * F)}
 
   def packs():
     """(layer, col0, n, (wp, bp, ws, wh)) of the 45 matrices."""
     for layer in layers:
-      yield layer, 0, opt.params['logits/%s/biases' % layer].numel(), mode.head_packs[layer]
+      yield layer, 0, opt.params['logits/%s/biases' % layer].numel(), mode.packs['logits/' + layer][2]
     for layer, (kind, n) in sorted(sparse.items()):
       for o in range(O):
         yield layer, o * n, n, net._sparse_packs[o][kind]
 
   def device_route():
-    net.set_head_weights(opt.params, check=False)
+    net.set_weights(opt.params, check=False)
 
   def host_route():
     host = {k: v.cpu().numpy() for k, v in opt.params.items()}
@@ -107,7 +106,7 @@ def main():
   want = [t.clone() for t in dsts]
   for t in dsts:
     t.view(torch.uint8).fill_(0xA5)
-  status = net.set_head_weights(opt.params, check=False)
+  status = net.set_weights(opt.params, check=False)
   torch.cuda.synchronize()
   assert status.tolist() == [0] * 45
   for got, exp in zip(dsts, want):
@@ -118,7 +117,7 @@ def main():
            '%.2f M weights; medians of %d warm interleaved rounds (HIP events)' % (
                O, F, sum(n for _, _, n, _ in packs()) * 256 / 1e6, args.repeats)]
   a_ms, b_ms, c_ms = interleaved((device_route, host_route, floor))
-  line = ('(a) set_head_weights(check=False) %.4f ms; (b) download + host packers + copy_ '
+  line = ('(a) set_weights(check=False) %.4f ms; (b) download + host packers + copy_ '
           '%.2f ms; (c) device-to-device copies, %.1f MB of sources and %.1f MB of packs, '
           '%.4f ms; (b) / (a) = %.0f; (a) / (c) = %.2f' % (
               a_ms, b_ms, src_bytes / 1e6, dst_bytes / 1e6, c_ms, b_ms / a_ms, a_ms / c_ms))
@@ -137,14 +136,14 @@ def main():
 
   def parts():
     net.forward_logits(images, use_graph=True)
-    values, bad, grads = heads_train.net_head_grads(net, gt)
+    values, bad, grads = trainer.net_grads(net, gt, opt.params)
     opt.step(grads, lr)
 
   def step():
-    heads_train.train_step(net, images, gt, opt, lr)
+    trainer.train_step(net, images, gt, opt, lr)
 
   p_ms, s_ms = interleaved((parts, step))
-  line = ('B=1, %dx%d: forward_logits + net_head_grads + HeadsOptimizer.step %.4f ms; '
+  line = ('B=1, %dx%d: forward_logits + net_grads + Optimizer.step %.4f ms; '
           'train_step %.4f ms; the update adds %.4f ms (%.1f %%)' % (
               W, H, p_ms, s_ms, s_ms - p_ms, 100.0 * (s_ms - p_ms) / p_ms))
   print(line, flush=True)

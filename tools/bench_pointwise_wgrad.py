@@ -14,8 +14,8 @@ with A behind a ReLU and a third of G zero, as the layer has them:
 All are timed INTERLEAVED -- one call of each per round, each between its own two events -- and
 the medians of the rounds are reported, with the fp64 rate 2 M K N / time of (a) and (b). Before
 timing, (a) is compared with (b) to (M + 16) 2^-52 sum |A||G|.
-Then, on a 640 x 480 net with 21 objects and 64 fragments at B = 1: decoder_train's
-train_step_decoder against heads_train.train_step, interleaved the same way, at lr = 0.
+Then, on a 640 x 480 net with 21 objects and 64 fragments at B = 1: trainer.train_step with
+the layer trained against the logits-only step, interleaved the same way, at lr = 0.
 """
 import argparse
 import ctypes
@@ -35,7 +35,7 @@ IGNORE = 255
 
 def main():
   import torch
-  from epos_amd import _lib, decoder_train, heads_train, net as enet, synthetic, weights
+  from epos_amd import _lib, net as enet, synthetic, trainer, weights
   ap = argparse.ArgumentParser()
   ap.add_argument('--repeats', type=int, default=30)
   ap.add_argument('--out', default=None)
@@ -144,8 +144,8 @@ def main():
   # a training step with the layer unfrozen against the heads-only step, B = 1
   ckpt = weights.random_init('xception_65', num_objs=O, num_frags=F, seed=0, randomize_bn=True)
   net = enet.EposNet(ckpt, 1, H, W, O, F, device='cuda:0')
-  heads_opt = heads_train.HeadsOptimizer(ckpt, lr=1e-4)
-  layer_opt = decoder_train.DecoderOptimizer(ckpt, lr=1e-4)
+  heads_opt = trainer.Optimizer(ckpt, lr=1e-4)
+  layer_opt = trainer.Optimizer(ckpt, lr=1e-4, trainable=trainer.VARIABLES)
   images = torch.from_numpy(synthetic.image(0, H, W)[None].astype(np.uint8)).cuda()
   gt_h, _ = label_maps(1, 1)
   gt_h[:, :6] = IGNORE
@@ -156,17 +156,17 @@ def main():
   lr = 0.0                                      # the weights stay where they are
 
   def heads_step():
-    heads_train.train_step(net, images, gt, heads_opt, lr)
+    trainer.train_step(net, images, gt, heads_opt, lr)
 
   def layer_step():
-    decoder_train.train_step_decoder(net, images, gt, layer_opt, lr)
+    trainer.train_step(net, images, gt, layer_opt, lr)
 
   def forward():
     net.forward_logits(images, use_graph=True)
 
   f_ms, h_ms, l_ms = interleaved((forward, heads_step, layer_step))
-  say('B=1, %dx%d, presplit A = %s: forward_logits %.4f ms; heads_train.train_step %.4f ms; '
-      'decoder_train.train_step_decoder %.4f ms; the layer adds %.4f ms (%.1f %%)' % (
+  say('B=1, %dx%d, presplit A = %s: forward_logits %.4f ms; train_step, logits only %.4f ms; '
+      'train_step with the layer %.4f ms; the layer adds %.4f ms (%.1f %%)' % (
           W, H, net.pointwise_operand()['presplit'], f_ms, h_ms, l_ms, l_ms - h_ms,
           100.0 * (l_ms - h_ms) / h_ms))
   if args.out:

@@ -12,7 +12,7 @@ By default everything below the logits stays frozen, as the reference does with
 --freeze_regex_list. A list that leaves variables of decoder/decoder_conv1_pointwise trainable
 (its weights, BatchNorm/gamma, BatchNorm/beta: --freeze_regex_list
 '^(?!logits|decoder/decoder_conv1_pointwise)') trains them too, with the batch-norm statistics
-frozen (epos_amd/decoder_train.py); any other unfrozen scope is refused. No
+frozen (epos_amd/trainer.py); any other unfrozen scope is refused. No
 batch-norm statistics, one device, fp32, one scale. --data_augmentations (a mapping in the YAML
 format, on the command line or in params.yml, datagen.py:629-670) runs on the device between
 the upload of a batch and its forward pass (epos_amd/augment.py); its draws are keyed by
@@ -35,7 +35,7 @@ the upload of a batch and its forward pass (epos_amd/augment.py); its draws are 
     train/obj_cls_loss, train/frag_cls_loss, train/frag_loc_loss and train/total_loss every
     --log_steps, and one line per log step on stdout.
 
-Each step is enqueued without waiting for the device (heads_train.train_step). At every log
+Each step is enqueued without waiting for the device (trainer.train_step). At every log
 step and before every save the run reads back what the steps since the last look left behind:
 the weight packer's status words and the counts of pixels with non-finite logits. If the
 packer refused an update (non-finite weights: the run has diverged) the run ends with exit
@@ -51,7 +51,8 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 if ROOT not in sys.path:
   sys.path.insert(0, ROOT)
 
-from epos_amd import cli, decoder_train, eval_utils, heads_train   # noqa: E402
+from epos_amd import cli, eval_utils, trainer   # noqa: E402
+from epos_amd import weights as W   # noqa: E402
 
 
 def build_parser():
@@ -104,9 +105,8 @@ TRAINABLE_OF_KIND = {'conv': ('weights', 'BatchNorm/gamma', 'BatchNorm/beta'),
 def unfrozen_below_logits(regexes, args):
   """The trainable variables below the logits that none of `regexes` freezes, in the network's
   order: the reference filters per variable name (train.py:369-371)."""
-  from epos_amd import weights
   names = []
-  for kind, scope, _, _ in weights.variable_specs(
+  for kind, scope, _, _ in W.variable_specs(
       args.model_variant, 1, args.num_frags, tuple(cli.as_list(args.atrous_rates, int))):
     if scope.startswith('logits/'):
       continue
@@ -140,11 +140,12 @@ def prepare(argv=None):
     regexes = args.freeze_regex_list
     regexes = [regexes] if isinstance(regexes, str) else list(regexes)
     free = unfrozen_below_logits(regexes, args)
-    other = [n for n in free if n not in decoder_train.LAYER_VARIABLES]
+    other = [n for n in free if n not in trainer.VARIABLES]
     if other:
       raise NotImplementedError(
           'freeze_regex_list=%r leaves %s trainable: train_heads.py trains the logits layers '
-          'and %s only' % (regexes, other[0], decoder_train.LAYER))
+          'and %s only' % (regexes, other[0], ', '.join(
+              s for s in W.TRAINABLE_LAYERS if s not in W.LOGITS_LAYERS)))
     args.layer_trainable = tuple(free)
   if not (args.dataset and os.environ.get('BOP_PATH')):
     raise ValueError('train_heads.py needs --dataset and $BOP_PATH (object models)')
@@ -156,7 +157,7 @@ def prepare(argv=None):
 
 
 def schedule(args, step):
-  return heads_train.learning_rate(
+  return trainer.learning_rate(
       step, args.learning_policy, args.base_learning_rate, args.learning_rate_decay_step,
       args.learning_rate_decay_factor, args.train_steps, args.learning_power,
       args.slow_start_step, args.slow_start_learning_rate)
@@ -210,18 +211,12 @@ def main(argv=None):
   net = model.get_net(ckpt, B, h, w, num_objs, args.num_frags,
                       cli.model_options(args, num_objs, w, h, None), dev)
   out_size = (net.out_w, net.out_h)
+  opt = trainer.Optimizer(
+      raw, args.base_learning_rate, args.momentum, args.weight_decay,
+      args.last_layer_gradient_multiplier, cli.str2bool(args.last_layers_contain_logits_only),
+      trainable=loss.HEAD_VARIABLES + args.layer_trainable, device=dev)
   if args.layer_trainable:
-    opt = decoder_train.DecoderOptimizer(
-        raw, args.base_learning_rate, args.momentum, args.weight_decay,
-        args.last_layer_gradient_multiplier, cli.str2bool(args.last_layers_contain_logits_only),
-        trainable=loss.HEAD_VARIABLES + args.layer_trainable, device=dev)
-    train_step = decoder_train.train_step_decoder
     print('Training below the logits: {}'.format(', '.join(args.layer_trainable)))
-  else:
-    opt = heads_train.HeadsOptimizer(
-        raw, args.base_learning_rate, args.momentum, args.weight_decay,
-        args.last_layer_gradient_multiplier, device=dev)
-    train_step = heads_train.train_step
   augmenter = None
   if args.data_augmentations:
     augmenter = augment.Augmenter(args.data_augmentations, args.seed, dev)
@@ -232,9 +227,9 @@ def main(argv=None):
   held_max = 2
   feed = eframes.Prefetcher(order, B, h, w, workers=args.decode_threads or None,
                             ahead=max(1, args.prefetch), inflight=held_max)
-  # what the steps since the last look left behind, on the device
-  refused = torch.zeros(3 + 2 * num_objs + bool(args.layer_trainable), dtype=torch.int32,
-                        device=dev)
+  # what the steps since the last look left behind, on the device (refused: sized by the first
+  # step's status words)
+  refused = None
   bad_pixels = torch.zeros((), dtype=torch.int64, device=dev)
   events = tf_events.EventWriter(checkpoint_dir) if todo else None
 
@@ -254,9 +249,9 @@ def main(argv=None):
                                                input_size=(w, h)) for f in chunk]
     gt = {k: torch.stack([f[k] for f in fields]) for k in loss.GT_KEYS}
     lr = schedule(args, step)
-    values, bad, status = train_step(net, imgs, gt, opt, lr, weights, augment=augmenter,
-                                     step=step)
-    refused.bitwise_or_(status)
+    values, bad, status = trainer.train_step(net, imgs, gt, opt, lr, weights,
+                                             augment=augmenter, step=step)
+    refused = status.clone() if refused is None else refused.bitwise_or_(status)
     bad_pixels.add_(bad.sum())
     step += 1
     last = step == args.train_steps
