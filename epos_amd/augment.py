@@ -18,8 +18,8 @@ import ctypes
 
 import numpy as np
 
+from epos_amd import _call as C
 from epos_amd import _lib
-from epos_amd._lib import EposError
 
 NONE, BRIGHTNESS, CONTRAST, SATURATION, HUE, BLUR, NOISE, JPEG = range(8)
 MAX_OPS = 8
@@ -183,8 +183,7 @@ def apply_ops(images, table, workspace=None):
   is large enough. Returns the workspace used. Enqueues on the current stream."""
   import torch
   lib = _lib.load()
-  if not images.is_cuda:
-    raise EposError('augmentation needs a HIP device (there is no CPU fallback)')
+  C.need_device(images, 'augmentation needs a HIP device (there is no CPU fallback)')
   if images.dtype != torch.float32 or images.dim() != 4 or images.shape[3] != 3 or \
       not images.is_contiguous():
     raise ValueError('images must be a contiguous float32 tensor [B,H,W,3], got %s %s' % (
@@ -198,12 +197,10 @@ def apply_ops(images, table, workspace=None):
   nbytes = _lib.check(lib.epos_augment_workspace_bytes(B, h, w), 'epos_augment_workspace_bytes')
   ws = workspace
   if ws is None or ws.device != dev or ws.numel() * ws.element_size() < nbytes:
-    ws = torch.empty(((nbytes + 7) // 8 or 1,), dtype=torch.int64, device=dev)
-  stream = torch.cuda.current_stream(dev)
-  with torch.cuda.device(dev):
+    ws = C.workspace(None, dev, nbytes)     # a small or foreign one is replaced, not refused
+  with C.launch(dev) as q:
+    q.keep(ws)
     _lib.check(lib.epos_augment_f32(
-        ctypes.c_void_p(images.data_ptr()), B, h, w, ctypes.c_void_p(table.ctypes.data), n_ops,
-        ctypes.c_void_p(ws.data_ptr()), ctypes.c_void_p(stream.cuda_stream)),
+        C.ptr(images), B, h, w, ctypes.c_void_p(table.ctypes.data), n_ops, C.ptr(ws), q.handle),
                'epos_augment_f32')
-  ws.record_stream(stream)
   return ws

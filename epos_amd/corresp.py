@@ -12,15 +12,9 @@ import ctypes
 import numpy as np
 import torch
 
+from epos_amd import _call as C
 from epos_amd import _lib
-
-
-def _ptr(t):
-  return ctypes.c_void_p(t.data_ptr())
-
-
-def _stream(dev):
-  return ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+from epos_amd._call import ptr as _ptr
 
 
 def pack_model_store(model_store, num_objs, num_frags):
@@ -55,8 +49,7 @@ class CorrExtractor(object):
 
   def __init__(self, batch, out_h, out_w, num_objs, num_frags, frag_centers,
                frag_sizes, max_slots, capacity, device='cuda:0'):
-    if not torch.cuda.is_available():
-      raise _lib.EposError('CorrExtractor needs a HIP device (no CPU fallback).')
+    C.need_device(None, 'CorrExtractor needs a HIP device (no CPU fallback).')
     self.lib = _lib.load()
     self.dev = torch.device(device)
     self.B, self.h, self.w = batch, out_h, out_w
@@ -110,7 +103,7 @@ class CorrExtractor(object):
     """Launches mask + scan + slot bases; nothing synchronises."""
     if not self.S:
       return
-    s = _stream(self.dev)
+    s = C.stream_handle(self.dev)[1]
     _lib.check(self.lib.epos_corr_count(
         _ptr(obj_confs), _ptr(frag_confs), _ptr(self.slots), self.S, self.B,
         self.P, self.O, self.F, float(np.float32(min_obj_conf)),
@@ -131,7 +124,7 @@ class CorrExtractor(object):
         self.P, self.w, self.O, self.F, 1.0 / output_scale, _ptr(self.px_off),
         _ptr(self.corr_off), _ptr(self.frag_mask), _ptr(self.slot_base),
         self.capacity, ctypes.byref(self._out), _ptr(self.overflow),
-        _stream(self.dev)), 'epos_corr_fill')
+        C.stream_handle(self.dev)[1]), 'epos_corr_fill')
 
 
 def confidence_order(conf):
@@ -178,8 +171,8 @@ class CorrOrderer(object):
         _ptr(ex.conf), _ptr(ex.px_id), _ptr(ex.coord_2d), _ptr(ex.coord_3d),
         _ptr(ex.slot_base), ex.S, ex.capacity, ex.w, self.max_corr, self.always_sort,
         _ptr(self.work), _ptr(self.slot_base), _ptr(self.coord_2d), _ptr(self.coord_3d),
-        _ptr(self.src_row), _ptr(self.yorder), _ptr(self.ypos), _stream(ex.dev)),
-               'epos_corr_order_by_conf')
+        _ptr(self.src_row), _ptr(self.yorder), _ptr(self.ypos),
+        C.stream_handle(ex.dev)[1]), 'epos_corr_order_by_conf')
 
 
 NO_MODELS_MESSAGE = (
@@ -215,8 +208,7 @@ class MeshProjector(object):
     _lib.check(self.lib.epos_project_rows_to_mesh_f64(
         _ptr(ex.coord_3d), _ptr(ex.slot_base), _ptr(ex.slots), ex.S, ex.capacity,
         _ptr(t.recs_dev), t.num_objs, _ptr(t.geom_dev), _ptr(t.fid_dev),
-        _ptr(face_idx) if face_idx is not None else None,
-        _ptr(visited) if visited is not None else None, _stream(ex.dev)),
+        _ptr(face_idx), _ptr(visited), C.stream_handle(ex.dev)[1]),
                'epos_project_rows_to_mesh_f64')
 
 
@@ -249,12 +241,13 @@ def establish_many_to_many(
   centers, sizes = pack_model_store(model_store, num_objs, num_frags)
   ex = CorrExtractor(1, h, w, num_objs, num_frags, centers, sizes,
                      max_slots=len(obj_ids), capacity=0, device=device)
-  ex.set_slots([(0, o) for o in obj_ids])
-  ex.count(obj_confs, frag_confs, min_obj_conf, min_frag_rel_conf)
-  totals = ex.totals[:ex.S].cpu().numpy()          # sync: sizes are data dependent
-  base = np.concatenate([[0], np.cumsum(totals[:, 1], dtype=np.int64)])
-  ex._alloc_out(int(base[-1]))
-  ex.fill(obj_confs, frag_confs, frag_coords, output_scale)
+  with C.launch(dev):                               # count and fill take dev's current stream
+    ex.set_slots([(0, o) for o in obj_ids])
+    ex.count(obj_confs, frag_confs, min_obj_conf, min_frag_rel_conf)
+    totals = ex.totals[:ex.S].cpu().numpy()        # sync: sizes are data dependent
+    base = np.concatenate([[0], np.cumsum(totals[:, 1], dtype=np.int64)])
+    ex._alloc_out(int(base[-1]))
+    ex.fill(obj_confs, frag_confs, frag_coords, output_scale)
   if int(ex.overflow.item()):
     raise _lib.EposError('correspondence buffer overflow')
   host = {k: getattr(ex, k).cpu().numpy() for k in
@@ -284,9 +277,10 @@ def project_pts_to_model(pts, verts, faces, device='cuda:0', return_faces=False)
   Fc = torch.as_tensor(np.ascontiguousarray(faces, np.int32)).to(dev)
   out = torch.empty_like(P)
   fidx = torch.empty(P.shape[0], dtype=torch.int32, device=dev)
-  _lib.check(lib.epos_project_to_mesh_f64(
-      _ptr(P), P.shape[0], _ptr(V), V.shape[0], _ptr(Fc), Fc.shape[0], _ptr(out),
-      _ptr(fidx), _stream(dev)), 'epos_project_to_mesh_f64')
+  with C.launch(dev) as q:
+    _lib.check(lib.epos_project_to_mesh_f64(
+        _ptr(P), P.shape[0], _ptr(V), V.shape[0], _ptr(Fc), Fc.shape[0], _ptr(out),
+        _ptr(fidx), q.handle), 'epos_project_to_mesh_f64')
   if return_faces:
     return out.cpu().numpy(), fidx.cpu().numpy()
   return out.cpu().numpy()

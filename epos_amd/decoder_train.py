@@ -18,9 +18,9 @@ torch's fp64 autograd; parity with TensorFlow's gradients is unpinned. There is 
 """
 import ctypes
 
+from epos_amd import _call as C
 from epos_amd import _lib
 from epos_amd._lib import EposError
-from epos_amd import loss as L
 from epos_amd import weights as W
 
 LAYER = W.DECODER_CONV1_POINTWISE
@@ -54,8 +54,7 @@ def pointwise_weight_grads(a, g, weights, bn=None, eps=BN_EPS, a_h2=None, out=No
   the current stream; does not synchronise."""
   import torch
   lib = _lib.load()
-  if not g.is_cuda:
-    raise EposError('the weight gradients need a HIP device (there is no CPU fallback)')
+  C.need_device(g, 'the weight gradients need a HIP device (there is no CPU fallback)')
   dev = g.device
   for t, what in ((a, 'a'), (g, 'g'), (weights, 'weights')):
     if t.device != dev:
@@ -67,8 +66,8 @@ def pointwise_weight_grads(a, g, weights, bn=None, eps=BN_EPS, a_h2=None, out=No
     raise ValueError('weights must be [1, 1, %d, %d], got %s' % (K, N, tuple(weights.shape)))
   if not weights.is_contiguous():
     raise ValueError('weights must be contiguous')
-  a2, lda = L._rows(a, K)
-  g2, ldg = L._rows(g, N)
+  a2, lda = C.rows(a, K)
+  g2, ldg = C.rows(g, N)
   M = int(a2.shape[0])
   if g2.shape[0] != M or M < 1:
     raise ValueError('a holds %d rows, g %d' % (M, g2.shape[0]))
@@ -80,10 +79,7 @@ def pointwise_weight_grads(a, g, weights, bn=None, eps=BN_EPS, a_h2=None, out=No
     if len(bn) != 3:
       raise ValueError('bn = (gamma, moving_mean, moving_variance)')
     for t, what in zip(bn, ('gamma', 'moving_mean', 'moving_variance')):
-      if (t.device != dev or t.dtype != torch.float32 or tuple(t.shape) != (N,) or
-          not t.is_contiguous()):
-        raise ValueError('%s must be a contiguous float32 tensor of shape (%d,) on %s' % (
-            what, N, dev))
+      C.dense(t, dev, torch.float32, what, shape=(N,), name='float32')
     consts = list(bn)
   slots = [None, None]
   gain = bias = 0.0
@@ -98,25 +94,24 @@ def pointwise_weight_grads(a, g, weights, bn=None, eps=BN_EPS, a_h2=None, out=No
       raise ValueError('a_h2: a pre-split a needs its absmax slot')
   result = {}
   for name in names:
-    result[name] = L._out((out or {}).get(name), dev, torch.float32,
+    result[name] = C.out((out or {}).get(name), dev, torch.float32,
                           W.variable_shapes(name, K, N)[0], 'out[%r]' % name, flat=True)
-  ws = L._workspace(workspace, dev, 8 * workspace_words(M, K, N), torch.int64)
+  ws = C.workspace(workspace, dev, 8 * workspace_words(M, K, N), torch.int64)
   S, gsum, slabs = ws[:K * N], ws[K * N:K * N + N], ws[K * N + N:]
   args = _lib.PointwiseWgradArgs(
-      A=L._ptr(a2), lda=lda, G=L._ptr(g2), ldg=ldg, M=M, K=K, N=N,
-      a_presplit=int(a_h2 is not None), a_amax=L._ptr(slots[0]), a_amax2=L._ptr(slots[1]),
-      a_gain=gain, a_bias=bias, S=L._ptr(S), g=L._ptr(gsum),
-      workspace=L._ptr(slabs) if slabs.numel() else None)
-  stream, sp = L._stream_handle(dev)
-  with torch.cuda.device(dev):
-    _lib.check(lib.epos_pointwise_wgrad_f32(ctypes.byref(args), sp), 'epos_pointwise_wgrad_f32')
+      A=C.ptr(a2), lda=lda, G=C.ptr(g2), ldg=ldg, M=M, K=K, N=N,
+      a_presplit=int(a_h2 is not None), a_amax=C.ptr(slots[0]), a_amax2=C.ptr(slots[1]),
+      a_gain=gain, a_bias=bias, S=C.ptr(S), g=C.ptr(gsum),
+      workspace=C.ptr(slabs) if slabs.numel() else None)
+  with C.launch(dev) as q:
+    q.keep(a2, g2, ws)
+    _lib.check(lib.epos_pointwise_wgrad_f32(ctypes.byref(args), q.handle),
+               'epos_pointwise_wgrad_f32')
     _lib.check(lib.epos_pointwise_wgrad_close_f32(
-        L._ptr(S), L._ptr(gsum), L._ptr(weights), K, N, L._ptr(consts[0]), L._ptr(consts[1]),
-        L._ptr(consts[2]), float(eps), L._ptr(result['weights']),
-        L._ptr(result['BatchNorm/gamma']) if bn is not None else None,
-        L._ptr(result[names[-1]]), sp), 'epos_pointwise_wgrad_close_f32')
-  for t in (a2, g2, ws):
-    t.record_stream(stream)             # temporaries and dense copies made here outlive the call
+        C.ptr(S), C.ptr(gsum), C.ptr(weights), K, N, C.ptr(consts[0]), C.ptr(consts[1]),
+        C.ptr(consts[2]), float(eps), C.ptr(result['weights']),
+        C.ptr(result['BatchNorm/gamma']) if bn is not None else None,
+        C.ptr(result[names[-1]]), q.handle), 'epos_pointwise_wgrad_close_f32')
   return result
 
 

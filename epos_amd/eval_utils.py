@@ -13,12 +13,12 @@ metric (include/epos_hip.h, "Evaluation"; DESIGN.md, "Evaluation").
 
 There is no CPU fallback: without the library or a device SegmentationEval raises EposError.
 """
-import ctypes
 import json
 import os
 
 import numpy as np
 
+from epos_amd import _call as C
 from epos_amd import _lib
 from epos_amd._lib import EposError
 
@@ -27,10 +27,6 @@ TAG_MIOU_FG = 'eval/obj_cls_miou_fg'         # eval_utils.py:113
 TAG_FRAG_ACC = 'eval/frag_acc'               # this build
 TAG_FRAG_ACC_SEG = 'eval/frag_acc_seg'
 LAST_EVALUATION = 'last_evaluation.json'
-
-
-def _ptr(t):
-  return ctypes.c_void_p(t.data_ptr()) if t is not None else None
 
 
 def miou_from_confusion(cm):
@@ -81,8 +77,7 @@ class SegmentationEval(object):
 
   def __init__(self, num_objs, ignore_label=255, device=None, num_frags=None):
     import torch
-    if not torch.cuda.is_available():
-      raise EposError('evaluation needs a HIP device (there is no CPU fallback)')
+    C.need_device(None, 'evaluation needs a HIP device (there is no CPU fallback)')
     self.lib = _lib.load()
     self.device = torch.device(device if device is not None else 'cuda:0')
     self.num_objs, self.num_cls = int(num_objs), int(num_objs) + 1
@@ -92,43 +87,32 @@ class SegmentationEval(object):
     self.bad = torch.zeros((1,), dtype=torch.int64, device=self.device)
     self.frag_counts = torch.zeros((self.num_cls, 3), dtype=torch.int64, device=self.device)
 
-  def _flat(self, t, dtype, numel=None, what=''):
-    if t.device != self.device:
-      raise EposError('%s is on %s, the evaluation on %s' % (what, t.device, self.device))
-    if t.dtype != dtype:
-      raise TypeError('%s must be %s, got %s' % (what, dtype, t.dtype))
-    t = t.contiguous().reshape(-1)
-    if numel is not None and t.numel() != numel:
-      raise ValueError('%s holds %d values, expected %d' % (what, t.numel(), numel))
-    return t
-
   def update(self, gt_obj_label, pred_obj_label, gt_frag_label=None, pred_frag_conf=None):
     """Adds one batch: gt_obj_label i32 and pred_obj_label i64 of one (any) batch shape, and
     for the fragment counts gt_frag_label i32 of that shape and pred_frag_conf f32 [..., O, F].
     Enqueues on the current stream; does not synchronise."""
     import torch
-    gt = self._flat(gt_obj_label, torch.int32, None, 'gt_obj_label')
+    def flat(t, dtype, numel, what):
+      return C.flat(t, self.device, dtype, numel, what, 'the evaluation')
+
+    gt = flat(gt_obj_label, torch.int32, None, 'gt_obj_label')
     P = gt.numel()
-    pred = self._flat(pred_obj_label, torch.int64, P, 'pred_obj_label')
-    stream = torch.cuda.current_stream(self.device)
-    s = ctypes.c_void_p(stream.cuda_stream)
-    held = [gt, pred]
-    with torch.cuda.device(self.device):
+    pred = flat(pred_obj_label, torch.int64, P, 'pred_obj_label')
+    with C.launch(self.device) as q:
+      q.keep(gt, pred)                  # contiguous copies made here outlive this call
       _lib.check(self.lib.epos_eval_confusion(
-          _ptr(gt), _ptr(pred), P, self.num_cls, self.ignore_label, _ptr(self.cm),
-          _ptr(self.bad), s), 'epos_eval_confusion')
+          C.ptr(gt), C.ptr(pred), P, self.num_cls, self.ignore_label, C.ptr(self.cm),
+          C.ptr(self.bad), q.handle), 'epos_eval_confusion')
       if gt_frag_label is not None or pred_frag_conf is not None:
         if self.num_frags is None or gt_frag_label is None or pred_frag_conf is None:
           raise ValueError('fragment counts need num_frags, gt_frag_label and pred_frag_conf')
-        gf = self._flat(gt_frag_label, torch.int32, P, 'gt_frag_label')
-        conf = self._flat(pred_frag_conf, torch.float32, P * self.num_objs * self.num_frags,
-                          'pred_frag_conf')
+        gf = flat(gt_frag_label, torch.int32, P, 'gt_frag_label')
+        conf = flat(pred_frag_conf, torch.float32, P * self.num_objs * self.num_frags,
+                    'pred_frag_conf')
+        q.keep(gf, conf)
         _lib.check(self.lib.epos_eval_frag_hits(
-            _ptr(gt), _ptr(gf), _ptr(pred), _ptr(conf), P, self.num_objs, self.num_frags,
-            self.ignore_label, _ptr(self.frag_counts), s), 'epos_eval_frag_hits')
-        held += [gf, conf]
-    for t in held:                      # contiguous copies made here outlive this call
-      t.record_stream(stream)
+            C.ptr(gt), C.ptr(gf), C.ptr(pred), C.ptr(conf), P, self.num_objs, self.num_frags,
+            self.ignore_label, C.ptr(self.frag_counts), q.handle), 'epos_eval_frag_hits')
 
   def confusion_matrix(self):
     """The matrix as a host int64 array (synchronises). Raises EposError when a label outside

@@ -2,25 +2,20 @@
 ``epos_lib/fragment.py::fragmentation_fps`` (fragment.py:8-54) and the size rule
 of ``ObjectModelStore.fragment_models`` (datagen.py:86-126); writes / reads the
 reference's ``fragments.pkl`` (datagen.py:254-296)."""
-import ctypes
 import pickle
 
 import numpy as np
 import torch
 
+from epos_amd import _call as C
 from epos_amd import _lib
-
-
-def _ptr(t):
-  return ctypes.c_void_p(t.data_ptr())
 
 
 def fragmentation_fps(vertices, num_frags, device='cuda:0'):
   """Same contract as fragment.py:8-54: returns ([num_frags,3] f64 fragment
   centres, [num_vertices] int64 fragment id per vertex). Runs the HIP kernels of
   csrc/fragment.hip."""
-  if not torch.cuda.is_available():
-    raise _lib.EposError('fragmentation_fps needs a HIP device (no CPU fallback).')
+  C.need_device(None, 'fragmentation_fps needs a HIP device (no CPU fallback).')
   lib = _lib.load()
   v = torch.as_tensor(np.ascontiguousarray(vertices, np.float64)).to(device)
   n = v.shape[0]
@@ -29,10 +24,10 @@ def fragmentation_fps(vertices, num_frags, device='cuda:0'):
   centers = torch.empty(num_frags, 3, dtype=torch.float64, device=device)
   cidx = torch.empty(num_frags, dtype=torch.int32, device=device)
   ids = torch.empty(n, dtype=torch.int32, device=device)
-  stream = ctypes.c_void_p(torch.cuda.current_stream(v.device).cuda_stream)
-  _lib.check(lib.epos_fragmentation_fps(_ptr(v), n, num_frags, _ptr(nn),
-                                        _ptr(centers), _ptr(cidx), _ptr(ids),
-                                        stream), 'epos_fragmentation_fps')
+  with C.launch(v.device) as q:
+    _lib.check(lib.epos_fragmentation_fps(C.ptr(v), n, num_frags, C.ptr(nn),
+                                          C.ptr(centers), C.ptr(cidx), C.ptr(ids),
+                                          q.handle), 'epos_fragmentation_fps')
   return centers.cpu().numpy(), ids.cpu().numpy().astype(np.int64)
 
 

@@ -21,6 +21,7 @@ Pinned to tests/helpers/heads_wgrad_ref.py and, through loss_grad_ref.py, to tor
 autograd; parity with TensorFlow's numbers is unpinned, as for the losses. There is no CPU
 fallback: without the library or a device this raises EposError.
 """
+from epos_amd import _call as C
 from epos_amd import _lib
 from epos_amd._lib import EposError
 from epos_amd import loss as L
@@ -41,13 +42,13 @@ def heads_weight_grads(features, logits, gt, scales, upstream=None, ignore_label
   written. Enqueues on the current stream; does not synchronise."""
   import torch
   lib = _lib.load()
-  bt = L._Batch(logits, gt, 'the weight gradients need', scales, upstream)
+  bt = L.Batch(logits, gt, 'the weight gradients need', scales, upstream)
   dev, B, P, O, F, n = bt.dev, bt.B, bt.P, bt.O, bt.F, bt.n
   if features.device != dev:
     raise EposError('features are on %s, the logits on %s' % (features.device, dev))
-  L._need_fp32(features)
+  L.need_fp32(features)
   K = int(features.shape[-1])
-  feat2, lda = L._rows(features, K)
+  feat2, lda = C.rows(features, K)
   if feat2.shape[0] != n:
     raise ValueError('features hold %d rows, expected %d' % (feat2.shape[0], n))
   widths = (O + 1, O * F, O * F * 3)
@@ -58,20 +59,18 @@ def heads_weight_grads(features, logits, gt, scales, upstream=None, ignore_label
       given = (out or {}).get(head)
       for j, shape in enumerate(((K, widths[k]), (widths[k],))):
         if given is None or given[j] is not None:
-          pair[j] = L._out(given and given[j], dev, torch.float32, shape,
+          pair[j] = C.out(given and given[j], dev, torch.float32, shape,
                            'out[%r][%d]' % (head, j))
     ptrs += pair
     result[head] = tuple(pair) if need[k] else None
   nbytes = lib.epos_heads_wgrad_workspace_bytes(B, P, O, F, K)
   _lib.check(nbytes, 'epos_heads_wgrad_workspace_bytes')
-  ws = L._workspace(workspace, dev, nbytes)
-  stream, sp = L._stream_handle(dev)
-  with torch.cuda.device(dev):
+  ws = C.workspace(workspace, dev, nbytes)
+  with C.launch(dev) as q:
+    q.keep(feat2, ws, *bt.keep)
     _lib.check(lib.epos_heads_wgrad_f32(
-        L._ptr(feat2), lda, K, *bt.grad_args(ignore_label), L._ptr(ws),
-        *[L._ptr(t) for t in ptrs], sp), 'epos_heads_wgrad_f32')
-  for t in bt.keep + [feat2, ws]:
-    t.record_stream(stream)           # temporaries and dense copies made here outlive the call
+        C.ptr(feat2), lda, K, *bt.grad_args(ignore_label), C.ptr(ws),
+        *[C.ptr(t) for t in ptrs], q.handle), 'epos_heads_wgrad_f32')
   return result
 
 
@@ -91,7 +90,7 @@ def heads_input_grad(logits, gt, scales, head_weights, upstream=None, relu_of=No
   written. Enqueues on the current stream; does not synchronise."""
   import torch
   lib = _lib.load()
-  bt = L._Batch(logits, gt, 'the input gradient needs', scales, upstream)
+  bt = L.Batch(logits, gt, 'the input gradient needs', scales, upstream)
   dev, O, F, n = bt.dev, bt.O, bt.F, bt.n
   widths = (O + 1, O * F, O * F * 3)
   mats, K = [], None
@@ -108,7 +107,7 @@ def heads_input_grad(logits, gt, scales, head_weights, upstream=None, relu_of=No
       raise ValueError('%s has %d input channels, expected %d' % (wname, m.shape[-2], K))
     mats.append(m.reshape(K, width))
   rows = sum(widths)
-  wt = L._workspace(workspace, dev, 4 * rows * K, torch.float32).view(-1)[:rows * K].view(rows, K)
+  wt = C.workspace(workspace, dev, 4 * rows * K, torch.float32).view(-1)[:rows * K].view(rows, K)
   r0 = 0
   for m, width in zip(mats, widths):
     wt[r0:r0 + width].copy_(m.t())                 # to the device and to float32 where needed
@@ -120,21 +119,19 @@ def heads_input_grad(logits, gt, scales, head_weights, upstream=None, relu_of=No
     if relu_of.dtype != torch.float32 or relu_of.shape[-1] != K:
       raise TypeError('relu_of must be torch.float32 [..., %d], got %s %s' % (
           K, relu_of.dtype, tuple(relu_of.shape)))
-    y2, ldy = L._rows(relu_of, K)
+    y2, ldy = C.rows(relu_of, K)
     if y2.shape[0] != n:
       raise ValueError('relu_of holds %d rows, expected %d' % (y2.shape[0], n))
-  out = L._out(out, dev, torch.float32, (n, K), 'out', rows=True)
-  out2, ldx = L._rows(out, K)
+  out = C.out(out, dev, torch.float32, (n, K), 'out', rows=True)
+  out2, ldx = C.rows(out, K)
   if out2.data_ptr() != out.data_ptr() or out2.shape[0] != n:
     raise ValueError('out: %d rows of dX must lie a constant stride apart' % n)
-  stream, sp = L._stream_handle(dev)
-  with torch.cuda.device(dev):
+  with C.launch(dev) as q:
+    q.keep(wt, y2, *bt.keep)
     _lib.check(lib.epos_heads_dgrad_f32(
-        *bt.grad_args(ignore_label), L._ptr(wt[:widths[0]]),
-        L._ptr(wt[widths[0]:widths[0] + widths[1]]), L._ptr(wt[widths[0] + widths[1]:]), K, K,
-        L._ptr(y2), ldy, L._ptr(out2), ldx, sp), 'epos_heads_dgrad_f32')
-  for t in bt.keep + [wt] + ([y2] if y2 is not None else []):
-    t.record_stream(stream)           # temporaries and dense copies made here outlive the call
+        *bt.grad_args(ignore_label), C.ptr(wt[:widths[0]]),
+        C.ptr(wt[widths[0]:widths[0] + widths[1]]), C.ptr(wt[widths[0] + widths[1]:]), K, K,
+        C.ptr(y2), ldy, C.ptr(out2), ldx, q.handle), 'epos_heads_dgrad_f32')
   return out
 
 
@@ -145,19 +142,14 @@ def momentum_step(param, accum, grad, lr, momentum=0.9, weight_decay=0.0, grad_m
   stream; does not synchronise."""
   import torch
   lib = _lib.load()
-  if not param.is_cuda:
-    raise EposError('the momentum step needs a HIP device (there is no CPU fallback)')
+  C.need_device(param, 'the momentum step needs a HIP device (there is no CPU fallback)')
   n = param.numel()
   for t, what in ((param, 'param'), (accum, 'accum'), (grad, 'grad')):
-    if (t.device != param.device or t.dtype != torch.float32 or t.numel() != n or
-        not t.is_contiguous()):
-      raise ValueError('%s must be a contiguous float32 tensor of %d values on %s' % (
-          what, n, param.device))
-  with torch.cuda.device(param.device):
+    C.dense(t, param.device, torch.float32, what, numel=n, name='float32')
+  with C.launch(param.device) as q:
     _lib.check(lib.epos_momentum_step_f32(
-        L._ptr(param), L._ptr(accum), L._ptr(grad), n, float(lr), float(momentum),
-        float(weight_decay), float(grad_mult), L._stream_handle(param.device)[1]),
-               'epos_momentum_step_f32')
+        C.ptr(param), C.ptr(accum), C.ptr(grad), n, float(lr), float(momentum),
+        float(weight_decay), float(grad_mult), q.handle), 'epos_momentum_step_f32')
   return param
 
 
@@ -173,7 +165,7 @@ def net_logits(net):
 
 def _net_losses(net, gt, weights, reduction, ignore_label):
   """loss_terms -> loss_values on an fp32 net's logits: (logits, values, bad, scales)."""
-  L._need_fp32(net.decoder_out)
+  L.need_fp32(net.decoder_out)
   logits = net_logits(net)
   sums, counts, bad = L.loss_terms(logits, gt, ignore_label)
   values, scales = L.loss_values(sums, counts, weights, reduction)

@@ -29,10 +29,10 @@ epos_amd/heads_train.py; DESIGN.md, "Losses", "Input gradient".
 
 There is no CPU fallback: without the library or a device this raises EposError.
 """
-import ctypes
 import json
 import os
 
+from epos_amd import _call as C
 from epos_amd import _lib
 from epos_amd._lib import EposError
 from epos_amd import weights as W
@@ -42,81 +42,11 @@ TAGS = tuple('eval/' + n for n in NAMES)
 GT_KEYS = ('obj_label', 'frag_label', 'frag_loc', 'frag_weight')
 
 
-def _ptr(t):
-  return ctypes.c_void_p(t.data_ptr()) if t is not None else None
-
-
-def _flat(t, device, dtype, numel, what):
-  if t.device != device:
-    raise EposError('%s is on %s, the losses on %s' % (what, t.device, device))
-  if t.dtype != dtype:
-    raise TypeError('%s must be %s, got %s' % (what, dtype, t.dtype))
-  t = t.contiguous().reshape(-1)
-  if t.numel() != numel:
-    raise ValueError('%s holds %d values, expected %d' % (what, t.numel(), numel))
-  return t
-
-
-def _need_fp32(features):
+def need_fp32(features):
   import torch
   if features.dtype != torch.float32:
     raise TypeError('features must be torch.float32, got %s (a bf16 decoder_out is not '
                     'supported: run the net with precision=\'fp32\')' % features.dtype)
-
-
-def _rows(t, width):
-  """(tensor, row stride) of obj logits [..., width]: a view whose rows lie a constant stride
-  apart is taken as it is (a slice of a wider head buffer), anything else is made dense."""
-  if t.stride(-1) == 1:
-    try:
-      v = t.view(-1, width)
-      if v.shape[0] < 2 or v.stride(0) >= width:
-        return v, (v.stride(0) if v.shape[0] > 1 else width)
-    except RuntimeError:
-      pass
-  return t.contiguous().view(-1, width), width
-
-
-def _out(t, device, dtype, shape, what, flat=False, rows=False):
-  """The output tensor t after its check, or a new one for None: a contiguous `dtype` tensor of
-  `shape` on `device` -- flat: of as many values in any shape; rows: [..., shape[-1]], which the
-  caller passes through _rows -- else ValueError."""
-  import torch
-  if t is None:
-    return torch.empty(shape, dtype=dtype, device=device)
-  if rows:
-    fits = t.shape[-1] == shape[-1]
-  elif flat:
-    fits = t.is_contiguous() and t.numel() == torch.Size(shape).numel()
-  else:
-    fits = t.is_contiguous() and tuple(t.shape) == tuple(shape)
-  if t.device != device or t.dtype != dtype or not fits:
-    raise ValueError('%s must be a %s%s tensor of shape %s on %s' % (
-        what, '' if rows else 'contiguous ', dtype,
-        '[..., %d]' % shape[-1] if rows else tuple(shape), device))
-  return t
-
-
-def _workspace(t, device, nbytes, dtype=None):
-  """The workspace tensor t after its check, or a new one for None: contiguous, on `device`, of
-  at least nbytes bytes and, where one is given, of `dtype` (a new one: int64), else
-  ValueError."""
-  import torch
-  if t is None:
-    new = dtype or torch.int64
-    return torch.empty((max(-(-nbytes // new.itemsize), 1),), dtype=new, device=device)
-  if (t.device != device or not t.is_contiguous() or (dtype is not None and t.dtype != dtype) or
-      t.numel() * t.element_size() < nbytes):
-    raise ValueError('workspace must be a contiguous %stensor of at least %d bytes on %s' % (
-        '%s ' % dtype if dtype else '', nbytes, device))
-  return t
-
-
-def _stream_handle(device):
-  """(the current torch stream of `device`, its hipStream_t as the C entries take it)."""
-  import torch
-  stream = torch.cuda.current_stream(device)
-  return stream, ctypes.c_void_p(stream.cuda_stream)
 
 
 HEADS = (W.PRED_OBJ_CONF, W.PRED_FRAG_CONF, W.PRED_FRAG_LOC)
@@ -136,18 +66,20 @@ def _head_dicts(obj, frag, loc, gt_obj, gt_frag, gt_loc, gt_weight):
           dict(zip(GT_KEYS, (gt_obj, gt_frag, gt_loc, gt_weight))))
 
 
-class _Batch(object):
+class Batch(object):
   """A batch of logits and ground truth as the C entries take it: dev, B, P, O, F, n = B * P;
   shapes of the three logit tensors; ins = [obj rows, frag, loc, obj_label, frag_label, frag_loc,
   frag_weight] flattened, in ABI order, with ld the row stride of the first; scales and upstream
-  flattened (or None); keep = what to record_stream after the launch."""
+  flattened (or None); keep = what the launch keeps (_call.launch.keep)."""
 
   def __init__(self, logits, gt, who, scales=None, upstream=None):
     import torch
     obj, frag, loc = (logits[k] for k in HEADS)
-    if not obj.is_cuda:
-      raise EposError('%s a HIP device (there is no CPU fallback)' % who)
+    C.need_device(obj, '%s a HIP device (there is no CPU fallback)' % who)
     dev = obj.device
+
+    def flat(t, dtype, numel, what):
+      return C.flat(t, dev, dtype, numel, what, 'the losses')
     if frag.dim() < 3 or obj.dim() < 2:
       raise ValueError('pred_frag_conf must be [..., O, F] and pred_obj_conf [..., O+1]')
     O, F = int(frag.shape[-2]), int(frag.shape[-1])
@@ -161,34 +93,34 @@ class _Batch(object):
       raise ValueError('obj_label must be [B, ...] with B >= 1')
     if obj.dtype != torch.float32:
       raise TypeError('pred_obj_conf must be torch.float32, got %s' % obj.dtype)
-    obj2, self.ld = _rows(obj, O + 1)
+    obj2, self.ld = C.rows(obj, O + 1)
     if obj2.shape[0] != n:
       raise ValueError('pred_obj_conf holds %d rows, expected %d' % (obj2.shape[0], n))
     self.dev, self.B, self.P, self.O, self.F, self.n = dev, B, n // B, O, F, n
     self.shapes = (obj.shape, frag.shape, loc.shape)
     self.ins = [obj2,
-                _flat(frag, dev, torch.float32, n * O * F, 'pred_frag_conf'),
-                _flat(loc, dev, torch.float32, n * O * F * 3, 'pred_frag_loc'),
-                _flat(gt_obj, dev, torch.int32, n, 'obj_label'),
-                _flat(gt['frag_label'], dev, torch.int32, n, 'frag_label'),
-                _flat(gt['frag_loc'], dev, torch.float32, n * 3, 'frag_loc'),
-                _flat(gt['frag_weight'], dev, torch.float32, n, 'frag_weight')]
+                flat(frag, torch.float32, n * O * F, 'pred_frag_conf'),
+                flat(loc, torch.float32, n * O * F * 3, 'pred_frag_loc'),
+                flat(gt_obj, torch.int32, n, 'obj_label'),
+                flat(gt['frag_label'], torch.int32, n, 'frag_label'),
+                flat(gt['frag_loc'], torch.float32, n * 3, 'frag_loc'),
+                flat(gt['frag_weight'], torch.float32, n, 'frag_weight')]
     self.scales = self.upstream = None
     if scales is not None:
-      self.scales = _flat(scales, dev, torch.float64, B * 3, 'scales')
+      self.scales = flat(scales, torch.float64, B * 3, 'scales')
     if upstream is not None:
-      self.upstream = _flat(upstream, dev, torch.float64, 4, 'upstream')
-    self.keep = self.ins + [t for t in (self.scales, self.upstream) if t is not None]
+      self.upstream = flat(upstream, torch.float64, 4, 'upstream')
+    self.keep = self.ins + [self.scales, self.upstream]
 
   def args(self, ignore_label):
     """The arguments every entry shares: obj, ld_obj, frag, loc, the four ground-truth fields,
     B, P, O, F, ignore_label."""
-    i = [_ptr(t) for t in self.ins]
+    i = [C.ptr(t) for t in self.ins]
     return (i[0], self.ld) + tuple(i[1:]) + (self.B, self.P, self.O, self.F, int(ignore_label))
 
   def grad_args(self, ignore_label):
     """args, then scales and upstream (NULL without)."""
-    return self.args(ignore_label) + (_ptr(self.scales), _ptr(self.upstream))
+    return self.args(ignore_label) + (C.ptr(self.scales), C.ptr(self.upstream))
 
 
 def loss_terms(logits, gt, ignore_label=255, out=None):
@@ -200,22 +132,20 @@ def loss_terms(logits, gt, ignore_label=255, out=None):
   larger table) to write into. Enqueues on the current stream; does not synchronise."""
   import torch
   lib = _lib.load()
-  bt = _Batch(logits, gt, 'the losses need')
+  bt = Batch(logits, gt, 'the losses need')
   dev, B, P, O, F = bt.dev, bt.B, bt.P, bt.O, bt.F
   sums, counts, bad = (
-      _out(t, dev, dtype, shape, 'out: ' + what, flat=True) for t, dtype, shape, what in zip(
+      C.out(t, dev, dtype, shape, 'out: ' + what, flat=True) for t, dtype, shape, what in zip(
           out or (None, None, None), (torch.float64, torch.int64, torch.int64),
           ((B, O + 1, 3), (B, O + 1, 2), (B,)), ('sums', 'counts', 'bad')))
   nbytes = lib.epos_loss_workspace_bytes(B, P, O, F)
   _lib.check(nbytes, 'epos_loss_workspace_bytes')
-  ws = torch.empty((max(nbytes // 8, 1),), dtype=torch.int64, device=dev)
-  stream, sp = _stream_handle(dev)
-  with torch.cuda.device(dev):
+  ws = C.workspace(None, dev, nbytes)
+  with C.launch(dev) as q:
+    q.keep(ws, *bt.keep)
     _lib.check(lib.epos_loss_terms(
-        *bt.args(ignore_label), _ptr(ws), _ptr(sums), _ptr(counts), _ptr(bad), sp),
+        *bt.args(ignore_label), C.ptr(ws), C.ptr(sums), C.ptr(counts), C.ptr(bad), q.handle),
                'epos_loss_terms')
-  for t in bt.keep + [ws]:
-    t.record_stream(stream)           # temporaries and dense copies made here outlive the call
   return sums, counts, bad
 
 
@@ -298,8 +228,7 @@ class LossEval(object):
   def __init__(self, num_objs, num_frags, device=None, obj_cls_loss_weight=1.0,
                frag_cls_loss_weight=1.0, frag_loc_loss_weight=100.0, ignore_label=255):
     import torch
-    if not torch.cuda.is_available():
-      raise EposError('the losses need a HIP device (there is no CPU fallback)')
+    C.need_device(None, 'the losses need a HIP device (there is no CPU fallback)')
     _lib.load()
     self.device = torch.device(device if device is not None else 'cuda:0')
     self.num_objs, self.num_frags = int(num_objs), int(num_frags)
@@ -398,8 +327,7 @@ def loss_values(sums, counts, weights, reduction='mean', out=None):
   lib = _lib.load()
   if reduction not in REDUCTIONS:
     raise ValueError("reduction must be 'mean' or 'pooled', got %r" % (reduction,))
-  if not sums.is_cuda:
-    raise EposError('the losses need a HIP device (there is no CPU fallback)')
+  C.need_device(sums, 'the losses need a HIP device (there is no CPU fallback)')
   dev = sums.device
   if sums.dim() != 3 or sums.shape[0] < 1 or sums.shape[2] != 3:
     raise ValueError('sums must be [B, O+1, 3] with B >= 1')
@@ -412,14 +340,12 @@ def loss_values(sums, counts, weights, reduction='mean', out=None):
                                 (counts, torch.int64, B * O1 * 2, 'counts'),
                                 (values, torch.float64, 4, 'values'),
                                 (scales, torch.float64, B * 3, 'scales')):
-    if t.device != dev or t.dtype != dtype or t.numel() != numel or not t.is_contiguous():
-      raise ValueError('%s must be a contiguous %s tensor of %d values on %s' % (
-          what, dtype, numel, dev))
+    C.dense(t, dev, dtype, what, numel=numel)
   w_obj, w_cls, w_loc = (float(w) for w in weights)
-  with torch.cuda.device(dev):
+  with C.launch(dev) as q:
     _lib.check(lib.epos_loss_reduce(
-        _ptr(sums), _ptr(counts), B, O1 - 1, w_obj, w_cls, w_loc, REDUCTIONS[reduction],
-        _ptr(values), _ptr(scales), _stream_handle(dev)[1]), 'epos_loss_reduce')
+        C.ptr(sums), C.ptr(counts), B, O1 - 1, w_obj, w_cls, w_loc, REDUCTIONS[reduction],
+        C.ptr(values), C.ptr(scales), q.handle), 'epos_loss_reduce')
   return values, scales
 
 
@@ -435,7 +361,7 @@ def loss_grads(logits, gt, scales, upstream=None, ignore_label=255, need=(True, 
   pixels get zero gradient. Enqueues on the current stream; does not synchronise."""
   import torch
   lib = _lib.load()
-  bt = _Batch(logits, gt, 'the losses need', scales, upstream)
+  bt = Batch(logits, gt, 'the losses need', scales, upstream)
   dev, O, shapes = bt.dev, bt.O, bt.shapes
   outs = list(out) if out is not None else [None, None, None]
   for k in range(3):
@@ -449,16 +375,14 @@ def loss_grads(logits, gt, scales, upstream=None, ignore_label=255, need=(True, 
           k, tuple(shapes[k]), dev, ', contiguous' if k else ''))
   d_obj2, ld_d = None, O + 1
   if outs[0] is not None:
-    d_obj2, ld_d = _rows(outs[0], O + 1)
+    d_obj2, ld_d = C.rows(outs[0], O + 1)
     if d_obj2.data_ptr() != outs[0].data_ptr():
       raise ValueError('out[0]: the rows of d_obj must lie a constant stride apart')
-  stream, sp = _stream_handle(dev)
-  with torch.cuda.device(dev):
+  with C.launch(dev) as q:
+    q.keep(*bt.keep)
     _lib.check(lib.epos_loss_grads(
-        *bt.grad_args(ignore_label), _ptr(d_obj2), ld_d, _ptr(outs[1]), _ptr(outs[2]), sp),
-               'epos_loss_grads')
-  for t in bt.keep:
-    t.record_stream(stream)           # temporaries and dense copies made here outlive the call
+        *bt.grad_args(ignore_label), C.ptr(d_obj2), ld_d, C.ptr(outs[1]), C.ptr(outs[2]),
+        q.handle), 'epos_loss_grads')
   return tuple(outs)
 
 
@@ -591,13 +515,11 @@ def differentiable_losses_from_features(features, head_weights, gt, weights=(1.0
   through epos_heads_wgrad_f32 (heads_train.heads_weight_grads), each only where a gradient is
   needed; the dense logit gradients are never formed. The logits themselves are kept for the
   backward pass. Nothing synchronises."""
-  import torch
   _lib.load()
-  if not torch.cuda.is_available() or not features.is_cuda:
-    raise EposError('the losses need a HIP device (there is no CPU fallback)')
+  C.need_device(features, 'the losses need a HIP device (there is no CPU fallback)')
   if reduction not in REDUCTIONS:
     raise ValueError("reduction must be 'mean' or 'pooled', got %r" % (reduction,))
-  _need_fp32(features)
+  need_fp32(features)
   for name in HEAD_VARIABLES:
     if name not in head_weights:
       raise KeyError('head_weights lack %r' % name)
@@ -617,11 +539,9 @@ def differentiable_losses(logits, gt, weights=(1.0, 1.0, 100.0), reduction='mean
   Nothing synchronises: the caller decides when to look at `bad`. Bad and ignored pixels get
   ZERO gradient and add nothing to the values -- a batch with bad pixels is not refused here as
   LossEval.result refuses it. total_loss has no regularisation term (module docstring)."""
-  import torch
   _lib.load()
   obj = logits[W.PRED_OBJ_CONF]
-  if not torch.cuda.is_available() or not obj.is_cuda:
-    raise EposError('the losses need a HIP device (there is no CPU fallback)')
+  C.need_device(obj, 'the losses need a HIP device (there is no CPU fallback)')
   if reduction not in REDUCTIONS:
     raise ValueError("reduction must be 'mean' or 'pooled', got %r" % (reduction,))
   return _losses_function().apply(

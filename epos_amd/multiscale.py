@@ -23,15 +23,14 @@ size, and runs them one after the other on the caller's stream:
 The whole forward is one linear sequence of launches (no parallel branches): each scale's plan
 fills the GPU on its own. DESIGN.md, "multi-scale mode".
 """
-import ctypes
 import math
 
 import torch
 
 from epos_amd import _lib
+from epos_amd._call import ptr as _ptr
 from epos_amd import net as _net
 from epos_amd import weights as W
-from epos_amd.net_modes import _ptr
 
 MAX_SCALES = 8                     # epos_resize_merge_f32: 1 <= S <= 8
 MERGE_METHODS = {'max': _lib.MERGE_MAX, 'avg': _lib.MERGE_MEAN}   # common.py:140-141

@@ -35,9 +35,11 @@ import os
 import numpy as np
 import torch
 
+from epos_amd import _call as C
 from epos_amd import _lib
 from epos_amd import weights as W
-from epos_amd.net_modes import Bf16Mode, Fp32Mode, _ptr
+from epos_amd._call import ptr as _ptr
+from epos_amd.net_modes import Bf16Mode, Fp32Mode
 
 XCEPTION_BN_EPS = 1e-3   # feature.py:300-307
 HEAD_BN_EPS = 1e-5       # model.py:194-199, 307-312
@@ -658,7 +660,7 @@ class EposNet(object):
 
   # ----------------------------------------------------------- running ---
   def _stream(self):
-    return ctypes.c_void_p(torch.cuda.current_stream(self.dev).cuda_stream)
+    return C.stream_handle(self.dev)[1]
 
   def sync_current(self):
     torch.cuda.current_stream(self.dev).synchronize()
@@ -812,13 +814,11 @@ class EposNet(object):
       raise NotImplementedError('set_weights: more than 126 objects')
     if not layers:
       return torch.zeros(0, dtype=torch.int32, device=self.dev)
-    with torch.cuda.device(self.dev):
+    with C.launch(self.dev) as q:
       packed, keep = self._pack_problems(layers)
+      q.keep(*keep)                      # uploaded copies outlive the call
       status = torch.empty(len(packed), dtype=torch.int32, device=self.dev)
-      self.mode.pack_launch([p[0] for p in packed], status, self._stream())
-    stream = torch.cuda.current_stream(self.dev)
-    for t in keep:
-      t.record_stream(stream)            # uploaded copies outlive the call
+      self.mode.pack_launch([p[0] for p in packed], status, q.handle)
     if check:
       bad = [packed[i][1:] for i in torch.nonzero(status.cpu()).flatten().tolist()]
       bad = ['%s (sparse pack of object %d)' % b if b[1] else b[0] for b in bad]

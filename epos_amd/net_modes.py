@@ -16,11 +16,8 @@ import numpy as np
 import torch
 
 from epos_amd import _lib
+from epos_amd._call import ptr as _ptr
 from epos_amd import weights as W
-
-
-def _ptr(t, offset_elems=0):
-  return ctypes.c_void_p(t.data_ptr() + offset_elems * t.element_size())
 
 
 def _fold(w_kn, scale, kmult):

@@ -19,6 +19,7 @@ import numpy as np
 import torch
 
 from epos_amd import _lib
+from epos_amd._call import ptr as _ptr
 from epos_amd import corresp as _corresp
 from epos_amd import fitting as _fitting
 from epos_amd import model as _model
@@ -27,10 +28,6 @@ from epos_amd import weights as W
 
 LOCALIZATION = 'localization'   # common.py
 DETECTION = 'detection'
-
-
-def _ptr(t):
-  return ctypes.c_void_p(t.data_ptr())
 
 
 _STREAMS = {}
@@ -216,6 +213,7 @@ class EposPipeline(object):
     self.corr.totals = mv(self.res_dev, self._res_layout, 'totals').view(S, 2)
     self.corr.overflow = mv(self.res_dev, self._res_layout, 'overflow')
     self.stream = _pipeline_stream(self.dev, instance)
+    self._stream_handle = ctypes.c_void_p(self.stream.cuda_stream)
     self._dones = [torch.cuda.Event() for _ in range(self.queue)]
     self._pending = collections.deque()        # launched, not yet collected (oldest first)
     self._launches = 0
@@ -353,7 +351,7 @@ class EposPipeline(object):
               _ptr(src.slot_base), S, self.corr.capacity, _ptr(self.Ks),
               ctypes.byref(self.cv_params), _ptr(self.work), _ptr(self.poses),
               _ptr(self.num_models), _ptr(self.labels), None,
-              ctypes.c_void_p(self.stream.cuda_stream)), 'epos_solve_pnp_ransac_device')
+              self._stream_handle), 'epos_solve_pnp_ransac_device')
         elif self.order is not None:
           _lib.check(self.lib.epos_find6d_poses_device_ordered(
               _ptr(src.coord_2d), _ptr(src.coord_3d),
@@ -361,7 +359,7 @@ class EposPipeline(object):
               _ptr(self.max_models), _ptr(self.seeds), ctypes.byref(self.fit),
               max_k, _ptr(self.work), _ptr(self.poses), _ptr(self.scores),
               _ptr(self.num_models), _ptr(self.labels),
-              ctypes.c_void_p(self.stream.cuda_stream), _ptr(src.yorder), _ptr(src.ypos)),
+              self._stream_handle, _ptr(src.yorder), _ptr(src.ypos)),
                      'epos_find6d_poses_device_ordered')
         else:
           _lib.check(self.lib.epos_find6d_poses_device(
@@ -370,7 +368,7 @@ class EposPipeline(object):
               _ptr(self.max_models), _ptr(self.seeds), ctypes.byref(self.fit),
               max_k, _ptr(self.work), _ptr(self.poses), _ptr(self.scores),
               _ptr(self.num_models), _ptr(self.labels),
-              ctypes.c_void_p(self.stream.cuda_stream)), 'epos_find6d_poses_device')
+              self._stream_handle), 'epos_find6d_poses_device')
         # NB: poses / scores are laid out [S, max_k(call), ...] for this call.
         if timing:
           ev[3].record()

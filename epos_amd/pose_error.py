@@ -17,8 +17,8 @@ import os
 
 import numpy as np
 
+from epos_amd import _call as C
 from epos_amd import _lib
-from epos_amd._lib import EposError
 
 MAX_SYM_DISC_STEP = 0.01
 MSSD_FACTORS = tuple(0.05 * k for k in range(1, 11))     # x object diameter
@@ -88,10 +88,6 @@ def translation_error(t_e, t_g):
   return float(np.sqrt(np.sum(d * d)))
 
 
-def _ptr(t):
-  return ctypes.c_void_p(t.data_ptr())
-
-
 class PoseErrorEval(object):
   """The vertices of ``models`` ({obj_id: {'pts': [V,3]}}, as ply.load_models returns them) and
   the symmetry sets of ``models_info`` ({obj_id: record}), pooled on the device once."""
@@ -99,8 +95,7 @@ class PoseErrorEval(object):
   def __init__(self, models, models_info, device=None, max_sym_disc_step=MAX_SYM_DISC_STEP,
                chunk_pairs=1 << 16):
     import torch
-    if not torch.cuda.is_available():
-      raise EposError('pose errors need a HIP device (there is no CPU fallback)')
+    C.need_device(None, 'pose errors need a HIP device (there is no CPU fallback)')
     self.lib = _lib.load()
     self.device = torch.device(device if device is not None else 'cuda:0')
     self.chunk_pairs = int(chunk_pairs)
@@ -162,16 +157,14 @@ class PoseErrorEval(object):
   def enqueue(self, host, dev, err, want_adi=True):
     """One launcher call per chunk_pairs records on the current stream; nothing is awaited, so
     `host` and `dev` stay alive until the stream has been synchronised."""
-    import torch
     n, size = err.shape[0], PAIR_DTYPE.itemsize
-    s = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-    with torch.cuda.device(self.device):
+    with C.launch(self.device) as q:
       for i0 in range(0, n, self.chunk_pairs):
         m = min(self.chunk_pairs, n - i0)
         _lib.check(self.lib.epos_pose_errors_f64(
-            _ptr(self.verts), self.n_verts_total, _ptr(self.syms), self.n_syms_total,
-            ctypes.c_void_p(host.data_ptr() + i0 * size), _ptr(dev), m, int(bool(want_adi)),
-            ctypes.c_void_p(err.data_ptr() + i0 * 32), s), 'epos_pose_errors_f64')
+            C.ptr(self.verts), self.n_verts_total, C.ptr(self.syms), self.n_syms_total,
+            C.ptr(host, i0 * size), C.ptr(dev), m, int(bool(want_adi)), C.ptr(err, i0 * 4),
+            q.handle), 'epos_pose_errors_f64')
 
   def device_errors(self, tab, want_adi=True):
     """f64 [n, 4] (mssd, mspd, add, adi; adi = nan without want_adi) of a record table whose

@@ -14,6 +14,7 @@ import ctypes
 
 import numpy as np
 
+from epos_amd import _call as C
 from epos_amd import _lib
 from epos_amd._lib import EposError
 
@@ -27,14 +28,9 @@ _INST = np.dtype([('vert_base', np.int32), ('face_base', np.int32), ('n_faces', 
 assert _INST.itemsize == ctypes.sizeof(_lib.RenderInst) == 144
 
 
-def _ptr(t):
-  return ctypes.c_void_p(t.data_ptr()) if t is not None else None
-
-
 def _torch_device(device):
   import torch
-  if not torch.cuda.is_available():
-    raise EposError('the mesh renderer needs a HIP device (there is no CPU fallback)')
+  C.need_device(None, 'the mesh renderer needs a HIP device (there is no CPU fallback)')
   return torch.device(device if device is not None else 'cuda:0')
 
 
@@ -170,17 +166,16 @@ class Renderer(object):
       return ws
     verts, faces, colors = self._upload()
     insts = torch.from_numpy(tab.view(np.uint8).reshape(n, -1)).to(self.device)
-    stream = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-    with torch.cuda.device(self.device):
+    with C.launch(self.device) as q:
+      q.keep(insts)
       _lib.check(self.lib.epos_render_raster(
-          _ptr(verts), self._nv, _ptr(faces), self._nf, _ptr(insts), n, h, w, self.near,
-          _ptr(ws['keys']), stream), 'epos_render_raster')
+          C.ptr(verts), self._nv, C.ptr(faces), self._nf, C.ptr(insts), n, h, w, self.near,
+          C.ptr(ws['keys']), q.handle), 'epos_render_raster')
       _lib.check(self.lib.epos_render_resolve(
-          _ptr(ws['keys']), _ptr(verts), self._nv, _ptr(faces), self._nf, _ptr(colors),
-          _ptr(insts), n, h, w, self.near,
-          *[_ptr(ws.get(k)) for k in OUTPUTS], stream),
+          C.ptr(ws['keys']), C.ptr(verts), self._nv, C.ptr(faces), self._nf, C.ptr(colors),
+          C.ptr(insts), n, h, w, self.near,
+          *[C.ptr(ws.get(k)) for k in OUTPUTS], q.handle),
                  'epos_render_resolve')
-    insts.record_stream(torch.cuda.current_stream(self.device))
     return ws
 
   # ---- bop_renderer's single-object form ----
@@ -232,8 +227,7 @@ def gt_fields_device(depth, local_pos, obj_ids, centers, sizes, masks=None):
   import torch
   lib = _lib.load()
   dev = depth.device
-  if dev.type != 'cuda':
-    raise EposError('the ground-truth fields need a HIP device (there is no CPU fallback)')
+  C.need_device(depth, 'the ground-truth fields need a HIP device (there is no CPU fallback)')
   n, h, w = depth.shape
   centers = np.ascontiguousarray(centers, np.float64)
   sizes = np.ascontiguousarray(sizes, np.float64)
@@ -249,14 +243,13 @@ def gt_fields_device(depth, local_pos, obj_ids, centers, sizes, masks=None):
          'frag_label': torch.empty((h, w), dtype=torch.int32, device=dev),
          'frag_loc': torch.empty((h, w, 3), dtype=torch.float32, device=dev),
          'frag_weight': torch.empty((h, w), dtype=torch.float32, device=dev)}
-  with torch.cuda.device(dev):
+  with C.launch(dev) as q:
+    q.keep(ids, c_dev, s_dev)
     _lib.check(lib.epos_gt_fields(
-        _ptr(depth), _ptr(local_pos), _ptr(masks), _ptr(ids), n, h, w, _ptr(c_dev),
-        _ptr(s_dev), O, F, _ptr(out['obj_label']), _ptr(out['instance']),
-        _ptr(out['frag_label']), _ptr(out['frag_loc']), _ptr(out['frag_weight']),
-        ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), 'epos_gt_fields')
-  for t in (ids, c_dev, s_dev):
-    t.record_stream(torch.cuda.current_stream(dev))
+        C.ptr(depth), C.ptr(local_pos), C.ptr(masks), C.ptr(ids), n, h, w, C.ptr(c_dev),
+        C.ptr(s_dev), O, F, C.ptr(out['obj_label']), C.ptr(out['instance']),
+        C.ptr(out['frag_label']), C.ptr(out['frag_loc']), C.ptr(out['frag_weight']),
+        q.handle), 'epos_gt_fields')
   return out
 
 

@@ -16,8 +16,8 @@ import ctypes
 
 import numpy as np
 
+from epos_amd import _call as C
 from epos_amd import _lib, pose_error
-from epos_amd._lib import EposError
 
 VSD_DELTA = 15.0                                          # mm, the visibility tolerance
 VSD_TAUS = tuple(0.05 * k for k in range(1, 11))          # x object diameter
@@ -111,20 +111,14 @@ def default_max_instances(h, w, budget=MEMORY_BUDGET):
   return max(2, min(int(budget) // (BYTES_PER_PIXEL * px), (2 ** 31 - 1) // px))
 
 
-def _ptr(t):
-  return ctypes.c_void_p(t.data_ptr())
-
-
 class VsdEval(object):
   """A render.Renderer with the `models` ({obj_id: {'pts', 'faces'}}, the 'eval' models) and
   the diameters of `models_info`. max_instances: instances per chunk (None: derived from the
   image size, default_max_instances)."""
 
   def __init__(self, models, models_info, device=None, max_instances=None):
-    import torch
     from epos_amd import cli
-    if not torch.cuda.is_available():
-      raise EposError('VSD needs a HIP device (there is no CPU fallback)')
+    C.need_device(None, 'VSD needs a HIP device (there is no CPU fallback)')
     self.lib = _lib.load()
     self.renderer = cli.eval_renderer(models, device)
     self.device = self.renderer.device
@@ -235,13 +229,11 @@ class VsdEval(object):
     dev = torch.empty(host.shape, dtype=torch.uint8, device=self.device)
     taus = np.ascontiguousarray(taus, np.float64)
     n_img, h, w = depth_test.shape
-    with torch.cuda.device(self.device):
+    with C.launch(self.device) as q:
       _lib.check(self.lib.epos_vsd_counts(
-          _ptr(depth_test), n_img, _ptr(depth_model), depth_model.shape[0], h, w,
-          ctypes.c_void_p(host.data_ptr()), _ptr(dev), n, float(delta),
-          ctypes.c_void_p(taus.ctypes.data), len(taus), _ptr(counts),
-          ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)),
-                 'epos_vsd_counts')
+          C.ptr(depth_test), n_img, C.ptr(depth_model), depth_model.shape[0], h, w,
+          C.ptr(host), C.ptr(dev), n, float(delta), ctypes.c_void_p(taus.ctypes.data), len(taus),
+          C.ptr(counts), q.handle), 'epos_vsd_counts')
     return host, dev
 
   def counts(self, frames, pairs, delta=VSD_DELTA, taus=VSD_TAUS):
