@@ -211,6 +211,22 @@ class PointwiseWgradArgs(ctypes.Structure):
               ('S', vp), ('g', vp), ('workspace', vp)]
 
 
+class PointwiseDgradArgs(ctypes.Structure):
+  _fields_ = [('G', vp), ('ldg', ctypes.c_int64), ('W', vp), ('gamma', vp),
+              ('moving_variance', vp), ('eps', ctypes.c_double),
+              ('mask', vp), ('ldm', ctypes.c_int64),
+              ('mask_h2', ctypes.c_int32), ('reserved0', ctypes.c_int32),
+              ('M', ctypes.c_int64), ('K', ctypes.c_int32), ('N', ctypes.c_int32),
+              ('D', vp), ('ldd', ctypes.c_int64), ('workspace', vp)]
+
+
+class DepthwiseWgradArgs(ctypes.Structure):
+  _fields_ = [('X', vp), ('ldx', ctypes.c_int64), ('D', vp), ('ldd', ctypes.c_int64),
+              ('B', ctypes.c_int32), ('H', ctypes.c_int32), ('W', ctypes.c_int32),
+              ('C', ctypes.c_int32), ('stride', ctypes.c_int32), ('rate', ctypes.c_int32),
+              ('T', vp), ('t', vp), ('workspace', vp)]
+
+
 class FitParams(ctypes.Structure):
   _fields_ = [
       ('threshold', ctypes.c_double),
@@ -427,6 +443,18 @@ SYMBOLS = {
     'epos_pointwise_wgrad_f32': (ctypes.c_int, [ctypes.POINTER(PointwiseWgradArgs), vp]),
     'epos_pointwise_wgrad_close_f32': (ctypes.c_int, [
         vp, vp, vp, ctypes.c_int, ctypes.c_int, vp, vp, vp, ctypes.c_double, vp, vp, vp, vp]),
+    # backward through a separable conv: the 1x1 layer's input gradient, the depthwise layer's
+    # weight sums and input gradient
+    'epos_pointwise_dgrad_workspace_bytes': (ctypes.c_int64, [ctypes.c_int, ctypes.c_int]),
+    'epos_pointwise_dgrad_f32': (ctypes.c_int, [ctypes.POINTER(PointwiseDgradArgs), vp]),
+    'epos_depthwise_wgrad_range_pixels': (ctypes.c_int64, [
+        ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    'epos_depthwise_wgrad_workspace_bytes': (ctypes.c_int64, [
+        ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    'epos_depthwise_wgrad_f32': (ctypes.c_int, [ctypes.POINTER(DepthwiseWgradArgs), vp]),
+    'epos_depthwise_dgrad_f32': (ctypes.c_int, [
+        vp, ctypes.c_int64, vp, vp, ctypes.c_int64, vp, ctypes.c_int64, ctypes.c_int,
+        ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp]),
     # weight update: the packers on the device
     'epos_pack_weights_device_f32': (ctypes.c_int, [
         ctypes.POINTER(WeightPackArgs), ctypes.c_int, vp, vp]),

@@ -7,14 +7,29 @@
                           of one with biases) from its input A -- fp32 or the fp16 pairs the
                           depthwise kernel wrote -- and the gradient G at its pre-activation.
 
+  pointwise_input_grad    epos_pointwise_dgrad_f32: D = mask (.) (G Wf^T), the gradient that
+                          crosses the layer, at the pre-activation of decoder_conv1_depthwise
+                          (csrc/pointwise_dgrad.hip; "Pointwise input gradient").
+  depthwise_weight_grads  epos_depthwise_wgrad_f32 + epos_pointwise_wgrad_close_f32 with K = 9:
+                          dw, dgamma and dbeta of a 3x3 depthwise layer with a frozen batch norm
+                          (csrc/depthwise_grad.hip; "Depthwise gradients").
+  depthwise_input_grad    epos_depthwise_dgrad_f32: the gradient that crosses the depthwise layer,
+                          at the pre-activation of decoder_conv0_pointwise.
+
 The nine variables' gradients from a running net, the optimiser and the training step are
-epos_amd/trainer.py; the in-place weight update is EposNet.set_weights.
+epos_amd/trainer.py, and so is the chain of all five wrappers (trainer.decoder_conv1_grads); the
+in-place weight update is EposNet.set_weights.
 
 The batch-norm statistics are frozen (the reference's fine_tune_batch_norm=False): moving_mean
-and moving_variance are inputs. Not built: the input gradient of this layer, G W^T, and with it
-everything from decoder_conv1_depthwise down; batch-norm statistics, bf16 mode, multi-scale nets
-and more than one device. Pinned to tests/helpers/pointwise_wgrad_ref.py and, through it, to
-torch's fp64 autograd; parity with TensorFlow's gradients is unpinned. There is no CPU fallback.
+and moving_variance are inputs. Built: the three gradients above ("Losses", "Backward
+through decoder_conv1"). Not built: the in-place update of the depthwise layer's weights -- its
+folded weights set the bound |Y| <= gain max|X| + bias0 that the plan bakes by value into the
+layer's EposDepthwiseArgs and into its consumer's a_gain / a_bias, and captured graphs have
+copied those values, so an update needs a design for that bound; everything below
+decoder_conv0_pointwise's pre-activation; batch-norm statistics, bf16 mode, multi-scale nets and
+more than one device. Pinned to tests/helpers/pointwise_wgrad_ref.py and
+tests/helpers/decoder_backward_ref.py and, through them, to torch's fp64 autograd; parity with
+TensorFlow's gradients is unpinned. There is no CPU fallback.
 """
 import ctypes
 
@@ -113,6 +128,207 @@ def pointwise_weight_grads(a, g, weights, bn=None, eps=BN_EPS, a_h2=None, out=No
         C.ptr(result['BatchNorm/gamma']) if bn is not None else None,
         C.ptr(result[names[-1]]), q.handle), 'epos_pointwise_wgrad_close_f32')
   return result
+
+
+def _same_device_f32(dev, first, *named):
+  import torch
+  for t, what in named:
+    if t.device != dev:
+      raise EposError('%s is on %s, %s on %s' % (what, t.device, first, dev))
+    if t.dtype != torch.float32:
+      raise TypeError('%s must be torch.float32, got %s' % (what, t.dtype))
+
+
+def _out_rows(out, dev, n, width, what):
+  """(out, its [n, width] view, row stride): a new tensor, or the caller's, whose rows must lie
+  a constant stride apart so that the kernel writes into it and not into a copy."""
+  import torch
+  out = C.out(out, dev, torch.float32, (n, width), what, rows=True)
+  out2, ld = C.rows(out, width)
+  if out2.data_ptr() != out.data_ptr() or out2.shape[0] != n:
+    raise ValueError('%s: %d rows must lie a constant stride apart' % (what, n))
+  return out, out2, ld
+
+
+def pointwise_input_grad(g, weights, bn=None, eps=BN_EPS, relu_of=None, relu_of_h2=False,
+                         out=None, workspace=None):
+  """epos_pointwise_dgrad_f32: the gradient that crosses the layer y = relu(scale (.) (A W) +
+  bias), D = G Wf^T with Wf = the folded weights the forward multiplied by. g: f32 [..., N], the
+  gradient at the layer's pre-activation, rows a constant stride apart. weights: f32 [1,1,K,N]
+  or [K,N] on the device, contiguous. bn = (gamma, moving_variance), f32 [N] on the device,
+  with eps; None: a conv with biases (Wf = W). relu_of: the layer's input A, f32 [..., K], rows
+  a constant stride apart -- or, with relu_of_h2, the fp16 pairs the depthwise kernel wrote into
+  such a tensor (EposNet.pointwise_operand's 'a'): the result is +0.0 wherever it is <= 0, the
+  gradient at the pre-activation of the layer that produced A. Returns D f32 [rows, K], or `out`
+  (f32 [..., K], rows a constant stride apart; its padding columns are kept). `workspace`: a
+  float64 tensor of at least epos_pointwise_dgrad_workspace_bytes(K, N) / 8 values. Every
+  element is written. Enqueues on the current stream; does not synchronise."""
+  import torch
+  lib = _lib.load()
+  C.need_device(g, 'the input gradient needs a HIP device (there is no CPU fallback)')
+  dev = g.device
+  _same_device_f32(dev, 'g', (g, 'g'), (weights, 'weights'))
+  N = int(g.shape[-1])
+  if weights.dim() < 2 or weights.shape[-1] != N or weights.numel() != weights.shape[-2] * N:
+    raise ValueError('weights must be [1, 1, K, %d], got %s' % (N, tuple(weights.shape)))
+  if not weights.is_contiguous():
+    raise ValueError('weights must be contiguous')
+  K = int(weights.shape[-2])
+  g2, ldg = C.rows(g, N)
+  M = int(g2.shape[0])
+  if M < 1:
+    raise ValueError('g holds no rows')
+  consts = [None, None]
+  if bn is not None:
+    if len(bn) != 2:
+      raise ValueError('bn = (gamma, moving_variance)')
+    for t, what in zip(bn, ('gamma', 'moving_variance')):
+      C.dense(t, dev, torch.float32, what, shape=(N,), name='float32')
+    consts = list(bn)
+  m2, ldm = None, K
+  if relu_of is not None:
+    _same_device_f32(dev, 'g', (relu_of, 'relu_of'))
+    if relu_of.shape[-1] != K:
+      raise ValueError('relu_of must be [..., %d], got %s' % (K, tuple(relu_of.shape)))
+    m2, ldm = C.rows(relu_of, K)
+    if m2.shape[0] != M:
+      raise ValueError('relu_of holds %d rows, g %d' % (m2.shape[0], M))
+    if relu_of_h2 and m2.data_ptr() != relu_of.data_ptr():
+      raise ValueError('a pre-split relu_of must have rows a constant stride apart')
+  out, out2, ldd = _out_rows(out, dev, M, K, 'out')
+  nbytes = lib.epos_pointwise_dgrad_workspace_bytes(K, N)
+  _lib.check(nbytes, 'epos_pointwise_dgrad_workspace_bytes')
+  ws = C.workspace(workspace, dev, nbytes, torch.float64)
+  args = _lib.PointwiseDgradArgs(
+      G=C.ptr(g2), ldg=ldg, W=C.ptr(weights), gamma=C.ptr(consts[0]),
+      moving_variance=C.ptr(consts[1]), eps=float(eps), mask=C.ptr(m2), ldm=ldm,
+      mask_h2=int(bool(relu_of_h2) and m2 is not None), M=M, K=K, N=N, D=C.ptr(out2), ldd=ldd,
+      workspace=C.ptr(ws))
+  with C.launch(dev) as q:
+    q.keep(g2, m2, ws)
+    _lib.check(lib.epos_pointwise_dgrad_f32(ctypes.byref(args), q.handle),
+               'epos_pointwise_dgrad_f32')
+  return out
+
+
+def _nhwc(t, what):
+  """(t as [B*H*W, C] rows, pixel stride, (B, H, W, C)) of an NHWC tensor whose pixels lie a
+  constant stride apart (a slice of a wider buffer); anything else is made dense."""
+  if t.dim() != 4:
+    raise ValueError('%s must be [B, H, W, C], got %s' % (what, tuple(t.shape)))
+  t2, ld = C.rows(t, int(t.shape[-1]))
+  return t2, ld, tuple(int(v) for v in t.shape)
+
+
+def depthwise_workspace_words(B, H, Wd, Cc):
+  """int64 words depthwise_weight_grads needs: T and t in fp64 and the kernel's slabs."""
+  nbytes = _lib.load().epos_depthwise_wgrad_workspace_bytes(B, H, Wd, Cc)
+  _lib.check(nbytes, 'epos_depthwise_wgrad_workspace_bytes')
+  return 10 * Cc + (nbytes + 7) // 8
+
+
+def depthwise_weight_grads(x, d, depthwise_weights, bn, eps, rate=1, out=None, workspace=None):
+  """epos_depthwise_wgrad_f32 + epos_pointwise_wgrad_close_f32 with K = 9: the weight and
+  batch-norm gradients of a 3x3 depthwise layer (stride 1, 'SAME') with a frozen batch norm. x:
+  the layer's input, f32 [B,H,W,C], pixels a constant stride apart (EposNet.depthwise_operand's
+  'x'); d: f32 [B,H,W,C] or [B*H*W,C], the gradient at the layer's pre-activation, as
+  pointwise_input_grad(relu_of=...) writes it. depthwise_weights: f32 [3,3,C,1] on the device,
+  contiguous; bn = (gamma, moving_mean, moving_variance), f32 [C] on the device, with eps.
+  Returns {'depthwise_weights': f32 [3,3,C,1], 'BatchNorm/gamma': f32 [C], 'BatchNorm/beta':
+  f32 [C]}. `out` = such a dict of contiguous tensors to write into; `workspace` = an int64
+  tensor of at least depthwise_workspace_words(B, H, W, C) values. Every element of every
+  output is written. Enqueues on the current stream; does not synchronise."""
+  import torch
+  lib = _lib.load()
+  C.need_device(d, 'the depthwise gradients need a HIP device (there is no CPU fallback)')
+  dev = d.device
+  _same_device_f32(dev, 'd', (x, 'x'), (d, 'd'), (depthwise_weights, 'depthwise_weights'))
+  x2, ldx, (B, H, Wd, Cc) = _nhwc(x, 'x')
+  d2, ldd = C.rows(d, Cc) if d.shape[-1] == Cc else (None, 0)
+  if d2 is None or d2.shape[0] != B * H * Wd:
+    raise ValueError('d must hold %d rows of %d values, got %s' % (
+        B * H * Wd, Cc, tuple(d.shape)))
+  if depthwise_weights.numel() != 9 * Cc or tuple(depthwise_weights.shape[:2]) != (3, 3) or \
+      not depthwise_weights.is_contiguous():
+    raise ValueError('depthwise_weights must be a contiguous [3, 3, %d, 1] tensor, got %s' % (
+        Cc, tuple(depthwise_weights.shape)))
+  if bn is None or len(bn) != 3:
+    raise ValueError('bn = (gamma, moving_mean, moving_variance)')
+  for t, what in zip(bn, ('gamma', 'moving_mean', 'moving_variance')):
+    C.dense(t, dev, torch.float32, what, shape=(Cc,), name='float32')
+  shapes = {'depthwise_weights': (3, 3, Cc, 1), 'BatchNorm/gamma': (Cc,),
+            'BatchNorm/beta': (Cc,)}
+  result = {name: C.out((out or {}).get(name), dev, torch.float32, shape, 'out[%r]' % name,
+                        flat=True) for name, shape in shapes.items()}
+  ws = C.workspace(workspace, dev, 8 * depthwise_workspace_words(B, H, Wd, Cc), torch.int64)
+  T, tsum, slabs = ws[:9 * Cc], ws[9 * Cc:10 * Cc], ws[10 * Cc:]
+  args = _lib.DepthwiseWgradArgs(
+      X=C.ptr(x2), ldx=ldx, D=C.ptr(d2), ldd=ldd, B=B, H=H, W=Wd, C=Cc, stride=1,
+      rate=int(rate), T=C.ptr(T), t=C.ptr(tsum),
+      workspace=C.ptr(slabs) if slabs.numel() else None)
+  with C.launch(dev) as q:
+    q.keep(x2, d2, ws)
+    _lib.check(lib.epos_depthwise_wgrad_f32(ctypes.byref(args), q.handle),
+               'epos_depthwise_wgrad_f32')
+    _lib.check(lib.epos_pointwise_wgrad_close_f32(
+        C.ptr(T), C.ptr(tsum), C.ptr(depthwise_weights), 9, Cc, C.ptr(bn[0]), C.ptr(bn[1]),
+        C.ptr(bn[2]), float(eps), C.ptr(result['depthwise_weights']),
+        C.ptr(result['BatchNorm/gamma']), C.ptr(result['BatchNorm/beta']), q.handle),
+        'epos_pointwise_wgrad_close_f32')
+  return result
+
+
+def depthwise_input_grad(d, w9c, rate=1, relu_of=None, out=None):
+  """epos_depthwise_dgrad_f32: the gradient that crosses a 3x3 depthwise layer (stride 1,
+  'SAME'). d: f32 [B,H,W,C], pixels a constant stride apart, the gradient at the layer's
+  pre-activation; w9c: f32 [9,C] on the device, contiguous, the FOLDED weights the forward reads
+  (EposNet.depthwise_operand's 'w9c'). relu_of: the layer's input x, f32 [B,H,W,C], pixels a
+  constant stride apart: the result is +0.0 wherever it is <= 0, the gradient at the
+  pre-activation of the layer that produced x. Returns dX f32 [B,H,W,C], or `out` (f32
+  [B,H,W,C], pixels a constant stride apart; its padding columns are kept). Every element is
+  written. Enqueues on the current stream; does not synchronise."""
+  import torch
+  lib = _lib.load()
+  C.need_device(d, 'the depthwise input gradient needs a HIP device (there is no CPU fallback)')
+  dev = d.device
+  _same_device_f32(dev, 'd', (d, 'd'), (w9c, 'w9c'))
+  d2, ldd, (B, H, Wd, Cc) = _nhwc(d, 'd')
+  C.dense(w9c, dev, torch.float32, 'w9c', shape=(9, Cc), name='float32')
+  y2, ldy = None, Cc
+  if relu_of is not None:
+    _same_device_f32(dev, 'd', (relu_of, 'relu_of'))
+    if tuple(relu_of.shape) != (B, H, Wd, Cc):
+      raise ValueError('relu_of must be %s, got %s' % ((B, H, Wd, Cc), tuple(relu_of.shape)))
+    y2, ldy = C.rows(relu_of, Cc)
+  if out is not None and tuple(out.shape) != (B, H, Wd, Cc):
+    raise ValueError('out must be %s, got %s' % ((B, H, Wd, Cc), tuple(out.shape)))
+  out, out2, ldx = _out_rows(out, dev, B * H * Wd, Cc, 'out')
+  with C.launch(dev) as q:
+    q.keep(d2, y2)
+    _lib.check(lib.epos_depthwise_dgrad_f32(
+        C.ptr(d2), ldd, C.ptr(w9c), C.ptr(y2), ldy, C.ptr(out2), ldx, B, H, Wd, Cc, int(rate),
+        q.handle), 'epos_depthwise_dgrad_f32')
+  return out.view(B, H, Wd, Cc) if out.dim() == 2 else out
+
+
+DEPTHWISE_LAYER = W.DECODER_CONV1_DEPTHWISE
+DEPTHWISE_VARIABLES = tuple(DEPTHWISE_LAYER + '/' + v for v in W.DEPTHWISE_VARIABLES)
+DEPTHWISE_CONSTANTS = (DEPTHWISE_LAYER + '/BatchNorm/moving_mean',
+                       DEPTHWISE_LAYER + '/BatchNorm/moving_variance')
+
+
+def _depthwise_inputs(net, variables):
+  """(depthwise_weights, (gamma, moving_mean, moving_variance)) of decoder_conv1_depthwise on the
+  net's device: each from `variables` where given, otherwise the copy the net uploaded from its
+  checkpoint once (EposNet.depthwise_constants). With tensors on the device, or none, given,
+  nothing is copied from the host and nothing waited for."""
+  import torch
+  got = list(net.depthwise_constants(DEPTHWISE_LAYER))
+  for i, n in enumerate(DEPTHWISE_VARIABLES[:2] + DEPTHWISE_CONSTANTS):
+    v = variables.get(n)
+    if v is not None:
+      got[i] = torch.as_tensor(v, dtype=torch.float32).to(net.dev).contiguous()
+  return got[0], tuple(got[1:])
 
 
 def _layer_inputs(net, variables):

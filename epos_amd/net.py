@@ -142,6 +142,8 @@ class EposNet(object):
     self._sparse_packs = None
     self._layer_consts = {}      # trainable layer -> (moving_mean, moving_variance) on the device
     self._decoder_x = None
+    self._dw_operands = {}       # layer of weights.DEPTHWISE_BACKWARD_LAYERS -> depthwise_operand
+    self._dw_consts = {}         # ... -> its variables and statistics on the device
     self.mode = MODES[precision](self)
     self.act_dtype = self.mode.dtype
     self._build_plan()
@@ -287,6 +289,10 @@ class EposNet(object):
     ho, wo = (hi - 1) // stride + 1, (wi - 1) // stride + 1
     w9c, bias, gain, bias0 = self._dw_params(name, eps)
     y = self._act(B, ho, wo, c)
+    if name in W.DEPTHWISE_BACKWARD_LAYERS:
+      assert stride == 1 and not relu_in and relu_out, name
+      self._dw_operands[name] = {'x': x, 'ldx': ldx, 'b': B, 'h': hi, 'w': wi, 'c': c,
+                                 'rate': rate, 'w9c': w9c, 'bias': bias, 'eps': eps}
     ein = self._expr_of(x, 0, c)
     if relu_in:
       ein = self._relu_expr(ein)
@@ -882,6 +888,34 @@ class EposNet(object):
               float(args.a_bias))
     return {'a': a, 'lda': lda, 'm': m, 'k': k, 'n': n, 'presplit': presplit, 'a_h2': a_h2,
             'packs': self.mode.packs[name][2], 'eps': W.TRAINABLE_LAYERS[name]}
+
+  def depthwise_operand(self, name=W.DECODER_CONV1_DEPTHWISE):
+    """What the backward pass through a 3x3 depthwise layer of
+    weights.DEPTHWISE_BACKWARD_LAYERS needs of the plan, as it was recorded while the plan was
+    built (a dry run records it too): {'x': the layer's input, the buffer [B,h,w,ldx] the layer
+    below writes behind its ReLU and the net keeps alive; 'ldx', 'b', 'h', 'w', 'c', 'rate';
+    'w9c': the folded weights f32 [9,c] and 'bias': the folded bias f32 [c] its launch reads;
+    'eps': the batch norm's}. The layer's output is EposNet.pointwise_operand's 'a'."""
+    self._need_fp32_plan('depthwise_operand', device=False)
+    if name not in self._dw_operands:
+      raise ValueError('%r is not a depthwise layer the backward pass crosses (%s)' % (
+          name, ', '.join(W.DEPTHWISE_BACKWARD_LAYERS)))
+    return dict(self._dw_operands[name])
+
+  def depthwise_constants(self, name=W.DECODER_CONV1_DEPTHWISE):
+    """(depthwise_weights [3,3,C,1], gamma, moving_mean, moving_variance [C]) of a layer of
+    weights.DEPTHWISE_BACKWARD_LAYERS on the device, f32, uploaded from the checkpoint once and
+    kept: nothing updates that layer's variables, and a backward pass that asks for them enqueues
+    no copy and waits for none."""
+    if name not in W.DEPTHWISE_BACKWARD_LAYERS:
+      raise ValueError('%r is not a depthwise layer the backward pass crosses (%s)' % (
+          name, ', '.join(W.DEPTHWISE_BACKWARD_LAYERS)))
+    if name not in self._dw_consts:
+      self._dw_consts[name] = tuple(
+          torch.from_numpy(np.ascontiguousarray(self.ckpt[name + '/' + v], np.float32)).to(self.dev)
+          for v in ('depthwise_weights', 'BatchNorm/gamma', 'BatchNorm/moving_mean',
+                    'BatchNorm/moving_variance'))
+    return self._dw_consts[name]
 
   def layer_constants(self, name=W.DECODER_CONV1_POINTWISE):
     """(moving_mean, moving_variance) of a trainable layer's batch norm on the device, f32 [N],

@@ -11,15 +11,22 @@ any subset of their variables -- not a choice between code paths.
                   EposNet.set_weights (the device weight packer, csrc/weight_pack.hip: the
                   updated weights reach the built net, its captured graphs included, without a
                   round trip through the host).
+  decoder_conv1_grads  net_grads' nine gradients plus the backward pass through the separable
+                  conv decoder_conv1, down to decoder_conv0_pointwise's pre-activation.
   learning_rate   the reference's schedules (train_utils.py:117-195) in Python floats.
 
 The kernels' wrappers are epos_amd/heads_train.py (the logits layers' weight and input
 gradients, the momentum step) and epos_amd/decoder_train.py (the weight and batch-norm
 gradients of decoder_conv1_pointwise); the loop itself, its checkpoints and its logging are
 train_heads.py; augmentation is epos_amd/augment.py, applied between the upload and the
-forward pass. Not built: backpropagation from decoder_conv1_depthwise down, which starts with
-the input gradient G W^T of decoder_conv1_pointwise; batch-norm statistics, bf16 mode,
-multi-scale nets and more than one device. A further trained layer is a row of
+forward pass. decoder_conv1_grads runs the whole backward pass of the separable conv
+decoder_conv1 -- the input gradient of decoder_conv1_pointwise, the weight, batch-norm and input
+gradients of decoder_conv1_depthwise -- and returns the gradient at decoder_conv0_pointwise's
+pre-activation. Not built: the in-place update of the depthwise layer's weights (its folded
+weights set the bound gain / bias0 that the plan and its captured graphs hold by value: an
+update needs a design for that bound), everything below decoder_conv0_pointwise's
+pre-activation; batch-norm statistics, bf16 mode, multi-scale nets and more than one device. A
+further trained layer is a row of
 weights.TRAINABLE_LAYERS, its gradient kernel's wrapper and a clause in net_grads.
 
 Parity with TensorFlow's numbers is unpinned -- that holds for learning_rate too: TensorFlow
@@ -141,24 +148,74 @@ def net_grads(net, gt, variables, trainable_layers=W.LOGITS_LAYERS, weights=(1.0
   bad as loss.differentiable_losses returns them, grads = {'<scope>/weights': f32 [1,1,K,N],
   '<scope>/biases' or '<scope>/BatchNorm/gamma', '/BatchNorm/beta': f32 [N]} on the device for
   every variable of trainable_layers. fp32 single-scale nets only. Does not synchronise."""
-  layer = DT.LAYER in trainable_layers
+  values, bad, by_layer, _ = _grads_above(net, gt, variables, DT.LAYER in trainable_layers,
+                                         weights, reduction, ignore_label)
+  return values, bad, _checkpoint_names(by_layer)
+
+
+def _grads_above(net, gt, variables, layer, weights, reduction, ignore_label):
+  """What net_grads and decoder_conv1_grads share: the losses and the logits layers' weight
+  gradients and, with `layer`, heads_input_grad(relu_of=decoder_out) and the weight gradients of
+  decoder_conv1_pointwise on the net's own A. Returns (values, bad, {scope: {short name:
+  gradient}}, None or (G, A, the layer's operand, its weights, its (gamma, mean, variance)))."""
   op = net.pointwise_operand(DT.LAYER) if layer else None
   logits, values, bad, scales = HT._net_losses(net, gt, weights, reduction, ignore_label)
   raw = HT.heads_weight_grads(net.decoder_out, logits, gt, scales, ignore_label=ignore_label)
   by_layer = {'logits/' + head: dict(zip(W.layer_variables('logits/' + head), raw[head]))
               for head in HT.HEADS}
-  if layer:
-    G = HT.heads_input_grad(logits, gt, scales, variables, relu_of=net.decoder_out,
-                            ignore_label=ignore_label)
-    w, bn = DT._layer_inputs(net, variables)
-    a = op['a'].view(-1, op['a'].shape[-1])[:, :op['k']] if op['lda'] != op['k'] else op['a']
-    by_layer[DT.LAYER] = DT.pointwise_weight_grads(a, G, w, bn=bn, eps=op['eps'],
-                                                   a_h2=op['a_h2'])
+  if not layer:
+    return values, bad, by_layer, None
+  G = HT.heads_input_grad(logits, gt, scales, variables, relu_of=net.decoder_out,
+                          ignore_label=ignore_label)
+  w, bn = DT._layer_inputs(net, variables)
+  a = op['a'].view(-1, op['a'].shape[-1])[:, :op['k']] if op['lda'] != op['k'] else op['a']
+  by_layer[DT.LAYER] = DT.pointwise_weight_grads(a, G, w, bn=bn, eps=op['eps'],
+                                                 a_h2=op['a_h2'])
+  return values, bad, by_layer, (G, a, op, w, bn)
+
+
+def _checkpoint_names(by_layer):
+  """{'<scope>/<short name>': gradient} in the checkpoint's layout: matrices as [1,1,K,N]."""
   grads = {}
   for scope, by_short in by_layer.items():
-    for short, t in by_short.items():            # the checkpoint's layout: matrices as [1,1,K,N]
+    for short, t in by_short.items():
       grads[scope + '/' + short] = t.view(1, 1, *t.shape) if t.dim() == 2 else t
-  return values, bad, grads
+  return grads
+
+
+def decoder_conv1_grads(net, gt, variables, weights=(1.0, 1.0, 100.0), reduction='pooled',
+                        ignore_label=255):
+  """The whole backward pass of the separable conv decoder_conv1: call after
+  net.forward_logits(). variables as net_grads takes them, with all four layers of
+  weights.TRAINABLE_LAYERS; the depthwise layer's three variables and its statistics come from
+  `variables` where given, otherwise from the copy of the net's checkpoint that it keeps on the
+  device (EposNet.depthwise_constants). Runs the losses and the logits
+  layers' weight gradients as net_grads does, then
+    heads_input_grad(relu_of=decoder_out)          G, at decoder_conv1_pointwise's pre-activation
+    pointwise_weight_grads                         that layer's dW, dgamma, dbeta
+    pointwise_input_grad(relu_of=the net's own A)  D, at decoder_conv1_depthwise's pre-activation
+                                                   (the mask: fp16 pairs or fp32, as the plan has it)
+    depthwise_weight_grads                         that layer's dw, dgamma, dbeta
+    depthwise_input_grad(relu_of=x)                d_in
+  Returns (values, bad, grads, d_in): values, bad and the nine gradients as net_grads returns
+  them, byte for byte, plus 'decoder/decoder_conv1_depthwise/depthwise_weights' f32 [3,3,C,1],
+  '.../BatchNorm/gamma' and '.../BatchNorm/beta' f32 [C]; d_in f32 [B,h,w,C]: the gradient at
+  decoder_conv0_pointwise's pre-activation, the G that pointwise_weight_grads takes for that
+  layer. The gradients of the depthwise layer are for inspection and for a trainer to come:
+  Optimizer and EposNet.set_weights do not take them. fp32 single-scale nets only. Does not
+  synchronise."""
+  dw = net.depthwise_operand(DT.DEPTHWISE_LAYER)
+  values, bad, by_layer, (G, a, op, w, bn) = _grads_above(net, gt, variables, True, weights,
+                                                          reduction, ignore_label)
+  D = DT.pointwise_input_grad(G, w, bn=(bn[0], bn[2]), eps=op['eps'], relu_of=a,
+                              relu_of_h2=op['presplit'])
+  x = dw['x'][..., :dw['c']]
+  D4 = D.view(dw['b'], dw['h'], dw['w'], dw['c'])
+  dww, dbn = DT._depthwise_inputs(net, variables)
+  by_layer[DT.DEPTHWISE_LAYER] = DT.depthwise_weight_grads(x, D4, dww, dbn, dw['eps'],
+                                                           rate=dw['rate'])
+  d_in = DT.depthwise_input_grad(D4, dw['w9c'], rate=dw['rate'], relu_of=x)
+  return values, bad, _checkpoint_names(by_layer), d_in
 
 
 def learning_rate(step, policy='poly', base_learning_rate=1e-4, decay_step=2000,

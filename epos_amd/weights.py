@@ -105,6 +105,13 @@ TRAINABLE_LAYERS = {
     DECODER_CONV1_POINTWISE: 1e-5,
 }
 LOGITS_LAYERS = tuple(s for s in TRAINABLE_LAYERS if s.startswith('logits/'))
+DECODER_CONV1_DEPTHWISE = 'decoder/decoder_conv1_depthwise'
+# The 3x3 depthwise layers the backward pass crosses (trainer.decoder_conv1_grads): scope -> the
+# eps of its frozen batch norm. The plan records their operands (EposNet.depthwise_operand).
+# NOT trainable layers: a depthwise layer's folded weights set the bound (gain, bias0) that the
+# plan bakes into its launches by value, so an in-place update needs a design of its own.
+DEPTHWISE_BACKWARD_LAYERS = {DECODER_CONV1_DEPTHWISE: 1e-5}
+DEPTHWISE_VARIABLES = ('depthwise_weights', 'BatchNorm/gamma', 'BatchNorm/beta')
 # a 1x1 conv layer's trained variables by whether it has a batch norm, `weights` first: what is
 # given together to EposNet.set_weights and what a gradient wrapper's result is keyed by
 CONV_VARIABLES = {False: ('weights', 'biases'),

@@ -1360,6 +1360,10 @@ int epos_heads_dgrad_f32(const float* obj_logits, int64_t ld_obj, const float* f
  * rounded to fp32 once; a result of -0.0 is written as +0.0. With gamma NULL (a conv with
  * biases and no batch norm; moving_mean, moving_variance and dgamma must then be NULL, W is
  * not read): dW = fl32(S), dbeta = fl32(g) is the gradient of `biases`. One launch.
+ *   It is also the closing of the depthwise gradients ("Depthwise gradients" below): the
+ *   checkpoint's depthwise_weights [3,3,C,1] is a contiguous [9][C] matrix, and with K = 9,
+ *   N = C, S = T and g = t the three formulas are dw = scale T, dbeta = t and dgamma = rstd
+ *   (sum_tap w T - mean t). No other entry closes them.
  *   Refused with EPOS_E_INVALID: K or N < 1; a null S, g, dW or dbeta; with gamma, a null W,
  *   moving_mean, moving_variance or dgamma, or an eps that is negative or NaN; without gamma, a
  *   non-null moving_mean, moving_variance or dgamma; a misaligned pointer. */
@@ -1384,6 +1388,129 @@ int epos_pointwise_wgrad_close_f32(const double* S, const double* g, const float
                                    const float* gamma, const float* moving_mean,
                                    const float* moving_variance, double eps, float* dW,
                                    float* dgamma, float* dbeta, void* stream);
+
+/* Pointwise input gradient (csrc/pointwise_dgrad.hip; added without an ABI version change). The
+ * gradient that crosses a 1x1 conv layer with a folded batch norm --
+ * decoder/decoder_conv1_pointwise -- from the gradient G at its pre-activation to the
+ * pre-activation of the layer that produced its input: D = mask (.) (G Wf^T).
+ * tests/helpers/decoder_backward_ref.py restates it in numpy.
+ *
+ * The layer's forward is y = relu(scale (.) (A W) + bias), scale_c = fl32(gamma_c / sqrt(var_c +
+ * eps)) exactly as "Pointwise weight gradient" defines it. The forward multiplies by the FOLDED
+ * matrix Wf[k,c] = fl32(W[k,c] * scale_c), a single fp32 product, as EposNet.set_weights and the
+ * plan's host fold compute it; this entry multiplies by the same matrix. With gamma NULL the
+ * layer is a conv with biases: Wf = W, and moving_variance must be NULL too.
+ *
+ * epos_pointwise_dgrad_f32. G f32 [M,N] with row stride ldg; W f32 [K,N] contiguous, the
+ * checkpoint's layout; gamma, moving_variance f32 [N]; D f32 [M,K] with row stride ldd [device].
+ *     D[p,k] = fl32( sum_c (double)G[p,c] * (double)Wf[k,c] )
+ *   Arithmetic. Every product is exact in fp64; one fp64 accumulator per (p, k) from +0.0 on the
+ *   matrix pipe (v_mfma_f64_16x16x4_f64), the c in an order that (K, N) alone fix, rounded to
+ *   fp32 once. N is a layer width (<= 1024): no split over c, no slabs, no atomics. The same
+ *   bytes in every run, for a row alone and at any position of M, and for every alignment of the
+ *   buffers. Within 2^-24 |exact| + (N + 16) 2^-52 sum_c |G||Wf| of the exact sum.
+ *   Mask. mask NULL, or M rows of K columns with row stride ldm: the layer's input A, that is
+ *   the output of the layer below behind its ReLU. D[p,k] is written as +0.0 wherever the mask
+ *   value is <= 0 (-0.0 counts, a NaN does not): D is then the gradient at the pre-activation of
+ *   the layer below. With mask_h2 != 0 the mask holds the fp16 pairs EposDepthwiseArgs.y_h2
+ *   writes, per 16 bytes [hi(k..k+3) | mid(k..k+3)], and its value is hi + mid 2^-11: only the
+ *   sign matters, so no absmax slot is read. That is the value the forward GEMM multiplied: a
+ *   y > 0 that the split flushed to zero is masked, as the forward saw a zero there.
+ *   EVERY element of D is WRITTEN; the padding columns of G, mask and D are never read or
+ *   written. A non-finite G[p,.] reaches row p only, a non-finite weight column k only (by IEEE
+ *   rules, 0 * Inf included); a masked element is +0.0 whatever the sum.
+ *   workspace [device]: epos_pointwise_dgrad_workspace_bytes(K, N) bytes, 16-byte aligned: Wf in
+ *   fp64, its rows padded to a multiple of 64 and its columns to one of 16 with +0.0. Contents
+ *   undefined before, Wf after.
+ *   Launches: two on `stream`, the fold and the GEMM; no allocation, no host synchronisation,
+ *   capturable in a graph.
+ *   Refused with EPOS_E_INVALID before any launch, nothing written: null args, G, W, D or
+ *   workspace; M, K or N < 1; K or N > 1024; ldg < N; ldd < K; ldm < K with a mask; gamma
+ *   without moving_variance or the reverse; with gamma an eps that is negative or NaN; a pointer
+ *   that is not 4-byte (the workspace: 16-byte) aligned; mask_h2 with K % 4 != 0, ldm % 4 != 0
+ *   or a mask that is not 16-byte aligned; D starting at G or at mask. */
+typedef struct EposPointwiseDgradArgs {
+  const float* G; int64_t ldg;
+  const float* W;               /* [K,N] */
+  const float* gamma;           /* [N], or NULL with moving_variance NULL */
+  const float* moving_variance;
+  double eps;
+  const void* mask; int64_t ldm;   /* or NULL */
+  int32_t mask_h2;
+  int32_t reserved0;            /* 0 */
+  int64_t M;
+  int32_t K, N;
+  float* D; int64_t ldd;
+  void* workspace;
+} EposPointwiseDgradArgs;
+int64_t epos_pointwise_dgrad_workspace_bytes(int K, int N);
+int epos_pointwise_dgrad_f32(const EposPointwiseDgradArgs* args, void* stream);
+
+/* Depthwise gradients (csrc/depthwise_grad.hip; added without an ABI version change). The
+ * backward pass of a 3x3 depthwise layer with a FROZEN batch norm, stride 1 --
+ * decoder/decoder_conv1_depthwise. tests/helpers/decoder_backward_ref.py restates both entries.
+ *
+ * The layer's forward is a = relu(scale_c sum_tap w[tap,c] X[b, y+(ky-1)r, x+(kx-1)r, c] +
+ * bias_c), TF 'SAME' (zero) padding, r = rate, tap = 3 ky + kx as in EposDepthwiseArgs. D f32
+ * [B,H,W,C] is dL/d(pre-activation): what epos_pointwise_dgrad_f32 writes with the mask.
+ *
+ * epos_depthwise_wgrad_f32: T f64 [9,C] and t f64 [C] [device], every element WRITTEN.
+ *     T[tap,c] = sum_{b,y,x} X[b, y+(ky-1)r, x+(kx-1)r, c] * D[b,y,x,c]
+ *     t[c]     = sum_{b,y,x} D[b,y,x,c]
+ *   A tap in the padding adds nothing; a tap never reads a neighbouring image of the batch. X
+ *   f32 with pixel stride ldx, D f32 with pixel stride ldd, C % 4 == 0 as in the forward; the
+ *   padding columns are never read. Products exact in fp64, sums in fp64 from +0.0: within
+ *   (B H W + 16) 2^-52 sum |X||D| of the exact sum whatever the order.
+ *   Order of the sums (no atomics, the same bytes in every run). The B H W pixels, in (b, y, x)
+ *   order, are cut into ranges of epos_depthwise_wgrad_range_pixels(B, H, W, C) pixels, the
+ *   last one shorter: a function of its arguments only. With one range the sums are written to
+ *   T and t; with more, range r writes slab r of the workspace, f64 [9*C + C], and a closing
+ *   launch adds the slabs in range order from +0.0. Within a range: with s = 256 / min(C / 4,
+ *   16) pixel slots, slot j adds the range's pixels j, j + s, j + 2 s, ... in ascending order
+ *   from +0.0, then the slots' sums are added in slot order from +0.0.
+ *   workspace [device]: epos_depthwise_wgrad_workspace_bytes(B, H, W, C) bytes (0 with one
+ *   range: it may then be NULL), 8-byte aligned.
+ *   The checkpoint-shaped gradients need NO kernel of their own: depthwise_weights [3,3,C,1] is
+ *   a contiguous [9][C] matrix, and epos_pointwise_wgrad_close_f32(T, t, w, K = 9, N = C, gamma,
+ *   moving_mean, moving_variance, eps, ...) is exactly dw = scale T, dbeta = t, dgamma = rstd
+ *   (sum_tap w T - mean t).
+ *   Launches: one, or two with more than one range; no allocation, no host synchronisation,
+ *   capturable in a graph.
+ *   Refused with EPOS_E_INVALID before the launch, nothing written: null args, X, D, T or t; B,
+ *   H, W or C < 1; C % 4 != 0; stride != 1; rate < 1; ldx or ldd < C or not a multiple of 4; X
+ *   or D not 16-byte, T or t not 8-byte aligned; a missing or misaligned workspace when one is
+ *   needed.
+ *
+ * epos_depthwise_dgrad_f32: dX f32 [B,H,W,C] with pixel stride ldx [device].
+ *     dX[b,y,x,c] = fl32( sum_tap (double)w9c[tap,c] * (double)D[b, y-(ky-1)r, x-(kx-1)r, c] )
+ *   w9c f32 [9][C]: the FOLDED weights the forward reads (EposDepthwiseArgs.w9c). A tap whose
+ *   source pixel lies outside the image is skipped. One fp64 accumulator per element from +0.0,
+ *   the taps in ascending order, each product exact, rounded to fp32 once: reproducible bit for
+ *   bit. With Y non-NULL (pixel stride ldy) dX is written as +0.0 wherever Y <= 0 (-0.0 counts,
+ *   a NaN does not), the rule of epos_heads_dgrad_f32: Y is the activation the layer below
+ *   produced, X itself, and dX is then the gradient at that layer's pre-activation -- for
+ *   decoder_conv1_depthwise the G that epos_pointwise_wgrad_f32 takes for
+ *   decoder_conv0_pointwise. EVERY element is WRITTEN; padding columns are not touched. One
+ *   launch; the same bytes in every run, for an image alone and at any position of a batch.
+ *   Refused with EPOS_E_INVALID: a null D, w9c or dX; B, H, W or C < 1; C % 4 != 0; rate < 1;
+ *   ldd, ldx or (with Y) ldy < C or not a multiple of 4; a pointer that is not 16-byte aligned;
+ *   dX starting at D. */
+typedef struct EposDepthwiseWgradArgs {
+  const float* X; int64_t ldx;
+  const float* D; int64_t ldd;
+  int32_t B, H, W, C;
+  int32_t stride;               /* 1 */
+  int32_t rate;
+  double* T;
+  double* t;
+  void* workspace;
+} EposDepthwiseWgradArgs;
+int64_t epos_depthwise_wgrad_range_pixels(int B, int H, int W, int C);
+int64_t epos_depthwise_wgrad_workspace_bytes(int B, int H, int W, int C);
+int epos_depthwise_wgrad_f32(const EposDepthwiseWgradArgs* args, void* stream);
+int epos_depthwise_dgrad_f32(const float* D, int64_t ldd, const float* w9c,
+                             const float* Y /* or NULL */, int64_t ldy, float* dX, int64_t ldx,
+                             int B, int H, int W, int C, int rate, void* stream);
 
 /* Weight update (csrc/weight_pack.hip; added without an ABI version change). The three host
  * packers above restated as device kernels, so that weights updated on the device (the momentum
