@@ -128,8 +128,8 @@ def _pack_split(lib, w_kn):
 def test_pointwise_gemm_split_ring(lib, k, m, n, aligned, res):
   """Split-operand kernel (fp32 GEMM on the bf16 matrix pipe, taken when Ws is given):
   every prologue / steady / tail path of the four-stage ring (1..46 K steps, partial
-  last step) in both tile shapes (64 x 128 for small grids, 128 x 128 from 512 tiles
-  on: the two 16 000-row cases), ragged M and N tiles, the float4 and the scalar epilogue, residual +
+  last step) in both tile shapes (64 x 128 for small grids, 128 x 128 from 200 tiles of
+  128 x 128 on: the two 16 000-row cases, 524 and 516 tiles), ragged M and N tiles, the float4 and the scalar epilogue, residual +
   ReLU; NaNs behind every row of A poison any read past K. Tolerance as for the fp32
   kernels (the accuracy comparison proper is test_pointwise_gemm_split_accuracy)."""
   from epos_amd import _lib
@@ -290,8 +290,10 @@ def test_conv3x3_implicit_gemm(lib, b, h, w, cin, cout, stride, rate, split):
   block outside the image) vs conv2d_same of the oracle
   (external/slim/nets/resnet_utils.py:77-122), through the fp32-MFMA kernel (both
   tile layouts: Cout <= 64 and > 64) and, with the split-packed weights, through the
-  split-operand kernel (both tile shapes: the last case has >= 200 tiles); one and
-  several channel blocks per tap, ragged M tiles."""
+  split-operand kernel (its 64-row tile only: the last and largest case, M = 19200 and
+  N = 64, has 150 tiles of 128 x 128, below the 200 from which the 128-row tile is taken;
+  tests/test_gpu_conv3x3_regimes.py runs that one); one and several channel blocks per tap,
+  ragged M tiles."""
   from epos_amd import _lib
   from oracle import net_ref
   rng = np.random.RandomState(b * h + cin)
