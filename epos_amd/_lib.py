@@ -435,6 +435,27 @@ SYMBOLS = {
         vp, ctypes.c_int64, vp, vp, vp, vp, vp, vp, ctypes.c_int, ctypes.c_int64, ctypes.c_int,
         ctypes.c_int, ctypes.c_int, vp, vp, vp, vp, vp, ctypes.c_int64, ctypes.c_int, vp,
         ctypes.c_int64, vp, ctypes.c_int64, vp]),
+    # k nearest fragments per pixel: each entry is its sibling plus `int knn`
+    'epos_gt_fields_knn': (ctypes.c_int, [
+        vp, vp, vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp, ctypes.c_int,
+        ctypes.c_int, ctypes.c_int, vp, vp, vp, vp, vp, vp]),
+    'epos_loss_terms_knn': (ctypes.c_int, [
+        vp, ctypes.c_int64, vp, vp, vp, vp, vp, vp, ctypes.c_int, ctypes.c_int64, ctypes.c_int,
+        ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp, vp]),
+    'epos_loss_reduce_knn': (ctypes.c_int, [
+        vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double,
+        ctypes.c_int, ctypes.c_int, vp, vp, vp]),
+    'epos_loss_grads_knn': (ctypes.c_int, [
+        vp, ctypes.c_int64, vp, vp, vp, vp, vp, vp, ctypes.c_int, ctypes.c_int64, ctypes.c_int,
+        ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp, vp, ctypes.c_int64, vp, vp, vp]),
+    'epos_heads_wgrad_knn_f32': (ctypes.c_int, [
+        vp, ctypes.c_int64, ctypes.c_int, vp, ctypes.c_int64, vp, vp, vp, vp, vp, vp,
+        ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp,
+        vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    'epos_heads_dgrad_knn_f32': (ctypes.c_int, [
+        vp, ctypes.c_int64, vp, vp, vp, vp, vp, vp, ctypes.c_int, ctypes.c_int64, ctypes.c_int,
+        ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp, vp, ctypes.c_int64,
+        ctypes.c_int, vp, ctypes.c_int64, vp, ctypes.c_int64, vp]),
     # weight and batch-norm gradients of a 1x1 conv layer
     'epos_pointwise_wgrad_workspace_bytes': (ctypes.c_int64, [
         ctypes.c_int64, ctypes.c_int, ctypes.c_int]),

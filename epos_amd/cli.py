@@ -115,6 +115,16 @@ def check_supported_flags(args):
         'flags outside what this build implements (common.py:60-154): ' + '; '.join(bad))
 
 
+def check_gt_knn_frags(args):
+  """args.gt_knn_frags (the command line's, or params.yml's) as an int; ValueError unless
+  1 <= gt_knn_frags <= min(num_frags, 4), before a device is touched."""
+  from epos_amd import loss
+  k = args.gt_knn_frags
+  if isinstance(k, bool) or not isinstance(k, int):
+    raise ValueError('gt_knn_frags must be an integer, got %r' % (k,))
+  return loss.check_knn(k, int(args.num_frags))
+
+
 # The flags infer.py and eval.py share, in the groups in which both parsers list them (each
 # script puts its own flags between the groups: the order of --help is part of the contract).
 def add_model_name_flags(ap):

@@ -50,4 +50,13 @@ constexpr int DW_PRIO = 3;
     }                                            \
   } while (0)
 
+// EPOS_REQUIRE in the name of the entry `fn`: an entry and its _knn sibling share one body
+#define EPOS_REQUIRE_FN(fn, cond, msg)           \
+  do {                                           \
+    if (!(cond)) {                               \
+      ::epos::set_error("%s: %s", fn, msg);      \
+      return EPOS_E_INVALID;                     \
+    }                                            \
+  } while (0)
+
 }  // namespace epos

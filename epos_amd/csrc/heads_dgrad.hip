@@ -16,7 +16,8 @@
 // Every output row is computed by one wave from its own pixel, the weights and s_k only, one
 // accumulator per (pixel, k), the active columns in the stated order: no workspace, no atomics,
 // the same bytes in every run, at every position of every batch and for every alignment.
-// fp64 on the fp32 values, -ffp-contract=off.
+// fp64 on the fp32 values, -ffp-contract=off. With knn slots per pixel ("k nearest fragments")
+// the three localisation columns of every slot follow, the slots by ascending fragment.
 #include "loss_rows.h"
 
 namespace epos {
@@ -65,17 +66,18 @@ __device__ __forceinline__ void add_rows(double (&acc)[J * KV], const float* __r
     add_row<KV, J>(acc, rows + e * ldwt, K, lane, static_cast<double>(from_lane(dv, e)));
 }
 
-template <int KV, int J>
+template <int SLOTS, int KV, int J>
 __global__ __launch_bounds__(LOSS_THREADS) void heads_dgrad_kernel(
     const float* __restrict__ obj_logits, int64_t ld_obj, const float* __restrict__ frag_logits,
     const float* __restrict__ frag_loc, const int32_t* __restrict__ gt_obj,
     const int32_t* __restrict__ gt_frag, const float* __restrict__ gt_loc,
     const float* __restrict__ gt_weight, int64_t P, int64_t blocks_per_image, int num_objs,
-    int num_frags, int ignore_label, int L, const double* __restrict__ scales,
+    int num_frags, int ignore_label, int knn_arg, int L, const double* __restrict__ scales,
     const double* __restrict__ upstream, const float* __restrict__ Wt_obj,
     const float* __restrict__ Wt_frag, const float* __restrict__ Wt_loc, int64_t ldwt, int K,
     const float* Y, int64_t ldy, float* dX, int64_t ldx) {
-  __shared__ ShareRows<DG_SHARE> sh;
+  const int knn = slots_of<SLOTS>(knn_arg);
+  __shared__ ShareRows<DG_SHARE, SLOTS> sh;
   const int64_t image = blockIdx.x / blocks_per_image;
   const int64_t p0 = (blockIdx.x % blocks_per_image) * DG_SHARE;
   const int64_t p1 = p0 + DG_SHARE < P ? p0 + DG_SHARE : P;
@@ -86,10 +88,10 @@ __global__ __launch_bounds__(LOSS_THREADS) void heads_dgrad_kernel(
   const int per_pass = LOSS_THREADS / L;
   for (int base = 0; base < n_here; base += per_pass) {     // uniform trip count: shuffles below
     const int i = base + threadIdx.x / L;
-    const PixelRows r = pixel_rows<false, false>(obj_logits, ld_obj, frag_logits, gt_obj, gt_frag,
-                                                 gt_weight, pix0 + i, i < n_here, num_objs, F,
-                                                 ignore_label, true, true, sub, L);
-    if (i < n_here && sub == 0) sh.put(i, r);
+    const PixelRows<SLOTS> r = pixel_rows<SLOTS, false, false>(
+        obj_logits, ld_obj, frag_logits, gt_obj, gt_frag, gt_weight, pix0 + i, i < n_here,
+        num_objs, F, ignore_label, knn, true, true, sub, L);
+    if (i < n_here && sub == 0) sh.put(i, r, knn);
   }
   __syncthreads();
   double s[3];
@@ -112,22 +114,44 @@ __global__ __launch_bounds__(LOSS_THREADS) void heads_dgrad_kernel(
       }
     }
     if (g > 0) {
-      const int f = __builtin_amdgcn_readfirstlane(sh.frag[i]);
       const int64_t row0 = static_cast<int64_t>(g - 1) * F;  // the pixel's row of O * F
       const int64_t frag_row = frag_row_offset(p, num_objs, g, F);
       const double m = static_cast<double>(sh.m_frag[i]), S = sh.s_frag[i];
+      // one slot: its fragment in a scalar register, as before there were slots
+      const int f0 = __builtin_amdgcn_readfirstlane(sh.frag[i][0]);
       for (int c0 = 0; c0 < F; c0 += 64) {                   // the fragment head
         const int c = c0 + lane;
         float dv = 0.f;
-        if (c < F) dv = softmax_grad(frag_logits[frag_row + c], m, S, c == f, s[1]);
+        if (c < F) {
+          if constexpr (SLOTS == 1)
+            dv = softmax_grad(frag_logits[frag_row + c], m, S, c == f0, s[1]);
+          else
+            dv = softmax_grad_knn(frag_logits[frag_row + c], m, S, is_slot(sh.frag[i], knn, c),
+                                  s[1], static_cast<double>(knn));
+        }
         add_rows<KV, J>(acc, Wt_frag + (row0 + c0) * ldwt, ldwt, F - c0 < 64 ? F - c0 : 64, K,
                         lane, dv);
       }
-      float dv = 0.f;                                        // the three localisation values
-      if (lane < 3)
-        dv = huber_grad(frag_loc[(frag_row + f) * 3 + lane], gt_loc[p * 3 + lane], sh.wgt[i],
-                        s[2]);
-      add_rows<KV, J>(acc, Wt_loc + (row0 + f) * 3 * ldwt, ldwt, 3, K, lane, dv);
+      // the three localisation values of every slot, the slots by ascending fragment (they
+      // name different fragments): the columns in ascending order
+      int f = -1;
+      for (int a = 0; a < knn; ++a) {
+        int next = F, slot = 0;
+        if constexpr (SLOTS == 1) {
+          next = f0;
+        } else {
+          for (int j = 0; j < knn; ++j) {
+            const int fj = __builtin_amdgcn_readfirstlane(sh.frag[i][j]);
+            if (fj > f && fj < next) { next = fj; slot = j; }
+          }
+        }
+        f = next;
+        float dv = 0.f;
+        if (lane < 3)
+          dv = huber_grad(frag_loc[(frag_row + f) * 3 + lane],
+                          gt_loc[(p * knn + slot) * 3 + lane], sh.wgt[i][slot], s[2]);
+        add_rows<KV, J>(acc, Wt_loc + (row0 + f) * 3 * ldwt, ldwt, 3, K, lane, dv);
+      }
     }
     // an ignored or bad pixel: the sums are still +0.0
 #pragma unroll
@@ -160,25 +184,28 @@ __global__ __launch_bounds__(LOSS_THREADS) void heads_dgrad_kernel(
 
 using namespace epos;
 
-extern "C" int epos_heads_dgrad_f32(const float* obj_logits, int64_t ld_obj,
-                                    const float* frag_logits, const float* frag_loc,
-                                    const int32_t* gt_obj, const int32_t* gt_frag,
-                                    const float* gt_loc, const float* gt_weight, int B, int64_t P,
-                                    int num_objs, int num_frags, int ignore_label,
-                                    const double* scales, const double* upstream,
-                                    const float* Wt_obj, const float* Wt_frag,
-                                    const float* Wt_loc, int64_t ldwt, int K, const float* Y,
-                                    int64_t ldy, float* dX, int64_t ldx, void* stream) {
-  const int rc = check_dims(__func__, B, P, num_objs, num_frags, K);
+namespace {
+
+// epos_heads_dgrad_knn_f32, refusing in the name of the entry that was called
+int heads_dgrad(const char* fn, const float* obj_logits, int64_t ld_obj, const float* frag_logits,
+                const float* frag_loc, const int32_t* gt_obj, const int32_t* gt_frag,
+                const float* gt_loc, const float* gt_weight, int B, int64_t P, int num_objs,
+                int num_frags, int ignore_label, int knn, const double* scales,
+                const double* upstream, const float* Wt_obj, const float* Wt_frag,
+                const float* Wt_loc, int64_t ldwt, int K, const float* Y, int64_t ldy, float* dX,
+                int64_t ldx, void* stream) {
+  const int rc = check_dims(fn, B, P, num_objs, num_frags, K);
   if (rc != EPOS_OK) return rc;
-  EPOS_REQUIRE(ldx >= K, "ldx must be >= K");
-  EPOS_REQUIRE(ldwt >= K, "ldwt must be >= K");
-  EPOS_REQUIRE(!Y || ldy >= K, "ldy must be >= K");
-  EPOS_REQUIRE(ld_obj >= num_objs + 1, "ld_obj must be >= num_objs + 1");
+  const int rk = check_knn(fn, knn, num_frags);
+  if (rk != EPOS_OK) return rk;
+  EPOS_REQUIRE_FN(fn, ldx >= K, "ldx must be >= K");
+  EPOS_REQUIRE_FN(fn, ldwt >= K, "ldwt must be >= K");
+  EPOS_REQUIRE_FN(fn, !Y || ldy >= K, "ldy must be >= K");
+  EPOS_REQUIRE_FN(fn, ld_obj >= num_objs + 1, "ld_obj must be >= num_objs + 1");
   if (B == 0 || P == 0) return EPOS_OK;
-  EPOS_REQUIRE(obj_logits && frag_logits && frag_loc && gt_obj && gt_frag && gt_loc &&
+  EPOS_REQUIRE_FN(fn, obj_logits && frag_logits && frag_loc && gt_obj && gt_frag && gt_loc &&
                gt_weight && scales && Wt_obj && Wt_frag && Wt_loc && dX, "null pointer");
-  const int alias = check_no_alias(__func__, {obj_logits, frag_logits, frag_loc, gt_obj, gt_frag,
+  const int alias = check_no_alias(fn, {obj_logits, frag_logits, frag_loc, gt_obj, gt_frag,
                                               gt_loc, gt_weight, scales, upstream, Wt_obj, Wt_frag,
                                               Wt_loc, Y}, {dX});
   if (alias != EPOS_OK) return alias;
@@ -190,20 +217,53 @@ extern "C" int epos_heads_dgrad_f32(const float* obj_logits, int64_t ld_obj,
   const int groups = static_cast<int>(ceil_div(K, vec ? 256 : 64));   // of 64 lanes
   const dim3 grid(static_cast<unsigned>(B * per_image));
   hipStream_t s = static_cast<hipStream_t>(stream);
-#define EPOS_DGRAD_LAUNCH(KV, J)                                                               \
-  hipLaunchKernelGGL((heads_dgrad_kernel<KV, J>), grid, dim3(LOSS_THREADS), 0, s, obj_logits,  \
-                     ld_obj, frag_logits, frag_loc, gt_obj, gt_frag, gt_loc, gt_weight, P,     \
-                     per_image, num_objs, num_frags, ignore_label, L, scales, upstream,        \
-                     Wt_obj, Wt_frag, Wt_loc, ldwt, K, Y, ldy, dX, ldx)
-  if (vec) {
-    if (groups <= 1) EPOS_DGRAD_LAUNCH(4, 1);
-    else if (groups <= 2) EPOS_DGRAD_LAUNCH(4, 2);
-    else EPOS_DGRAD_LAUNCH(4, 4);
-  } else {
-    if (groups <= 1) EPOS_DGRAD_LAUNCH(1, 1);
-    else if (groups <= 4) EPOS_DGRAD_LAUNCH(1, 4);
-    else EPOS_DGRAD_LAUNCH(1, 16);
+#define EPOS_DGRAD_LAUNCH(SLOTS, KV, J)                                                        \
+  hipLaunchKernelGGL((heads_dgrad_kernel<SLOTS, KV, J>), grid, dim3(LOSS_THREADS), 0, s,       \
+                     obj_logits, ld_obj, frag_logits, frag_loc, gt_obj, gt_frag, gt_loc,       \
+                     gt_weight, P, per_image, num_objs, num_frags, ignore_label, knn, L,       \
+                     scales, upstream, Wt_obj, Wt_frag, Wt_loc, ldwt, K, Y, ldy, dX, ldx)
+#define EPOS_DGRAD_WIDTH(SLOTS)                           \
+  if (vec) {                                              \
+    if (groups <= 1) EPOS_DGRAD_LAUNCH(SLOTS, 4, 1);      \
+    else if (groups <= 2) EPOS_DGRAD_LAUNCH(SLOTS, 4, 2); \
+    else EPOS_DGRAD_LAUNCH(SLOTS, 4, 4);                  \
+  } else {                                                \
+    if (groups <= 1) EPOS_DGRAD_LAUNCH(SLOTS, 1, 1);      \
+    else if (groups <= 4) EPOS_DGRAD_LAUNCH(SLOTS, 1, 4); \
+    else EPOS_DGRAD_LAUNCH(SLOTS, 1, 16);                 \
   }
+  EPOS_FOR_SLOTS(knn, EPOS_DGRAD_WIDTH);
+#undef EPOS_DGRAD_WIDTH
 #undef EPOS_DGRAD_LAUNCH
   return launch_status("heads_dgrad_kernel");
+}
+
+}  // namespace
+
+extern "C" int epos_heads_dgrad_f32(const float* obj_logits, int64_t ld_obj,
+                                    const float* frag_logits, const float* frag_loc,
+                                    const int32_t* gt_obj, const int32_t* gt_frag,
+                                    const float* gt_loc, const float* gt_weight, int B, int64_t P,
+                                    int num_objs, int num_frags, int ignore_label,
+                                    const double* scales, const double* upstream,
+                                    const float* Wt_obj, const float* Wt_frag,
+                                    const float* Wt_loc, int64_t ldwt, int K, const float* Y,
+                                    int64_t ldy, float* dX, int64_t ldx, void* stream) {
+  return heads_dgrad(__func__, obj_logits, ld_obj, frag_logits, frag_loc, gt_obj, gt_frag, gt_loc,
+                     gt_weight, B, P, num_objs, num_frags, ignore_label, 1, scales, upstream,
+                     Wt_obj, Wt_frag, Wt_loc, ldwt, K, Y, ldy, dX, ldx, stream);
+}
+
+extern "C" int epos_heads_dgrad_knn_f32(const float* obj_logits, int64_t ld_obj,
+                                        const float* frag_logits, const float* frag_loc,
+                                        const int32_t* gt_obj, const int32_t* gt_frag,
+                                        const float* gt_loc, const float* gt_weight, int B,
+                                        int64_t P, int num_objs, int num_frags, int ignore_label,
+                                        int knn, const double* scales, const double* upstream,
+                                        const float* Wt_obj, const float* Wt_frag,
+                                        const float* Wt_loc, int64_t ldwt, int K, const float* Y,
+                                        int64_t ldy, float* dX, int64_t ldx, void* stream) {
+  return heads_dgrad(__func__, obj_logits, ld_obj, frag_logits, frag_loc, gt_obj, gt_frag, gt_loc,
+                     gt_weight, B, P, num_objs, num_frags, ignore_label, knn, scales, upstream,
+                     Wt_obj, Wt_frag, Wt_loc, ldwt, K, Y, ldy, dX, ldx, stream);
 }

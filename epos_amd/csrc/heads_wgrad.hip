@@ -28,7 +28,9 @@
 // thread, or of a fixed sequence of threads and slabs, in a fixed order -- no atomics, the same
 // bytes in every run. fp64 on the fp32 values, -ffp-contract=off; the logit gradients that are
 // multiplied with the features are softmax_grad and huber_grad of loss_rows.h, the functions
-// epos_loss_grads writes its outputs with.
+// epos_loss_grads writes its outputs with. With knn slots per pixel ("k nearest fragments") a
+// batch holds knn (fragment, weight, three localisation gradients) per pixel; the slots of a
+// pixel name different fragments, so a cell of the localisation table still takes a pixel once.
 #include "loss_rows.h"
 
 namespace epos {
@@ -92,20 +94,22 @@ __device__ __forceinline__ void store_sum(double sum, int64_t kq, int K, double*
   }
 }
 
+template <int SLOTS>
 __global__ __launch_bounds__(LOSS_THREADS) void wgrad_rows_kernel(
     const float* __restrict__ obj_logits, int64_t ld_obj, const float* __restrict__ frag_logits,
     const int32_t* __restrict__ gt_obj, const int32_t* __restrict__ gt_frag,
     const float* __restrict__ gt_weight, int64_t n_pix, int num_objs, int num_frags,
-    int ignore_label, int L, bool want_obj, bool want_frag, double* __restrict__ s_obj,
+    int ignore_label, int knn_arg, int L, bool want_obj, bool want_frag, double* __restrict__ s_obj,
     double* __restrict__ s_frag, float* __restrict__ m_obj) {
+  const int knn = slots_of<SLOTS>(knn_arg);
   const int sub = threadIdx.x % L;                           // L is a power of two <= 64
   const int per_pass = LOSS_THREADS / L;
   const int64_t p0 = blockIdx.x * WG_ROWS_PIXELS;
   for (int base = 0; base < WG_ROWS_PIXELS; base += per_pass) {   // uniform: shuffles below
     const int64_t p = p0 + base + threadIdx.x / L;
-    const PixelRows r = pixel_rows<false, false>(obj_logits, ld_obj, frag_logits, gt_obj, gt_frag,
-                                                 gt_weight, p, p < n_pix, num_objs, num_frags,
-                                                 ignore_label, want_obj, want_frag, sub, L);
+    const PixelRows<SLOTS> r = pixel_rows<SLOTS, false, false>(
+        obj_logits, ld_obj, frag_logits, gt_obj, gt_frag, gt_weight, p, p < n_pix, num_objs,
+        num_frags, ignore_label, knn, want_obj, want_frag, sub, L);
     if (p < n_pix && sub == 0) {
       if (want_obj) {
         s_obj[p] = r.s_obj;
@@ -116,29 +120,33 @@ __global__ __launch_bounds__(LOSS_THREADS) void wgrad_rows_kernel(
   }
 }
 
+template <int SLOTS>
 struct FragShared {
   double loc[WG_LOC];                 // [f][component][k of the slice]
   float df[WG_DF];                    // [pixel of the batch][F]
   float a[WG_BATCH * WG_KS];          // [pixel of the batch][k of the slice]
-  float dl[WG_BATCH * 3];
+  float dl[WG_BATCH * SLOTS * 3];     // [pixel of the batch][slot][component]
   double s_frag[WG_BATCH];
   int64_t pixel[WG_BATCH];            // pixel of the whole batch of images
-  float m_frag[WG_BATCH], wgt[WG_BATCH];
-  int frag[WG_BATCH];
+  float m_frag[WG_BATCH], wgt[WG_BATCH][SLOTS];
+  int frag[WG_BATCH][SLOTS];
   uint32_t ring[WG_RING];             // pixels of class g of the current image, in order
   int count[WG_SCAN][LOSS_THREADS / 64];
 };
 
+template <int SLOTS>
 __global__ __launch_bounds__(LOSS_THREADS) void wgrad_frag_kernel(
     const float* __restrict__ A, int64_t lda, int K, const float* __restrict__ frag_logits,
     const float* __restrict__ frag_loc, const int32_t* __restrict__ gt_obj,
     const int32_t* __restrict__ gt_frag, const float* __restrict__ gt_loc,
     const float* __restrict__ gt_weight, int B, int64_t P, int num_objs, int num_frags,
-    int ignore_label, const double* __restrict__ scales, const double* __restrict__ upstream,
-    const double* __restrict__ s_frag, int ks, int slice0, int batch, int64_t range,
+    int ignore_label, int knn_arg, const double* __restrict__ scales,
+    const double* __restrict__ upstream, const double* __restrict__ s_frag, int ks,
+    int slice0, int batch, int64_t range,
     double* __restrict__ slabs, float* __restrict__ dW_frag, float* __restrict__ db_frag,
     float* __restrict__ dW_loc, float* __restrict__ db_loc) {
-  __shared__ FragShared sh;
+  const int knn = slots_of<SLOTS>(knn_arg);
+  __shared__ FragShared<SLOTS> sh;
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   const int g = blockIdx.y + 1;                              // the object, 1..O
   const int k0 = (slice0 + blockIdx.x) * ks;                 // k == K is the bias row
@@ -155,6 +163,7 @@ __global__ __launch_bounds__(LOSS_THREADS) void wgrad_frag_kernel(
   if (want_loc)
     for (int e = t; e < ks * F * 3; e += LOSS_THREADS) sh.loc[e] = 0.0;
   const double u1 = upstream_factor(upstream, 1), u2 = upstream_factor(upstream, 2);
+  const double kd = static_cast<double>(knn);
   __syncthreads();
 
   for (int b = 0; b < B; ++b) {
@@ -169,10 +178,8 @@ __global__ __launch_bounds__(LOSS_THREADS) void wgrad_frag_kernel(
 #pragma unroll
         for (int j = 0; j < WG_SCAN; ++j) {
           const int64_t pp = base + j * LOSS_THREADS + t;
-          int f = 0;
-          float wgt = 0.f;
-          match[j] = pp < r1 && pixel_class(gt_obj, gt_frag, gt_weight, img + pp, num_objs, F,
-                                           ignore_label, f, wgt) == g;
+          match[j] = pp < r1 && pixel_class<SLOTS>(gt_obj, gt_frag, gt_weight, img + pp, num_objs,
+                                                  F, ignore_label, knn) == g;
           mask[j] = __ballot(match[j]);
           if (lane == 0) sh.count[j][wave] = __popcll(mask[j]);
         }
@@ -213,26 +220,30 @@ __global__ __launch_bounds__(LOSS_THREADS) void wgrad_frag_kernel(
             sh.pixel[i] = p;
             sh.m_frag[i] = m;
             sh.s_frag[i] = want_frag ? s_frag[p] : 0.0;
-            sh.frag[i] = gt_frag[p];
-            sh.wgt[i] = gt_weight[p];
+            for (int j = 0; j < knn; ++j) {
+              sh.frag[i][j] = gt_frag[p * knn + j];
+              sh.wgt[i][j] = gt_weight[p * knn + j];
+            }
           }
         }
         __syncthreads();
         if (want_frag) {
           for (int e = t; e < n * F; e += LOSS_THREADS) {
             const int i = e / F, c = e - i * F;
-            sh.df[e] = softmax_grad(frag_logits[frag_row_offset(sh.pixel[i], num_objs, g, F) + c],
-                                    static_cast<double>(sh.m_frag[i]), sh.s_frag[i],
-                                    c == sh.frag[i], s1);
+            sh.df[e] = softmax_grad_knn(
+                frag_logits[frag_row_offset(sh.pixel[i], num_objs, g, F) + c],
+                static_cast<double>(sh.m_frag[i]), sh.s_frag[i], is_slot(sh.frag[i], knn, c), s1,
+                kd);
           }
         }
         if (want_loc) {
-          for (int e = t; e < n * 3; e += LOSS_THREADS) {
-            const int i = e / 3, c = e - i * 3;
+          for (int e = t; e < n * knn * 3; e += LOSS_THREADS) {
+            const int ij = e / 3, c = e - ij * 3;            // ij = i * knn + j
+            const int i = ij / knn, j = ij - i * knn;
             const int64_t p = sh.pixel[i];
             sh.dl[e] = huber_grad(
-                frag_loc[(frag_row_offset(p, num_objs, g, F) + sh.frag[i]) * 3 + c],
-                gt_loc[p * 3 + c], sh.wgt[i], s2);
+                frag_loc[(frag_row_offset(p, num_objs, g, F) + sh.frag[i][j]) * 3 + c],
+                gt_loc[(p * knn + j) * 3 + c], sh.wgt[i][j], s2);
           }
         }
         for (int e = t; e < n * ks; e += LOSS_THREADS) {
@@ -251,12 +262,15 @@ __global__ __launch_bounds__(LOSS_THREADS) void wgrad_frag_kernel(
           }
         }
         if (want_loc && loc_fs < FS) {
+          // a pixel's slots name different fragments: it adds to a cell at most once
           for (int i = 0; i < n; ++i) {
-            const int f = sh.frag[i];
-            if (f % FS == loc_fs)
-              sh.loc[(f * 3 + loc_c) * ks + loc_k] +=
-                  static_cast<double>(sh.a[i * ks + loc_k]) *
-                  static_cast<double>(sh.dl[i * 3 + loc_c]);
+            for (int j = 0; j < knn; ++j) {
+              const int f = sh.frag[i][j];
+              if (f % FS == loc_fs)
+                sh.loc[(f * 3 + loc_c) * ks + loc_k] +=
+                    static_cast<double>(sh.a[i * ks + loc_k]) *
+                    static_cast<double>(sh.dl[(i * knn + j) * 3 + loc_c]);
+            }
           }
         }
         __syncthreads();
@@ -298,14 +312,17 @@ __global__ __launch_bounds__(LOSS_THREADS) void wgrad_frag_kernel(
   }
 }
 
+template <int SLOTS>
 __global__ __launch_bounds__(LOSS_THREADS) void wgrad_obj_kernel(
     const float* __restrict__ A, int64_t lda, int K, const float* __restrict__ obj_logits,
     int64_t ld_obj, const int32_t* __restrict__ gt_obj, const int32_t* __restrict__ gt_frag,
     const float* __restrict__ gt_weight, int B, int64_t P, int num_objs, int num_frags,
-    int ignore_label, const double* __restrict__ scales, const double* __restrict__ upstream,
-    const double* __restrict__ s_obj, const float* __restrict__ m_obj, int slice0,
+    int ignore_label, int knn_arg, const double* __restrict__ scales,
+    const double* __restrict__ upstream, const double* __restrict__ s_obj,
+    const float* __restrict__ m_obj, int slice0,
     int64_t range, double* __restrict__ slabs, float* __restrict__ dW_obj,
     float* __restrict__ db_obj) {
+  const int knn = slots_of<SLOTS>(knn_arg);
   __shared__ double part[OBJ_LANES][OBJ_COLS][WG_KS];
   const int t = threadIdx.x;
   const int cc = t % OBJ_COLS, pl = t / OBJ_COLS;
@@ -335,10 +352,8 @@ __global__ __launch_bounds__(LOSS_THREADS) void wgrad_obj_kernel(
         s[j] = 1.0;
         if (pp < r1 && c < O1) {
           const int64_t p = img + pp;
-          int f = 0;
-          float wgt = 0.f;
-          code[j] = pixel_class(gt_obj, gt_frag, gt_weight, p, num_objs, num_frags, ignore_label,
-                                f, wgt);
+          code[j] = pixel_class<SLOTS>(gt_obj, gt_frag, gt_weight, p, num_objs, num_frags,
+                                       ignore_label, knn);
           if (code[j] >= 0) {
             x[j] = obj_logits[p * ld_obj + c];
             m[j] = m_obj[p];
@@ -452,30 +467,33 @@ extern "C" int64_t epos_heads_wgrad_workspace_bytes(int B, int64_t P, int num_ob
   return 20 * (static_cast<int64_t>(B) * P) + (R > 1 ? R * 8 * (int64_t(K) + 1) * N : 0);
 }
 
-extern "C" int epos_heads_wgrad_f32(const float* A, int64_t lda, int K, const float* obj_logits,
-                                    int64_t ld_obj, const float* frag_logits,
-                                    const float* frag_loc, const int32_t* gt_obj,
-                                    const int32_t* gt_frag, const float* gt_loc,
-                                    const float* gt_weight, int B, int64_t P, int num_objs,
-                                    int num_frags, int ignore_label, const double* scales,
-                                    const double* upstream, void* workspace, float* dW_obj,
-                                    float* db_obj, float* dW_frag, float* db_frag, float* dW_loc,
-                                    float* db_loc, void* stream) {
-  const int rc = check_dims(__func__, B, P, num_objs, num_frags, K);
+namespace {
+
+// epos_heads_wgrad_knn_f32, refusing in the name of the entry that was called
+int heads_wgrad(const char* fn, const float* A, int64_t lda, int K, const float* obj_logits,
+                int64_t ld_obj, const float* frag_logits, const float* frag_loc,
+                const int32_t* gt_obj, const int32_t* gt_frag, const float* gt_loc,
+                const float* gt_weight, int B, int64_t P, int num_objs, int num_frags,
+                int ignore_label, int knn, const double* scales, const double* upstream,
+                void* workspace, float* dW_obj, float* db_obj, float* dW_frag, float* db_frag,
+                float* dW_loc, float* db_loc, void* stream) {
+  const int rc = check_dims(fn, B, P, num_objs, num_frags, K);
   if (rc != EPOS_OK) return rc;
-  EPOS_REQUIRE(lda >= K, "lda must be >= K");
-  EPOS_REQUIRE(ld_obj >= num_objs + 1, "ld_obj must be >= num_objs + 1");
+  const int rk = check_knn(fn, knn, num_frags);
+  if (rk != EPOS_OK) return rk;
+  EPOS_REQUIRE_FN(fn, lda >= K, "lda must be >= K");
+  EPOS_REQUIRE_FN(fn, ld_obj >= num_objs + 1, "ld_obj must be >= num_objs + 1");
   const bool want_obj = dW_obj || db_obj, want_frag = dW_frag || db_frag,
              want_loc = dW_loc || db_loc;
   if (!want_obj && !want_frag && !want_loc) return EPOS_OK;
   const int64_t n_pix = static_cast<int64_t>(B) * P;
   if (n_pix > 0) {
-    EPOS_REQUIRE(A && obj_logits && frag_logits && frag_loc && gt_obj && gt_frag && gt_loc &&
+    EPOS_REQUIRE_FN(fn, A && obj_logits && frag_logits && frag_loc && gt_obj && gt_frag && gt_loc &&
                  gt_weight && scales && workspace, "null pointer");
-    EPOS_REQUIRE(reinterpret_cast<uintptr_t>(workspace) % 8 == 0,
+    EPOS_REQUIRE_FN(fn, reinterpret_cast<uintptr_t>(workspace) % 8 == 0,
                  "workspace must be 8-byte aligned");
   }
-  const int alias = check_no_alias(__func__, {A, obj_logits, frag_logits, frag_loc, gt_obj, gt_frag,
+  const int alias = check_no_alias(fn, {A, obj_logits, frag_logits, frag_loc, gt_obj, gt_frag,
                                               gt_loc, gt_weight, scales, upstream, workspace},
                                    {dW_obj, db_obj, dW_frag, db_frag, dW_loc, db_loc});
   if (alias != EPOS_OK) return alias;
@@ -494,10 +512,13 @@ extern "C" int epos_heads_wgrad_f32(const float* A, int64_t lda, int K, const fl
   float* m_obj = s_obj ? reinterpret_cast<float*>(s_frag + n_pix) : nullptr;
   if (n_pix > 0 && (want_obj || want_frag)) {
     const dim3 grid(static_cast<unsigned>(ceil_div(n_pix, WG_ROWS_PIXELS)));
-    hipLaunchKernelGGL(wgrad_rows_kernel, grid, dim3(LOSS_THREADS), 0, s, obj_logits, ld_obj,
-                       frag_logits, gt_obj, gt_frag, gt_weight, n_pix, num_objs, num_frags,
-                       ignore_label, loss_lanes(num_frags), want_obj, want_frag, s_obj, s_frag,
-                       m_obj);
+#define EPOS_WGRAD_ROWS(SLOTS)                                                                 \
+  hipLaunchKernelGGL(wgrad_rows_kernel<SLOTS>, grid, dim3(LOSS_THREADS), 0, s, obj_logits,     \
+                     ld_obj, frag_logits, gt_obj, gt_frag, gt_weight, n_pix, num_objs,         \
+                     num_frags, ignore_label, knn, loss_lanes(num_frags), want_obj, want_frag, \
+                     s_obj, s_frag, m_obj)
+    EPOS_FOR_SLOTS(knn, EPOS_WGRAD_ROWS);
+#undef EPOS_WGRAD_ROWS
     const int st = launch_status("wgrad_rows_kernel");
     if (st != EPOS_OK) return st;
   }
@@ -506,10 +527,13 @@ extern "C" int epos_heads_wgrad_f32(const float* A, int64_t lda, int K, const fl
     const int slices = static_cast<int>(ceil_div(K + 1, WG_KS));
     const int slice0 = dW_obj ? 0 : K / WG_KS;
     const dim3 grid(slices - slice0, static_cast<unsigned>(ceil_div(num_objs + 1, OBJ_COLS)), R);
-    hipLaunchKernelGGL(wgrad_obj_kernel, grid, dim3(LOSS_THREADS), 0, s, A, lda, K, obj_logits,
-                       ld_obj, gt_obj, gt_frag, gt_weight, B, P, num_objs, num_frags,
-                       ignore_label, scales, upstream, s_obj, m_obj, slice0, range, slabs,
-                       dW_obj, db_obj);
+#define EPOS_WGRAD_OBJ(SLOTS)                                                                  \
+  hipLaunchKernelGGL(wgrad_obj_kernel<SLOTS>, grid, dim3(LOSS_THREADS), 0, s, A, lda, K,       \
+                     obj_logits, ld_obj, gt_obj, gt_frag, gt_weight, B, P, num_objs,           \
+                     num_frags, ignore_label, knn, scales, upstream, s_obj, m_obj, slice0,     \
+                     range, slabs, dW_obj, db_obj)
+    EPOS_FOR_SLOTS(knn, EPOS_WGRAD_OBJ);
+#undef EPOS_WGRAD_OBJ
     const int st = launch_status("wgrad_obj_kernel");
     if (st != EPOS_OK) return st;
   }
@@ -518,10 +542,14 @@ extern "C" int epos_heads_wgrad_f32(const float* A, int64_t lda, int K, const fl
     const int slices = static_cast<int>(ceil_div(K + 1, ks));
     const int slice0 = (dW_frag || dW_loc) ? 0 : K / ks;
     const dim3 grid(slices - slice0, num_objs, R);
-    hipLaunchKernelGGL(wgrad_frag_kernel, grid, dim3(LOSS_THREADS), 0, s, A, lda, K, frag_logits,
-                       frag_loc, gt_obj, gt_frag, gt_loc, gt_weight, B, P, num_objs, num_frags,
-                       ignore_label, scales, upstream, s_frag, ks, slice0,
-                       frag_batch(num_frags), range, slabs, dW_frag, db_frag, dW_loc, db_loc);
+#define EPOS_WGRAD_FRAG(SLOTS)                                                                 \
+  hipLaunchKernelGGL(wgrad_frag_kernel<SLOTS>, grid, dim3(LOSS_THREADS), 0, s, A, lda, K,      \
+                     frag_logits, frag_loc, gt_obj, gt_frag, gt_loc, gt_weight, B, P,          \
+                     num_objs, num_frags, ignore_label, knn, scales, upstream, s_frag, ks,     \
+                     slice0, frag_batch(num_frags), range, slabs, dW_frag, db_frag, dW_loc,    \
+                     db_loc)
+    EPOS_FOR_SLOTS(knn, EPOS_WGRAD_FRAG);
+#undef EPOS_WGRAD_FRAG
     const int st = launch_status("wgrad_frag_kernel");
     if (st != EPOS_OK) return st;
   }
@@ -533,6 +561,39 @@ extern "C" int epos_heads_wgrad_f32(const float* A, int64_t lda, int K, const fl
     if (st != EPOS_OK) return st;
   }
   return EPOS_OK;
+}
+
+}  // namespace
+
+extern "C" int epos_heads_wgrad_f32(const float* A, int64_t lda, int K, const float* obj_logits,
+                                    int64_t ld_obj, const float* frag_logits,
+                                    const float* frag_loc, const int32_t* gt_obj,
+                                    const int32_t* gt_frag, const float* gt_loc,
+                                    const float* gt_weight, int B, int64_t P, int num_objs,
+                                    int num_frags, int ignore_label, const double* scales,
+                                    const double* upstream, void* workspace, float* dW_obj,
+                                    float* db_obj, float* dW_frag, float* db_frag, float* dW_loc,
+                                    float* db_loc, void* stream) {
+  return heads_wgrad(__func__, A, lda, K, obj_logits, ld_obj, frag_logits, frag_loc, gt_obj,
+                     gt_frag, gt_loc, gt_weight, B, P, num_objs, num_frags, ignore_label, 1,
+                     scales, upstream, workspace, dW_obj, db_obj, dW_frag, db_frag, dW_loc,
+                     db_loc, stream);
+}
+
+extern "C" int epos_heads_wgrad_knn_f32(const float* A, int64_t lda, int K,
+                                        const float* obj_logits, int64_t ld_obj,
+                                        const float* frag_logits, const float* frag_loc,
+                                        const int32_t* gt_obj, const int32_t* gt_frag,
+                                        const float* gt_loc, const float* gt_weight, int B,
+                                        int64_t P, int num_objs, int num_frags, int ignore_label,
+                                        int knn, const double* scales, const double* upstream,
+                                        void* workspace, float* dW_obj, float* db_obj,
+                                        float* dW_frag, float* db_frag, float* dW_loc,
+                                        float* db_loc, void* stream) {
+  return heads_wgrad(__func__, A, lda, K, obj_logits, ld_obj, frag_logits, frag_loc, gt_obj,
+                     gt_frag, gt_loc, gt_weight, B, P, num_objs, num_frags, ignore_label, knn,
+                     scales, upstream, workspace, dW_obj, db_obj, dW_frag, db_frag, dW_loc,
+                     db_loc, stream);
 }
 
 extern "C" int epos_momentum_step_f32(float* w, float* accum, const float* grad, int64_t n,

@@ -16,7 +16,8 @@
 // fp64 on the fp32 values, -ffp-contract=off (no FMA). Background, ignored and bad pixels read
 // no fragment value; a foreground pixel reads its object's F logits and 3 localisation values.
 // The class of a pixel, m and S of a row and the Huber term are loss_rows.h's, next to their
-// derivatives.
+// derivatives. With knn slots per pixel ("k nearest fragments") the two fragment terms are the
+// sums over the slots, in order, of the one-slot terms; epos_loss_terms is knn = 1.
 #include "loss_rows.h"
 
 namespace epos {
@@ -51,13 +52,15 @@ __device__ __forceinline__ double row_cross_entropy(const float* __restrict__ ro
   return log(s) + (md - static_cast<double>(row[target]));
 }
 
-template <bool VEC_OBJ, bool VEC_FRAG>
+template <int SLOTS, bool VEC_OBJ, bool VEC_FRAG>
 __global__ __launch_bounds__(LOSS_THREADS) void loss_terms_kernel(
     const float* __restrict__ obj_logits, int64_t ld_obj, const float* __restrict__ frag_logits,
     const float* __restrict__ frag_loc, const int32_t* __restrict__ gt_obj,
     const int32_t* __restrict__ gt_frag, const float* __restrict__ gt_loc,
     const float* __restrict__ gt_weight, int64_t P, int64_t share, int64_t blocks_per_image,
-    int num_objs, int num_frags, int ignore_label, int L, double* __restrict__ ws) {
+    int num_objs, int num_frags, int ignore_label, int knn_arg, int L,
+    double* __restrict__ ws) {
+  const int knn = slots_of<SLOTS>(knn_arg);
   __shared__ double term[3 * LOSS_SHARE_MAX];
   __shared__ int code[LOSS_SHARE_MAX];
   const int64_t image = blockIdx.x / blocks_per_image;
@@ -69,24 +72,31 @@ __global__ __launch_bounds__(LOSS_THREADS) void loss_terms_kernel(
   for (int base = 0; base < n_here; base += per_pass) {     // uniform trip count: shuffles below
     const int i = base + threadIdx.x / L;
     const int64_t p = image * P + p0 + i;         // pixel of the whole batch
-    int g = CODE_NONE, f = 0;
-    float wgt = 0.f;
+    int g = CODE_NONE, f[SLOTS];
+    float wgt[SLOTS];
     if (i < n_here)
-      g = pixel_class(gt_obj, gt_frag, gt_weight, p, num_objs, num_frags, ignore_label, f, wgt);
+      g = pixel_class<SLOTS>(gt_obj, gt_frag, gt_weight, p, num_objs, num_frags, ignore_label,
+                             knn, f, wgt);
     const double ce_obj = row_cross_entropy<VEC_OBJ>(obj_logits + p * ld_obj, num_objs + 1, g,
                                                      g >= 0, sub, L);
     const int64_t frag_row = g > 0 ? frag_row_offset(p, num_objs, g, num_frags) : 0;
-    const double ce_frag = row_cross_entropy<VEC_FRAG>(frag_logits + frag_row, num_frags, f,
-                                                       g > 0, sub, L);
+    double m_frag, s_frag;
+    row_max_sum<VEC_FRAG>(frag_logits + frag_row, num_frags, g > 0, sub, L, m_frag, s_frag);
     if (i < n_here && sub == 0) {
-      double hub = 0.0;
+      double ce_frag = 0.0, hub = 0.0;
       if (g > 0) {
-        const float* q = frag_loc + (frag_row + f) * 3;
-        const float* t = gt_loc + p * 3;
-        const double h0 = huber1(static_cast<double>(q[0]) - static_cast<double>(t[0]));
-        const double h1 = huber1(static_cast<double>(q[1]) - static_cast<double>(t[1]));
-        const double h2 = huber1(static_cast<double>(q[2]) - static_cast<double>(t[2]));
-        hub = static_cast<double>(wgt) * ((h0 + h1) + h2);
+        // the slots in order, each summand as with one slot
+#pragma unroll
+        for (int j = 0; j < SLOTS; ++j) {
+          if (j >= knn) continue;
+          ce_frag += log(s_frag) + (m_frag - static_cast<double>(frag_logits[frag_row + f[j]]));
+          const float* q = frag_loc + (frag_row + f[j]) * 3;
+          const float* t = gt_loc + (p * knn + j) * 3;
+          const double h0 = huber1(static_cast<double>(q[0]) - static_cast<double>(t[0]));
+          const double h1 = huber1(static_cast<double>(q[1]) - static_cast<double>(t[1]));
+          const double h2 = huber1(static_cast<double>(q[2]) - static_cast<double>(t[2]));
+          hub += static_cast<double>(wgt[j]) * ((h0 + h1) + h2);
+        }
       }
       code[i] = g;
       term[3 * i] = ce_obj;
@@ -172,19 +182,24 @@ extern "C" int64_t epos_loss_workspace_bytes(int B, int64_t P, int num_objs, int
   return B * ceil_div(P, loss_share(P)) * loss_row_words(num_objs) * 8;
 }
 
-extern "C" int epos_loss_terms(const float* obj_logits, int64_t ld_obj, const float* frag_logits,
-                               const float* frag_loc, const int32_t* gt_obj,
-                               const int32_t* gt_frag, const float* gt_loc,
-                               const float* gt_weight, int B, int64_t P, int num_objs,
-                               int num_frags, int ignore_label, void* workspace, double* sums,
-                               int64_t* counts, int64_t* bad, void* stream) {
-  const int rc = check_dims(__func__, B, P, num_objs, num_frags);
+namespace {
+
+// epos_loss_terms_knn, refusing in the name of the entry that was called
+int loss_terms(const char* fn, const float* obj_logits, int64_t ld_obj, const float* frag_logits,
+               const float* frag_loc, const int32_t* gt_obj, const int32_t* gt_frag,
+               const float* gt_loc, const float* gt_weight, int B, int64_t P, int num_objs,
+               int num_frags, int ignore_label, int knn, void* workspace, double* sums,
+               int64_t* counts, int64_t* bad, void* stream) {
+  const int rc = check_dims(fn, B, P, num_objs, num_frags);
   if (rc != EPOS_OK) return rc;
-  EPOS_REQUIRE(ld_obj >= num_objs + 1, "ld_obj must be >= num_objs + 1");
+  const int rk = check_knn(fn, knn, num_frags);
+  if (rk != EPOS_OK) return rk;
+  EPOS_REQUIRE_FN(fn, ld_obj >= num_objs + 1, "ld_obj must be >= num_objs + 1");
   if (B == 0 || P == 0) return EPOS_OK;
-  EPOS_REQUIRE(obj_logits && frag_logits && frag_loc && gt_obj && gt_frag && gt_loc &&
+  EPOS_REQUIRE_FN(fn, obj_logits && frag_logits && frag_loc && gt_obj && gt_frag && gt_loc &&
                gt_weight && workspace && sums && counts && bad, "null pointer");
-  EPOS_REQUIRE(reinterpret_cast<uintptr_t>(workspace) % 8 == 0, "workspace must be 8-byte aligned");
+  EPOS_REQUIRE_FN(fn, reinterpret_cast<uintptr_t>(workspace) % 8 == 0,
+                  "workspace must be 8-byte aligned");
   const int64_t share = loss_share(P);
   const int64_t per_image = ceil_div(P, share);
   const int L = loss_lanes(num_frags);            // 1..64 lanes per pixel
@@ -194,14 +209,18 @@ extern "C" int epos_loss_terms(const float* obj_logits, int64_t ld_obj, const fl
   const dim3 grid(static_cast<unsigned>(B * per_image));
   hipStream_t s = static_cast<hipStream_t>(stream);
   double* ws = static_cast<double*>(workspace);
-#define EPOS_LOSS_LAUNCH(VO, VF)                                                               \
-  hipLaunchKernelGGL((loss_terms_kernel<VO, VF>), grid, dim3(LOSS_THREADS), 0, s, obj_logits,  \
-                     ld_obj, frag_logits, frag_loc, gt_obj, gt_frag, gt_loc, gt_weight, P,     \
-                     share, per_image, num_objs, num_frags, ignore_label, L, ws)
-  if (vec_obj && vec_frag) EPOS_LOSS_LAUNCH(true, true);
-  else if (vec_obj) EPOS_LOSS_LAUNCH(true, false);
-  else if (vec_frag) EPOS_LOSS_LAUNCH(false, true);
-  else EPOS_LOSS_LAUNCH(false, false);
+#define EPOS_LOSS_LAUNCH(SLOTS, VO, VF)                                                        \
+  hipLaunchKernelGGL((loss_terms_kernel<SLOTS, VO, VF>), grid, dim3(LOSS_THREADS), 0, s,       \
+                     obj_logits, ld_obj, frag_logits, frag_loc, gt_obj, gt_frag, gt_loc,       \
+                     gt_weight, P, share, per_image, num_objs, num_frags, ignore_label, knn, L, \
+                     ws)
+#define EPOS_LOSS_VEC(SLOTS)                                       \
+  if (vec_obj && vec_frag) EPOS_LOSS_LAUNCH(SLOTS, true, true);    \
+  else if (vec_obj) EPOS_LOSS_LAUNCH(SLOTS, true, false);          \
+  else if (vec_frag) EPOS_LOSS_LAUNCH(SLOTS, false, true);         \
+  else EPOS_LOSS_LAUNCH(SLOTS, false, false)
+  EPOS_FOR_SLOTS(knn, EPOS_LOSS_VEC);
+#undef EPOS_LOSS_VEC
 #undef EPOS_LOSS_LAUNCH
   const int st = launch_status("loss_terms_kernel");
   if (st != EPOS_OK) return st;
@@ -210,4 +229,29 @@ extern "C" int epos_loss_terms(const float* obj_logits, int64_t ld_obj, const fl
   hipLaunchKernelGGL(loss_close_kernel, cgrid, dim3(LOSS_THREADS), 0, s, ws, per_image, num_objs,
                      sums, counts, bad);
   return launch_status("loss_close_kernel");
+}
+
+}  // namespace
+
+extern "C" int epos_loss_terms(const float* obj_logits, int64_t ld_obj, const float* frag_logits,
+                               const float* frag_loc, const int32_t* gt_obj,
+                               const int32_t* gt_frag, const float* gt_loc,
+                               const float* gt_weight, int B, int64_t P, int num_objs,
+                               int num_frags, int ignore_label, void* workspace, double* sums,
+                               int64_t* counts, int64_t* bad, void* stream) {
+  return loss_terms(__func__, obj_logits, ld_obj, frag_logits, frag_loc, gt_obj, gt_frag, gt_loc,
+                    gt_weight, B, P, num_objs, num_frags, ignore_label, 1, workspace, sums,
+                    counts, bad, stream);
+}
+
+extern "C" int epos_loss_terms_knn(const float* obj_logits, int64_t ld_obj,
+                                   const float* frag_logits, const float* frag_loc,
+                                   const int32_t* gt_obj, const int32_t* gt_frag,
+                                   const float* gt_loc, const float* gt_weight, int B, int64_t P,
+                                   int num_objs, int num_frags, int ignore_label, int knn,
+                                   void* workspace, double* sums, int64_t* counts, int64_t* bad,
+                                   void* stream) {
+  return loss_terms(__func__, obj_logits, ld_obj, frag_logits, frag_loc, gt_obj, gt_frag, gt_loc,
+                    gt_weight, B, P, num_objs, num_frags, ignore_label, knn, workspace, sums,
+                    counts, bad, stream);
 }

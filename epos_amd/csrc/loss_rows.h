@@ -3,7 +3,8 @@
 // limits and entry checks, the class of a pixel, the row scheme -- L lanes share a pixel's row,
 // each lane adds its own values in index order, the lanes' partial sums are added in a
 // butterfly --, what phase one leaves of a pixel, and the value of one gradient element: fp64
-// on the fp32 values, one product for s_k, rounded to float last.
+// on the fp32 values, one product for s_k, rounded to float last. A foreground pixel carries knn
+// slots (fragment, weight): the k nearest fragments of include/epos_hip.h, "k nearest fragments".
 #pragma once
 #include <math.h>
 
@@ -18,6 +19,8 @@ constexpr int LOSS_MAX_OBJS = 4095, LOSS_MAX_FRAGS = 256;
 constexpr int64_t LOSS_MAX_PIXELS = int64_t(1) << 31;
 constexpr int64_t LOSS_MAX_BLOCKS = (int64_t(1) << 31) - 1;
 constexpr int HEADS_MAX_K = 1024;            // feature channels of the logits layers
+// fragments per foreground pixel, at most (include/epos_hip.h, "k nearest fragments")
+constexpr int LOSS_MAX_KNN = EPOS_LOSS_MAX_KNN;
 
 // classes of a pixel slot in LDS besides 0..O
 constexpr int CODE_IGNORED = -1, CODE_BAD = -2, CODE_NONE = -3;
@@ -42,6 +45,13 @@ inline int check_loss_dims(const char* fn, int B, int64_t P, int num_objs, int n
   else if (B > 65535) msg = "B must be <= 65535";
   if (!msg) return EPOS_OK;
   set_error("%s: %s", fn, msg);
+  return EPOS_E_INVALID;
+}
+
+// 1 <= knn <= min(F, LOSS_MAX_KNN); F is checked before
+inline int check_knn(const char* fn, int knn, int num_frags) {
+  if (knn >= 1 && knn <= LOSS_MAX_KNN && knn <= num_frags) return EPOS_OK;
+  set_error("%s: knn must be in 1..min(num_frags, %d)", fn, LOSS_MAX_KNN);
   return EPOS_E_INVALID;
 }
 
@@ -70,25 +80,59 @@ inline int check_no_alias(const char* fn, std::initializer_list<const void*> inp
   return EPOS_OK;
 }
 
-// The class of pixel p: 0..O, CODE_IGNORED or CODE_BAD; the ignore rule first. f and wgt are
-// read for a foreground pixel only.
+// The kernels of the family are compiled for SLOTS = 1 and SLOTS = LOSS_MAX_KNN slots per pixel:
+// with one slot knn is the constant 1 and the code is what it was before there were slots.
+template <int SLOTS>
+__device__ __forceinline__ int slots_of(int knn) { return SLOTS == 1 ? 1 : knn; }
+// the launch for knn: SLOTS = 1 or LOSS_MAX_KNN
+#define EPOS_FOR_SLOTS(knn, LAUNCH)                  \
+  do {                                               \
+    if ((knn) == 1) { LAUNCH(1); }                   \
+    else { LAUNCH(::epos::LOSS_MAX_KNN); }           \
+  } while (0)
+
+// The class of pixel p: 0..O, CODE_IGNORED or CODE_BAD; the ignore rule first. The knn slots
+// f[j], wgt[j] are read for a foreground pixel only; the arrays are indexed by unrolled loops
+// alone, so they stay in registers.
+template <int SLOTS>
 __device__ __forceinline__ int pixel_class(const int32_t* __restrict__ gt_obj,
                                            const int32_t* __restrict__ gt_frag,
                                            const float* __restrict__ gt_weight, int64_t p,
-                                           int num_objs, int num_frags, int ignore_label, int& f,
-                                           float& wgt) {
+                                           int num_objs, int num_frags, int ignore_label, int knn,
+                                           int (&f)[SLOTS], float (&wgt)[SLOTS]) {
   int g = gt_obj[p];
   if (g == ignore_label) {
     g = CODE_IGNORED;
   } else if (g < 0 || g > num_objs) {
     g = CODE_BAD;
   } else if (g > 0) {
-    f = gt_frag[p];
-    wgt = gt_weight[p];
-    // !(w > 0) is true for a NaN; an infinite weight is refused as well
-    if (f < 0 || f >= num_frags || !(wgt > 0.f) || wgt == INFINITY) g = CODE_BAD;
+    bool bad = false;
+#pragma unroll
+    for (int j = 0; j < SLOTS; ++j) {
+      if (j >= knn) continue;
+      f[j] = gt_frag[p * knn + j];
+      wgt[j] = gt_weight[p * knn + j];
+      // !(w > 0) is true for a NaN; an infinite weight is refused as well
+      bad |= f[j] < 0 || f[j] >= num_frags || !(wgt[j] > 0.f) || wgt[j] == INFINITY;
+#pragma unroll
+      for (int i = 0; i < j; ++i) bad |= f[i] == f[j];       // two slots, one fragment
+    }
+    if (bad) g = CODE_BAD;
   }
   return g;
+}
+
+// The class alone
+template <int SLOTS>
+__device__ __forceinline__ int pixel_class(const int32_t* __restrict__ gt_obj,
+                                           const int32_t* __restrict__ gt_frag,
+                                           const float* __restrict__ gt_weight, int64_t p,
+                                           int num_objs, int num_frags, int ignore_label,
+                                           int knn) {
+  int f[SLOTS];
+  float wgt[SLOTS];
+  return pixel_class<SLOTS>(gt_obj, gt_frag, gt_weight, p, num_objs, num_frags, ignore_label,
+                            knn, f, wgt);
 }
 
 // The lane's part of a row of n values: four consecutive values per step, steps 4 * L apart
@@ -133,26 +177,27 @@ __device__ __forceinline__ int64_t frag_row_offset(int64_t p, int num_objs, int 
   return (p * num_objs + (g - 1)) * num_frags;
 }
 
-// What phase one leaves of a pixel: its class, fragment and weight (pixel_class), m and S of
+// What phase one leaves of a pixel: its class, fragments and weights (pixel_class), m and S of
 // its object row (class >= 0) and of its fragment row (class > 0)
+template <int SLOTS>
 struct PixelRows {
-  int code, frag;
-  float wgt;
+  int code, frag[SLOTS];
+  float wgt[SLOTS];
   double m_obj, s_obj, m_frag, s_frag;       // m is an fp32 value
 };
 
 // Phase one of pixel p for the L lanes that share it (all of them call, `valid` or not: the
 // shuffles of row_max_sum); a row that is not wanted is not read and leaves m = S = 0.
-template <bool VEC_OBJ, bool VEC_FRAG>
-__device__ __forceinline__ PixelRows pixel_rows(
+template <int SLOTS, bool VEC_OBJ, bool VEC_FRAG>
+__device__ __forceinline__ PixelRows<SLOTS> pixel_rows(
     const float* __restrict__ obj_logits, int64_t ld_obj, const float* __restrict__ frag_logits,
     const int32_t* __restrict__ gt_obj, const int32_t* __restrict__ gt_frag,
     const float* __restrict__ gt_weight, int64_t p, bool valid, int num_objs, int num_frags,
-    int ignore_label, bool want_obj, bool want_frag, int sub, int L) {
-  PixelRows r = {CODE_NONE, 0, 0.f, 0.0, 0.0, 0.0, 0.0};
+    int ignore_label, int knn, bool want_obj, bool want_frag, int sub, int L) {
+  PixelRows<SLOTS> r = {CODE_NONE, {}, {}, 0.0, 0.0, 0.0, 0.0};     // slots: 0, 0.f
   if (valid)
-    r.code = pixel_class(gt_obj, gt_frag, gt_weight, p, num_objs, num_frags, ignore_label,
-                         r.frag, r.wgt);
+    r.code = pixel_class<SLOTS>(gt_obj, gt_frag, gt_weight, p, num_objs, num_frags,
+                                ignore_label, knn, r.frag, r.wgt);
   if (want_obj)
     row_max_sum<VEC_OBJ>(obj_logits + (r.code >= 0 ? p * ld_obj : 0), num_objs + 1, r.code >= 0,
                          sub, L, r.m_obj, r.s_obj);
@@ -164,17 +209,21 @@ __device__ __forceinline__ PixelRows pixel_rows(
 }
 
 // Phase one of a share of N pixels at most, in LDS
-template <int N>
+template <int N, int SLOTS>
 struct ShareRows {
   double s_obj[N], s_frag[N];                // S of the two rows
   float m_obj[N], m_frag[N];                 // m of the two rows
-  float wgt[N];
-  int code[N], frag[N];
+  float wgt[N][SLOTS];
+  int code[N], frag[N][SLOTS];
 
-  __device__ __forceinline__ void put(int i, const PixelRows& r) {
+  __device__ __forceinline__ void put(int i, const PixelRows<SLOTS>& r, int knn) {
     code[i] = r.code;
-    frag[i] = r.frag;
-    wgt[i] = r.wgt;
+#pragma unroll
+    for (int j = 0; j < SLOTS; ++j) {
+      if (j >= knn) continue;
+      frag[i][j] = r.frag[j];
+      wgt[i][j] = r.wgt[j];
+    }
     m_obj[i] = static_cast<float>(r.m_obj);
     s_obj[i] = r.s_obj;
     m_frag[i] = static_cast<float>(r.m_frag);
@@ -198,6 +247,21 @@ __device__ __forceinline__ float softmax_grad(float x, double m, double S, bool 
                                               double s_k) {
   const double pr = exp(static_cast<double>(x) - m) / S;
   return static_cast<float>(s_k * (pr - (target ? 1.0 : 0.0)));
+}
+
+// softmax_grad with knn assigned fragments: the probability counts once per slot, target is
+// true for each of the pixel's fragments. knn == 1.0 gives softmax_grad's bytes: 1.0 * pr is pr.
+__device__ __forceinline__ float softmax_grad_knn(float x, double m, double S, bool target,
+                                                  double s_k, double knn) {
+  const double pr = exp(static_cast<double>(x) - m) / S;
+  return static_cast<float>(s_k * (knn * pr - (target ? 1.0 : 0.0)));
+}
+
+// c is one of the knn fragments at f
+__device__ __forceinline__ bool is_slot(const int* f, int knn, int c) {
+  bool hit = false;
+  for (int j = 0; j < knn; ++j) hit |= f[j] == c;
+  return hit;
 }
 
 // The Huber term of one localisation component, d = q - t ...

@@ -303,12 +303,18 @@ __global__ __launch_bounds__(256) void resolve_kernel(
   if (color) { color[3 * i] = c[0]; color[3 * i + 1] = c[1]; color[3 * i + 2] = c[2]; }
 }
 
+constexpr int GT_MAX_KNN = EPOS_LOSS_MAX_KNN;     // slots per pixel, at most
+
+// SLOTS = 1 (knn is then the constant 1: the kernel as it was before there were slots) or
+// GT_MAX_KNN
+template <int SLOTS>
 __global__ __launch_bounds__(256) void gt_fields_kernel(
     const float* __restrict__ depth, const float* __restrict__ local_pos,
     const uint8_t* __restrict__ masks, const int32_t* __restrict__ obj_ids, int n_inst, int h,
     int w, const double* __restrict__ centers, const double* __restrict__ sizes, int num_objs,
-    int num_frags, int32_t* obj_label, int32_t* inst_out, int32_t* frag_label, float* frag_loc,
-    float* frag_weight) {
+    int num_frags, int knn_arg, int32_t* obj_label, int32_t* inst_out, int32_t* frag_label,
+    float* frag_loc, float* frag_weight) {
+  const int knn = SLOTS == 1 ? 1 : knn_arg;
   const int64_t hw = static_cast<int64_t>(h) * w;
   const int64_t p = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
   if (p >= hw) return;
@@ -332,30 +338,55 @@ __global__ __launch_bounds__(256) void gt_fields_kernel(
       }
     }
   }
-  int32_t ol = 0, fl = 0;
-  float loc[3] = {0.f, 0.f, 0.f}, wt = 0.f;
+  // slot j: the j-th nearest centre, ascending distance, ties to the lower index. The arrays
+  // are indexed by unrolled loops alone, so they stay in registers.
+  int32_t ol = 0, fl[SLOTS];
+  double bd[SLOTS];
+#pragma unroll
+  for (int j = 0; j < SLOTS; ++j) { fl[j] = 0; bd[j] = INFINITY; }
+  double x = 0.0, y = 0.0, z = 0.0;
+  const double* c = centers;
   if (win >= 0) {
     ol = obj_ids[win];
     const float* xyz = local_pos + 3 * (win * hw + p);
-    const double x = xyz[0], y = xyz[1], z = xyz[2];
-    const double* c = centers + static_cast<int64_t>(ol - 1) * num_frags * 3;
-    double bd = INFINITY;
+    x = xyz[0]; y = xyz[1]; z = xyz[2];
+    c = centers + static_cast<int64_t>(ol - 1) * num_frags * 3;
     for (int f = 0; f < num_frags; ++f) {
       const double dx = x - c[3 * f], dy = y - c[3 * f + 1], dz = z - c[3 * f + 2];
       const double d2 = dx * dx + dy * dy + dz * dz;
-      if (d2 < bd) { bd = d2; fl = f; }
+      // insert in front of the first slot that is farther; from the last slot down, so a slot
+      // takes its neighbour's value before that one changes
+#pragma unroll
+      for (int j = SLOTS - 1; j >= 0; --j) {
+        if (j >= knn) continue;
+        const int below = j > 0 ? j - 1 : 0;
+        if (j > 0 && d2 < bd[below]) { bd[j] = bd[below]; fl[j] = fl[below]; }
+        else if (d2 < bd[j]) { bd[j] = d2; fl[j] = f; }
+      }
     }
-    const double s = sizes[static_cast<int64_t>(ol - 1) * num_frags + fl];
-    loc[0] = static_cast<float>((x - c[3 * fl]) / s);
-    loc[1] = static_cast<float>((y - c[3 * fl + 1]) / s);
-    loc[2] = static_cast<float>((z - c[3 * fl + 2]) / s);
-    wt = 1.f;
   }
   if (obj_label) obj_label[p] = ol;
   if (inst_out) inst_out[p] = win;
-  if (frag_label) frag_label[p] = fl;
-  if (frag_loc) { frag_loc[3 * p] = loc[0]; frag_loc[3 * p + 1] = loc[1]; frag_loc[3 * p + 2] = loc[2]; }
-  if (frag_weight) frag_weight[p] = wt;
+#pragma unroll
+  for (int j = 0; j < SLOTS; ++j) {
+    if (j >= knn) continue;
+    float loc[3] = {0.f, 0.f, 0.f}, wt = 0.f;
+    if (win >= 0) {
+      const double s = sizes[static_cast<int64_t>(ol - 1) * num_frags + fl[j]];
+      loc[0] = static_cast<float>((x - c[3 * fl[j]]) / s);
+      loc[1] = static_cast<float>((y - c[3 * fl[j] + 1]) / s);
+      loc[2] = static_cast<float>((z - c[3 * fl[j] + 2]) / s);
+      wt = 1.f;
+    }
+    const int64_t e = p * knn + j;
+    if (frag_label) frag_label[e] = fl[j];
+    if (frag_loc) {
+      frag_loc[3 * e] = loc[0];
+      frag_loc[3 * e + 1] = loc[1];
+      frag_loc[3 * e + 2] = loc[2];
+    }
+    if (frag_weight) frag_weight[e] = wt;
+  }
 }
 
 // pixels of one call (all instances): one lane per pixel in the resolve pass, so the grid stays
@@ -417,23 +448,57 @@ extern "C" int epos_render_resolve(const uint64_t* keys, const double* verts, in
   return launch_status("resolve_kernel");
 }
 
+namespace {
+
+// epos_gt_fields_knn, refusing in the name of the entry that was called
+int gt_fields(const char* fn, const float* depth, const float* local_pos, const uint8_t* masks,
+              const int32_t* obj_ids, int n_inst, int h, int w, const double* centers,
+              const double* sizes, int num_objs, int num_frags, int knn, int32_t* obj_label,
+              int32_t* instance, int32_t* frag_label, float* frag_loc, float* frag_weight,
+              void* stream) {
+  EPOS_REQUIRE_FN(fn, n_inst >= 0 && h >= 0 && w >= 0, "negative size");
+  EPOS_REQUIRE_FN(fn, num_objs >= 1, "num_objs must be >= 1");
+  EPOS_REQUIRE_FN(fn, num_frags >= 1 && num_frags <= 256, "num_frags must be in 1..256");
+  EPOS_REQUIRE_FN(fn, knn >= 1 && knn <= GT_MAX_KNN && knn <= num_frags,
+                  "knn must be in 1..min(num_frags, EPOS_LOSS_MAX_KNN)");
+  EPOS_REQUIRE_FN(fn, h <= 32768 && w <= 32768 && n_inst <= (1 << 20), "image or batch too large");
+  const int64_t hw = static_cast<int64_t>(h) * w;
+  if (hw == 0) return EPOS_OK;
+  EPOS_REQUIRE_FN(fn, centers && sizes, "null pointer");
+  EPOS_REQUIRE_FN(fn, n_inst == 0 || (depth && local_pos && obj_ids), "null pointer");
+  const dim3 grid(static_cast<unsigned>(ceil_div(hw, 256)));
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (knn == 1)
+    hipLaunchKernelGGL(gt_fields_kernel<1>, grid, dim3(256), 0, s, depth, local_pos, masks,
+                       obj_ids, n_inst, h, w, centers, sizes, num_objs, num_frags, knn,
+                       obj_label, instance, frag_label, frag_loc, frag_weight);
+  else
+    hipLaunchKernelGGL(gt_fields_kernel<GT_MAX_KNN>, grid, dim3(256), 0, s, depth, local_pos,
+                       masks, obj_ids, n_inst, h, w, centers, sizes, num_objs, num_frags, knn,
+                       obj_label, instance, frag_label, frag_loc, frag_weight);
+  return launch_status("gt_fields_kernel");
+}
+
+}  // namespace
+
 extern "C" int epos_gt_fields(const float* depth, const float* local_pos, const uint8_t* masks,
                               const int32_t* obj_ids, int n_inst, int h, int w,
                               const double* centers, const double* sizes, int num_objs,
                               int num_frags, int32_t* obj_label, int32_t* instance,
                               int32_t* frag_label, float* frag_loc, float* frag_weight,
                               void* stream) {
-  EPOS_REQUIRE(n_inst >= 0 && h >= 0 && w >= 0, "negative size");
-  EPOS_REQUIRE(num_objs >= 1, "num_objs must be >= 1");
-  EPOS_REQUIRE(num_frags >= 1 && num_frags <= 256, "num_frags must be in 1..256");
-  EPOS_REQUIRE(h <= 32768 && w <= 32768 && n_inst <= (1 << 20), "image or batch too large");
-  const int64_t hw = static_cast<int64_t>(h) * w;
-  if (hw == 0) return EPOS_OK;
-  EPOS_REQUIRE(centers && sizes, "null pointer");
-  EPOS_REQUIRE(n_inst == 0 || (depth && local_pos && obj_ids), "null pointer");
-  hipLaunchKernelGGL(gt_fields_kernel, dim3(static_cast<unsigned>(ceil_div(hw, 256))),
-                     dim3(256), 0, static_cast<hipStream_t>(stream), depth, local_pos, masks,
-                     obj_ids, n_inst, h, w, centers, sizes, num_objs, num_frags, obj_label,
-                     instance, frag_label, frag_loc, frag_weight);
-  return launch_status("gt_fields_kernel");
+  return gt_fields(__func__, depth, local_pos, masks, obj_ids, n_inst, h, w, centers, sizes,
+                   num_objs, num_frags, 1, obj_label, instance, frag_label, frag_loc, frag_weight,
+                   stream);
+}
+
+extern "C" int epos_gt_fields_knn(const float* depth, const float* local_pos,
+                                  const uint8_t* masks, const int32_t* obj_ids, int n_inst, int h,
+                                  int w, const double* centers, const double* sizes, int num_objs,
+                                  int num_frags, int knn, int32_t* obj_label, int32_t* instance,
+                                  int32_t* frag_label, float* frag_loc, float* frag_weight,
+                                  void* stream) {
+  return gt_fields(__func__, depth, local_pos, masks, obj_ids, n_inst, h, w, centers, sizes,
+                   num_objs, num_frags, knn, obj_label, instance, frag_label, frag_loc,
+                   frag_weight, stream);
 }

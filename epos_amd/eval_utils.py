@@ -175,13 +175,14 @@ def relabels_background(dataset_name, image_path):
 
 
 def gt_fields_device(renderer, frame, output_size, frag_pool, counts, input_size=None,
-                     allow_empty=True):
+                     allow_empty=True, knn_frags=1):
   """render.gt_fields of one frame's ground truth at output_size = (ow, oh), with the output
   camera, from the instance masks when the frame carries them (by nearest depth otherwise).
   Only the instances whose object the renderer holds and for which counts(obj_id) is true
   take part. frag_pool: (centers [O,F,3], sizes [O,F]) of render.pool_fragments. input_size =
   (w, h) of the frame's pixels (default: four times the output, the decoder stride). Without
-  such an instance the fields are those of an empty scene, or None with allow_empty=False."""
+  such an instance the fields are those of an empty scene, or None with allow_empty=False.
+  knn_frags: the fragments per pixel, as render.gt_fields_device takes it."""
   from epos_amd import render
   centers, sizes = frag_pool
   gi = [i for i, p in enumerate(frame.gt_poses or [])
@@ -202,7 +203,7 @@ def gt_fields_device(renderer, frame, output_size, frag_pool, counts, input_size
       renderer, output_K(frame.K, input_size, output_size), [p['obj_id'] for p in gt],
       np.stack([p['R'] for p in gt]) if gt else np.zeros((0, 3, 3)),
       np.stack([np.asarray(p['t']).reshape(3) for p in gt]) if gt else np.zeros((0, 3)),
-      (ow, oh), centers, sizes, masks)
+      (ow, oh), centers, sizes, masks, knn_frags)
 
 
 def gt_maps_device(renderer, frame, output_size, frag_pool, dataset_name=None, input_size=None,
@@ -222,15 +223,16 @@ def gt_maps_device(renderer, frame, output_size, frag_pool, dataset_name=None, i
 
 
 def gt_loss_fields_device(renderer, frame, output_size, frag_pool, dataset_name=None,
-                          input_size=None, ignore_label=255):
+                          input_size=None, ignore_label=255, knn_frags=1):
   """All four ground-truth maps of one frame, left on the device, as epos_amd/loss.py takes
   them: {obj_label i32 [oh,ow], frag_label i32 [oh,ow], frag_loc f32 [oh,ow,3], frag_weight
   f32 [oh,ow]} -- the fields gt_maps_device is built on (one assigned fragment per pixel), with
-  the same background rule of relabels_background."""
+  the same background rule of relabels_background. With knn_frags = k > 1 the three fragment
+  fields carry the k nearest fragments: [oh,ow,k], [oh,ow,k,3], [oh,ow,k]."""
   import torch
   O = frag_pool[1].shape[0]
   f = gt_fields_device(renderer, frame, output_size, frag_pool, lambda o: 1 <= o <= O,
-                       input_size)
+                       input_size, knn_frags=knn_frags)
   obj_label = f['obj_label']
   if relabels_background(dataset_name, frame.image_path):
     obj_label = torch.where(obj_label == 0, torch.full_like(obj_label, int(ignore_label)),

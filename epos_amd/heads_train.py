@@ -2,10 +2,10 @@
 (csrc/heads_wgrad.hip; include/epos_hip.h, "Weight gradients"; DESIGN.md, "Losses", "Weight
 gradients"): the next piece of a trainer after loss.differentiable_losses.
 
-  heads_weight_grads  epos_heads_wgrad_f32: dW and db of logits/pred_obj_conf, pred_frag_conf
+  heads_weight_grads  epos_heads_wgrad_knn_f32: dW and db of logits/pred_obj_conf, pred_frag_conf
                       and pred_frag_loc from EposNet.decoder_out and the raw logits, without the
                       dense logit gradients.
-  heads_input_grad    epos_heads_dgrad_f32 (csrc/heads_dgrad.hip; "Input gradient"): the gradient
+  heads_input_grad    epos_heads_dgrad_knn_f32 (csrc/heads_dgrad.hip; "Input gradient"): the gradient
                       at EposNet.decoder_out, or behind its ReLU, from the raw logits and the
                       three weight matrices, without the dense logit gradients.
   momentum_step       epos_momentum_step_f32: tf.train.MomentumOptimizer on the regularised,
@@ -32,7 +32,7 @@ HEADS, variable_names = L.HEADS, L.variable_names
 
 def heads_weight_grads(features, logits, gt, scales, upstream=None, ignore_label=255,
                        need=(True, True, True), out=None, workspace=None):
-  """epos_heads_wgrad_f32 over one batch. features: the tensor the logits layers read
+  """epos_heads_wgrad_knn_f32 over one batch. features: the tensor the logits layers read
   (EposNet.decoder_out), f32 [B,h,w,K] or [B*P,K], rows a constant stride apart; logits, gt,
   scales, upstream as loss.loss_grads takes them. Returns {head name: (dW f32 [K,N], db f32
   [N])} for pred_obj_conf (N = O+1), pred_frag_conf (O*F) and pred_frag_loc (O*F*3), None for a
@@ -68,15 +68,15 @@ def heads_weight_grads(features, logits, gt, scales, upstream=None, ignore_label
   ws = C.workspace(workspace, dev, nbytes)
   with C.launch(dev) as q:
     q.keep(feat2, ws, *bt.keep)
-    _lib.check(lib.epos_heads_wgrad_f32(
+    _lib.check(lib.epos_heads_wgrad_knn_f32(
         C.ptr(feat2), lda, K, *bt.grad_args(ignore_label), C.ptr(ws),
-        *[C.ptr(t) for t in ptrs], q.handle), 'epos_heads_wgrad_f32')
+        *[C.ptr(t) for t in ptrs], q.handle), 'epos_heads_wgrad_knn_f32')
   return result
 
 
 def heads_input_grad(logits, gt, scales, head_weights, upstream=None, relu_of=None,
                      ignore_label=255, out=None, workspace=None):
-  """epos_heads_dgrad_f32 over one batch: the gradient of the losses with respect to the tensor
+  """epos_heads_dgrad_knn_f32 over one batch: the gradient of the losses with respect to the tensor
   the logits layers read (EposNet.decoder_out), without the dense logit gradients. logits, gt,
   scales, upstream as loss.loss_grads takes them; head_weights = {variable name: tensor or
   array} with 'logits/<name>/weights' in the checkpoint layout [1,1,K,N] (or [K,N]), as
@@ -128,10 +128,10 @@ def heads_input_grad(logits, gt, scales, head_weights, upstream=None, relu_of=No
     raise ValueError('out: %d rows of dX must lie a constant stride apart' % n)
   with C.launch(dev) as q:
     q.keep(wt, y2, *bt.keep)
-    _lib.check(lib.epos_heads_dgrad_f32(
+    _lib.check(lib.epos_heads_dgrad_knn_f32(
         *bt.grad_args(ignore_label), C.ptr(wt[:widths[0]]),
         C.ptr(wt[widths[0]:widths[0] + widths[1]]), C.ptr(wt[widths[0] + widths[1]:]), K, K,
-        C.ptr(y2), ldy, C.ptr(out2), ldx, q.handle), 'epos_heads_dgrad_f32')
+        C.ptr(y2), ldy, C.ptr(out2), ldx, q.handle), 'epos_heads_dgrad_knn_f32')
   return out
 
 
@@ -168,7 +168,7 @@ def _net_losses(net, gt, weights, reduction, ignore_label):
   L.need_fp32(net.decoder_out)
   logits = net_logits(net)
   sums, counts, bad = L.loss_terms(logits, gt, ignore_label)
-  values, scales = L.loss_values(sums, counts, weights, reduction)
+  values, scales = L.loss_values(sums, counts, weights, reduction, knn=L.gt_knn(gt))
   return logits, values, bad, scales
 
 

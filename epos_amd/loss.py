@@ -5,8 +5,10 @@ reduction of csrc/loss.hip (include/epos_hip.h, "Losses").
 
 The losses are taken from the RAW logits (EposNet.forward_logits), never from probabilities,
 and from ground-truth fields with one assigned fragment per pixel (render.gt_fields /
-epos_gt_fields: the reference's gt_knn_frags = 1, train.py:82). The dense heads stay on the
-device; what comes down is one row of (O+1) x 5 + 1 numbers per image.
+epos_gt_fields: the reference's gt_knn_frags = 1, train.py:82) or with the k nearest
+(gt_knn_frags = k <= MAX_KNN: the fields carry a slot dimension and Batch reads k from their
+shapes; include/epos_hip.h, "k nearest fragments"). The dense heads stay on the device; what
+comes down is one row of (O+1) x 5 + 1 numbers per image.
 
 ``total_loss`` is the sum of the three weighted losses and has NO REGULARISATION TERM, unlike
 the total of train.py:280 (tf.losses.get_total_loss adds the weight decay): it is a
@@ -40,6 +42,30 @@ from epos_amd import weights as W
 NAMES = ('obj_cls_loss', 'frag_cls_loss', 'frag_loc_loss', 'total_loss')
 TAGS = tuple('eval/' + n for n in NAMES)
 GT_KEYS = ('obj_label', 'frag_label', 'frag_loc', 'frag_weight')
+MAX_KNN = 4                                  # EPOS_LOSS_MAX_KNN
+
+
+def check_knn(knn, num_frags=None):
+  """knn as an int; ValueError unless 1 <= knn <= min(num_frags, MAX_KNN)."""
+  k = int(knn)
+  top = MAX_KNN if num_frags is None else min(MAX_KNN, int(num_frags))
+  if k != knn or k < 1 or k > top:
+    raise ValueError('gt_knn_frags must be in 1..%d (at most %d fragments per pixel, and no '
+                     'more than num_frags), got %r' % (top, MAX_KNN, knn))
+  return k
+
+
+def gt_knn(gt):
+  """The number of fragments per pixel a ground truth carries: frag_label with one more
+  dimension than obj_label has it as its last dimension; the same number of dimensions is 1."""
+  extra = gt['frag_label'].dim() - gt['obj_label'].dim()
+  if extra == 0:
+    return 1
+  if extra != 1:
+    raise ValueError('frag_label must have the dimensions of obj_label, or one more (the '
+                     'fragments per pixel), got %s and %s' % (
+                         tuple(gt['frag_label'].shape), tuple(gt['obj_label'].shape)))
+  return int(gt['frag_label'].shape[-1])
 
 
 def need_fp32(features):
@@ -70,7 +96,9 @@ class Batch(object):
   """A batch of logits and ground truth as the C entries take it: dev, B, P, O, F, n = B * P;
   shapes of the three logit tensors; ins = [obj rows, frag, loc, obj_label, frag_label, frag_loc,
   frag_weight] flattened, in ABI order, with ld the row stride of the first; scales and upstream
-  flattened (or None); keep = what the launch keeps (_call.launch.keep)."""
+  flattened (or None); keep = what the launch keeps (_call.launch.keep); knn = the fragments
+  per pixel, read from the shapes (gt_knn): frag_label [..., knn], frag_loc [..., knn, 3] and
+  frag_weight [..., knn] against obj_label [...]."""
 
   def __init__(self, logits, gt, who, scales=None, upstream=None):
     import torch
@@ -98,13 +126,21 @@ class Batch(object):
       raise ValueError('pred_obj_conf holds %d rows, expected %d' % (obj2.shape[0], n))
     self.dev, self.B, self.P, self.O, self.F, self.n = dev, B, n // B, O, F, n
     self.shapes = (obj.shape, frag.shape, loc.shape)
+    knn = self.knn = gt_knn(gt)
+    if knn != 1:                             # knn == 1: the checks and messages of flat alone
+      check_knn(knn, F)
+      want = tuple(gt['frag_label'].shape)
+      if tuple(gt['frag_loc'].shape) != want + (3,) or tuple(gt['frag_weight'].shape) != want:
+        raise ValueError('with frag_label %s, frag_loc must be %s and frag_weight %s, got %s '
+                         'and %s' % (want, want + (3,), want, tuple(gt['frag_loc'].shape),
+                                     tuple(gt['frag_weight'].shape)))
     self.ins = [obj2,
                 flat(frag, torch.float32, n * O * F, 'pred_frag_conf'),
                 flat(loc, torch.float32, n * O * F * 3, 'pred_frag_loc'),
                 flat(gt_obj, torch.int32, n, 'obj_label'),
-                flat(gt['frag_label'], torch.int32, n, 'frag_label'),
-                flat(gt['frag_loc'], torch.float32, n * 3, 'frag_loc'),
-                flat(gt['frag_weight'], torch.float32, n, 'frag_weight')]
+                flat(gt['frag_label'], torch.int32, n * knn, 'frag_label'),
+                flat(gt['frag_loc'], torch.float32, n * knn * 3, 'frag_loc'),
+                flat(gt['frag_weight'], torch.float32, n * knn, 'frag_weight')]
     self.scales = self.upstream = None
     if scales is not None:
       self.scales = flat(scales, torch.float64, B * 3, 'scales')
@@ -113,10 +149,11 @@ class Batch(object):
     self.keep = self.ins + [self.scales, self.upstream]
 
   def args(self, ignore_label):
-    """The arguments every entry shares: obj, ld_obj, frag, loc, the four ground-truth fields,
-    B, P, O, F, ignore_label."""
+    """The arguments every _knn entry shares: obj, ld_obj, frag, loc, the four ground-truth
+    fields, B, P, O, F, ignore_label, knn."""
     i = [C.ptr(t) for t in self.ins]
-    return (i[0], self.ld) + tuple(i[1:]) + (self.B, self.P, self.O, self.F, int(ignore_label))
+    return (i[0], self.ld) + tuple(i[1:]) + (self.B, self.P, self.O, self.F, int(ignore_label),
+                                             self.knn)
 
   def grad_args(self, ignore_label):
     """args, then scales and upstream (NULL without)."""
@@ -124,10 +161,11 @@ class Batch(object):
 
 
 def loss_terms(logits, gt, ignore_label=255, out=None):
-  """epos_loss_terms over one batch. logits: the dict of EposNet.forward_logits --
+  """epos_loss_terms_knn over one batch. logits: the dict of EposNet.forward_logits --
   pred_obj_conf f32 [B,h,w,O+1], pred_frag_conf f32 [B,h,w,O,F], pred_frag_loc f32
   [B,h,w,O,F,3]; gt: {obj_label i32 [B,h,w], frag_label i32 [B,h,w], frag_loc f32 [B,h,w,3],
-  frag_weight f32 [B,h,w]} (render.gt_fields per image, stacked). Returns (sums f64 [B,O+1,3],
+  frag_weight f32 [B,h,w]} (render.gt_fields per image, stacked), or with k fragments per
+  pixel frag_label [B,h,w,k], frag_loc [B,h,w,k,3], frag_weight [B,h,w,k]. Returns (sums f64 [B,O+1,3],
   counts i64 [B,O+1,2], bad i64 [B]) on the device; `out` = three such tensors (rows of a
   larger table) to write into. Enqueues on the current stream; does not synchronise."""
   import torch
@@ -143,13 +181,13 @@ def loss_terms(logits, gt, ignore_label=255, out=None):
   ws = C.workspace(None, dev, nbytes)
   with C.launch(dev) as q:
     q.keep(ws, *bt.keep)
-    _lib.check(lib.epos_loss_terms(
+    _lib.check(lib.epos_loss_terms_knn(
         *bt.args(ignore_label), C.ptr(ws), C.ptr(sums), C.ptr(counts), C.ptr(bad), q.handle),
-               'epos_loss_terms')
+               'epos_loss_terms_knn')
   return sums, counts, bad
 
 
-def image_losses(sums, counts, weights):
+def image_losses(sums, counts, weights, knn=1):
   """One image's losses as the reference's batch of one (loss.py:149,224-229,298-303), from
   its host rows sums [O+1,3] and counts [O+1,2]:
     obj_cls_loss  = w_obj * sum_g sums[g,0] / P -- over ALL P pixels, ignored ones included
@@ -157,10 +195,11 @@ def image_losses(sums, counts, weights):
     frag_cls_loss = w_cls * sum_{g>=1} sums[g,1] / n_fg
     frag_loc_loss = w_loc * sum_{g>=1} sums[g,2] / (3 n_fg)
   both fragment losses 0 when n_fg = 0; objects added in index order, the mean taken first and
-  the weight applied last; total_loss = their sum, without a regularisation term."""
+  the weight applied last; total_loss = their sum, without a regularisation term. With knn
+  fragments per pixel the two fragment means run over the n_fg * knn (pixel, fragment) rows."""
   w_obj, w_cls, w_loc = weights
   P = int(counts[:, 0].sum()) + int(counts[0, 1])
-  n_fg = int(counts[1:, 0].sum())
+  n_fg = int(counts[1:, 0].sum()) * int(knn)
   s = [0.0, 0.0, 0.0]
   for g in range(sums.shape[0]):
     s[0] += float(sums[g, 0])
@@ -174,8 +213,10 @@ def image_losses(sums, counts, weights):
   return out
 
 
-def summarize(sums, counts, bad, weights, num_objs):
-  """LossEval.result on host tables sums f64 [N,O+1,3], counts i64 [N,O+1,2], bad i64 [N]."""
+def summarize(sums, counts, bad, weights, num_objs, knn=1):
+  """LossEval.result on host tables sums f64 [N,O+1,3], counts i64 [N,O+1,2], bad i64 [N]; knn
+  = the fragments per pixel the tables were taken with (they do not carry it). per_object keeps
+  counting pixels."""
   import numpy as np
   n_bad = int(np.asarray(bad).sum())
   if n_bad:
@@ -186,7 +227,8 @@ def summarize(sums, counts, bad, weights, num_objs):
     raise EposError('Loss is inf or nan.')                       # train.py:281
   w_obj, w_cls, w_loc = weights
   N, O1 = sums.shape[0], sums.shape[1]
-  per_image = [image_losses(sums[i], counts[i], weights) for i in range(N)]
+  knn = check_knn(knn)
+  per_image = [image_losses(sums[i], counts[i], weights, knn) for i in range(N)]
   mean = {}
   for name in NAMES:
     acc = 0.0
@@ -200,7 +242,7 @@ def summarize(sums, counts, bad, weights, num_objs):
     tot += sums[i]
     n += counts[i, :, 0]
     pixels += int(counts[i, :, 0].sum()) + int(counts[i, 0, 1])
-  n_fg = int(n[1:].sum())
+  n_fg = int(n[1:].sum()) * knn
   s = [0.0, 0.0, 0.0]
   for g in range(O1):
     s[0] += float(tot[g, 0])
@@ -215,23 +257,26 @@ def summarize(sums, counts, bad, weights, num_objs):
   per_object = {}
   for g in range(1, O1):
     c = int(n[g])
-    per_object[g] = {'frag_cls_loss': w_cls * (float(tot[g, 1]) / c) if c else 0.0,
-                     'frag_loc_loss': w_loc * (float(tot[g, 2]) / (3 * c)) if c else 0.0,
+    rows = c * knn
+    per_object[g] = {'frag_cls_loss': w_cls * (float(tot[g, 1]) / rows) if c else 0.0,
+                     'frag_loc_loss': w_loc * (float(tot[g, 2]) / (3 * rows)) if c else 0.0,
                      'pixels': c}
   return {'per_image': per_image, 'mean': mean, 'pooled': pooled, 'per_object': per_object}
 
 
 class LossEval(object):
   """Device-resident loss tables, one row per image: sums f64 [N,O+1,3], counts i64
-  [N,O+1,2], bad i64 [N]. The weight defaults are those of train.py:72-80."""
+  [N,O+1,2], bad i64 [N]. The weight defaults are those of train.py:72-80. knn = the fragments
+  per pixel of every ground truth passed to update (the reference's gt_knn_frags)."""
 
   def __init__(self, num_objs, num_frags, device=None, obj_cls_loss_weight=1.0,
-               frag_cls_loss_weight=1.0, frag_loc_loss_weight=100.0, ignore_label=255):
+               frag_cls_loss_weight=1.0, frag_loc_loss_weight=100.0, ignore_label=255, knn=1):
     import torch
     C.need_device(None, 'the losses need a HIP device (there is no CPU fallback)')
     _lib.load()
     self.device = torch.device(device if device is not None else 'cuda:0')
     self.num_objs, self.num_frags = int(num_objs), int(num_frags)
+    self.knn = check_knn(knn, self.num_frags)
     self.weights = (float(obj_cls_loss_weight), float(frag_cls_loss_weight),
                     float(frag_loc_loss_weight))
     self.ignore_label = int(ignore_label)
@@ -257,6 +302,9 @@ class LossEval(object):
     if (int(O), int(F)) != (self.num_objs, self.num_frags):
       raise ValueError('logits of %d objects x %d fragments, expected %d x %d' % (
           O, F, self.num_objs, self.num_frags))
+    if gt_knn(gt_fields) != self.knn:
+      raise ValueError('ground truth with %d fragment(s) per pixel, expected %d' % (
+          gt_knn(gt_fields), self.knn))
     B = int(gt_fields['obj_label'].shape[0])
     capacity = self.tables[2].shape[0]
     if self.rows + B > capacity:
@@ -286,7 +334,8 @@ class LossEval(object):
                         bad[:n].reshape(n, 1)], dim=1).cpu().numpy()
     h_sums = packed[:, :3 * O1].copy().view('float64').reshape(n, O1, 3)
     h_counts = packed[:, 3 * O1:5 * O1].reshape(n, O1, 2)
-    return summarize(h_sums, h_counts, packed[:, 5 * O1], self.weights, self.num_objs)
+    return summarize(h_sums, h_counts, packed[:, 5 * O1], self.weights, self.num_objs,
+                     self.knn)
 
   def write(self, log_dir, global_step, image_keys=None):
     """losses_<step>.json -- mean, pooled, per_object, the weights, the number of images and
@@ -305,6 +354,8 @@ class LossEval(object):
            'mean': res['mean'], 'pooled': res['pooled'],
            'per_object': {str(o): v for o, v in res['per_object'].items()},
            'per_image': dict(zip(keys, res['per_image']))}
+    if self.knn != 1:                        # with one fragment per pixel: the file as before
+      doc['gt_knn_frags'] = self.knn
     with open(os.path.join(log_dir, 'losses_{}.json'.format(global_step)), 'w') as f:
       json.dump(doc, f)
     res['event_file'] = tf_events.write_scalars(
@@ -316,17 +367,19 @@ class LossEval(object):
 REDUCTIONS = {'mean': 0, 'pooled': 1}        # EPOS_LOSS_MEAN, EPOS_LOSS_POOLED
 
 
-def loss_values(sums, counts, weights, reduction='mean', out=None):
-  """epos_loss_reduce over the tables loss_terms wrote (device tensors sums f64 [B,O+1,3],
+def loss_values(sums, counts, weights, reduction='mean', out=None, knn=1):
+  """epos_loss_reduce_knn over the tables loss_terms wrote (device tensors sums f64 [B,O+1,3],
   counts i64 [B,O+1,2]): returns (values f64 [4], scales f64 [B,3]) on the device -- the
   batch's weighted obj_cls_loss, frag_cls_loss, frag_loc_loss and total_loss, bit-equal to
   summarize(...)['mean'] or ['pooled'], and the per-image factors loss_grads multiplies the
   per-pixel derivatives with. weights = (w_obj, w_cls, w_loc); `out` = two such tensors to
-  write into. Enqueues on the current stream; does not synchronise."""
+  write into; knn = the fragments per pixel loss_terms ran with (the tables do not carry it).
+  Enqueues on the current stream; does not synchronise."""
   import torch
   lib = _lib.load()
   if reduction not in REDUCTIONS:
     raise ValueError("reduction must be 'mean' or 'pooled', got %r" % (reduction,))
+  knn = check_knn(knn)
   C.need_device(sums, 'the losses need a HIP device (there is no CPU fallback)')
   dev = sums.device
   if sums.dim() != 3 or sums.shape[0] < 1 or sums.shape[2] != 3:
@@ -343,15 +396,15 @@ def loss_values(sums, counts, weights, reduction='mean', out=None):
     C.dense(t, dev, dtype, what, numel=numel)
   w_obj, w_cls, w_loc = (float(w) for w in weights)
   with C.launch(dev) as q:
-    _lib.check(lib.epos_loss_reduce(
-        C.ptr(sums), C.ptr(counts), B, O1 - 1, w_obj, w_cls, w_loc, REDUCTIONS[reduction],
-        C.ptr(values), C.ptr(scales), q.handle), 'epos_loss_reduce')
+    _lib.check(lib.epos_loss_reduce_knn(
+        C.ptr(sums), C.ptr(counts), B, O1 - 1, w_obj, w_cls, w_loc, REDUCTIONS[reduction], knn,
+        C.ptr(values), C.ptr(scales), q.handle), 'epos_loss_reduce_knn')
   return values, scales
 
 
 def loss_grads(logits, gt, scales, upstream=None, ignore_label=255, need=(True, True, True),
                out=None):
-  """epos_loss_grads over one batch: the derivative of the losses with respect to the three
+  """epos_loss_grads_knn over one batch: the derivative of the losses with respect to the three
   logit tensors. logits and gt as loss_terms takes them; scales f64 [B,3] from loss_values;
   upstream f64 [4] on the device (the gradient arriving at loss_values' values; None = the
   total loss alone). Returns (d_obj, d_frag, d_loc), f32 tensors shaped like pred_obj_conf,
@@ -380,9 +433,9 @@ def loss_grads(logits, gt, scales, upstream=None, ignore_label=255, need=(True, 
       raise ValueError('out[0]: the rows of d_obj must lie a constant stride apart')
   with C.launch(dev) as q:
     q.keep(*bt.keep)
-    _lib.check(lib.epos_loss_grads(
+    _lib.check(lib.epos_loss_grads_knn(
         *bt.grad_args(ignore_label), C.ptr(d_obj2), ld_d, C.ptr(outs[1]), C.ptr(outs[2]),
-        q.handle), 'epos_loss_grads')
+        q.handle), 'epos_loss_grads_knn')
   return tuple(outs)
 
 
@@ -405,7 +458,7 @@ def _losses_function():
                 ignore_label):
       logits, gt = _head_dicts(obj, frag, loc, gt_obj, gt_frag, gt_loc, gt_weight)
       sums, counts, bad = loss_terms(logits, gt, ignore_label)
-      values, scales = loss_values(sums, counts, weights, reduction)
+      values, scales = loss_values(sums, counts, weights, reduction, knn=gt_knn(gt))
       ctx.save_for_backward(obj, frag, loc, gt_obj, gt_frag, gt_loc, gt_weight, scales)
       ctx.ignore_label = ignore_label
       ctx.mark_non_differentiable(bad)
@@ -464,7 +517,7 @@ def _features_losses_function():
       made = logits_from_features(features, dict(zip(HEAD_VARIABLES, variables)))
       logits, gt = _head_dicts(*(made[k] for k in HEADS), gt_obj, gt_frag, gt_loc, gt_weight)
       sums, counts, bad = loss_terms(logits, gt, ignore_label)
-      values, scales = loss_values(sums, counts, weights, reduction)
+      values, scales = loss_values(sums, counts, weights, reduction, knn=gt_knn(gt))
       ctx.save_for_backward(features, w_obj, w_frag, w_loc, *(logits[k] for k in HEADS),
                             gt_obj, gt_frag, gt_loc, gt_weight, scales)
       ctx.ignore_label = ignore_label

@@ -220,10 +220,15 @@ def pool_fragments(frag_centers, frag_sizes, num_objs=None):
   return centers, sizes
 
 
-def gt_fields_device(depth, local_pos, obj_ids, centers, sizes, masks=None):
-  """epos_gt_fields on device tensors depth f32 [N,h,w], local_pos f32 [N,h,w,3], optional
+MAX_KNN_FRAGS = 4                            # EPOS_LOSS_MAX_KNN
+
+
+def gt_fields_device(depth, local_pos, obj_ids, centers, sizes, masks=None, knn_frags=1):
+  """epos_gt_fields_knn on device tensors depth f32 [N,h,w], local_pos f32 [N,h,w,3], optional
   masks u8 [N,h,w]; obj_ids a sequence, centers / sizes the pooled host arrays. Returns
-  {obj_label, instance, frag_label, frag_loc, frag_weight} as device tensors."""
+  {obj_label, instance, frag_label, frag_loc, frag_weight} as device tensors. knn_frags = k > 1
+  (at most min(F, 4)): frag_label [h,w,k], frag_loc [h,w,k,3] and frag_weight [h,w,k] hold the
+  k nearest fragments in ascending distance; with 1 the shapes are [h,w], [h,w,3], [h,w]."""
   import torch
   lib = _lib.load()
   dev = depth.device
@@ -236,20 +241,24 @@ def gt_fields_device(depth, local_pos, obj_ids, centers, sizes, masks=None):
     raise ValueError('centers %s do not match sizes %s' % (centers.shape, sizes.shape))
   if masks is not None and tuple(masks.shape) != (n, h, w):
     raise ValueError('masks %s do not match depth %s' % (tuple(masks.shape), (n, h, w)))
+  k = int(knn_frags)
+  if k != knn_frags or k < 1 or k > min(F, MAX_KNN_FRAGS):
+    raise ValueError('knn_frags must be in 1..%d, got %r' % (min(F, MAX_KNN_FRAGS), knn_frags))
+  slots = () if k == 1 else (k,)
   ids = torch.tensor([int(o) for o in obj_ids] or [0], dtype=torch.int32, device=dev)
   c_dev, s_dev = torch.from_numpy(centers).to(dev), torch.from_numpy(sizes).to(dev)
   out = {'obj_label': torch.empty((h, w), dtype=torch.int32, device=dev),
          'instance': torch.empty((h, w), dtype=torch.int32, device=dev),
-         'frag_label': torch.empty((h, w), dtype=torch.int32, device=dev),
-         'frag_loc': torch.empty((h, w, 3), dtype=torch.float32, device=dev),
-         'frag_weight': torch.empty((h, w), dtype=torch.float32, device=dev)}
+         'frag_label': torch.empty((h, w) + slots, dtype=torch.int32, device=dev),
+         'frag_loc': torch.empty((h, w) + slots + (3,), dtype=torch.float32, device=dev),
+         'frag_weight': torch.empty((h, w) + slots, dtype=torch.float32, device=dev)}
   with C.launch(dev) as q:
     q.keep(ids, c_dev, s_dev)
-    _lib.check(lib.epos_gt_fields(
+    _lib.check(lib.epos_gt_fields_knn(
         C.ptr(depth), C.ptr(local_pos), C.ptr(masks), C.ptr(ids), n, h, w, C.ptr(c_dev),
-        C.ptr(s_dev), O, F, C.ptr(out['obj_label']), C.ptr(out['instance']),
+        C.ptr(s_dev), O, F, k, C.ptr(out['obj_label']), C.ptr(out['instance']),
         C.ptr(out['frag_label']), C.ptr(out['frag_loc']), C.ptr(out['frag_weight']),
-        q.handle), 'epos_gt_fields')
+        q.handle), 'epos_gt_fields_knn')
   return out
 
 
@@ -261,13 +270,14 @@ def _masks_to_device(masks, device):
   return torch.from_numpy(m).to(device)
 
 
-def gt_fields(renderer, K, obj_ids, Rs, ts, size, centers, sizes, masks=None):
+def gt_fields(renderer, K, obj_ids, Rs, ts, size, centers, sizes, masks=None, knn_frags=1):
   """Renders every instance at `size` = (w, h) and builds the ground-truth maps; returns the
-  dict of gt_fields_device. masks: optional [N,h,w] instance masks (host)."""
+  dict of gt_fields_device. masks: optional [N,h,w] instance masks (host); knn_frags: the
+  fragments per pixel, as gt_fields_device takes it."""
   out = renderer.render_instances(obj_ids, Rs, ts, K, size=size,
                                   outputs=('depth', 'local_pos'))
   return gt_fields_device(out['depth'], out['local_pos'], obj_ids, centers, sizes,
-                          _masks_to_device(masks, renderer.device))
+                          _masks_to_device(masks, renderer.device), knn_frags)
 
 
 def make_masks_exclusive(renderer, K, obj_ids, Rs, ts, masks):
@@ -291,28 +301,33 @@ def gt_label_map(renderer, K, obj_ids, Rs, ts, size, masks=None):
 
 
 class FragmentFieldGenerator(object):
-  """datagen_utils.FragmentFieldGenerator over epos_gt_fields (knn_frags = 1)."""
+  """datagen_utils.FragmentFieldGenerator over epos_gt_fields_knn: knn_frags nearest fragments
+  per pixel, 1..min(num_frags, 4)."""
 
   def __init__(self, frag_centers, frag_sizes, renderer, knn_frags=1):
-    if knn_frags != 1:
-      raise EposError('knn_frags must be 1')
     self.frag_centers, self.frag_sizes = frag_centers, frag_sizes
     self.renderer = renderer
-    self.knn_frags = 1
     self.centers, self.sizes = pool_fragments(frag_centers, frag_sizes)
+    self.knn_frags = int(knn_frags)
+    if self.knn_frags != knn_frags or not 1 <= self.knn_frags <= min(self.sizes.shape[1],
+                                                                     MAX_KNN_FRAGS):
+      raise EposError('knn_frags must be in 1..%d, got %r' % (
+          min(self.sizes.shape[1], MAX_KNN_FRAGS), knn_frags))
 
   def construct_frag_fields(self, width, height, K, gt_obj_ids, gt_obj_Rs, gt_obj_trans,
                             gt_obj_masks=None, return_all=False):
-    """-> (frag_ids i32 [h,w,1], frag_coords f32 [h,w,1,3], frag_weights f32 [h,w,1]) as
-    construct_frag_fields_py returns them. gt_obj_Rs: rotations [N,3,3] or quaternions [N,4]
-    (w, x, y, z). return_all: the whole dict of host arrays instead (label map, instances)."""
+    """-> (frag_ids i32 [h,w,k], frag_coords f32 [h,w,k,3], frag_weights f32 [h,w,k]) as
+    construct_frag_fields_py returns them, k = knn_frags. gt_obj_Rs: rotations [N,3,3] or
+    quaternions [N,4] (w, x, y, z). return_all: the whole dict of host arrays instead (label map, instances)."""
     for o in gt_obj_ids:
       if int(o) not in self.frag_centers:
         raise EposError('object %d has no fragments' % int(o))
     f = gt_fields(self.renderer, K, list(gt_obj_ids), gt_obj_Rs, gt_obj_trans,
-                  (width, height), self.centers, self.sizes, gt_obj_masks)
+                  (width, height), self.centers, self.sizes, gt_obj_masks, self.knn_frags)
     f = {k: v.cpu().numpy() for k, v in f.items()}
     if return_all:
       return f
-    return (f['frag_label'][:, :, None], f['frag_loc'][:, :, None, :],
-            f['frag_weight'][:, :, None])
+    if self.knn_frags == 1:
+      return (f['frag_label'][:, :, None], f['frag_loc'][:, :, None, :],
+              f['frag_weight'][:, :, None])
+    return f['frag_label'], f['frag_loc'], f['frag_weight']

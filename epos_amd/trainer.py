@@ -26,6 +26,8 @@ pre-activation. Not built: the in-place update of the depthwise layer's weights 
 weights set the bound gain / bias0 that the plan and its captured graphs hold by value: an
 update needs a design for that bound), everything below decoder_conv0_pointwise's
 pre-activation; batch-norm statistics, bf16 mode, multi-scale nets and more than one device. A
+ground truth with the k nearest fragments per pixel (the reference's gt_knn_frags; loss.Batch
+reads k from its shapes) goes through every entry here unchanged. A
 further trained layer is a row of
 weights.TRAINABLE_LAYERS, its gradient kernel's wrapper and a clause in net_grads.
 

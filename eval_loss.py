@@ -21,8 +21,10 @@ contract of ``eval.py``:
 total_loss is the sum of the three weighted losses WITHOUT the regularisation term that
 train.py:280 adds (epos_amd/loss.py; DESIGN.md, "Losses").
 
-The ground-truth fields are rendered on the device from the object meshes with one assigned
-fragment per pixel (the reference's gt_knn_frags = 1, train.py:82), so the run needs --dataset
+The ground-truth fields are rendered on the device from the object meshes with the
+--gt_knn_frags nearest fragments per pixel (train.py:82; default 1, at most 4 and no more than
+--num_frags; a training params.yml supplies it; with more than one, losses_<global_step>.json
+carries a gt_knn_frags key), so the run needs --dataset
 and $BOP_PATH with the 'eval' models. The network runs without its softmax (raw logits); each
 batch's forward pass, ground-truth fields and loss sums are enqueued on one stream and one row
 of numbers per image is downloaded at the end. A single-scale network only: the reference adds
@@ -61,6 +63,8 @@ def build_parser():
   a('--obj_cls_loss_weight', type=float, default=1.0)
   a('--frag_cls_loss_weight', type=float, default=1.0)
   a('--frag_loc_loss_weight', type=float, default=100.0)
+  a('--gt_knn_frags', type=int, default=1,
+    help='fragments a pixel is assigned to (train.py:82), 1..min(num_frags, 4)')
   # this build
   a('--batch_size', type=int, default=1, help='images per step')
   return ap
@@ -81,6 +85,7 @@ def prepare(argv=None):
     raise ValueError('eval_loss.py needs --dataset and $BOP_PATH (object models)')
   if args.batch_size < 1:
     raise ValueError('--batch_size must be >= 1')
+  args.gt_knn_frags = cli.check_gt_knn_frags(args)
   return args, model_dir
 
 
@@ -115,7 +120,8 @@ def main(argv=None):
                       precision=args.precision)
   out_size = (net.out_w, net.out_h)
   ev = loss.LossEval(num_objs, args.num_frags, dev, args.obj_cls_loss_weight,
-                     args.frag_cls_loss_weight, args.frag_loc_loss_weight, ignore_label=255)
+                     args.frag_cls_loss_weight, args.frag_loc_loss_weight, ignore_label=255,
+                     knn=args.gt_knn_frags)
   held_max = 2                                   # batches whose uploads may still be pending
   feed = eframes.Prefetcher(frames, B, h, w, workers=args.decode_threads or None,
                             ahead=max(1, args.prefetch), inflight=held_max)
@@ -129,7 +135,9 @@ def main(argv=None):
     logits = net.forward_logits(imgs, use_graph=True)
     n_real = len(frames[i0:i0 + B])
     fields = [eval_utils.gt_loss_fields_device(renderer, f, out_size, frag_pool, args.dataset,
-                                               input_size=(w, h)) for f in chunk[:n_real]]
+                                               input_size=(w, h),
+                                               knn_frags=args.gt_knn_frags)
+              for f in chunk[:n_real]]
     ev.update({k: v[:n_real] for k, v in logits.items()},
               {k: torch.stack([f[k] for f in fields]) for k in loss.GT_KEYS})
     if (i0 // B + 1) % 100 == 0:

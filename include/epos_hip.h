@@ -1309,6 +1309,97 @@ int epos_heads_dgrad_f32(const float* obj_logits, int64_t ld_obj, const float* f
                          int64_t ldwt, int K, const float* Y /* or NULL */, int64_t ldy,
                          float* dX, int64_t ldx, void* stream);
 
+/* k nearest fragments (csrc/render.hip, loss.hip, loss_grad.hip, heads_wgrad.hip,
+ * heads_dgrad.hip; added without an ABI version change: no existing entry gains, loses or
+ * reorders an argument). The reference's gt_knn_frags (train.py:82, datagen_utils.py:161-199,
+ * loss.py:186-229 and 267-303): every foreground pixel is assigned to its knn nearest fragments
+ * and the two fragment losses run over the n * knn (pixel, fragment) rows. Each entry below takes
+ * the arguments of its sibling plus `int knn`, and the sibling is the same body called with
+ * knn = 1: at knn = 1 every output of every entry is the same bytes. Everything the sections
+ * above say holds, with the following changes. tests/helpers/knn_ref.py restates them in
+ * element-wise numpy.
+ *
+ *   1 <= knn <= min(F, EPOS_LOSS_MAX_KNN); anything else is EPOS_E_INVALID before the first
+ *   launch. The cap is 4: the fragment kernel of the weight gradient keeps a batch's slots in
+ *   static LDS -- 64 pixels x knn x (fragment, weight, three localisation gradients), 20 bytes
+ *   per slot -- next to its tables; that is 55.9 KB at one slot and 59.7 KB at four, and the
+ *   next power of two would leave less than 1 KB of the 64 KB a static allocation may have.
+ *
+ *   Ground truth (epos_gt_fields_knn). frag_label i32 [h,w,knn], frag_loc f32 [h,w,knn,3],
+ *   frag_weight f32 [h,w,knn]. Slot j of a pixel an instance takes holds the j-th nearest
+ *   fragment centre: the distance dx^2 + dy^2 + dz^2 summed in that order in fp64 on the fp32
+ *   xyz, the slots in ascending distance, ties to the lower fragment index. frag_loc[...,j,:]
+ *   and frag_weight[...,j] are those of epos_gt_fields for that fragment. A pixel no instance
+ *   takes gets label 0, location 0 and weight 0 in every slot.
+ *
+ *   The loss entries read gt_frag i32 [B*P, knn], gt_loc f32 [B*P, knn, 3] and gt_weight f32
+ *   [B*P, knn].
+ *   Pixel class. As above, and a foreground pixel is also bad if ANY slot's fragment is outside
+ *   0..F-1, if any slot's weight is not a finite number > 0, or if two slots name the same
+ *   fragment.
+ *   Forward (epos_loss_terms_knn). With m and s of the row frag_logits[p,g-1,:] as above and
+ *   slot j's fragment f_j and weight w_j:
+ *     sums[b,g,1] += sum_j ( log(s) + (m - x_{f_j}) )
+ *     sums[b,g,2] += sum_j w_j * ((hub_0 + hub_1) + hub_2), hub_k of frag_loc[p,g-1,f_j,k] -
+ *     gt_loc[p,j,k]
+ *   both sums over j ascending from 0.0, each summand taken exactly as with one slot. counts
+ *   keep counting pixels.
+ *   Reduce (epos_loss_reduce_knn). n_b is replaced by n_b * knn (N_fg by N_fg * knn) in the two
+ *   fragment means and in scales[b,1] and scales[b,2]; the integer product is exact, and the
+ *   result is 0 when n_b == 0. Bit-equal to loss.summarize(..., knn=knn). knn outside
+ *   1..EPOS_LOSS_MAX_KNN is refused (the entry does not know F).
+ *   Logit gradients (epos_loss_grads_knn).
+ *     d_frag[p,g-1,c] = fl32( s_1 * ((double)knn * pr_c - t_c) ), pr_c = exp(x_c - m) / S and
+ *     t_c = 1 when c is one of the pixel's fragments, else 0;
+ *     d_loc at (g-1, f_j, .) is the value above with w_j and gt_loc[p,j,.], for every slot;
+ *     everything else is +0.0.
+ *   Weight gradient (epos_heads_wgrad_knn_f32). ACTIVE are the O+1 object values, the F values
+ *   of the row g-1 and the 3 * knn localisation values at (g-1, f_j). A pixel contributes to a
+ *   given (k, column) cell at most once, so the order per cell is still pixel order; ranges,
+ *   slabs, closing pass and epos_heads_wgrad_workspace_bytes are unchanged.
+ *   Input gradient (epos_heads_dgrad_knn_f32). The order stays "obj, frag, loc, ascending n
+ *   within a head": a pixel's slots are visited in ascending fragment index, whatever their
+ *   order in gt_frag. At most O+1 + F + 3 * knn active columns.
+ *   Launches, workspaces, share, range and workspace functions: those of the siblings. */
+#define EPOS_LOSS_MAX_KNN 4
+int epos_gt_fields_knn(const float* depth, const float* local_pos, const uint8_t* masks,
+                       const int32_t* obj_ids, int n_inst, int h, int w, const double* centers,
+                       const double* sizes, int num_objs, int num_frags, int knn,
+                       int32_t* obj_label, int32_t* instance, int32_t* frag_label,
+                       float* frag_loc, float* frag_weight, void* stream);
+int epos_loss_terms_knn(const float* obj_logits, int64_t ld_obj, const float* frag_logits,
+                        const float* frag_loc, const int32_t* gt_obj, const int32_t* gt_frag,
+                        const float* gt_loc, const float* gt_weight, int B, int64_t P,
+                        int num_objs, int num_frags, int ignore_label, int knn, void* workspace,
+                        double* sums, int64_t* counts, int64_t* bad, void* stream);
+int epos_loss_reduce_knn(const double* sums, const int64_t* counts, int B, int num_objs,
+                         double w_obj, double w_cls, double w_loc, int reduction, int knn,
+                         double* values /* [4] */, double* scales /* [B,3] */, void* stream);
+int epos_loss_grads_knn(const float* obj_logits, int64_t ld_obj, const float* frag_logits,
+                        const float* frag_loc, const int32_t* gt_obj, const int32_t* gt_frag,
+                        const float* gt_loc, const float* gt_weight, int B, int64_t P,
+                        int num_objs, int num_frags, int ignore_label, int knn,
+                        const double* scales,
+                        const double* upstream /* device [4], or NULL = {0,0,0,1} */,
+                        float* d_obj, int64_t ld_dobj, float* d_frag, float* d_loc, void* stream);
+int epos_heads_wgrad_knn_f32(const float* A, int64_t lda, int K, const float* obj_logits,
+                             int64_t ld_obj, const float* frag_logits, const float* frag_loc,
+                             const int32_t* gt_obj, const int32_t* gt_frag, const float* gt_loc,
+                             const float* gt_weight, int B, int64_t P, int num_objs,
+                             int num_frags, int ignore_label, int knn, const double* scales,
+                             const double* upstream /* device [4], or NULL = {0,0,0,1} */,
+                             void* workspace, float* dW_obj, float* db_obj, float* dW_frag,
+                             float* db_frag, float* dW_loc, float* db_loc, void* stream);
+int epos_heads_dgrad_knn_f32(const float* obj_logits, int64_t ld_obj, const float* frag_logits,
+                             const float* frag_loc, const int32_t* gt_obj, const int32_t* gt_frag,
+                             const float* gt_loc, const float* gt_weight, int B, int64_t P,
+                             int num_objs, int num_frags, int ignore_label, int knn,
+                             const double* scales,
+                             const double* upstream /* device [4], or NULL = {0,0,0,1} */,
+                             const float* Wt_obj, const float* Wt_frag, const float* Wt_loc,
+                             int64_t ldwt, int K, const float* Y /* or NULL */, int64_t ldy,
+                             float* dX, int64_t ldx, void* stream);
+
 /* Pointwise weight gradient (csrc/pointwise_wgrad.hip; added without an ABI version change). The
  * gradients of a 1x1 conv layer with a FROZEN batch norm -- decoder/decoder_conv1_pointwise,
  * the layer below the logits -- from its input A and the gradient G at its pre-activation

@@ -13,7 +13,9 @@ By default everything below the logits stays frozen, as the reference does with
 (its weights, BatchNorm/gamma, BatchNorm/beta: --freeze_regex_list
 '^(?!logits|decoder/decoder_conv1_pointwise)') trains them too, with the batch-norm statistics
 frozen (epos_amd/trainer.py); any other unfrozen scope is refused. No
-batch-norm statistics, one device, fp32, one scale. --data_augmentations (a mapping in the YAML
+batch-norm statistics, one device, fp32, one scale. --gt_knn_frags (train.py:82; default 1, at
+most 4 and no more than --num_frags) assigns every pixel to its k nearest fragments, and the two
+fragment losses run over the (pixel, fragment) rows. --data_augmentations (a mapping in the YAML
 format, on the command line or in params.yml, datagen.py:629-670) runs on the device between
 the upload of a batch and its forward pass (epos_amd/augment.py); its draws are keyed by
 (--seed, global step, image), so a resumed run augments as an uninterrupted one would.
@@ -74,6 +76,8 @@ def build_parser():
   a('--obj_cls_loss_weight', type=float, default=1.0)
   a('--frag_cls_loss_weight', type=float, default=1.0)
   a('--frag_loc_loss_weight', type=float, default=100.0)
+  a('--gt_knn_frags', type=int, default=1,
+    help='fragments a pixel is assigned to (train.py:82), 1..min(num_frags, 4)')
   a('--freeze_regex_list', action='append', default=None,
     help='accepted when every variable it leaves trainable below the logits belongs to '
          'decoder/decoder_conv1_pointwise; default: everything below the logits frozen')
@@ -153,6 +157,7 @@ def prepare(argv=None):
     raise ValueError('--train_batch_size must be >= 1')
   if args.log_steps < 1 or args.save_interval_steps < 1:
     raise ValueError('--log_steps and --save_interval_steps must be >= 1')
+  args.gt_knn_frags = cli.check_gt_knn_frags(args)
   return args, model_dir
 
 
@@ -246,7 +251,8 @@ def main(argv=None):
   time_start, saved = time.time(), None
   for _, chunk, imgs in cli.steps_released_in_order(feed, held_max):
     fields = [eval_utils.gt_loss_fields_device(renderer, f, out_size, frag_pool, args.dataset,
-                                               input_size=(w, h)) for f in chunk]
+                                               input_size=(w, h),
+                                               knn_frags=args.gt_knn_frags) for f in chunk]
     gt = {k: torch.stack([f[k] for f in fields]) for k in loss.GT_KEYS}
     lr = schedule(args, step)
     values, bad, status = trainer.train_step(net, imgs, gt, opt, lr, weights,
