@@ -476,6 +476,10 @@ SYMBOLS = {
     'epos_depthwise_dgrad_f32': (ctypes.c_int, [
         vp, ctypes.c_int64, vp, vp, ctypes.c_int64, vp, ctypes.c_int64, ctypes.c_int,
         ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp]),
+    # the adjoint of the align-corners bilinear resize
+    'epos_resize_bilinear_dgrad_f32': (ctypes.c_int, [
+        vp, ctypes.c_int64, vp, ctypes.c_int64, vp, ctypes.c_int64, ctypes.c_int, ctypes.c_int,
+        ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp]),
     # weight update: the packers on the device
     'epos_pack_weights_device_f32': (ctypes.c_int, [
         ctypes.POINTER(WeightPackArgs), ctypes.c_int, vp, vp]),

@@ -15,19 +15,27 @@
                           (csrc/depthwise_grad.hip; "Depthwise gradients").
   depthwise_input_grad    epos_depthwise_dgrad_f32: the gradient that crosses the depthwise layer,
                           at the pre-activation of decoder_conv0_pointwise.
+  resize_input_grad       epos_resize_bilinear_dgrad_f32: the gradient that crosses the decoder's
+                          align-corners bilinear resize, at the pre-activation of
+                          concat_projection (csrc/resize_grad.hip; "Resize input gradient").
 
 The nine variables' gradients from a running net, the optimiser and the training step are
-epos_amd/trainer.py, and so is the chain of all five wrappers (trainer.decoder_conv1_grads); the
-in-place weight update is EposNet.set_weights.
+epos_amd/trainer.py, and so are the chain of the first five wrappers (trainer.decoder_conv1_grads)
+and the chain through the whole decoder (trainer.decoder_grads); the in-place weight update is
+EposNet.set_weights.
 
 The batch-norm statistics are frozen (the reference's fine_tune_batch_norm=False): moving_mean
-and moving_variance are inputs. Built: the three gradients above ("Losses", "Backward
-through decoder_conv1"). Not built: the in-place update of the depthwise layer's weights -- its
+and moving_variance are inputs. Built: the gradients above ("Losses", "Backward
+through decoder_conv1" and "Backward through the decoder"). Not built: the in-place update of
+any depthwise layer's weights -- its
 folded weights set the bound |Y| <= gain max|X| + bias0 that the plan bakes by value into the
 layer's EposDepthwiseArgs and into its consumer's a_gain / a_bias, and captured graphs have
-copied those values, so an update needs a design for that bound; everything below
-decoder_conv0_pointwise's pre-activation; batch-norm statistics, bf16 mode, multi-scale nets and
-more than one device. Pinned to tests/helpers/pointwise_wgrad_ref.py and
+copied those values, so an update needs a design for that bound; training the four layers
+below decoder_conv1 (weights.POINTWISE_CHAIN_LAYERS, DEPTHWISE_CHAIN_LAYERS: their gradients
+are computed, the tables of trainable layers do not hold them); everything below
+concat_projection's pre-activation -- ASPP, the adjoint of the image-pooling broadcast (a plain
+sum, which resize_input_grad refuses) and the backbone; batch-norm statistics, bf16 mode,
+multi-scale nets and more than one device. Pinned to tests/helpers/pointwise_wgrad_ref.py and
 tests/helpers/decoder_backward_ref.py and, through them, to torch's fp64 autograd; parity with
 TensorFlow's gradients is unpinned. There is no CPU fallback.
 """
@@ -311,20 +319,75 @@ def depthwise_input_grad(d, w9c, rate=1, relu_of=None, out=None):
   return out.view(B, H, Wd, Cc) if out.dim() == 2 else out
 
 
+def resize_input_grad(d, in_hw, relu_of=None, out=None):
+  """epos_resize_bilinear_dgrad_f32: the gradient that crosses an align-corners bilinear resize
+  from in_hw = (Hi, Wi) to d's size, the adjoint of the plan's resize with the forward's own fp32
+  coordinates. d: f32 [B,Ho,Wo,C], pixels a constant stride apart (a channel slice of a wider
+  buffer goes straight through), the gradient at the resize's output. relu_of: the resize's
+  source, f32 [B,Hi,Wi,C], pixels a constant stride apart: the result is +0.0 wherever it is
+  <= 0, the gradient at the pre-activation of the layer that produced the source. Returns dX
+  f32 [B,Hi,Wi,C], or `out` (f32 [B,Hi,Wi,C], pixels a constant stride apart; its padding
+  columns are kept). Every element is written. A source of one row or column under a larger
+  output (the image-pooling broadcast) is refused. Enqueues on the current stream; does not
+  synchronise."""
+  import torch
+  lib = _lib.load()
+  C.need_device(d, 'the resize input gradient needs a HIP device (there is no CPU fallback)')
+  dev = d.device
+  _same_device_f32(dev, 'd', (d, 'd'))
+  d2, ldd, (B, Ho, Wo, Cc) = _nhwc(d, 'd')
+  Hi, Wi = (int(v) for v in in_hw)
+  y2, ldy = None, Cc
+  if relu_of is not None:
+    _same_device_f32(dev, 'd', (relu_of, 'relu_of'))
+    if tuple(relu_of.shape) != (B, Hi, Wi, Cc):
+      raise ValueError('relu_of must be %s, got %s' % ((B, Hi, Wi, Cc), tuple(relu_of.shape)))
+    y2, ldy = C.rows(relu_of, Cc)
+  if out is not None and tuple(out.shape) != (B, Hi, Wi, Cc):
+    raise ValueError('out must be %s, got %s' % ((B, Hi, Wi, Cc), tuple(out.shape)))
+  if Hi < 1 or Wi < 1:
+    raise ValueError('in_hw must be positive, got %s' % ((Hi, Wi),))
+  out, out2, ldx = _out_rows(out, dev, B * Hi * Wi, Cc, 'out')
+  with C.launch(dev) as q:
+    q.keep(d2, y2)
+    _lib.check(lib.epos_resize_bilinear_dgrad_f32(
+        C.ptr(d2), ldd, C.ptr(y2), ldy, C.ptr(out2), ldx, B, Hi, Wi, Ho, Wo, Cc, q.handle),
+        'epos_resize_bilinear_dgrad_f32')
+  return out.view(B, Hi, Wi, Cc) if out.dim() == 2 else out
+
+
 DEPTHWISE_LAYER = W.DECODER_CONV1_DEPTHWISE
 DEPTHWISE_VARIABLES = tuple(DEPTHWISE_LAYER + '/' + v for v in W.DEPTHWISE_VARIABLES)
 DEPTHWISE_CONSTANTS = (DEPTHWISE_LAYER + '/BatchNorm/moving_mean',
                        DEPTHWISE_LAYER + '/BatchNorm/moving_variance')
 
 
-def _depthwise_inputs(net, variables):
-  """(depthwise_weights, (gamma, moving_mean, moving_variance)) of decoder_conv1_depthwise on the
+def _depthwise_inputs(net, variables, layer=DEPTHWISE_LAYER):
+  """(depthwise_weights, (gamma, moving_mean, moving_variance)) of a depthwise layer the backward
+  pass crosses (decoder_conv1_depthwise by default) on the
   net's device: each from `variables` where given, otherwise the copy the net uploaded from its
-  checkpoint once (EposNet.depthwise_constants). With tensors on the device, or none, given,
-  nothing is copied from the host and nothing waited for."""
+  checkpoint once (EposNet.depthwise_constants, crossed_depthwise_constants). With tensors on
+  the device, or none, given, nothing is copied from the host and nothing waited for."""
+  kept = (net.depthwise_constants(layer) if layer in W.DEPTHWISE_BACKWARD_LAYERS else
+          net.crossed_depthwise_constants(layer))
+  return _given_or_kept(net, variables, layer, kept, ('depthwise_weights', 'BatchNorm/gamma'))
+
+
+def _crossed_inputs(net, variables, layer):
+  """(weights, (gamma, moving_mean, moving_variance)) of a 1x1 layer of
+  weights.POINTWISE_CHAIN_LAYERS on the net's device, as _depthwise_inputs gives a depthwise
+  layer's: from `variables` where given, otherwise the copy the net keeps
+  (EposNet.pointwise_constants)."""
+  return _given_or_kept(net, variables, layer, net.pointwise_constants(layer),
+                        ('weights', 'BatchNorm/gamma'))
+
+
+def _given_or_kept(net, variables, layer, kept, shorts):
   import torch
-  got = list(net.depthwise_constants(DEPTHWISE_LAYER))
-  for i, n in enumerate(DEPTHWISE_VARIABLES[:2] + DEPTHWISE_CONSTANTS):
+  got = list(kept)
+  names = tuple(layer + '/' + v for v in shorts + ('BatchNorm/moving_mean',
+                                                   'BatchNorm/moving_variance'))
+  for i, n in enumerate(names):
     v = variables.get(n)
     if v is not None:
       got[i] = torch.as_tensor(v, dtype=torch.float32).to(net.dev).contiguous()

@@ -142,8 +142,11 @@ class EposNet(object):
     self._sparse_packs = None
     self._layer_consts = {}      # trainable layer -> (moving_mean, moving_variance) on the device
     self._decoder_x = None
-    self._dw_operands = {}       # layer of weights.DEPTHWISE_BACKWARD_LAYERS -> depthwise_operand
+    self._dw_operands = {}       # layer of weights.DEPTHWISE_BACKWARD_LAYERS or
+    #                              DEPTHWISE_CHAIN_LAYERS -> depthwise_operand
     self._dw_consts = {}         # ... -> its variables and statistics on the device
+    self._pw_consts = {}         # layer of weights.POINTWISE_CHAIN_LAYERS -> pointwise_constants
+    self._chain = {}             # the buffers trainer.decoder_grads needs: chain_operands
     self.mode = MODES[precision](self)
     self.act_dtype = self.mode.dtype
     self._build_plan()
@@ -289,7 +292,7 @@ class EposNet(object):
     ho, wo = (hi - 1) // stride + 1, (wi - 1) // stride + 1
     w9c, bias, gain, bias0 = self._dw_params(name, eps)
     y = self._act(B, ho, wo, c)
-    if name in W.DEPTHWISE_BACKWARD_LAYERS:
+    if name in W.DEPTHWISE_BACKWARD_LAYERS or name in W.DEPTHWISE_CHAIN_LAYERS:
       assert stride == 1 and not relu_in and relu_out, name
       self._dw_operands[name] = {'x': x, 'ldx': ldx, 'b': B, 'h': hi, 'w': wi, 'c': c,
                                  'rate': rate, 'w9c': w9c, 'bias': bias, 'eps': eps}
@@ -576,6 +579,10 @@ class EposNet(object):
       mode.same_bound(dcat, low)
     mode.concat_bound(dcat, proj)
     self.decoder_concat = dcat[..., :304]
+    # what the backward pass through the decoder reads (chain_operands): records only
+    self._chain = {'decoder_concat': dcat, 'ld_concat': ldd, 'concat_projection': proj,
+                   'aspp_concat': cat, 'ld_aspp': ldcat, 'low_level': ll, 'low_level_c': lc,
+                   'low_level_hw': (lh, lw), 'encoder_hw': (eh, ew), 'decoder_hw': (dh, dw_)}
     x, c = dcat, 304
     for j in range(2):
       scope = 'decoder/decoder_conv%d' % j
@@ -877,9 +884,12 @@ class EposNet(object):
     or None, gain, bias), the very values the layer's PointwiseArgs carry; 'packs': the (plain,
     bias, split, fp16-pair) weight tensors its launch points at; 'eps': the batch norm's}."""
     self._need_fp32_plan('pointwise_operand')
-    if name not in self.mode.layer_operands:
+    if name not in W.TRAINABLE_LAYERS or name not in self.mode.layer_operands:
       raise ValueError('%r is not a trainable layer (%s)' % (
-          name, ', '.join(self.mode.layer_operands)))
+          name, ', '.join(n for n in self.mode.layer_operands if n in W.TRAINABLE_LAYERS)))
+    return self._pointwise_record(name, self.mode.packs[name][2], W.TRAINABLE_LAYERS[name])
+
+  def _pointwise_record(self, name, packs, eps):
     a, lda, m, k, n, args, ab = self.mode.layer_operands[name]
     presplit = bool(args.a_presplit)
     a_h2 = None
@@ -887,7 +897,49 @@ class EposNet(object):
       a_h2 = (self.mode.slot_words(ab[0]), self.mode.slot_words(ab[1]), float(args.a_gain),
               float(args.a_bias))
     return {'a': a, 'lda': lda, 'm': m, 'k': k, 'n': n, 'presplit': presplit, 'a_h2': a_h2,
-            'packs': self.mode.packs[name][2], 'eps': W.TRAINABLE_LAYERS[name]}
+            'packs': packs, 'eps': eps}
+
+  def crossed_pointwise_operand(self, name):
+    """pointwise_operand for a 1x1 conv layer of weights.POINTWISE_CHAIN_LAYERS, which the
+    backward pass crosses without training it: the same record, with 'packs' None (nothing
+    repacks its weights) and 'eps' from that table. pointwise_operand itself keeps refusing
+    these names: it answers for the layers EposNet.set_weights updates."""
+    self._need_fp32_plan('crossed_pointwise_operand', device=False)
+    if name not in W.POINTWISE_CHAIN_LAYERS or name not in self.mode.layer_operands:
+      raise ValueError('%r is not a 1x1 layer the backward pass crosses (%s)' % (
+          name, ', '.join(W.POINTWISE_CHAIN_LAYERS)))
+    return self._pointwise_record(name, None, W.POINTWISE_CHAIN_LAYERS[name])
+
+  def pointwise_constants(self, name):
+    """(weights [1,1,K,N], gamma, moving_mean, moving_variance [N]) of a layer of
+    weights.POINTWISE_CHAIN_LAYERS on the device, f32, uploaded from the checkpoint once and
+    kept, as depthwise_constants keeps a depthwise layer's: nothing updates these variables."""
+    if name not in W.POINTWISE_CHAIN_LAYERS:
+      raise ValueError('%r is not a 1x1 layer the backward pass crosses (%s)' % (
+          name, ', '.join(W.POINTWISE_CHAIN_LAYERS)))
+    if name not in self._pw_consts:
+      self._pw_consts[name] = tuple(
+          torch.from_numpy(np.ascontiguousarray(self.ckpt[name + '/' + v], np.float32)).to(self.dev)
+          for v in ('weights', 'BatchNorm/gamma', 'BatchNorm/moving_mean',
+                    'BatchNorm/moving_variance'))
+    return self._pw_consts[name]
+
+  def chain_operands(self):
+    """The buffers the backward pass through the decoder reads (trainer.decoder_grads), as they
+    were recorded while the plan was built (a dry run records them too); the net keeps them
+    alive. {'decoder_concat': [B,h,w,304] = [resize(concat_projection) : 256 |
+    feature_projection0 : 48], the input of decoder_conv0_depthwise; 'concat_projection':
+    [B,eh,ew,256] behind its ReLU; 'aspp_concat': [B,eh,ew,1280], concat_projection's input;
+    'low_level': the backbone's tap, feature_projection0's input, as [B,lh,lw,c] channels;
+    'low_level_hw', 'encoder_hw', 'decoder_hw': the three sizes}."""
+    self._need_fp32_plan('chain_operands', device=False)
+    r = self._chain
+    ll, (lh, lw) = r['low_level'], r['low_level_hw']
+    return {'decoder_concat': r['decoder_concat'][..., :304],
+            'concat_projection': r['concat_projection'], 'aspp_concat': r['aspp_concat'],
+            'low_level': ll.view(self.B, lh, lw, -1)[..., :r['low_level_c']],
+            'low_level_hw': (lh, lw), 'encoder_hw': r['encoder_hw'],
+            'decoder_hw': r['decoder_hw']}
 
   def depthwise_operand(self, name=W.DECODER_CONV1_DEPTHWISE):
     """What the backward pass through a 3x3 depthwise layer of
@@ -896,10 +948,20 @@ class EposNet(object):
     below writes behind its ReLU and the net keeps alive; 'ldx', 'b', 'h', 'w', 'c', 'rate';
     'w9c': the folded weights f32 [9,c] and 'bias': the folded bias f32 [c] its launch reads;
     'eps': the batch norm's}. The layer's output is EposNet.pointwise_operand's 'a'."""
-    self._need_fp32_plan('depthwise_operand', device=False)
-    if name not in self._dw_operands:
+    return self._depthwise_record('depthwise_operand', name, W.DEPTHWISE_BACKWARD_LAYERS)
+
+  def crossed_depthwise_operand(self, name=W.DECODER_CONV0_DEPTHWISE):
+    """depthwise_operand for a layer of weights.DEPTHWISE_CHAIN_LAYERS: the same record. For
+    decoder_conv0_depthwise 'x' is the decoder's concat buffer, [resize(concat_projection) : 256
+    | feature_projection0 : 48], of which only the last 48 channels lie behind a ReLU of their
+    own; its output is crossed_pointwise_operand('decoder/decoder_conv0_pointwise')'s 'a'."""
+    return self._depthwise_record('crossed_depthwise_operand', name, W.DEPTHWISE_CHAIN_LAYERS)
+
+  def _depthwise_record(self, what, name, table):
+    self._need_fp32_plan(what, device=False)
+    if name not in table or name not in self._dw_operands:
       raise ValueError('%r is not a depthwise layer the backward pass crosses (%s)' % (
-          name, ', '.join(W.DEPTHWISE_BACKWARD_LAYERS)))
+          name, ', '.join(table)))
     return dict(self._dw_operands[name])
 
   def depthwise_constants(self, name=W.DECODER_CONV1_DEPTHWISE):
@@ -907,9 +969,16 @@ class EposNet(object):
     weights.DEPTHWISE_BACKWARD_LAYERS on the device, f32, uploaded from the checkpoint once and
     kept: nothing updates that layer's variables, and a backward pass that asks for them enqueues
     no copy and waits for none."""
-    if name not in W.DEPTHWISE_BACKWARD_LAYERS:
+    return self._depthwise_consts(name, W.DEPTHWISE_BACKWARD_LAYERS)
+
+  def crossed_depthwise_constants(self, name=W.DECODER_CONV0_DEPTHWISE):
+    """depthwise_constants for a layer of weights.DEPTHWISE_CHAIN_LAYERS."""
+    return self._depthwise_consts(name, W.DEPTHWISE_CHAIN_LAYERS)
+
+  def _depthwise_consts(self, name, table):
+    if name not in table:
       raise ValueError('%r is not a depthwise layer the backward pass crosses (%s)' % (
-          name, ', '.join(W.DEPTHWISE_BACKWARD_LAYERS)))
+          name, ', '.join(table)))
     if name not in self._dw_consts:
       self._dw_consts[name] = tuple(
           torch.from_numpy(np.ascontiguousarray(self.ckpt[name + '/' + v], np.float32)).to(self.dev)

@@ -13,6 +13,9 @@ any subset of their variables -- not a choice between code paths.
                   round trip through the host).
   decoder_conv1_grads  net_grads' nine gradients plus the backward pass through the separable
                   conv decoder_conv1, down to decoder_conv0_pointwise's pre-activation.
+  decoder_grads   decoder_conv1_grads plus the backward pass through decoder_conv0, the split of
+                  the decoder's concat, feature_projection0 and the decoder's resize, down to
+                  concat_projection's pre-activation at the encoder's size.
   learning_rate   the reference's schedules (train_utils.py:117-195) in Python floats.
 
 The kernels' wrappers are epos_amd/heads_train.py (the logits layers' weight and input
@@ -22,10 +25,15 @@ train_heads.py; augmentation is epos_amd/augment.py, applied between the upload 
 forward pass. decoder_conv1_grads runs the whole backward pass of the separable conv
 decoder_conv1 -- the input gradient of decoder_conv1_pointwise, the weight, batch-norm and input
 gradients of decoder_conv1_depthwise -- and returns the gradient at decoder_conv0_pointwise's
-pre-activation. Not built: the in-place update of the depthwise layer's weights (its folded
+pre-activation; decoder_grads goes on through the rest of the decoder ("Losses",
+"Backward through the decoder") and returns the gradient at concat_projection's pre-activation.
+Not built: the in-place update of any depthwise layer's weights (its folded
 weights set the bound gain / bias0 that the plan and its captured graphs hold by value: an
-update needs a design for that bound), everything below decoder_conv0_pointwise's
-pre-activation; batch-norm statistics, bf16 mode, multi-scale nets and more than one device. A
+update needs a design for that bound); training the four layers below decoder_conv1, whose
+gradients decoder_grads computes (they are rows of weights.POINTWISE_CHAIN_LAYERS and
+DEPTHWISE_CHAIN_LAYERS, not of TRAINABLE_LAYERS); everything below concat_projection's
+pre-activation -- ASPP, the image-pooling broadcast's adjoint and the backbone; batch-norm
+statistics, bf16 mode, multi-scale nets and more than one device. A
 ground truth with the k nearest fragments per pixel (the reference's gt_knn_frags; loss.Batch
 reads k from its shapes) goes through every entry here unchanged. A
 further trained layer is a row of
@@ -206,6 +214,13 @@ def decoder_conv1_grads(net, gt, variables, weights=(1.0, 1.0, 100.0), reduction
   layer. The gradients of the depthwise layer are for inspection and for a trainer to come:
   Optimizer and EposNet.set_weights do not take them. fp32 single-scale nets only. Does not
   synchronise."""
+  values, bad, by_layer, d_in = _conv1_chain(net, gt, variables, weights, reduction, ignore_label)
+  return values, bad, _checkpoint_names(by_layer), d_in
+
+
+def _conv1_chain(net, gt, variables, weights, reduction, ignore_label):
+  """decoder_conv1_grads before the gradients get their checkpoint names: (values, bad, {scope:
+  {short name: gradient}}, d_in). decoder_grads goes on from here."""
   dw = net.depthwise_operand(DT.DEPTHWISE_LAYER)
   values, bad, by_layer, (G, a, op, w, bn) = _grads_above(net, gt, variables, True, weights,
                                                           reduction, ignore_label)
@@ -217,7 +232,82 @@ def decoder_conv1_grads(net, gt, variables, weights=(1.0, 1.0, 100.0), reduction
   by_layer[DT.DEPTHWISE_LAYER] = DT.depthwise_weight_grads(x, D4, dww, dbn, dw['eps'],
                                                            rate=dw['rate'])
   d_in = DT.depthwise_input_grad(D4, dw['w9c'], rate=dw['rate'], relu_of=x)
-  return values, bad, _checkpoint_names(by_layer), d_in
+  return values, bad, by_layer, d_in
+
+
+def decoder_grads(net, gt, variables, weights=(1.0, 1.0, 100.0), reduction='pooled',
+                  ignore_label=255):
+  """The backward pass through the whole decoder: call after net.forward_logits(). variables as
+  decoder_conv1_grads takes them; the variables and statistics of the four layers below
+  (weights.POINTWISE_CHAIN_LAYERS, weights.DEPTHWISE_CHAIN_LAYERS) come from `variables` where
+  given, otherwise from the copies of its checkpoint the net keeps on the device
+  (EposNet.pointwise_constants, crossed_depthwise_constants). Runs what decoder_conv1_grads runs, then,
+  with G0 = its d_in and A0 = the net's own output of decoder_conv0_depthwise (fp16 pairs or
+  fp32, as the plan has it),
+    pointwise_weight_grads(A0, G0)                 decoder_conv0_pointwise's dW, dgamma, dbeta
+    pointwise_input_grad(G0, relu_of=A0)           D0 [M,304], at decoder_conv0_depthwise's
+                                                   pre-activation
+    depthwise_weight_grads(decoder_concat, D0)     that layer's dw, dgamma, dbeta
+    depthwise_input_grad, channels 0:256           the gradient at the resize's output: NO mask,
+                                                   behind it lies the resize and not a ReLU
+    depthwise_input_grad, channels 256:304,        the gradient at feature_projection0's
+      relu_of=decoder_concat[..., 256:]            pre-activation
+    pointwise_weight_grads(the low-level tap, that 48-wide slice at row stride 304)
+                                                   feature_projection0's dW, dgamma, dbeta
+    resize_input_grad(channels 0:256, (eh, ew), relu_of=concat_projection)
+                                                   d_proj [B,eh,ew,256]
+    pointwise_weight_grads(aspp_concat, d_proj)    concat_projection's dW, dgamma, dbeta (K = 1280)
+  Returns (values, bad, grads, d_proj): values, bad and the twelve gradients of
+  decoder_conv1_grads byte for byte, plus the twelve new ones under their checkpoint names
+  (matrices [1,1,K,N], 'decoder/decoder_conv0_depthwise/depthwise_weights' [3,3,304,1]); d_proj:
+  the gradient at concat_projection's pre-activation, at the encoder's size -- the G from which
+  ASPP and the backbone start. The new gradients are for inspection and for a trainer to come:
+  Optimizer and EposNet.set_weights do not take them. fp32 single-scale nets whose low-level
+  features already have the decoder's size. Copies nothing from the host and does not
+  synchronise when `variables` holds device tensors, or none of the new names."""
+  import torch
+  ch = net.chain_operands()
+  if ch['low_level_hw'] != ch['decoder_hw']:
+    raise EposError('decoder_grads: the low-level features (%dx%d) are resized to the decoder\'s '
+                    'size (%dx%d); that resize has no backward pass here' % (
+                        ch['low_level_hw'] + ch['decoder_hw']))
+  op0 = net.crossed_pointwise_operand(W.DECODER_CONV0_POINTWISE)
+  opf = net.crossed_pointwise_operand(W.FEATURE_PROJECTION0)
+  opc = net.crossed_pointwise_operand(W.CONCAT_PROJECTION)
+  dw = net.crossed_depthwise_operand(W.DECODER_CONV0_DEPTHWISE)
+  values, bad, by_layer, d_in = _conv1_chain(net, gt, variables, weights, reduction, ignore_label)
+
+  def rows_of(op):
+    return op['a'].view(-1, op['a'].shape[-1])[:, :op['k']] if op['lda'] != op['k'] else op['a']
+
+  G0 = d_in.view(-1, d_in.shape[-1])
+  a0 = rows_of(op0)
+  w0, bn0 = DT._crossed_inputs(net, variables, W.DECODER_CONV0_POINTWISE)
+  by_layer[W.DECODER_CONV0_POINTWISE] = DT.pointwise_weight_grads(
+      a0, G0, w0, bn=bn0, eps=op0['eps'], a_h2=op0['a_h2'])
+  D0 = DT.pointwise_input_grad(G0, w0, bn=(bn0[0], bn0[2]), eps=op0['eps'], relu_of=a0,
+                               relu_of_h2=op0['presplit'])
+  B, h, w, c = dw['b'], dw['h'], dw['w'], dw['c']
+  x = dw['x'][..., :c]
+  D4 = D0.view(B, h, w, c)
+  dww, dbn = DT._depthwise_inputs(net, variables, W.DECODER_CONV0_DEPTHWISE)
+  by_layer[W.DECODER_CONV0_DEPTHWISE] = DT.depthwise_weight_grads(x, D4, dww, dbn, dw['eps'],
+                                                                  rate=dw['rate'])
+  n = ch['concat_projection'].shape[-1]                # 256: where the concat is split
+  d_cat = torch.empty((B, h, w, c), dtype=torch.float32, device=d_in.device)
+  DT.depthwise_input_grad(D4[..., :n], dw['w9c'][:, :n].contiguous(), rate=dw['rate'],
+                          out=d_cat[..., :n])
+  DT.depthwise_input_grad(D4[..., n:], dw['w9c'][:, n:].contiguous(), rate=dw['rate'],
+                          relu_of=x[..., n:], out=d_cat[..., n:])
+  wf, bnf = DT._crossed_inputs(net, variables, W.FEATURE_PROJECTION0)
+  by_layer[W.FEATURE_PROJECTION0] = DT.pointwise_weight_grads(
+      rows_of(opf), d_cat[..., n:], wf, bn=bnf, eps=opf['eps'], a_h2=opf['a_h2'])
+  d_proj = DT.resize_input_grad(d_cat[..., :n], ch['encoder_hw'],
+                                relu_of=ch['concat_projection'])
+  wc, bnc = DT._crossed_inputs(net, variables, W.CONCAT_PROJECTION)
+  by_layer[W.CONCAT_PROJECTION] = DT.pointwise_weight_grads(
+      rows_of(opc), d_proj, wc, bn=bnc, eps=opc['eps'], a_h2=opc['a_h2'])
+  return values, bad, _checkpoint_names(by_layer), d_proj
 
 
 def learning_rate(step, policy='poly', base_learning_rate=1e-4, decay_step=2000,

@@ -112,6 +112,22 @@ DECODER_CONV1_DEPTHWISE = 'decoder/decoder_conv1_depthwise'
 # plan bakes into its launches by value, so an in-place update needs a design of its own.
 DEPTHWISE_BACKWARD_LAYERS = {DECODER_CONV1_DEPTHWISE: 1e-5}
 DEPTHWISE_VARIABLES = ('depthwise_weights', 'BatchNorm/gamma', 'BatchNorm/beta')
+# The layers the backward pass crosses below decoder_conv1 (trainer.decoder_grads), in the order
+# it meets them, kept in tables of their own beside the two above: their gradients are for
+# inspection and for a trainer to come, and nothing here makes them trainable -- Optimizer,
+# EposNet.set_weights and the plan's weight packs (Fp32Mode.packs) hold TRAINABLE_LAYERS only.
+# scope -> the eps of its frozen batch norm (net.HEAD_BN_EPS). The plan records the operands of
+# the 1x1 layers (EposNet.crossed_pointwise_operand, 'packs' None) and of the depthwise layer
+# (EposNet.crossed_depthwise_operand); pointwise_operand and depthwise_operand keep answering for
+# the two tables above only. Not built: training these layers, and everything below
+# concat_projection's pre-activation (ASPP, the image-pooling broadcast's adjoint, the backbone).
+DECODER_CONV0_POINTWISE = 'decoder/decoder_conv0_pointwise'
+DECODER_CONV0_DEPTHWISE = 'decoder/decoder_conv0_depthwise'
+FEATURE_PROJECTION0 = 'decoder/feature_projection0'
+CONCAT_PROJECTION = 'concat_projection'
+POINTWISE_CHAIN_LAYERS = {DECODER_CONV0_POINTWISE: 1e-5, FEATURE_PROJECTION0: 1e-5,
+                          CONCAT_PROJECTION: 1e-5}
+DEPTHWISE_CHAIN_LAYERS = {DECODER_CONV0_DEPTHWISE: 1e-5}
 # a 1x1 conv layer's trained variables by whether it has a batch norm, `weights` first: what is
 # given together to EposNet.set_weights and what a gradient wrapper's result is keyed by
 CONV_VARIABLES = {False: ('weights', 'biases'),

@@ -1603,6 +1603,53 @@ int epos_depthwise_dgrad_f32(const float* D, int64_t ldd, const float* w9c,
                              const float* Y /* or NULL */, int64_t ldy, float* dX, int64_t ldx,
                              int B, int H, int W, int C, int rate, void* stream);
 
+/* Resize input gradient (csrc/resize_grad.hip; added without an ABI version change). The adjoint
+ * of the align-corners bilinear resize -- decoder/resize, from the decoder's size back to the
+ * encoder's. tests/helpers/resize_grad_ref.py restates it operation for operation.
+ *
+ * The forward it is the adjoint of (bilinear_sample, csrc/nhwc.h), per axis in -> out:
+ *   s = float(in - 1) / float(out - 1) in fp32, 0 for out == 1; f = o s in fp32;
+ *   i0 = min(floor f, in - 1), i1 = min(ceil f, in - 1); l = f - i0 in fp32;
+ *   out = top + (bot - top) ly with top = tl + (tr - tl) lx.
+ * The weight of source index i on output index o, in fp64 from the fp32 l, every term exact:
+ *   w(o, i) = [i0 == i](1 - l) + [i1 == i] l, and exactly 1 where i0 == i1 == i (l == 0, and the
+ *   clamped last coordinate).
+ *
+ * epos_resize_bilinear_dgrad_f32: dX f32 [B,Hi,Wi,C] with pixel stride ldx [device] from D f32
+ * [B,Ho,Wo,C] with pixel stride ldd [device], the gradient at the resize's output.
+ *     dX[b,yi,xi,c] = fl32( sum_{yo,xo} (wy(yo,yi) wx(xo,xi)) * (double)D[b,yo,xo,c] )
+ *   over the output pixels whose row has a tap at yi and whose column has a tap at xi.
+ *   Footprint. Which (yo, xo) those are is decided by the forward's own fp32 expressions above,
+ *   evaluated per output index, never by a closed form of (i +- 1) / s: where fp32 rounding moved
+ *   a sample into the neighbouring cell (it does at 59 / 119), the adjoint follows the forward.
+ *   i0 and i1 do not decrease with o and differ by at most 1, so the outputs of a source index
+ *   are one interval [first o with i1(o) >= i, last o with i0(o) <= i], found by binary search
+ *   over those expressions; it may be empty (downscaling), and dX is then +0.0.
+ *   Order and arithmetic. One fp64 accumulator per element from +0.0; the output pixels of the
+ *   footprint in (yo, xo) order, rows ascending, columns ascending within a row: an order fixed
+ *   by the sizes alone. Per pixel w = wy * wx, p = w * (double)D, acc += p, each rounded once
+ *   (the library is built with -ffp-contract=off); the sum is rounded to fp32 once. Within
+ *   2^-24 |exact| + (n + 16) 2^-52 sum |w||D| of the exact sum, n = the pixels of the footprint.
+ *   The identity (Hi == Ho, Wi == Wo) yields the bytes of D (a -0.0 of D becomes +0.0: the sum
+ *   starts from +0.0).
+ *   Mask. With Y non-NULL (f32 [B,Hi,Wi,C], pixel stride ldy: the source activation) dX is
+ *   written as +0.0 wherever Y <= 0 (-0.0 counts, a NaN does not), the rule of
+ *   epos_depthwise_dgrad_f32: dX is then the gradient at the pre-activation of the layer that
+ *   produced the source -- for decoder/resize, concat_projection.
+ *   C % 4 == 0, pitches multiples of 4, rows 16-byte aligned; padding columns are never read or
+ *   written, EVERY element of dX is WRITTEN. A thread owns four channels of one source pixel
+ *   (16-byte loads and store, consecutive threads along the channel axis). One launch, no
+ *   workspace, no atomics, no host synchronisation, capturable in a graph; the same bytes in
+ *   every run, for an image alone and at any position of a batch.
+ *   Refused with EPOS_E_INVALID before the launch, nothing written: a null D or dX; B, Hi, Wi,
+ *   Ho, Wo or C < 1; C % 4 != 0; Hi, Wi, Ho or Wo > 2^22; ldd, ldx or (with Y) ldy < C or not a
+ *   multiple of 4; a pointer that is not 16-byte aligned; dX starting at D or at Y; in == 1 with
+ *   out > 1 in either dimension -- the image-pooling broadcast, whose adjoint is a plain sum and
+ *   not this entry. */
+int epos_resize_bilinear_dgrad_f32(const float* D, int64_t ldd, const float* Y /* or NULL */,
+                                   int64_t ldy, float* dX, int64_t ldx, int B, int Hi, int Wi,
+                                   int Ho, int Wo, int C, void* stream);
+
 /* Weight update (csrc/weight_pack.hip; added without an ABI version change). The three host
  * packers above restated as device kernels, so that weights updated on the device (the momentum
  * step) reach a built plan without a round trip through the host: a grouped call packs fp32
