@@ -227,6 +227,30 @@ class DepthwiseWgradArgs(ctypes.Structure):
               ('T', vp), ('t', vp), ('workspace', vp)]
 
 
+class AsppJoinDw(ctypes.Structure):
+  _fields_ = [('D', vp), ('ldd', ctypes.c_int64), ('w9c', vp), ('rate', ctypes.c_int32),
+              ('reserved0', ctypes.c_int32)]
+
+
+class AsppJoinPlain(ctypes.Structure):
+  _fields_ = [('E', vp), ('lde', ctypes.c_int64)]
+
+
+class AsppJoinArgs(ctypes.Structure):
+  _fields_ = [('B', ctypes.c_int32), ('H', ctypes.c_int32), ('W', ctypes.c_int32),
+              ('C', ctypes.c_int32), ('n_dw', ctypes.c_int32), ('n_plain', ctypes.c_int32),
+              ('dw', AsppJoinDw * 4), ('plain', AsppJoinPlain * 2),
+              ('Pool', vp), ('ldp', ctypes.c_int64), ('pool_div', ctypes.c_int64),
+              ('Y', vp), ('ldy', ctypes.c_int64), ('dX', vp), ('ldx', ctypes.c_int64),
+              ('partition', ctypes.c_int32), ('reserved0', ctypes.c_int32)]
+
+
+# EPOS_ASPP_JOIN_*: how epos_aspp_join_dgrad_f32 deals its elements to workgroups (0: the
+# shipped one); never what they hold
+ASPP_JOIN_PARTITIONS = {'shipped': 0, 'pixel': 1, 'slice32': 2, 'slice64': 3, 'slice32x2': 4,
+                        'slice32x4': 5}
+
+
 class FitParams(ctypes.Structure):
   _fields_ = [
       ('threshold', ctypes.c_double),
@@ -480,6 +504,15 @@ SYMBOLS = {
     'epos_resize_bilinear_dgrad_f32': (ctypes.c_int, [
         vp, ctypes.c_int64, vp, ctypes.c_int64, vp, ctypes.c_int64, ctypes.c_int, ctypes.c_int,
         ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp]),
+    # ASPP gradients: the adjoint of the image-pooling broadcast, the join of the branches
+    'epos_pool_broadcast_dgrad_range_pixels': (ctypes.c_int64, [
+        ctypes.c_int, ctypes.c_int64, ctypes.c_int]),
+    'epos_pool_broadcast_dgrad_workspace_bytes': (ctypes.c_int64, [
+        ctypes.c_int, ctypes.c_int64, ctypes.c_int]),
+    'epos_pool_broadcast_dgrad_f32': (ctypes.c_int, [
+        vp, ctypes.c_int64, vp, ctypes.c_int64, ctypes.c_int, ctypes.c_int64, ctypes.c_int, vp,
+        vp]),
+    'epos_aspp_join_dgrad_f32': (ctypes.c_int, [ctypes.POINTER(AsppJoinArgs), vp]),
     # weight update: the packers on the device
     'epos_pack_weights_device_f32': (ctypes.c_int, [
         ctypes.POINTER(WeightPackArgs), ctypes.c_int, vp, vp]),

@@ -18,26 +18,35 @@
   resize_input_grad       epos_resize_bilinear_dgrad_f32: the gradient that crosses the decoder's
                           align-corners bilinear resize, at the pre-activation of
                           concat_projection (csrc/resize_grad.hip; "Resize input gradient").
+  pool_broadcast_grad     epos_pool_broadcast_dgrad_f32: the adjoint of ASPP's image-pooling
+                          broadcast, a per-image column sum in fp64 (csrc/aspp_grad.hip; "ASPP
+                          gradients").
+  aspp_join_grad          epos_aspp_join_dgrad_f32: the gradient at the encoder output, which
+                          feeds ASPP's five branches -- the plain terms, the mirrored taps of the
+                          depthwise terms and the per-image term in one fp64 sum per element, one
+                          pass over the output.
 
 The nine variables' gradients from a running net, the optimiser and the training step are
-epos_amd/trainer.py, and so are the chain of the first five wrappers (trainer.decoder_conv1_grads)
-and the chain through the whole decoder (trainer.decoder_grads); the in-place weight update is
-EposNet.set_weights.
+epos_amd/trainer.py, and so are the chain of the first five wrappers (trainer.decoder_conv1_grads),
+the chain through the whole decoder (trainer.decoder_grads) and the one through ASPP
+(trainer.aspp_grads); the in-place weight update is EposNet.set_weights.
 
 The batch-norm statistics are frozen (the reference's fine_tune_batch_norm=False): moving_mean
 and moving_variance are inputs. Built: the gradients above ("Losses", "Backward
-through decoder_conv1" and "Backward through the decoder"). Not built: the in-place update of
+through decoder_conv1", "Backward through the decoder" and "Backward through ASPP");
+pointwise_input_grad at any K (the entry takes K <= 1024: a wider K goes to it in k_blocks).
+Not built: the in-place update of
 any depthwise layer's weights -- its
 folded weights set the bound |Y| <= gain max|X| + bias0 that the plan bakes by value into the
 layer's EposDepthwiseArgs and into its consumer's a_gain / a_bias, and captured graphs have
 copied those values, so an update needs a design for that bound; training the four layers
-below decoder_conv1 (weights.POINTWISE_CHAIN_LAYERS, DEPTHWISE_CHAIN_LAYERS: their gradients
-are computed, the tables of trainable layers do not hold them); everything below
-concat_projection's pre-activation -- ASPP, the adjoint of the image-pooling broadcast (a plain
-sum, which resize_input_grad refuses) and the backbone; batch-norm statistics, bf16 mode,
-multi-scale nets and more than one device. Pinned to tests/helpers/pointwise_wgrad_ref.py and
-tests/helpers/decoder_backward_ref.py and, through them, to torch's fp64 autograd; parity with
-TensorFlow's gradients is unpinned. There is no CPU fallback.
+below decoder_conv1 and ASPP's (weights.POINTWISE_CHAIN_LAYERS, DEPTHWISE_CHAIN_LAYERS,
+weights.aspp_layers: their gradients are computed, the tables of trainable layers do not hold
+them); the backbone, everything below the encoder output's pre-activation; batch-norm
+statistics, bf16 mode, multi-scale nets and more than one device. Pinned to
+tests/helpers/pointwise_wgrad_ref.py, decoder_backward_ref.py, resize_grad_ref.py and
+aspp_grad_ref.py and, through them, to torch's fp64 autograd; parity with TensorFlow's gradients
+is unpinned, and the formulas for the frozen batch norm are this build's own. There is no CPU fallback.
 """
 import ctypes
 
@@ -169,8 +178,10 @@ def pointwise_input_grad(g, weights, bn=None, eps=BN_EPS, relu_of=None, relu_of_
   such a tensor (EposNet.pointwise_operand's 'a'): the result is +0.0 wherever it is <= 0, the
   gradient at the pre-activation of the layer that produced A. Returns D f32 [rows, K], or `out`
   (f32 [..., K], rows a constant stride apart; its padding columns are kept). `workspace`: a
-  float64 tensor of at least epos_pointwise_dgrad_workspace_bytes(K, N) / 8 values. Every
-  element is written. Enqueues on the current stream; does not synchronise."""
+  float64 tensor of at least epos_pointwise_dgrad_workspace_bytes(min(K, 1024), N) / 8 values.
+  The entry takes K <= 1024: a wider K (ASPP's 1280 and 2048) goes to it in k_blocks(K), one
+  call per block on weights[k0:k1], out[:, k0:k1] and relu_of[:, k0:k1], the same bytes as an
+  uncut call would give. N > 1024 stays refused. Every element is written. Enqueues on the current stream; does not synchronise."""
   import torch
   lib = _lib.load()
   C.need_device(g, 'the input gradient needs a HIP device (there is no CPU fallback)')
@@ -204,19 +215,37 @@ def pointwise_input_grad(g, weights, bn=None, eps=BN_EPS, relu_of=None, relu_of_
     if relu_of_h2 and m2.data_ptr() != relu_of.data_ptr():
       raise ValueError('a pre-split relu_of must have rows a constant stride apart')
   out, out2, ldd = _out_rows(out, dev, M, K, 'out')
-  nbytes = lib.epos_pointwise_dgrad_workspace_bytes(K, N)
+  blocks = k_blocks(K)
+  nbytes = lib.epos_pointwise_dgrad_workspace_bytes(blocks[0][1], N)
   _lib.check(nbytes, 'epos_pointwise_dgrad_workspace_bytes')
   ws = C.workspace(workspace, dev, nbytes, torch.float64)
-  args = _lib.PointwiseDgradArgs(
-      G=C.ptr(g2), ldg=ldg, W=C.ptr(weights), gamma=C.ptr(consts[0]),
-      moving_variance=C.ptr(consts[1]), eps=float(eps), mask=C.ptr(m2), ldm=ldm,
-      mask_h2=int(bool(relu_of_h2) and m2 is not None), M=M, K=K, N=N, D=C.ptr(out2), ldd=ldd,
-      workspace=C.ptr(ws))
+  w2 = weights.view(K, N)
   with C.launch(dev) as q:
     q.keep(g2, m2, ws)
-    _lib.check(lib.epos_pointwise_dgrad_f32(ctypes.byref(args), q.handle),
-               'epos_pointwise_dgrad_f32')
+    for k0, k1 in blocks:
+      args = _lib.PointwiseDgradArgs(
+          G=C.ptr(g2), ldg=ldg, W=C.ptr(w2, k0 * N), gamma=C.ptr(consts[0]),
+          moving_variance=C.ptr(consts[1]), eps=float(eps), mask=C.ptr(m2, k0), ldm=ldm,
+          mask_h2=int(bool(relu_of_h2) and m2 is not None), M=M, K=k1 - k0, N=N,
+          D=C.ptr(out2, k0), ldd=ldd, workspace=C.ptr(ws))
+      _lib.check(lib.epos_pointwise_dgrad_f32(ctypes.byref(args), q.handle),
+                 'epos_pointwise_dgrad_f32')
   return out
+
+
+DGRAD_MAX_K = 1024     # epos_pointwise_dgrad_f32 refuses a wider K; its tests pin the refusal
+
+
+def k_blocks(K, width=DGRAD_MAX_K):
+  """[(k0, k1), ...]: the K columns of pointwise_input_grad's result cut into consecutive blocks
+  of at most `width` (a multiple of 4, so that the quads of a pre-split mask stay whole), one
+  call of the entry each. The kernel keeps one accumulator per (row, k) and its reduction runs
+  over N, which is never cut: the cut changes no byte. K <= width is one block, the call it
+  always was."""
+  if K < 1 or width < 4 or width % 4:
+    raise ValueError('k_blocks: K >= 1 and a width that is a multiple of 4, got %r, %r' % (
+        K, width))
+  return [(k0, min(k0 + width, K)) for k0 in range(0, K, width)]
 
 
 def _nhwc(t, what):
@@ -354,6 +383,123 @@ def resize_input_grad(d, in_hw, relu_of=None, out=None):
         C.ptr(d2), ldd, C.ptr(y2), ldy, C.ptr(out2), ldx, B, Hi, Wi, Ho, Wo, Cc, q.handle),
         'epos_resize_bilinear_dgrad_f32')
   return out.view(B, Hi, Wi, Cc) if out.dim() == 2 else out
+
+
+def pool_workspace_bytes(B, P, Cc):
+  """Bytes of workspace pool_broadcast_grad needs: the ranges' slabs, 0 with one range."""
+  nbytes = _lib.load().epos_pool_broadcast_dgrad_workspace_bytes(B, P, Cc)
+  _lib.check(nbytes, 'epos_pool_broadcast_dgrad_workspace_bytes')
+  return nbytes
+
+
+def pool_broadcast_grad(d, out=None, workspace=None):
+  """epos_pool_broadcast_dgrad_f32: the adjoint of broadcasting a [B,C] tensor over the pixels
+  of each image (ASPP's image pooling), g[b,c] = the fp64 sum of d[b,:,c] rounded once. d: f32
+  [B,H,W,C] or [B,P,C], pixels a constant stride apart (a column slice of a wider buffer goes
+  straight through). Returns g f32 [B,C], or `out` (f32 [B,C], rows a constant stride apart;
+  its padding columns are kept). `workspace`: a float64 tensor of at least
+  pool_workspace_bytes(B, P, C) / 8 values. Every element is written. Enqueues on the current
+  stream; does not synchronise."""
+  import torch
+  lib = _lib.load()
+  C.need_device(d, 'the broadcast\'s adjoint needs a HIP device (there is no CPU fallback)')
+  dev = d.device
+  _same_device_f32(dev, 'd', (d, 'd'))
+  if d.dim() not in (3, 4) or d.numel() < 1:
+    raise ValueError('d must be [B, H, W, C] or [B, P, C], got %s' % (tuple(d.shape),))
+  B, Cc = int(d.shape[0]), int(d.shape[-1])
+  d2, ldd = C.rows(d, Cc)
+  P = int(d2.shape[0]) // B
+  if out is not None and tuple(out.shape) != (B, Cc):
+    raise ValueError('out must be %s, got %s' % ((B, Cc), tuple(out.shape)))
+  out, out2, ldg = _out_rows(out, dev, B, Cc, 'out')
+  nbytes = lib.epos_pool_broadcast_dgrad_workspace_bytes(B, P, Cc)
+  _lib.check(nbytes, 'epos_pool_broadcast_dgrad_workspace_bytes')
+  ws = C.workspace(workspace, dev, nbytes, torch.float64) if nbytes else None
+  with C.launch(dev) as q:
+    q.keep(d2, ws)
+    _lib.check(lib.epos_pool_broadcast_dgrad_f32(
+        C.ptr(d2), ldd, C.ptr(out2), ldg, B, P, Cc, C.ptr(ws), q.handle),
+        'epos_pool_broadcast_dgrad_f32')
+  return out
+
+
+def aspp_join_grad(depthwise=(), plain=(), pooled=None, relu_of=None, out=None,
+                   partition='shipped'):
+  """epos_aspp_join_dgrad_f32: the gradient at a tensor X [B,H,W,C] that feeds several branches
+  (ASPP's encoder output), in one pass: per element one fp64 sum of the plain terms, the
+  mirrored taps of the depthwise terms and the per-image term, in that order, rounded once.
+  depthwise: up to four (D f32 [B,H,W,C], w9c f32 [9,C] contiguous, rate) -- D the gradient at
+  a 3x3 depthwise branch's pre-activation, w9c its FOLDED weights, as depthwise_input_grad
+  takes them; plain: up to two f32 [B,H,W,C] or [B*H*W,C], the gradients 1x1 branches sent
+  down (pointwise_input_grad's results); pooled = (Pool f32 [B,C], div): the gradient at a mean
+  over div pixels, which adds Pool[b,c] / div to every pixel of image b. relu_of: X itself, f32
+  [B,H,W,C]: the result is +0.0 wherever it is <= 0. Every tensor may be a slice of a wider
+  buffer with pixels a constant stride apart. Returns dX f32 [B,H,W,C], or `out`.
+  partition: a key of _lib.ASPP_JOIN_PARTITIONS -- which workgroup computes an element, never
+  its value. With one depthwise term alone the bytes are depthwise_input_grad's. Every element
+  is written. Enqueues on the current stream; does not synchronise."""
+  import torch
+  lib = _lib.load()
+  depthwise, plain = list(depthwise), list(plain)
+  first = (depthwise[0][0] if depthwise else relu_of if relu_of is not None else
+           out if out is not None else next((t for t in plain if t.dim() == 4), None))
+  if first is None or first.dim() != 4:
+    raise ValueError('aspp_join_grad: a [B, H, W, C] tensor among depthwise, relu_of, out or '
+                     'plain must give the shape')
+  C.need_device(first, 'the ASPP join needs a HIP device (there is no CPU fallback)')
+  dev = first.device
+  B, H, Wd, Cc = (int(v) for v in first.shape)
+  if len(depthwise) > 4 or len(plain) > 2:
+    raise ValueError('aspp_join_grad takes at most 4 depthwise and 2 plain terms, got %d and '
+                     '%d' % (len(depthwise), len(plain)))
+  if not depthwise and not plain and pooled is None:
+    raise ValueError('aspp_join_grad: at least one term must be present')
+  args = _lib.AsppJoinArgs(B=B, H=H, W=Wd, C=Cc, n_dw=len(depthwise), n_plain=len(plain),
+                           partition=_lib.ASPP_JOIN_PARTITIONS[partition])
+  kept = []
+  for i, (d, w9c, rate) in enumerate(depthwise):
+    _same_device_f32(dev, 'the first tensor', (d, 'depthwise[%d] D' % i),
+                     (w9c, 'depthwise[%d] w9c' % i))
+    if tuple(d.shape) != (B, H, Wd, Cc):
+      raise ValueError('depthwise[%d] D must be %s, got %s' % (i, (B, H, Wd, Cc),
+                                                               tuple(d.shape)))
+    C.dense(w9c, dev, torch.float32, 'depthwise[%d] w9c' % i, shape=(9, Cc), name='float32')
+    d2, ldd = C.rows(d, Cc)
+    kept += [d2, w9c]
+    args.dw[i] = _lib.AsppJoinDw(D=C.ptr(d2), ldd=ldd, w9c=C.ptr(w9c), rate=int(rate))
+  for j, e in enumerate(plain):
+    _same_device_f32(dev, 'the first tensor', (e, 'plain[%d]' % j))
+    if e.shape[-1] != Cc or e.numel() != B * H * Wd * Cc:
+      raise ValueError('plain[%d] must hold %d rows of %d values, got %s' % (
+          j, B * H * Wd, Cc, tuple(e.shape)))
+    e2, lde = C.rows(e, Cc)
+    kept.append(e2)
+    args.plain[j] = _lib.AsppJoinPlain(E=C.ptr(e2), lde=lde)
+  if pooled is not None:
+    pool, div = pooled
+    _same_device_f32(dev, 'the first tensor', (pool, 'pooled'))
+    if tuple(pool.shape) != (B, Cc):
+      raise ValueError('pooled must be %s, got %s' % ((B, Cc), tuple(pool.shape)))
+    p2, ldp = C.rows(pool, Cc)
+    kept.append(p2)
+    args.Pool, args.ldp, args.pool_div = C.ptr(p2), ldp, int(div)
+  if relu_of is not None:
+    _same_device_f32(dev, 'the first tensor', (relu_of, 'relu_of'))
+    if tuple(relu_of.shape) != (B, H, Wd, Cc):
+      raise ValueError('relu_of must be %s, got %s' % ((B, H, Wd, Cc), tuple(relu_of.shape)))
+    y2, ldy = C.rows(relu_of, Cc)
+    kept.append(y2)
+    args.Y, args.ldy = C.ptr(y2), ldy
+  if out is not None and tuple(out.shape) != (B, H, Wd, Cc):
+    raise ValueError('out must be %s, got %s' % ((B, H, Wd, Cc), tuple(out.shape)))
+  out, out2, ldx = _out_rows(out, dev, B * H * Wd, Cc, 'out')
+  args.dX, args.ldx = C.ptr(out2), ldx
+  with C.launch(dev) as q:
+    q.keep(*kept)
+    _lib.check(lib.epos_aspp_join_dgrad_f32(ctypes.byref(args), q.handle),
+               'epos_aspp_join_dgrad_f32')
+  return out.view(B, H, Wd, Cc) if out.dim() == 2 else out
 
 
 DEPTHWISE_LAYER = W.DECODER_CONV1_DEPTHWISE

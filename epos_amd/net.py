@@ -147,6 +147,10 @@ class EposNet(object):
     self._dw_consts = {}         # ... -> its variables and statistics on the device
     self._pw_consts = {}         # layer of weights.POINTWISE_CHAIN_LAYERS -> pointwise_constants
     self._chain = {}             # the buffers trainer.decoder_grads needs: chain_operands
+    # ASPP's layers for these rates, whose operands the plan records (aspp_operands): records
+    # only, no launch, buffer or argument depends on them
+    self._aspp_pw, self._aspp_dw = W.aspp_layers(self.atrous_rates)
+    self._aspp = {}
     self.mode = MODES[precision](self)
     self.act_dtype = self.mode.dtype
     self._build_plan()
@@ -292,7 +296,8 @@ class EposNet(object):
     ho, wo = (hi - 1) // stride + 1, (wi - 1) // stride + 1
     w9c, bias, gain, bias0 = self._dw_params(name, eps)
     y = self._act(B, ho, wo, c)
-    if name in W.DEPTHWISE_BACKWARD_LAYERS or name in W.DEPTHWISE_CHAIN_LAYERS:
+    if name in W.DEPTHWISE_BACKWARD_LAYERS or name in W.DEPTHWISE_CHAIN_LAYERS or \
+        name in self._aspp_dw:
       assert stride == 1 and not relu_in and relu_out, name
       self._dw_operands[name] = {'x': x, 'ldx': ldx, 'b': B, 'h': hi, 'w': wi, 'c': c,
                                  'rate': rate, 'w9c': w9c, 'bias': bias, 'eps': eps}
@@ -548,6 +553,10 @@ class EposNet(object):
     self._conv1x1('concat_projection', HEAD_BN_EPS, cat, 0, ldcat, m_enc, ldcat, proj, 0,
                   256, relu=True)
     self.aspp_concat, self.concat_projection = cat, proj
+    # what the backward pass through ASPP reads (aspp_operands): records only
+    self._aspp = {'encoder': x, 'eh': eh, 'ew': ew, 'ec': ec, 'pooled': pooled,
+                  'pool_feat': pool_feat, 'aspp_concat': cat,
+                  'encoder_relu': self._expr_of(x, 0, ec).startswith('relu(')}
 
     # ---- decoder (model.py:268-393).
     ll, lh, lw, lc = low_level
@@ -923,6 +932,45 @@ class EposNet(object):
           for v in ('weights', 'BatchNorm/gamma', 'BatchNorm/moving_mean',
                     'BatchNorm/moving_variance'))
     return self._pw_consts[name]
+
+  def aspp_operands(self):
+    """The buffers and launch records the backward pass through ASPP reads (trainer.aspp_grads),
+    as they were recorded while the plan was built (a dry run records them too); the net keeps
+    them alive. {'encoder': [B,eh,ew,ec] channels of the encoder output, the input of all five
+    branches; 'encoder_relu': whether the plan's expression for it is a ReLU (Xception's exit
+    flow, the ResNet units) -- only then is it the mask of the gradient at its pre-activation;
+    'pooled': [B,ec], its mean, image_pooling's input; 'pool_feat': [B,256], image_pooling's
+    output behind its ReLU; 'aspp_concat': [B,eh,ew,256 (2 + rates)]; 'rates'; 'pointwise':
+    {scope: the record crossed_pointwise_operand gives, 'packs' None} for image_pooling, aspp0
+    and aspp<i>_pointwise; 'depthwise': {scope: the record depthwise_operand gives} for
+    aspp<i>_depthwise}."""
+    self._need_fp32_plan('aspp_operands', device=False)
+    r = self._aspp
+    B, eh, ew, ec = self.B, r['eh'], r['ew'], r['ec']
+    return {'encoder': r['encoder'].view(B, eh, ew, -1)[..., :ec],
+            'encoder_relu': r['encoder_relu'], 'pooled': r['pooled'],
+            'pool_feat': r['pool_feat'], 'aspp_concat': r['aspp_concat'],
+            'rates': self.atrous_rates,
+            'pointwise': {s: self._pointwise_record(s, None, eps)
+                          for s, eps in self._aspp_pw.items()},
+            'depthwise': {s: dict(self._dw_operands[s]) for s in self._aspp_dw}}
+
+  def aspp_constants(self, scope):
+    """(weights [1,1,K,256] or depthwise_weights [3,3,ec,1], gamma, moving_mean,
+    moving_variance) of an ASPP layer (weights.aspp_layers) on the device, f32, uploaded from
+    the checkpoint once and kept, as pointwise_constants and crossed_depthwise_constants keep
+    theirs: nothing updates these variables."""
+    if scope not in self._aspp_pw and scope not in self._aspp_dw:
+      raise ValueError('%r is not an ASPP layer (%s)' % (
+          scope, ', '.join(list(self._aspp_pw) + list(self._aspp_dw))))
+    kept = self._pw_consts if scope in self._aspp_pw else self._dw_consts
+    if scope not in kept:
+      first = 'weights' if scope in self._aspp_pw else 'depthwise_weights'
+      kept[scope] = tuple(
+          torch.from_numpy(np.ascontiguousarray(self.ckpt[scope + '/' + v], np.float32)).to(self.dev)
+          for v in (first, 'BatchNorm/gamma', 'BatchNorm/moving_mean',
+                    'BatchNorm/moving_variance'))
+    return kept[scope]
 
   def chain_operands(self):
     """The buffers the backward pass through the decoder reads (trainer.decoder_grads), as they

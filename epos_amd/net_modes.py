@@ -230,7 +230,7 @@ class Fp32Mode(object):
         a_gain=ab[2] if h else 0.0, a_bias=ab[3] if h else 0.0,
         a_presplit=int(presplit), c_amax=self._slot_ptr(cslot))
     if (name in W.TRAINABLE_LAYERS and name not in W.LOGITS_LAYERS) or \
-        name in W.POINTWISE_CHAIN_LAYERS:
+        name in W.POINTWISE_CHAIN_LAYERS or name in net._aspp_pw:
       assert a_off == 0 and sub == 1 and res is None, name
       self.layer_operands[name] = (a, lda, m, k, n, args, ab if h else None)
     # fp32 activations in and out, weights once (4 B each: what the layer IS; the

@@ -16,6 +16,8 @@ any subset of their variables -- not a choice between code paths.
   decoder_grads   decoder_conv1_grads plus the backward pass through decoder_conv0, the split of
                   the decoder's concat, feature_projection0 and the decoder's resize, down to
                   concat_projection's pre-activation at the encoder's size.
+  aspp_grads      decoder_grads plus the backward pass through concat_projection and ASPP's five
+                  branches, joined at the encoder output's pre-activation.
   learning_rate   the reference's schedules (train_utils.py:117-195) in Python floats.
 
 The kernels' wrappers are epos_amd/heads_train.py (the logits layers' weight and input
@@ -26,13 +28,15 @@ forward pass. decoder_conv1_grads runs the whole backward pass of the separable 
 decoder_conv1 -- the input gradient of decoder_conv1_pointwise, the weight, batch-norm and input
 gradients of decoder_conv1_depthwise -- and returns the gradient at decoder_conv0_pointwise's
 pre-activation; decoder_grads goes on through the rest of the decoder ("Losses",
-"Backward through the decoder") and returns the gradient at concat_projection's pre-activation.
+"Backward through the decoder") and returns the gradient at concat_projection's pre-activation;
+aspp_grads goes on through ASPP ("Backward through ASPP") and returns the gradient at the
+pre-activation of the backbone's last layer.
 Not built: the in-place update of any depthwise layer's weights (its folded
 weights set the bound gain / bias0 that the plan and its captured graphs hold by value: an
 update needs a design for that bound); training the four layers below decoder_conv1, whose
 gradients decoder_grads computes (they are rows of weights.POINTWISE_CHAIN_LAYERS and
-DEPTHWISE_CHAIN_LAYERS, not of TRAINABLE_LAYERS); everything below concat_projection's
-pre-activation -- ASPP, the image-pooling broadcast's adjoint and the backbone; batch-norm
+DEPTHWISE_CHAIN_LAYERS, not of TRAINABLE_LAYERS), or ASPP's (weights.aspp_layers); the
+backbone, everything below the encoder output's pre-activation; batch-norm
 statistics, bf16 mode, multi-scale nets and more than one device. A
 ground truth with the k nearest fragments per pixel (the reference's gt_knn_frags; loss.Batch
 reads k from its shapes) goes through every entry here unchanged. A
@@ -265,6 +269,15 @@ def decoder_grads(net, gt, variables, weights=(1.0, 1.0, 100.0), reduction='pool
   Optimizer and EposNet.set_weights do not take them. fp32 single-scale nets whose low-level
   features already have the decoder's size. Copies nothing from the host and does not
   synchronise when `variables` holds device tensors, or none of the new names."""
+  values, bad, by_layer, d_proj, _ = _decoder_chain(net, gt, variables, weights, reduction,
+                                                    ignore_label)
+  return values, bad, _checkpoint_names(by_layer), d_proj
+
+
+def _decoder_chain(net, gt, variables, weights, reduction, ignore_label):
+  """decoder_grads before the gradients get their checkpoint names: (values, bad, {scope: {short
+  name: gradient}}, d_proj, (concat_projection's record, weights, (gamma, mean, variance))).
+  aspp_grads goes on from here."""
   import torch
   ch = net.chain_operands()
   if ch['low_level_hw'] != ch['decoder_hw']:
@@ -307,7 +320,86 @@ def decoder_grads(net, gt, variables, weights=(1.0, 1.0, 100.0), reduction='pool
   wc, bnc = DT._crossed_inputs(net, variables, W.CONCAT_PROJECTION)
   by_layer[W.CONCAT_PROJECTION] = DT.pointwise_weight_grads(
       rows_of(opc), d_proj, wc, bn=bnc, eps=opc['eps'], a_h2=opc['a_h2'])
-  return values, bad, _checkpoint_names(by_layer), d_proj
+  return values, bad, by_layer, d_proj, (opc, wc, bnc)
+
+
+def aspp_grads(net, gt, variables, weights=(1.0, 1.0, 100.0), reduction='pooled',
+               ignore_label=255):
+  """The backward pass through the decoder and ASPP, down to the encoder output: call after
+  net.forward_logits(). variables as decoder_grads takes them; the variables and statistics of
+  ASPP's layers (weights.aspp_layers) come from `variables` where given, otherwise from the
+  copies of its checkpoint the net keeps on the device (EposNet.aspp_constants). Runs what
+  decoder_grads runs, then, with the records of EposNet.aspp_operands, M = B eh ew rows and Wc
+  = concat_projection's weights,
+    pointwise_input_grad(d_proj, Wc, relu_of=aspp_concat)   D_cat [M, 256 (2 + rates)]: slice s
+                                                   is the gradient at branch s's pre-activation
+                                                   (slice 0's mask is the broadcast pool_feat)
+    pool_broadcast_grad(D_cat[..., 0:256])         g_pool [B,256]
+    pointwise_weight_grads(pooled, g_pool)         image_pooling's dW, dgamma, dbeta (B rows)
+    pointwise_input_grad(g_pool), no mask          d_pooled [B,ec]
+    pointwise_weight_grads(encoder, slice 1)       aspp0's three
+    pointwise_input_grad(slice 1), no mask         E0 [M,ec]
+    per rate i, with a_i = the net's own output of aspp<i>_depthwise (fp16 pairs or fp32):
+      pointwise_weight_grads(a_i, slice i+1)       aspp<i>_pointwise's three
+      pointwise_input_grad(slice i+1, relu_of=a_i) D_i [M,ec]
+      depthwise_weight_grads(encoder, D_i, rate)   aspp<i>_depthwise's three
+    aspp_join_grad(depthwise=[(D_i, w9c_i, r_i)], plain=[E0], pooled=(d_pooled, eh ew),
+                   relu_of=encoder where it lies behind a ReLU)        d_enc [B,eh,ew,ec]
+  Returns (values, bad, grads, d_enc): values, bad and the 24 gradients of decoder_grads byte
+  for byte, plus the 3 (2 + 2 len(rates)) new ones under their checkpoint names (matrices
+  [1,1,K,N], depthwise weights [3,3,ec,1]); d_enc: the gradient at the pre-activation of the
+  backbone's last layer. The new gradients are for inspection and for a trainer to come:
+  Optimizer and EposNet.set_weights do not take them. fp32 single-scale nets only. Copies
+  nothing from the host and does not synchronise when `variables` holds device tensors, or
+  none of the new names."""
+  ap = net.aspp_operands()
+  values, bad, by_layer, d_proj, (opc, wc, bnc) = _decoder_chain(net, gt, variables, weights,
+                                                                 reduction, ignore_label)
+  enc, rates = ap['encoder'], ap['rates']
+  B, eh, ew, ec = (int(v) for v in enc.shape)
+  cat = ap['aspp_concat']
+  D_cat = DT.pointwise_input_grad(d_proj.view(-1, d_proj.shape[-1]), wc, bn=(bnc[0], bnc[2]),
+                                  eps=opc['eps'], relu_of=cat, relu_of_h2=opc['presplit'])
+  D_cat = D_cat.view(B, eh, ew, -1)
+
+  def inputs(scope, depthwise=False):
+    return DT._given_or_kept(net, variables, scope, net.aspp_constants(scope),
+                             ('depthwise_weights' if depthwise else 'weights',
+                              'BatchNorm/gamma'))
+
+  def rows_of(op):
+    return op['a'].view(-1, op['a'].shape[-1])[:, :op['k']] if op['lda'] != op['k'] else op['a']
+
+  def branch(s):                                       # slice s of the concat's gradient
+    return D_cat[..., 256 * s:256 * (s + 1)]
+
+  op = ap['pointwise'][W.IMAGE_POOLING]
+  w, bn = inputs(W.IMAGE_POOLING)
+  g_pool = DT.pool_broadcast_grad(branch(0))
+  by_layer[W.IMAGE_POOLING] = DT.pointwise_weight_grads(rows_of(op), g_pool, w, bn=bn,
+                                                        eps=op['eps'], a_h2=op['a_h2'])
+  d_pooled = DT.pointwise_input_grad(g_pool, w, bn=(bn[0], bn[2]), eps=op['eps'])
+  op = ap['pointwise'][W.ASPP0]
+  w, bn = inputs(W.ASPP0)
+  by_layer[W.ASPP0] = DT.pointwise_weight_grads(rows_of(op), branch(1), w, bn=bn, eps=op['eps'],
+                                                a_h2=op['a_h2'])
+  E0 = DT.pointwise_input_grad(branch(1), w, bn=(bn[0], bn[2]), eps=op['eps'])
+  terms = []
+  for i, rate in enumerate(rates, 1):
+    pw, dws = 'aspp%d_pointwise' % i, 'aspp%d_depthwise' % i
+    op, dw = ap['pointwise'][pw], ap['depthwise'][dws]
+    w, bn = inputs(pw)
+    a = rows_of(op)
+    by_layer[pw] = DT.pointwise_weight_grads(a, branch(i + 1), w, bn=bn, eps=op['eps'],
+                                             a_h2=op['a_h2'])
+    D = DT.pointwise_input_grad(branch(i + 1), w, bn=(bn[0], bn[2]), eps=op['eps'], relu_of=a,
+                                relu_of_h2=op['presplit']).view(B, eh, ew, ec)
+    dww, dbn = inputs(dws, depthwise=True)
+    by_layer[dws] = DT.depthwise_weight_grads(enc, D, dww, dbn, dw['eps'], rate=dw['rate'])
+    terms.append((D, dw['w9c'], dw['rate']))
+  d_enc = DT.aspp_join_grad(depthwise=terms, plain=[E0], pooled=(d_pooled, eh * ew),
+                            relu_of=enc if ap['encoder_relu'] else None)
+  return values, bad, _checkpoint_names(by_layer), d_enc
 
 
 def learning_rate(step, policy='poly', base_learning_rate=1e-4, decay_step=2000,

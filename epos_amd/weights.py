@@ -119,8 +119,9 @@ DEPTHWISE_VARIABLES = ('depthwise_weights', 'BatchNorm/gamma', 'BatchNorm/beta')
 # scope -> the eps of its frozen batch norm (net.HEAD_BN_EPS). The plan records the operands of
 # the 1x1 layers (EposNet.crossed_pointwise_operand, 'packs' None) and of the depthwise layer
 # (EposNet.crossed_depthwise_operand); pointwise_operand and depthwise_operand keep answering for
-# the two tables above only. Not built: training these layers, and everything below
-# concat_projection's pre-activation (ASPP, the image-pooling broadcast's adjoint, the backbone).
+# the two tables above only. ASPP's layers, which depend on the net's atrous rates, are
+# aspp_layers() below (trainer.aspp_grads). Not built: training any of these layers, and the
+# backbone below the encoder output's pre-activation.
 DECODER_CONV0_POINTWISE = 'decoder/decoder_conv0_pointwise'
 DECODER_CONV0_DEPTHWISE = 'decoder/decoder_conv0_depthwise'
 FEATURE_PROJECTION0 = 'decoder/feature_projection0'
@@ -128,6 +129,20 @@ CONCAT_PROJECTION = 'concat_projection'
 POINTWISE_CHAIN_LAYERS = {DECODER_CONV0_POINTWISE: 1e-5, FEATURE_PROJECTION0: 1e-5,
                           CONCAT_PROJECTION: 1e-5}
 DEPTHWISE_CHAIN_LAYERS = {DECODER_CONV0_DEPTHWISE: 1e-5}
+IMAGE_POOLING = 'image_pooling'
+ASPP0 = 'aspp0'
+
+
+def aspp_layers(atrous_rates):
+  """({1x1 scope: eps}, {depthwise scope: eps}) of ASPP for a net's atrous rates, in the order of
+  the concat's slices: 'image_pooling', 'aspp0', 'aspp1_pointwise', ... and 'aspp1_depthwise',
+  ...; eps: that of the frozen batch norm (net.HEAD_BN_EPS). The layers trainer.aspp_grads
+  crosses below concat_projection: the plan records their operands (EposNet.aspp_operands), and
+  nothing makes them trainable -- the four tables above stay as they are."""
+  n = len(tuple(atrous_rates))
+  pointwise = {IMAGE_POOLING: 1e-5, ASPP0: 1e-5}
+  pointwise.update(('aspp%d_pointwise' % i, 1e-5) for i in range(1, n + 1))
+  return pointwise, {'aspp%d_depthwise' % i: 1e-5 for i in range(1, n + 1)}
 # a 1x1 conv layer's trained variables by whether it has a batch norm, `weights` first: what is
 # given together to EposNet.set_weights and what a gradient wrapper's result is keyed by
 CONV_VARIABLES = {False: ('weights', 'biases'),

@@ -1650,6 +1650,96 @@ int epos_resize_bilinear_dgrad_f32(const float* D, int64_t ldd, const float* Y /
                                    int64_t ldy, float* dX, int64_t ldx, int B, int Hi, int Wi,
                                    int Ho, int Wo, int C, void* stream);
 
+/* ASPP gradients (csrc/aspp_grad.hip; added without an ABI version change). The two pieces the
+ * backward pass through ASPP lacked: the adjoint of the image-pooling broadcast and the join of
+ * the five branches' gradients at the encoder output. tests/helpers/aspp_grad_ref.py restates
+ * both.
+ *
+ * epos_pool_broadcast_dgrad_f32: g f32 [B][ldg] [device] from D f32 [B*P][ldd] [device], the
+ * gradient at a [B, C] tensor that was broadcast over the P pixels of each image.
+ *     g[b,c] = fl32( sum_p (double)D[b P + p, c] )
+ *   One fp64 sum per (b, c) from +0.0, rounded to fp32 once: within 2^-24 |exact| + (P + 16)
+ *   2^-52 sum |D| of the exact sum. EVERY element of the C columns of g is WRITTEN; padding
+ *   columns are not touched.
+ *   Order of the sum (no atomics; the same bytes in every run and for an image at any position
+ *   of a batch). The P pixels of an image are cut into ranges of
+ *   epos_pool_broadcast_dgrad_range_pixels(B, P, C) pixels -- max(64, ceil(P / 64)), a function
+ *   of P alone -- the last one shorter. Within a range: with s = 256 / min(C / 4, 16) pixel
+ *   slots, slot j adds the range's pixels j, j + s, j + 2 s, ... in ascending order from +0.0,
+ *   then the slots' sums are added in slot order from +0.0. With one range that sum is rounded
+ *   and written; with more, range r of image b writes slab [b][r] of the workspace, f64 [C], and
+ *   a closing launch adds an image's slabs in range order from +0.0.
+ *   workspace [device]: epos_pool_broadcast_dgrad_workspace_bytes(B, P, C) bytes (0 with one
+ *   range: it may then be NULL), 8-byte aligned.
+ *   Launches: one, or two with more than one range; no allocation, no host synchronisation,
+ *   capturable in a graph.
+ *   Refused with EPOS_E_INVALID before the launch, nothing written: B, P or C < 1; C % 4 != 0;
+ *   B > 65535 or B P > 2^40; ldd or ldg < C or not a multiple of 4; a null D or g; D or g not
+ *   16-byte aligned; g starting at D; a missing or misaligned workspace when one is needed.
+ *
+ * epos_aspp_join_dgrad_f32: dX f32 [B,H,W,C] with pixel stride ldx [device], the gradient at a
+ * tensor X that feeds n_plain 1x1 branches, n_dw 3x3 depthwise branches (stride 1, 'SAME') and,
+ * through a global mean, a per-image branch. Per element (pixel i = (b, y, x), channel c) ONE
+ * fp64 accumulator starts from +0.0 and adds, in this order:
+ *   1. the plain terms in index order: (double)E_j[i, c] -- the gradient a 1x1 branch sent down;
+ *   2. the depthwise terms in index order, within a term the taps in ascending tap = 3 ky + kx:
+ *      (double)w9c[tap, c] * (double)D[b, y - (ky-1) rate, x - (kx-1) rate, c], the product
+ *      exact -- the mirrored tap of epos_depthwise_dgrad_f32. A tap whose source pixel lies
+ *      outside the image adds +0.0 (never 0 * d);
+ *   3. the per-image term: (double)Pool[b, c] / (double)pool_div, an IEEE fp64 division --
+ *      the adjoint of a mean over pool_div pixels.
+ *   The accumulator is rounded to fp32 once. With Y non-NULL the result is written as +0.0
+ *   wherever Y[i, c] <= 0 (-0.0 counts, a NaN does not), the rule of epos_depthwise_dgrad_f32.
+ *   EVERY element of the C columns is WRITTEN; padding columns are not touched. With one
+ *   depthwise term and nothing else the bytes are those of epos_depthwise_dgrad_f32.
+ *   One launch, no workspace, no atomics, no host synchronisation, capturable in a graph; the
+ *   same bytes in every run, for an image alone and at any position of a batch.
+ *   partition: how the elements are dealt to workgroups -- never what they hold. 0 = the one this
+ *   build ships (EPOS_ASPP_JOIN_SHIPPED); the others are there to be measured against it
+ *(tools/bench_aspp_chain.py). PIXEL: all channels of a pixel together, as
+ *   epos_depthwise_dgrad_f32. SLICE32 / SLICE64: a workgroup owns 32 / 64 channels of 32 / 16
+ *   consecutive pixels, and the workgroups of a slice have ids congruent mod 8, which the
+ *   dispatcher has been seen to give to one XCD: a slice's nine taps are then re-read from that
+ *   XCD's L2. SLICE32X2 / SLICE32X4: SLICE32 with two / four pixels a thread, 32 apart, which
+ *   share each tap's weights. Nothing about the results depends on any of that.
+ *   Refused with EPOS_E_INVALID before the launch, nothing written: null args or dX; B, H, W or
+ *   C < 1; C % 4 != 0; too many pixels (epos_depthwise_dgrad_f32's limits); n_dw outside 0..4,
+ *   n_plain outside 0..2; no term at all; a null D, w9c or E of a term counted; rate outside
+ *   1..2^20; any ld < C or not a multiple of 4; pool_div < 1 with a Pool; a pointer that is not
+ *   16-byte aligned; dX starting at an input; an unknown partition. */
+#define EPOS_ASPP_JOIN_PIXEL 1
+#define EPOS_ASPP_JOIN_SLICE32 2
+#define EPOS_ASPP_JOIN_SLICE64 3
+#define EPOS_ASPP_JOIN_SLICE32X2 4
+#define EPOS_ASPP_JOIN_SLICE32X4 5
+#define EPOS_ASPP_JOIN_SHIPPED EPOS_ASPP_JOIN_SLICE64
+typedef struct EposAsppJoinDw {
+  const float* D; int64_t ldd;  /* f32 [B,H,W,C], the gradient at the branch's pre-activation */
+  const float* w9c;             /* f32 [9][C], the folded weights the forward reads */
+  int32_t rate;
+  int32_t reserved0;
+} EposAsppJoinDw;
+typedef struct EposAsppJoinPlain {
+  const float* E; int64_t lde;  /* f32 [B,H,W,C] */
+} EposAsppJoinPlain;
+typedef struct EposAsppJoinArgs {
+  int32_t B, H, W, C;
+  int32_t n_dw, n_plain;
+  EposAsppJoinDw dw[4];
+  EposAsppJoinPlain plain[2];
+  const float* Pool; int64_t ldp;   /* f32 [B][ldp] or NULL */
+  int64_t pool_div;                 /* >= 1 with a Pool */
+  const float* Y; int64_t ldy;      /* or NULL */
+  float* dX; int64_t ldx;
+  int32_t partition;                /* 0, or EPOS_ASPP_JOIN_* */
+  int32_t reserved0;
+} EposAsppJoinArgs;
+int64_t epos_pool_broadcast_dgrad_range_pixels(int B, int64_t P, int C);
+int64_t epos_pool_broadcast_dgrad_workspace_bytes(int B, int64_t P, int C);
+int epos_pool_broadcast_dgrad_f32(const float* D, int64_t ldd, float* g, int64_t ldg, int B,
+                                  int64_t P, int C, void* workspace /* or NULL */, void* stream);
+int epos_aspp_join_dgrad_f32(const EposAsppJoinArgs* args, void* stream);
+
 /* Weight update (csrc/weight_pack.hip; added without an ABI version change). The three host
  * packers above restated as device kernels, so that weights updated on the device (the momentum
  * step) reach a built plan without a round trip through the host: a grouped call packs fp32
