@@ -227,6 +227,23 @@ static int grouped_impl(const EposPointwiseArgs* args, int count, void* stream) 
   if (args[0].relu_in == 0 && use_dma != 0 && ref.dma)
     return ref.dma(args, count, s, nullptr, nullptr);
   if (ref.staged) return ref.staged(args, count, s);
+  // The product library: say which rule refused the problem when it is not the weights. Both
+  // product GEMM kernels need M > 8 and relu_in == 0; the GEMV above takes M <= 8 (and relu_in)
+  // only as ONE problem with sub == 1.
+  for (int i = 0; i < count; ++i)
+    if (args[i].M <= 8) {
+      set_error("epos_pointwise_conv_grouped_f32: problem %d of %d has M <= 8 rows (M = %d, "
+                "sub = %d): such a problem is served by the GEMV only, as a single problem "
+                "with sub == 1 -- not inside a group and not with a stride-2 gather, whatever "
+                "weights it brings", i, count, args[i].M, args[i].sub);
+      return EPOS_E_INVALID;
+    }
+  if (args[0].relu_in != 0) {
+    set_error("epos_pointwise_conv_grouped_f32: relu_in != 0 with M > 8 (M = %d): the "
+              "pre-activation ReLU is served by the GEMV only (one problem, M <= 8, sub == 1), "
+              "whatever weights the problem brings", args[0].M);
+    return EPOS_E_INVALID;
+  }
   return no_fp32_mfma("epos_pointwise_conv_grouped_f32");
 }
 

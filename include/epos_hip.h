@@ -132,13 +132,21 @@ typedef struct EposPointwiseArgs {
   float* C; int64_t ldc;
   int32_t M, N, K;
   int32_t relu;       /* apply ReLU last */
-  int32_t relu_in;    /* apply ReLU to A on load (pre-activation) */
+  int32_t relu_in;    /* apply ReLU to A on load (pre-activation). Served by the M <= 8 GEMV
+                       * only (below): with M > 8 the library refuses it (EPOS_E_INVALID) */
   int32_t sub;        /* spatial subsampling of A rows (1 or 2) */
   int32_t Ho, Wo, Hi, Wi;   /* only read when sub > 1 */
   const void* Ws;     /* optional [device]: the same weights packed by
                        * epos_pack_pointwise_weights_split (NULL = not provided) */
-  /* ---- ABI 5: fp16-pair GEMM (taken when Wh is given, relu_in == 0 and M > 8;
-   *      EPOS_GEMM_H2=0 disables it; otherwise Ws -> bf16 x 6 kernel, else fp32 MFMA) */
+  /* ---- Which kernel runs a call. ONE problem with M <= 8 and sub == 1: a GEMV on Wp alone
+   *      (Ws, Wh and the a_* fields are ignored; the only kernel that applies relu_in). Every
+   *      other call needs relu_in == 0 and M > 8 in every problem: the fp16-pair GEMM (ABI 5)
+   *      when every problem brings Wh (EPOS_GEMM_H2=0 disables it), else the bf16 x 6 kernel
+   *      when every problem brings Ws. Anything else is refused with EPOS_E_INVALID before a
+   *      launch: a problem with M <= 8 inside a group or with sub > 1 (whatever weights it
+   *      brings; epos_last_error() says so), relu_in with M > 8, and a problem with neither
+   *      Wh nor Ws -- the fp32-MFMA kernels are in the test build (libepos_hip_ref.so) only,
+   *      where they take these calls. */
   const void* Wh;     /* optional [device]: epos_pack_pointwise_weights_h2 of the weights */
   const uint32_t* a_amax;   /* optional [device]: slot bounding max|A| (see above). NULL
                        * with Wh given: the library measures A itself first (one memset +
@@ -224,7 +232,8 @@ typedef struct EposConv3x3Args {
   int32_t stride, rate;
   int32_t relu;
   const void* Ws;     /* optional [device]: epos_pack_pointwise_weights_split of the same
-                       * [9*Cin][Cout] matrix (NULL = fp32-MFMA kernel) */
+                       * [9*Cin][Cout] matrix (NULL without Wh: refused -- the
+                       * fp32-MFMA kernel is in the test build only) */
   /* ---- ABI 5, as in EposPointwiseArgs */
   const void* Wh;     /* optional [device]: epos_pack_pointwise_weights_h2 of that matrix */
   const uint32_t* x_amax;   /* optional [device]: slot bounding max|X| */
